@@ -8,7 +8,13 @@ One step (default workload "rl", BASELINE configs[2]) = frame-embed + encode + K
 global-norm clip + TF-form Adam -- the device work of reinforcement_multisampling_tf_s2vt.py:743-753 and :823-826.  The
 reward (external CIDEr-D host code) is replaced by synthetic r, b.
 
-  python bench.py --gpus N --steps K --warmup W [--workload rl|xe|multitask|e2e|e2e_xe]
+  python bench.py --gpus N --steps K --warmup W [--workload rl|xe|multitask|e2e|e2e_xe] [--full] [--dump-outputs DIR]
+A plain run sets up, runs W warm-up and K timed steps and prints the line (the roofline object is read off those same steps).
+--full adds what the headline figure does not need: the CPU baseline of the default workload at N=1 (`cpu_baseline`, up to ~90 s of
+host work; --no-cpu-baseline still drops it).
+--dump-outputs DIR: after the timed steps, what the LAST timed step handed back -- the step's scalars, the token ids it sampled, a
+fixed seeded sample of the variables after its update -- as DIR/<name>.npy (float32 / float64, a few MB); the inputs are seeded, so two
+builds run with the same arguments can be compared array for array.
 N>1: one rank per GPU, RCCL all-reduce of the flat gradient bucket (weak scaling: B per GPU fixed).  Either launched by
 torch.distributed.run (WORLD_SIZE in the environment), or -- plain `python bench.py --gpus N` -- this process starts
 `python -m torch.distributed.run --nproc-per-node N bench.py ...` itself, BEFORE anything here touches the GPU, relays
@@ -126,6 +132,10 @@ def launch_ranks(args):
            str(args.warmup), "--workload", args.workload]
     if args.no_cpu_baseline:
         cmd.append("--no-cpu-baseline")
+    if args.full:
+        cmd.append("--full")
+    if args.dump_outputs:
+        cmd += ["--dump-outputs", os.path.abspath(args.dump_outputs)]
     if args.batch_per_gpu > 0:
         cmd += ["--batch-per-gpu", str(args.batch_per_gpu)]
     r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, text=True)
@@ -214,6 +224,14 @@ def cpu_baseline():
     r = torch.rand(K * B, generator=g) * 2
     b = (torch.rand(B, generator=g) * 2).repeat(K)
     ncpu = os.cpu_count() or 1
+    # thread counts tried: at most the CPUs this process may use -- its affinity mask, and OMP_NUM_THREADS where the environment sets it (a
+    # shared host grants a share of its cores; a pool sized past that only slows itself down)
+    try:
+        avail = len(os.sched_getaffinity(0)) or ncpu
+    except (AttributeError, OSError):
+        avail = ncpu
+    if os.environ.get("OMP_NUM_THREADS", "").isdigit() and int(os.environ["OMP_NUM_THREADS"]) > 0:
+        avail = min(avail, int(os.environ["OMP_NUM_THREADS"]))
 
     def probe():
         t0 = time.time()
@@ -227,7 +245,7 @@ def cpu_baseline():
     except Exception:
         phys = ncpu
     best, tried = None, {}
-    for cores in sorted({min(ncpu, c) for c in (8, 16, 32, 64, phys)}, reverse=True):     # the best the host does, not a guess
+    for cores in sorted({min(avail, c) for c in (8, 16, 32, 64, phys)}, reverse=True):     # the best the host does, not a guess
         torch.set_num_threads(cores)
         probe()                                    # page-in / thread-pool warm-up
         tp = probe()
@@ -235,7 +253,7 @@ def cpu_baseline():
         if best is None or tp < best[1]:
             best = (cores, tp)
     cores, tp = best
-    probe_note = {"probe_seconds_by_threads": tried, "physical_cores": phys}
+    probe_note = {"probe_seconds_by_threads": tried, "physical_cores": phys, "threads_allowed": avail}
     torch.set_num_threads(cores)
     est = tp * (4 * K + 1)                         # (4K+1) sequence-forward equivalents per step
     if est > 90.0:
@@ -255,7 +273,7 @@ def cpu_baseline():
         step_i[0] += 1
         return time.time() - t0
     one_step()
-    cand = sorted({min(ncpu, c) for c in (cores, 16, 32, 64, phys) if c >= min(cores, 16)})
+    cand = sorted({min(avail, c) for c in (cores, 16, 32, 64, phys) if c >= min(cores, 16)})
     by_step, spent = {}, 0.0
     for c in cand:
         if spent > 45.0 and by_step:
@@ -331,9 +349,11 @@ def make_step(workload, mdl, dev, rank, B, K, info=None):
 
     if workload in ("rl", "rl_ref"):
         def step(i):
-            s, _greedy = mdl.sample(video, K, True, seed=2024 + i, video_base=rank * B)
-            return mdl.reinforce_update(video, s, None, rewards, baseline, lr=1e-6, clip_norm=5.0, video_base=rank * B,      # mask None: PG mask from the ids, in the library
-                                        reuse_sampler_state=True)    # LSTM1 trajectory of the sampler pass (same videos, same weights)
+            s, greedy = mdl.sample(video, K, True, seed=2024 + i, video_base=rank * B)
+            st = mdl.reinforce_update(video, s, None, rewards, baseline, lr=1e-6, clip_norm=5.0, video_base=rank * B,      # mask None: PG mask from the ids, in the library
+                                      reuse_sampler_state=True)    # LSTM1 trajectory of the sampler pass (same videos, same weights)
+            st.samples, st.greedy = s, greedy                      # (as e2e.reinforce_step hands them back: --dump-outputs reads them)
+            return st
         return step
     if workload in ("rl_msvd", "rl_msvd_eos"):
         stop = workload == "rl_msvd_eos"
@@ -354,9 +374,11 @@ def make_step(workload, mdl, dev, rank, B, K, info=None):
             info["live_fraction"] = round(float(mask.mean()), 3)
 
         def step(i):
-            mdl.sample(video, K, True, seed=2024 + i, video_base=rank * B, stop_at_eos=stop)
-            return mdl.reinforce_update(video, capd, mask, rewards, baseline, lr=1e-6, clip_norm=5.0, video_base=rank * B,
-                                        reuse_sampler_state=True)
+            s, greedy = mdl.sample(video, K, True, seed=2024 + i, video_base=rank * B, stop_at_eos=stop)
+            st = mdl.reinforce_update(video, capd, mask, rewards, baseline, lr=1e-6, clip_norm=5.0, video_base=rank * B,
+                                      reuse_sampler_state=True)
+            st.samples, st.greedy = s, greedy
+            return st
         return step
     # ground-truth captions: length 1 + min(Poisson(6), Tc - 2) words (MSVD mean 7.03), tokens U{2..V-1}, then <eos> = 0
     rng = np.random.default_rng(1234 + rank)
@@ -390,11 +412,50 @@ def make_step(workload, mdl, dev, rank, B, K, info=None):
     labels = (torch.rand(B, mdl.label_dim, generator=g) < 0.02).float().to(dev)           # bag-of-words attribute labels, ~8 of 400 set
 
     def step(i):
-        s, _greedy = mdl.sample(video, K, True, seed=2024 + i, video_base=rank * B)
-        return mdl.mixed_update(video, s, ops.caption_mask(s, want_target=False)[0], rewards, baseline, gt, gt_mask, lr=1e-6, lambda_loss=0.5, clip_norm=5.0,
-                                video_base=rank * B, true_labels=labels, decay_all=True,     # (the script's always-true decay predicate, :222)
-                                reuse_sampler_state=True)                                    # LSTM1 trajectory of the sampler pass, as the rl workload
+        s, greedy = mdl.sample(video, K, True, seed=2024 + i, video_base=rank * B)
+        st = mdl.mixed_update(video, s, ops.caption_mask(s, want_target=False)[0], rewards, baseline, gt, gt_mask, lr=1e-6, lambda_loss=0.5, clip_norm=5.0,
+                              video_base=rank * B, true_labels=labels, decay_all=True,     # (the script's always-true decay predicate, :222)
+                              reuse_sampler_state=True)                                    # LSTM1 trajectory of the sampler pass, as the rl workload
+        st.samples, st.greedy = s, greedy
+        return st
     return step
+
+
+DUMP_PARAM_SAMPLE = 1 << 20          # entries of the variables --dump-outputs keeps (the whole flat buffer is ~140 MB at the bench shapes)
+
+
+def step_outputs(st, mdl, info):
+    """What the timed path handed back in its last step, as host arrays: the step's scalars (loss, global gradient norm squared before
+    clipping, mask sum; the multitask steps' attribute-loss term), the token ids the sampler drew where the step samples, and a fixed,
+    seeded sample of the variables after the update (of the CNN's too on the e2e workloads).  Ids are exact in float32 (|V| < 2^24)."""
+    import numpy as np
+    import torch
+    out = {k: np.asarray([float(getattr(st, k))], np.float64) for k in ("loss", "grad_sumsq", "mask_sum")}
+    if getattr(st, "attr_loss", None) is not None:
+        out["attr_loss"] = np.asarray([float(st.attr_loss)], np.float64)
+    for k, name in (("samples", "sampled_ids"), ("greedy", "greedy_ids")):
+        ids = getattr(st, k, None)
+        if ids is not None:
+            out[name] = ids.cpu().numpy().astype(np.float32)
+
+    def sample(flat):
+        flat = flat.detach()
+        n = flat.numel()
+        if n <= DUMP_PARAM_SAMPLE:
+            return flat.cpu().numpy().astype(np.float32)
+        idx = np.sort(np.random.default_rng(20240607).integers(0, n, DUMP_PARAM_SAMPLE))
+        return flat[torch.as_tensor(idx, device=flat.device)].cpu().numpy().astype(np.float32)
+    out["params_sample"] = sample(mdl.store.theta)
+    if "trainer" in info:
+        out["cnn_params_sample"] = sample(info["trainer"].theta)
+    return out
+
+
+def write_outputs(d, outputs):
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(d, name + ".npy"), a)
 
 
 def main():
@@ -403,7 +464,10 @@ def main():
     ap.add_argument("--steps", type=int, default=150)      # ~2 s of GPU work at the default workload (SURVEY §8(d) asks >= 50 timed)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="rl")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline figure does not need: the CPU baseline (default "
+                    "workload, one GPU)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as DIR/<name>.npy")
     ap.add_argument("--batch-per-gpu", type=int, default=0, help="functional tests only (several ranks on one GPU): overrides the workload's "
                     "B per GPU; the line then carries config.batch_per_gpu_override and is NOT the BASELINE configuration")
     args = ap.parse_args()
@@ -413,6 +477,8 @@ def main():
         B = args.batch_per_gpu
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args))                 # before torch / HIP is touched in this process
     if int(os.environ.get("WORLD_SIZE", "1")) != args.gpus:
@@ -516,8 +582,15 @@ def main():
             info["cnn_timing"] = info["trainer"].timing_collect()
             info["trainer"].timing_enable(False)
         per_step = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps))
+        outputs = step_outputs(st, mdl, info) if args.dump_outputs and rank == 0 else None     # (host copies now: later probe steps move the variables)
         return dict(dt=dt, warm_rows=warm_rows, nprof=nprof, rows=rows, ar_ms=ar_ms, ar_n=ar_n, drift=drift, per_step=per_step, loss=float(st.loss) if st is not None else None,
-                    dp_overlap=bool(getattr(mdl, "dp_overlap", False)))
+                    dp_overlap=bool(getattr(mdl, "dp_overlap", False)), outputs=outputs)
+
+    def emit(line, m):
+        """Rank 0: the outputs of the measurement the line reports (--dump-outputs), then the line."""
+        if m["outputs"] is not None:
+            write_outputs(args.dump_outputs, m["outputs"])
+        print(json.dumps(line), flush=True)
 
     def make_line(m, probe):
         dt, warm_rows, rows, ar_ms, ar_n, drift, per_step = m["dt"], m["warm_rows"], m["rows"], m["ar_ms"], m["ar_n"], m["drift"], m["per_step"]
@@ -625,7 +698,7 @@ def main():
             out["config"]["unmasked_positions"] = info["live_fraction"]
         if "sampler" in info:
             out["config"]["sampler"] = info["sampler"]
-        if world == 1 and not args.no_cpu_baseline and args.workload == "rl":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.workload == "rl":
             out["cpu_baseline"] = cpu_baseline()
         return out
 
@@ -639,7 +712,7 @@ def main():
     if not probe_ok:
         m_ = measure()
         if rank == 0:
-            print(json.dumps(make_line(m_, None)), flush=True)
+            emit(make_line(m_, None), m_)
     else:
         import threading
         probe = {"off": probe_mode(False, 0), "on": None}
@@ -661,14 +734,14 @@ def main():
             done.set()
             if rank == 0:
                 line_off["config"]["dp_overlap_probe_ms"] = {"off": probe["off"], "on": f"{why}: the blocking-mode measurement is reported"}
-                print(json.dumps(line_off), flush=True)
+                emit(line_off, m_off)
             sys.stdout.flush(); sys.stderr.flush()
             os._exit(bad_exit)
         deadline = float(os.environ.get("S2VT_BENCH_WATCHDOG_S", "0")) or max(120.0, 40.0 * ms_off * args.steps / 1e3)
         wd = threading.Timer(deadline, give_up, args=("stalled",))
         wd.daemon = True
         wd.start()
-        out = None
+        out, m_out = None, m_off
         try:
             if os.environ.get("S2VT_BENCH_FAKE_STALL") == "1":      # test hook (tests/test_gpu_dp.py): the overlapped mode "hangs" -- the watchdog must deliver the line
                 time.sleep(1e6)
@@ -678,7 +751,7 @@ def main():
             if probe["on"] < probe["off"]:
                 mdl.dp_overlap = True
                 m_on = measure()
-                out = make_line(m_on, dict(probe)) if rank == 0 else None
+                out, m_out = (make_line(m_on, dict(probe)) if rank == 0 else None), m_on
             else:
                 mdl.dp_overlap = False
                 out = line_off
@@ -690,7 +763,7 @@ def main():
         done.set()
         wd.cancel()
         if rank == 0:
-            print(json.dumps(out), flush=True)
+            emit(out, m_out)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

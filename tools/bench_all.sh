@@ -3,7 +3,7 @@
 #   bash tools/bench_all.sh gpurun_out/r06lines   ->  <dir>/bench_<workload>.json
 out=${1:-gpurun_out/lines}; mkdir -p $out
 for w in rl xe multitask attention attention32 rl_msvd rl_msvd_eos rl_ref e2e e2e_xe; do
-  extra=$([ $w = rl ] && echo "" || echo "--no-cpu-baseline")
+  extra=$([ $w = rl ] && echo "--full" || echo "--no-cpu-baseline")      # the rl line carries the CPU baseline (--full)
   st=$(case $w in rl_ref) echo "--steps 20 --warmup 3";; e2e|e2e_xe) echo "--steps 10 --warmup 3";; *) echo "";; esac)
   python3 bench.py --workload $w $st $extra 2>/dev/null | tail -1 > $out/bench_$w.json
 done

@@ -11,7 +11,7 @@ WL="rl xe multitask attention attention32 rl_msvd rl_msvd_eos rl_ref"
 steps() { [ $1 = rl_ref ] && echo "--steps 3 --warmup 1" || echo "--steps 10 --warmup 2"; }
 psteps() { [ $1 = rl_ref ] && echo "--steps 1 --warmup 1" || echo "--steps 2 --warmup 1"; }
 for w in $WL; do
-  extra=$([ $w = rl ] && echo "" || echo "--no-cpu-baseline")
+  extra=$([ $w = rl ] && echo "--full" || echo "--no-cpu-baseline")      # the rl line carries the CPU baseline (--full)
   bs=$([ $w = rl_ref ] && echo "--steps 20 --warmup 3" || echo "")
   python3 bench.py --workload $w $bs $extra 2> $out/bench_$w.err | tail -1 > ${out}_bench_$w.json
 done
