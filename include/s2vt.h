@@ -191,6 +191,33 @@ int s2vt_sample_ex(const s2vt_dims* d, const s2vt_params* p, const float* video,
                    uint64_t seed, int32_t video_base, int32_t flags, int32_t* ids_out, void* workspace, size_t workspace_bytes,
                    s2vt_stream stream);
 
+/* ---- batched beam search: build_generator(beam_size, length_normalization_factor) of final_beam_search.py:201-294 for B videos
+ * at once.  The reference runs one B = 1 graph per live beam per step (beam_probability, :203-224) and keeps the captions in TopN
+ * heaps (beam_search.py:44-80); here one call per decode step advances every live hypothesis of every video, and only the
+ * heap bookkeeping stays on the host.
+ *
+ * s2vt_vocab_topk: for each row r of logits [R, V] (row stride ld), ids[r, j] / logp[r, j] (j < k, 1 <= k <= 16) = the k largest
+ * logits ordered by value descending, then index ascending on exact ties (tf.nn.top_k's order, :217), and l[id] - lse with
+ * lse = max + log(sum exp(l - max)) evaluated exactly as s2vt_softmax_nll_fwd_bwd evaluates it: logp is bit-identical to that
+ * call's lp_target for target = id (same ld, same pointer alignment).  Finite logits only: NaN is out of scope. */
+int s2vt_vocab_topk(const float* logits, int32_t ld, int32_t R, int32_t V, int32_t k, int32_t* ids, float* logp, s2vt_stream stream);
+/* Workspace of a beam decoder for B videos and up to beam hypotheses per video (1 <= beam <= 16): the sampler's encode half for
+ * B rows plus LSTM2 state, gathered cell inputs and logits for B * beam rows.  0 on bad arguments. */
+size_t s2vt_beam_workspace_bytes(const s2vt_dims* d, int32_t B, int32_t beam);
+/* Frame embedding + encoding stage for the B videos (final_beam_search.py:226-253), as the samplers run it (persistent
+ * recurrences, no per-step cell launches), and the word-independent half of every decode step: the LSTM1 trajectory -- shared
+ * by all beams of a video, it never sees a word -- and its products h1 @ W2[0:H]. */
+int s2vt_beam_encode(const s2vt_dims* d, const s2vt_params* p, const float* video, int32_t B, int32_t beam, void* workspace,
+                     size_t workspace_bytes, s2vt_stream stream);
+/* Decode step t (0 <= t < Tc) for R <= B * beam live hypotheses (beam_probability, :203-224, with the expansion of :255-290 left
+ * to the caller), no host synchronisation.  Hypothesis m continues video video_of_row[m] from row parent[m] of step t - 1 (at
+ * t = 0: from the video's encoder state; parent is ignored) with word[m] (<bos> = 1 at t = 0).  The three int32 [R] arrays are
+ * device pointers (one host-to-device copy of a [3][R] block suits them); indices out of range are clamped, not reported.
+ * Writes top_ids / top_logp [R, k] (s2vt_vocab_topk of the step's logits) and, when logits_out is given, the logits [R, V]. */
+int s2vt_beam_step(const s2vt_dims* d, const s2vt_params* p, int32_t B, int32_t beam, int32_t t, int32_t R, const int32_t* video_of_row,
+                   const int32_t* parent, const int32_t* word, int32_t k, int32_t* top_ids, float* top_logp, float* logits_out,
+                   void* workspace, size_t workspace_bytes, s2vt_stream stream);
+
 /* ---- teacher-forced unroll: build_model (tf_s2vt.py:90-153) / build_loss
  * (reinforcement_multisampling_tf_s2vt.py:227-292) forward --------------------------------------
  * video [B,Tv,d]; the N = rep*B rows are sample-major copies of the B videos (row n uses video

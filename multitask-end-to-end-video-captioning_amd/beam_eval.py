@@ -1,0 +1,79 @@
+"""Beam-search captions for a test set from a checkpoint (the test() of final_beam_search.py:504-545 / e2e_beam_search.py, batched):
+
+    python -m s2vt_amd.beam_eval --checkpoint CKPT --test-sents SENTS --test-feats FEATS --vocab VOCAB \
+        [--beam 3] [--lnf 0.0] [--batch-size 64] [--n-caption-lstm-step 35] [--out captions.txt]
+
+The checkpoint is loaded with optimistic_restore (an .npz dump or a TensorFlow checkpoint); the model's dimensions are read from
+its variables, Tv from the feature file.  Writes one `video_id<TAB>sentence` line per test video, as the reference does (the
+caption cut at its first <eos>, <bos> / <eos> dropped), and prints the mean CIDEr-D against the test set's references."""
+from __future__ import annotations
+
+import argparse
+import sys
+
+
+def caption_text(ids, ixtoword) -> str:
+    """The reference's output sentence (final_beam_search.py:531-539): the words up to and including the first <eos>, joined,
+    with <bos> and <eos> removed.  (Without an <eos>, the reference's np.argmax(... == '<eos>') + 1 keeps only the first word;
+    here the whole caption is kept.)"""
+    words = []
+    for t in ids:
+        w = ixtoword[int(t)]
+        if w == "<eos>":
+            break
+        if w != "<bos>":
+            words.append(w)
+    return " ".join(words)
+
+
+def write_captions(path, captions) -> None:
+    """captions: iterable of (video_id, sentence text) -> `video_id<TAB>sentence` lines (final_beam_search.py:540-545)."""
+    with open(path, "w") as f:
+        for vid, text in captions:
+            f.write(f"{vid}\t{text}\n")
+
+
+def read_captions(path) -> dict:
+    out = {}
+    with open(path) as f:
+        for line in f:
+            vid, _, text = line.rstrip("\n").partition("\t")
+            out[vid] = text
+    return out
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--checkpoint", required=True)
+    ap.add_argument("--test-sents", required=True); ap.add_argument("--test-feats", required=True)
+    ap.add_argument("--vocab", required=True)
+    ap.add_argument("--beam", type=int, default=3); ap.add_argument("--lnf", type=float, default=0.0)
+    ap.add_argument("--batch-size", type=int, default=64)
+    ap.add_argument("--n-caption-lstm-step", type=int, default=35)
+    ap.add_argument("--out", default="beam_captions.txt")
+    a = ap.parse_args(argv)
+
+    from . import hostglue, reward, tfckpt
+    from . import model as M
+    from .train_common import Corpus, beam_eval, optimistic_restore
+    corpus = Corpus(a.test_sents, a.test_feats, vocabulary_file=a.vocab)
+    wordtoix, ixtoword = hostglue.preProBuildWordVocab(corpus.vocabulary)
+    raw = tfckpt.read_checkpoint(a.checkpoint)
+    V, E = raw["Wemb"].shape
+    D = raw["encode_image_W"].shape[0]
+    H = raw["embed_word_W"].shape[0]
+    if V != len(wordtoix):
+        raise SystemExit(f"checkpoint vocabulary has {V} words, {a.vocab} gives {len(wordtoix)}")
+    Tv = corpus.features.features.shape[1]
+    Tc = a.n_caption_lstm_step
+    model = M.Video_Caption_Generator(D, V, E, H, a.batch_size, Tv + Tc, Tv, Tc, bias_init_vector=None)
+    optimistic_restore(model, a.checkpoint)
+    scorer = reward.CiderD(corpus.index.refs_by_video(), wordtoix)
+    decoded, cider = beam_eval(model, corpus, ixtoword, scorer, a.batch_size, a.beam, a.lnf)
+    write_captions(a.out, [(v, caption_text([wordtoix[w] for w in decoded[v].split()], ixtoword)) for v in corpus.index.video_ids])
+    print(f"beam {a.beam} lnf {a.lnf}: {len(decoded)} videos, mean CIDEr-D {cider:.4f} -> {a.out}")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

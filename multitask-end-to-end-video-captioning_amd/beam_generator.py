@@ -150,3 +150,90 @@ class BeamSearchGenerator:
             final_captions = captions
         best = final_captions.best_first()[0]
         return best.sentence, best.logprob, best.score
+
+
+class BatchedBeamSearch:
+    """BeamSearchGenerator.generate for a batch of videos in lock step.  The device work of a step is ONE library call for every
+    live hypothesis of every video (ops.BeamDecoder: parent-state gather, LSTM2, logits, top-k with the log-normaliser); the
+    bookkeeping per video is BeamSearchGenerator.generate's, statement for statement -- the same BestK(k*k) / BestK(k) heaps, the
+    `exclude` counter, the length normalisation, the final_captions fallback.  A video whose loop would break (no mid captions,
+    or exclude == k) leaves the row list; the step's rows never depend on other videos', so a video decodes to the same bits
+    whatever batch it is in."""
+
+    def __init__(self, model, beam_size=3, length_normalization_factor=0.0):
+        self.m, self.beam_size, self.lnf = model, beam_size, length_normalization_factor
+        self._dec = None
+
+    def _decoder(self, B):
+        m = self.m
+        if self._dec is None or self._dec.max_B < B:
+            self._dec = ops.BeamDecoder(m.dims, B, self.beam_size, m.device)
+        return self._dec
+
+    def generate(self, video):
+        """video [B, Tv, d] -> [(sentence ids, logprob, score)] * B, the best caption of each video."""
+        m, k = self.m, self.beam_size
+        video = m._dev(video, torch.float32).view(-1, m.n_video_lstm_step, m.dim_image)
+        B = video.shape[0]
+        if B == 0:
+            return []
+        dec = self._decoder(B)
+        params = m.store.params
+        dec.encode(params, video)
+        captions = [BestK(k * k) for _ in range(B)]
+        final_captions = [BestK(k) for _ in range(B)]
+        exclude = [0] * B
+        rows = np.zeros((3, B), np.int32)
+        rows[0] = np.arange(B)
+        rows[2] = 1                                                                    # <bos>
+        wi, lp = dec.step(params, 0, rows, k)
+        for j in range(B):
+            for b in range(k):
+                captions[j].push(Hypothesis([int(wi[j, b])], j, float(lp[j, b]), float(lp[j, b])))
+        live = list(range(B))
+        for t in range(1, m.n_caption_lstm_step):
+            mids, vids, parents, words = [], [], [], []
+            still = []
+            for j in live:
+                mid = captions[j].best_first()[:k]
+                captions[j].clear()
+                if not mid:                                                            # this video's loop breaks
+                    continue
+                still.append(j)
+                mids.append(mid)
+                for cap in mid:
+                    vids.append(j); parents.append(cap.row); words.append(cap.sentence[-1])
+            live = still
+            if not live:
+                break
+            wi, lp = dec.step(params, t, np.array([vids, parents, words], np.int32), k)
+            r0 = 0
+            done = []
+            for j, mid in zip(live, mids):
+                for r, cap in enumerate(mid):
+                    m_row = r0 + r
+                    for b in range(k - exclude[j]):                                    # evaluated per caption, as the reference does
+                        w = int(wi[m_row, b])
+                        sentence = cap.sentence + [w]
+                        logprob = cap.logprob + float(lp[m_row, b])
+                        score = logprob
+                        if w == 0:
+                            if self.lnf > 0:
+                                score /= len(sentence) ** self.lnf
+                            final_captions[j].push(Hypothesis(sentence, m_row, logprob, score))
+                            exclude[j] += 1
+                        else:
+                            captions[j].push(Hypothesis(sentence, m_row, logprob, score))
+                r0 += len(mid)
+                if exclude[j] == k:
+                    done.append(j)
+            if done:
+                live = [j for j in live if j not in done]
+            if not live:
+                break
+        out = []
+        for j in range(B):
+            fc = final_captions[j] if final_captions[j].size() else captions[j]
+            best = fc.best_first()[0]
+            out.append((best.sentence, best.logprob, best.score))
+        return out

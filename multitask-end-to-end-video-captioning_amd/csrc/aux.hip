@@ -11,36 +11,9 @@
 #include "gemm_tn.h"
 #include "internal.h"
 #include "chain_common.h"
+#include "rowreduce.h"
 
 namespace s2vt {
-
-// ---------------------------------------------------------------------------------------------
-// wave / block reductions
-// ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ float wave_max(float v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-template <bool IS_MAX>
-__device__ __forceinline__ float block_reduce(float v, float* sh)
-{
-    v = IS_MAX ? wave_max(v) : wave_sum(v);
-    const int w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[w] = v;
-    __syncthreads();
-    float r = sh[0];
-    for (int i = 1; i < nw; ++i) r = IS_MAX ? fmaxf(r, sh[i]) : r + sh[i];
-    return r;
-}
 
 // ---------------------------------------------------------------------------------------------
 // caption [N,Tc] -> time-major previous-token and target arrays

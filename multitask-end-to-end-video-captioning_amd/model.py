@@ -473,6 +473,19 @@ class Video_Caption_Generator:
         sentence = [Output(f"word_{t}", fn, [video]) for t in range(Tc)]
         return video, sentence, []
 
+    def beam_search(self, video, beam_size=3, length_normalization_factor=0.0, batch_size=64):
+        """Beam search over a block of videos (features [n, Tv, dim_image], or frames once a CNN is attached): the captions
+        build_generator(beam_size, length_normalization_factor) returns one video at a time (final_beam_search.py:504-545,
+        e2e_beam_search.py), decoded batch_size videos at once (beam_generator.BatchedBeamSearch).  Returns
+        [(sentence ids, logprob, score)] * n."""
+        from .beam_generator import BatchedBeamSearch
+        gen = BatchedBeamSearch(self, beam_size, length_normalization_factor)
+        n = video.shape[0] if hasattr(video, "shape") else len(video)
+        out = []
+        for a in range(0, n, batch_size):
+            out += gen.generate(self._features(video[a:a + batch_size]))
+        return out
+
     # -------------------------------------------------------------------------------- training graphs
     @staticmethod
     def active_steps(mask):

@@ -655,6 +655,57 @@ class Session:
         return ids
 
 
+def vocab_topk(logits, k: int):
+    """s2vt_vocab_topk: (ids int32 [R, k], logp fp32 [R, k]) -- the k largest logits per row (value descending, index
+    ascending on ties) and their log-softmax values, bit-identical to softmax_nll_fwd_bwd's lp for that target.  `logits` may be
+    a row-strided view (stride(1) == 1)."""
+    _chk_f32(logits)
+    assert logits.dim() == 2 and logits.stride(1) == 1
+    R, V = logits.shape
+    ids = torch.empty((R, k), dtype=torch.int32, device=logits.device)
+    logp = torch.empty((R, k), dtype=torch.float32, device=logits.device)
+    check(lib().s2vt_vocab_topk(_ptr(logits), logits.stride(0), R, V, int(k), _ptr(ids), _ptr(logp), _stream()), "s2vt_vocab_topk")
+    return ids, logp
+
+
+class BeamDecoder:
+    """s2vt_beam_workspace_bytes / s2vt_beam_encode / s2vt_beam_step: a handle that owns the workspace of a batched beam search over
+    up to max_B videos with up to `beam` hypotheses each.  encode once per batch, then one step() per decode step: one
+    host-to-device copy of the row lists, one device-to-host copy of the top-k words and log-probabilities."""
+
+    def __init__(self, dims: Dims, max_B: int, beam: int, device="cuda"):
+        self.dims, self.max_B, self.beam, self.device = dims, int(max_B), int(beam), torch.device(device)
+        nbytes = lib().s2vt_beam_workspace_bytes(C.byref(dims), self.max_B, self.beam)
+        if not nbytes:
+            raise ValueError(f"beam decoder: bad shape (B={max_B}, beam={beam}; 1 <= beam <= 16)")
+        self.ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        assert self.ws.data_ptr() % 256 == 0
+        self._B = 0
+
+    def encode(self, params: Params, video):
+        _chk_f32(video)
+        assert video.is_contiguous() and video.shape[0] <= self.max_B
+        self._B = video.shape[0]
+        check(lib().s2vt_beam_encode(C.byref(self.dims), C.byref(params), _ptr(video), self._B, self.beam, _ptr(self.ws), self.ws.numel(),
+                                     _stream()), "s2vt_beam_encode")
+
+    def step(self, params: Params, t: int, rows, k: int, want_logits=False):
+        """rows: int32 [3, R] host array (video of each row, parent row of step t - 1, word).  Returns numpy (ids [R, k],
+        logp [R, k]) and, with want_logits, the step's logits [R, V] on the device."""
+        import numpy as np
+        rows = np.ascontiguousarray(rows, dtype=np.int32)
+        R = rows.shape[1]
+        dev = torch.from_numpy(rows).to(self.device)                            # the one host-to-device copy
+        out = torch.empty((2, R, k), dtype=torch.int32, device=self.device)    # ids, then the bits of logp
+        logits = torch.empty((R, self.dims.n_words), dtype=torch.float32, device=self.device) if want_logits else None
+        check(lib().s2vt_beam_step(C.byref(self.dims), C.byref(params), self._B, self.beam, int(t), R, _ptr(dev[0]), _ptr(dev[1]),
+                                   _ptr(dev[2]), int(k), _ptr(out[0]), _ptr(out[1]), _ptr(logits), _ptr(self.ws), self.ws.numel(),
+                                   _stream()), "s2vt_beam_step")
+        host = out.cpu().numpy()                                                # the one device-to-host copy
+        ids, logp = host[0], host[1].view(np.float32)
+        return (ids, logp, logits) if want_logits else (ids, logp)
+
+
 def pack_weights(W_tf, in_dim: int):
     _chk_f32(W_tf)
     H = W_tf.shape[1] // 4

@@ -236,6 +236,33 @@ def greedy_eval(model, corpus: Corpus, ixtoword, scorer: "reward.CiderD | None",
     return decoded, (total / count if count else None)
 
 
+def beam_eval(model, corpus: Corpus, ixtoword, scorer: "reward.CiderD | None", batch_size: int, beam_size: int, lnf: float,
+              par: "DataParallel | None" = None):
+    """greedy_eval with beam search (final_beam_search.py:504-545): the best caption of a beam of `beam_size` for every test video,
+    batch_size videos per model.beam_search call, and their mean CIDEr-D.  Same sharding and return value as greedy_eval; a
+    caption shorter than Tc is padded with <eos> = 0 for the decoder and the scorer."""
+    vids = corpus.index.video_ids
+    if par is not None and par.world > 1:
+        vids = vids[par.rank::par.world]
+    Tc = model.n_caption_lstm_step
+    decoded, total, count = {}, 0.0, 0
+    for a in range(0, len(vids), batch_size):
+        ids = vids[a:a + batch_size]
+        res = model.beam_search(corpus.features.batch(ids), beam_size, lnf, batch_size)
+        g = np.zeros((len(ids), Tc), np.int32)
+        for i, (sent, _, _) in enumerate(res):
+            g[i, :min(len(sent), Tc)] = sent[:Tc]
+        model.check_health()
+        for v, s in zip(ids, hostglue.decode_captions(g, ixtoword)):
+            decoded[v] = s
+        if scorer is not None:
+            sc = scorer.score_ids(g, [corpus.index.row[v] for v in ids])
+            total += float(sc.sum()); count += len(sc)
+    if par is not None and par.world > 1:
+        return par.gather_dict(decoded), (par.mean(total, count) if scorer is not None else None)
+    return decoded, (total / count if count else None)
+
+
 def save_checkpoint(model, cfg: Config, epoch: int, step_name: str = "g_step", tf_version: int = 2):
     """Variables under the reference's TF names plus what its tf.train.Saver keeps beside them when it is created after
     the optimizer (reinforcement_multisampling_tf_s2vt.py:661): Adam slots, beta powers, the step counter -- a resumed
