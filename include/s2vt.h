@@ -319,6 +319,31 @@ int s2vt_bptt_bwd_live(const s2vt_dims* d, const s2vt_params* p, const s2vt_para
                        uint64_t seed, const int32_t* video_id, const int32_t* sample_id, void* workspace, size_t workspace_bytes,
                        int32_t phase, s2vt_stream stream);
 
+/* ---- opt-in bf16 mode of the backward's gradient contractions (NON-PARITY) ------------------------------
+ * s2vt_bptt_bwd_bf16 is s2vt_bptt_bwd_live with every weight-gradient and data-gradient contraction on bf16 operands (round to
+ * nearest even) with fp32 accumulation; the recurrences, dropout, the embedding scatter, the bias gradients (fp32 column sums of
+ * the fp32 operands) and the gradient buffers stay fp32, and nothing before the backward changes: ids, logits, NLL and loss are
+ * those of the fp32 mode, only the gradients differ.  Everything runs on `stream`, deterministically.  bf16_ws: a scratch of its
+ * own (256-byte aligned) of s2vt_bf16_grad_workspace_bytes(d, B, N) bytes, returned 0 on bad arguments; at BASELINE configs[2]
+ * (H 1000, E 500, |V| 12000, B 64, N 320) it is 348 MB, the bf16 copies of dlogits (2 x 154 MB) the most of it. */
+size_t s2vt_bf16_grad_workspace_bytes(const s2vt_dims* d, int32_t B, int32_t N);
+int s2vt_bptt_bwd_bf16(const s2vt_dims* d, const s2vt_params* p, const s2vt_params* grads, const float* video, int32_t B,
+                       int32_t N, const float* dlogits, int32_t caption_steps, const int32_t* live_rows, int32_t n_live, float keep,
+                       uint64_t seed, const int32_t* video_id, const int32_t* sample_id, void* workspace, size_t workspace_bytes,
+                       int32_t phase, void* bf16_ws, size_t bf16_ws_bytes, s2vt_stream stream);
+
+/* fp32 -> bf16 (RNE, NaN kept), rows optionally gathered: row r of the input is src[rowidx ? rowidx[r] : r].
+ * transpose = 0: dst[r][c] for c < Kp = C rounded up to 64 (zeros past C); ldd >= Kp, ldd % 8 == 0, dst 16-byte aligned.
+ * transpose = 1: dst[c][r] for r < Rp (zeros for R <= r < Rp; Rp a multiple of 64, ldd >= Rp, ldd % 8 == 0); optionally also
+ *   the row form into row_dst (row_ldd >= Kp, row_ldd % 4 == 0) and colsum[c] += sum_r src[row r][c] in fp32 (fixed order, no
+ *   atomics) through `scratch` (4 * ceil(Rp / 256) * C bytes). */
+int s2vt_cast_bf16(const float* src, int32_t ld, const int32_t* rowidx, int32_t R, int32_t C, int32_t transpose, uint16_t* dst, int32_t ldd,
+                   int32_t Rp, float* colsum, uint16_t* row_dst, int32_t row_ldd, void* scratch, size_t scratch_bytes, s2vt_stream stream);
+/* C[M,N] (+)= A[M,Kp] B[N,Kp]^T: bf16 operands (Kp % 64 == 0, lda / ldb >= Kp and % 8 == 0, 16-byte aligned), fp32 accumulation,
+ * no atomics.  accumulate 1: C += the product.  mfma: 16 / 32 = v_mfma_f32_16x16x32_bf16 / _32x32x16_bf16, 0 = the library's choice. */
+int s2vt_gemm_bf16_nt(const uint16_t* A, int32_t lda, const uint16_t* B, int32_t ldb, float* C, int32_t ldc, int32_t M, int32_t N,
+                      int32_t Kp, int32_t accumulate, int32_t mfma, s2vt_stream stream);
+
 /* Gradient w.r.t. the frame features, for the end-to-end scripts where they are the CNN's output
  * (e2e_tf_s2vt.py:106-121,163-166: the optimizer differentiates through `video` into Inception-ResNet-v2):
  * d_video[B, Tv, dim_image] = d_emb @ encode_image_W^T, from the d_emb the preceding s2vt_bptt_bwd (phase 0 or 2)

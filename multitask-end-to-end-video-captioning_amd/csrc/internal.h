@@ -268,6 +268,27 @@ bool attn_bwd_chain_eligible(int B, int H, int Tv);
 void attn_bwd_chain_scratch(int H, size_t* img_floats, size_t* ex_floats, size_t* row_floats, size_t* sync_bytes);
 hipError_t launch_attn_bwd_chain(const AttnBwdChainLaunch& a, hipStream_t st);
 
+// ---- the opt-in bf16 mode of the S2VT backward's gradient contractions (bwd_bf16.hip): operands cast to bf16, fp32 accumulation
+constexpr int kBf16K = 64;                            // K step of gemm_bf16_nt: a bf16 operand row holds bf16_pad(K) elements, zeros past K
+__host__ __device__ inline int bf16_pad(int k) { return (k + kBf16K - 1) / kBf16K * kBf16K; }
+// dst[r][k] = bf16(src[row(r)][k]) (row(r) = rowidx ? rowidx[r] : r) for k < K, zeros up to bf16_pad(K); dst 16-byte aligned, ldd % 8 == 0
+hipError_t launch_cast_rows_bf16(const float* src, int ld, const int32_t* rowidx, int R, int K, uint16_t* dst, int ldd, hipStream_t st);
+// dst[c][r] = bf16(src[row(r)][c]) for r < R, zeros for R <= r < Rp (Rp a multiple of 64; dst 16-byte aligned, ldd % 8 == 0).
+// rdst (optional): the row form as well, rdst[r][c] for c < bf16_pad(C) (8-byte aligned, rldd % 4 == 0).
+// colsum (optional): += the column sums of the fp32 input rows (fixed order, no atomics), through part[cast_tr_part_floats(Rp, C)].
+struct CastTrArgs {
+    const float* src; int ld; const int32_t* rowidx; int R, C;
+    uint16_t* dst; int ldd; int Rp;
+    float* colsum; float* part;
+    uint16_t* rdst; int rldd;
+};
+hipError_t launch_cast_tr_bf16(const CastTrArgs& a, hipStream_t st);
+size_t cast_tr_part_floats(int Rp, int C);
+// C[M,N] (+)= A[M,Kp] B[N,Kp]^T, bf16 operands (rows 16-byte aligned, lda / ldb % 8 == 0, Kp % 64 == 0), fp32 accumulation, no atomics.
+// mfma: 16 (v_mfma_f32_16x16x32_bf16), 32 (v_mfma_f32_32x32x16_bf16), 0 = the library's choice
+hipError_t launch_gemm_bf16_nt(const uint16_t* A, int lda, const uint16_t* B, int ldb, float* C, int ldc, int M, int N, int Kp, int accumulate,
+                               int mfma, hipStream_t st);
+
 // order-free NN contraction for the backward data path with optional split-K slabs:
 // slab s (blockIdx.y) holds the partial over its K range at C + s * slab_stride.
 struct NnBwdArgs {

@@ -199,6 +199,31 @@ size_t carve_train(Carver& c, const s2vt_dims* d, int B, int N, TrainWs* out)
     return c.off;
 }
 
+// Scratch of the bf16 mode of the backward (s2vt_bptt_bwd_bf16): bf16 copies of the operands of every gradient contraction, reused
+// in stream order -- L: the left operand of a data-gradient product in row form (dlogits, dZ2, dZ1 rows); W: the weight it multiplies;
+// BT / AT: both operands of a weight gradient transposed ([column][reduction row], the rows of two segments -- encode steps, decode
+// steps -- each padded to the K step, so that a product over the decode steps only starts at a padded column); part: column-sum partials.
+struct Bf16Ws { uint16_t *L, *W, *AT, *BT; float* part; };
+
+size_t carve_bf16(Carver& c, const s2vt_dims* d, int B, int N, Bf16Ws* out)
+{
+    const size_t H = d->lstm_dim, E = d->word_dim, V = d->n_words, D = d->dim_image, Tv = d->n_video_lstm_step, Tc = d->n_caption_lstm_step;
+    const size_t T = Tv + Tc;
+    const size_t Kv = bf16_pad((int)V), K4 = bf16_pad((int)(4 * H)), Kr = bf16_pad((int)(Tc * N));
+    const size_t ke = bf16_pad((int)(Tv * N)), Kt = ke + Kr;                                       // LSTM2: encode | decode
+    const size_t ke1 = bf16_pad((int)(Tv * B)), K1 = ke1 + bf16_pad((int)(Tc * B));                // LSTM1: encode | decode
+    auto mx = [](std::initializer_list<size_t> l) { size_t m = 0; for (size_t v : l) m = v > m ? v : m; return m; };
+    Bf16Ws w;
+    w.L = c.take<uint16_t>(mx({Tc * N * Kv, T * N * K4, Tv * B * K4}));
+    w.W = c.take<uint16_t>(mx({H * Kv, (H + E) * K4, E * K4}));
+    w.BT = c.take<uint16_t>(mx({V * Kr, 4 * H * Kt, 4 * H * K1, E * ke1}));
+    w.AT = c.take<uint16_t>(mx({H * Kr, H * Kt, E * Kr, E * ke1, H * K1, D * ke1}));
+    w.part = c.take<float>(mx({cast_tr_part_floats((int)Kr, (int)V), cast_tr_part_floats((int)(ke > Kr ? ke : Kr), (int)(4 * H)),
+                               cast_tr_part_floats((int)(K1 - ke1 > ke1 ? K1 - ke1 : ke1), (int)(4 * H)), cast_tr_part_floats((int)ke1, (int)E)}));
+    if (out) *out = w;
+    return c.off;
+}
+
 bool params_ok(const s2vt_params* p)
 {
     return p && p->Wemb && p->encode_image_W && p->encode_image_b && p->lstm1_W && p->lstm1_b && p->lstm2_W && p->lstm2_b &&
@@ -553,16 +578,19 @@ int s2vt_bptt_bwd_steps(const s2vt_dims* d, const s2vt_params* p, const s2vt_par
                               workspace_bytes, phase, stream);
 }
 
-int s2vt_bptt_bwd_live(const s2vt_dims* d, const s2vt_params* p, const s2vt_params* grads, const float* video, int32_t B,
-                       int32_t N, const float* dlogits, int32_t caption_steps, const int32_t* live_rows, int32_t n_live, float keep,
-                       uint64_t seed, const int32_t* video_id, const int32_t* sample_id, void* workspace, size_t workspace_bytes,
-                       int32_t phase, s2vt_stream stream)
+// The backward of s2vt_bptt_bwd_live; bf16 != 0: its gradient contractions on bf16 operands (s2vt_bptt_bwd_bf16), bf16_ws their scratch
+static int bptt_bwd_body(const s2vt_dims* d, const s2vt_params* p, const s2vt_params* grads, const float* video, int32_t B,
+                         int32_t N, const float* dlogits, int32_t caption_steps, const int32_t* live_rows, int32_t n_live, float keep,
+                         uint64_t seed, const int32_t* video_id, const int32_t* sample_id, void* workspace, size_t workspace_bytes,
+                         int32_t phase, int bf16, void* bf16_ws, size_t bf16_ws_bytes, s2vt_stream stream)
 {
     if ((live_rows == nullptr) != (n_live == 0) || n_live < 0) return S2VT_E_BADARG;
+    if (bf16 && !bf16_ws) return S2VT_E_BADARG;
     if (phase < 0 || phase > 4) return S2VT_E_BADARG;
     if (!dims_ok(d) || !params_ok(p) || !params_ok(grads) || !video || !dlogits || !workspace || B <= 0 || N <= 0 || N % B)
         return S2VT_E_BADARG;
     if (reinterpret_cast<uintptr_t>(workspace) & 255u) return S2VT_E_ALIGN;
+    if (bf16 && (reinterpret_cast<uintptr_t>(bf16_ws) & 255u)) return S2VT_E_ALIGN;
     if (chain_fault()) return S2VT_E_CHAIN_TIMEOUT;
     if (caption_steps < 1 || caption_steps > d->n_caption_lstm_step) return S2VT_E_BADARG;
     if (live_rows && (n_live > caption_steps * N || ((d->lstm_dim | d->word_dim) & 3))) return S2VT_E_BADARG;
@@ -575,15 +603,33 @@ int s2vt_bptt_bwd_live(const s2vt_dims* d, const s2vt_params* p, const s2vt_para
     TrainWs w;
     carve_train(c, d, B, N, &w);
     if (!c.ok()) return S2VT_E_WORKSPACE;
+    Bf16Ws bw{};
+    if (bf16) {
+        Carver cb(bf16_ws, bf16_ws_bytes);
+        carve_bf16(cb, d, B, N, &bw);
+        if (!cb.ok()) return S2VT_E_WORKSPACE;
+    }
     hipStream_t st = S(stream);
     const size_t NH = (size_t)N * H;
+    // bf16 mode: each operand of a gradient contraction is cast once (a shared one serves every product that reads it), then
+    // gemm_bf16_nt; the recurrences, dropout reductions and the embedding scatter stay as they are.  Everything on the caller's stream.
+    const int K4 = bf16_pad(4 * H);
+    auto tr = [&](const float* src, int ld, const int32_t* idx, int R, int C, uint16_t* dst, int ldd, float* colsum = nullptr,
+                  uint16_t* rdst = nullptr, int rldd = 0) -> hipError_t {
+        CastTrArgs a{src, ld, idx, R, C, dst, ldd, bf16_pad(R), colsum, bw.part, rdst, rldd};
+        return launch_cast_tr_bf16(a, st);
+    };
+    auto mm = [&](const uint16_t* A, int lda, const uint16_t* Bm, int ldb, float* Cm, int ldc, int M, int Nn, int Kp, int acc) -> hipError_t {
+        return launch_gemm_bf16_nt(A, lda, Bm, ldb, Cm, ldc, M, Nn, Kp, acc, 0, st);
+    };
 
     // Phases, for data-parallel callers that start a slice's all-reduce as soon as its gradients are final:
     //   1 = the vocab projection (embed_word_W / _b final);  3 = LSTM2's recurrence + its weight gradients (lstm2_W / _b
     //   final);  4 = everything after (dX2, LSTM1, Wemb, frame embedding);  2 = 3 + 4;  0 = all.
     const bool do_vocab = phase == 0 || phase == 1, do_l2 = phase == 0 || phase == 2 || phase == 3,
                do_rest = phase == 0 || phase == 2 || phase == 4;
-    SideStream& ss = side_stream();
+    SideStream one_stream;                                   // (ok = false: the bf16 mode keeps to the caller's stream)
+    SideStream& ss = bf16 ? one_stream : side_stream();
     // gated overlap (mode 2): only beside recurrences that run as ONE-part persistent grids (<= 256 rows: room for a second wave per SIMD)
     const bool gate2 = ss.ok && ss.mode == 2 && phase == 0 && N <= 256 && bwd_chain_auto(N, H) && !(reinterpret_cast<uintptr_t>(p->lstm2_W) & 15);
     // (LSTM1's recurrence is gated only where LSTM2's is: at N > 256 rows -- the REINFORCE step's 320 -- LSTM2's three contractions are 0.6 ms
@@ -607,12 +653,21 @@ int s2vt_bptt_bwd_live(const s2vt_dims* d, const s2vt_params* p, const s2vt_para
         // [n_live, V], row r belonging to row live_rows[r] of the unroll; the masked rows' dlogits are exact zeros in the full
         // form, so leaving them out of the reductions changes nothing and their dO2 rows are the zeros written below)
         const int R = live_rows ? n_live : Tc * N;
+        float* const dO2t = live_rows ? w.dO2p : w.dO2;     // where the product lands: packed rows are scattered afterwards
+        if (bf16) {
+            // dlogits once, in both forms: transposed (dWout's B, + the bias gradient) and by rows (dO2's A)
+            const int Kr = bf16_pad(R), Kv = bf16_pad(V);
+            HIP_TRY(tr(dlogits, V, nullptr, R, V, bw.BT, Kr, grads->embed_word_b, bw.L, Kv));
+            HIP_TRY(tr(w.O2 + (size_t)Tv * NH, H, live_rows, R, H, bw.AT, Kr));
+            HIP_TRY(mm(bw.AT, Kr, bw.BT, Kr, grads->embed_word_W, V, H, V, Kr, 1));
+            HIP_TRY(launch_cast_rows_bf16(p->embed_word_W, V, nullptr, H, V, bw.W, Kv, st));
+            HIP_TRY(mm(bw.L, Kv, bw.W, Kv, dO2t, H, R, H, Kv, 0));
+        } else {
         TnArgs a{w.O2 + (size_t)Tv * NH, live_rows, H, dlogits, V, grads->embed_word_W, V, R, H, V, 1};
         a.gather_rows = live_rows ? Tc * N : 0;
         a.colsum = grads->embed_word_b;                     // the bias gradient rides in the same pass over dlogits
         if (gate2 && do_l2) { dwout = a; dwout_deferred = true; }
         else HIP_TRY(launch_gemm_tn(a, sv));
-        float* const dO2t = live_rows ? w.dO2p : w.dO2;     // where the product lands: packed rows are scattered afterwards
         int s2 = w.dO2s ? do2_splits(R, H, V) : 1;
         if ((size_t)s2 * R > w.dO2s_rows) s2 = 1;            // (a live-row count between two step counts the carve did not see)
         if (s2 > 1) {
@@ -622,6 +677,7 @@ int s2vt_bptt_bwd_live(const s2vt_dims* d, const s2vt_params* p, const s2vt_para
             HIP_TRY(launch_sum_slabs(dO2t, w.dO2s, (V + kper - 1) / kper, stride, stride, st));
         } else {
             HIP_TRY(nn_bwd(dlogits, V, p->embed_word_W, V, dO2t, H, R, H, V, 1, 0, st));
+        }
         }
         if (live_rows) {
             ZeroList z;
@@ -662,7 +718,22 @@ int s2vt_bptt_bwd_live(const s2vt_dims* d, const s2vt_params* p, const s2vt_para
     // only -- launched from the lambda below once that grid is resident; dX2 keeps the chip to itself)
     if (sd != st) HIP_TRY(fork_to(st, sd, ss.ev[1]));
     auto l2_weight_grads = [&]() -> int {
-    if (!live_rows) {
+    if (bf16) {
+        // dZ2 once: transposed over [encode steps | decode steps (live: the packed live rows)] -- the B operand of all three products,
+        // + lstm2_b -- and by rows (dX2's A, phase 4); out1 / h2 take the same two segments, the embedding rows the decode segment only
+        const int Re = Tv * N, Rd = live_rows ? n_live : Tc * N, ke = bf16_pad(Re), Kd = bf16_pad(Rd), Kt = ke + Kd;
+        const float* const dzd = live_rows ? w.dZ2p : w.dZ2 + (size_t)Tv * 4 * NH;
+        HIP_TRY(tr(w.dZ2, 4 * H, nullptr, Re, 4 * H, bw.BT, Kt, grads->lstm2_b, bw.L, K4));
+        HIP_TRY(tr(dzd, 4 * H, nullptr, Rd, 4 * H, bw.BT + ke, Kt, grads->lstm2_b, bw.L + (size_t)Re * K4, K4));
+        HIP_TRY(tr(w.O1, H, nullptr, Re, H, bw.AT, Kt));
+        HIP_TRY(tr(w.O1 + (size_t)Tv * NH, H, live_rows, Rd, H, bw.AT + ke, Kt));
+        HIP_TRY(mm(bw.AT, Kt, bw.BT, Kt, grads->lstm2_W, 4 * H, H, 4 * H, Kt, 1));
+        HIP_TRY(tr(p->Wemb, E, live_rows ? w.prevp : w.prev, Rd, E, bw.AT, Kd));                    // Wemb [V, E] rows of the previous words
+        HIP_TRY(mm(bw.AT, Kd, bw.BT + ke, Kt, grads->lstm2_W + (size_t)H * 4 * H, 4 * H, E, 4 * H, Kd, 1));
+        HIP_TRY(tr(w.H2, H, nullptr, Re, H, bw.AT, Kt));
+        HIP_TRY(tr(w.H2 + (size_t)Tv * NH, H, live_rows, Rd, H, bw.AT + ke, Kt));
+        HIP_TRY(mm(bw.AT, Kt, bw.BT, Kt, grads->lstm2_W + (size_t)(H + E) * 4 * H, 4 * H, H, 4 * H, Kt, 1));
+    } else if (!live_rows) {
         TnArgs a{w.O1, nullptr, H, w.dZ2, 4 * H, grads->lstm2_W, 4 * H, T * N, H, 4 * H, 1};
         HIP_TRY(launch_gemm_tn(a, sd));
         TnArgs b{p->Wemb, w.prev, E, w.dZ2 + (size_t)Tv * 4 * NH, 4 * H, grads->lstm2_W + (size_t)H * 4 * H, 4 * H, Tc * N, E,
@@ -702,7 +773,25 @@ int s2vt_bptt_bwd_live(const s2vt_dims* d, const s2vt_params* p, const s2vt_para
     if (!do_rest) return S2VT_OK;
     // d[out1 ; embed] for every step at once -- with live rows: the encode steps, then the live decode rows (from the packed dZ2
     // of the LSTM2 phase), scattered into the zeroed decode part
-    if (!live_rows) {
+    if (bf16) {
+        const int Re = Tv * N, Rd = live_rows ? n_live : Tc * N;
+        if (!do_l2) {                                        // (phase 4 alone: the row form phase 3 made in its fused cast, again)
+            HIP_TRY(launch_cast_rows_bf16(w.dZ2, 4 * H, nullptr, Re, 4 * H, bw.L, K4, st));
+            HIP_TRY(launch_cast_rows_bf16(live_rows ? w.dZ2p : w.dZ2 + (size_t)Tv * 4 * NH, 4 * H, nullptr, Rd, 4 * H, bw.L + (size_t)Re * K4, K4, st));
+        }
+        HIP_TRY(launch_cast_rows_bf16(p->lstm2_W, 4 * H, nullptr, H + E, 4 * H, bw.W, K4, st));
+        if (!live_rows) {
+            HIP_TRY(mm(bw.L, K4, bw.W, K4, w.dX2, H + E, T * N, H + E, K4, 0));
+        } else {
+            HIP_TRY(mm(bw.L, K4, bw.W, K4, w.dX2, H + E, Re, H + E, K4, 0));
+            HIP_TRY(mm(bw.L + (size_t)Re * K4, K4, bw.W, K4, w.dX2p, H + E, Rd, H + E, K4, 0));
+            float* const dec = w.dX2 + (size_t)Tv * N * (H + E);
+            ZeroList z;
+            z.add(dec, (size_t)Tc * N * (H + E) * 4);
+            HIP_TRY(launch_zero_regions(z, st));
+            HIP_TRY(launch_scatter_rows(w.dX2p, H + E, live_rows, n_live, H + E, dec, H + E, st));
+        }
+    } else if (!live_rows) {
         HIP_TRY(nn_bwd_slabs(w.dZ2, 4 * H, p->lstm2_W, 4 * H, w.dX2, H + E, T * N, H + E, 4 * H, w.dXs, st, w.dXs_floats));
     } else {
         HIP_TRY(nn_bwd_slabs(w.dZ2, 4 * H, p->lstm2_W, 4 * H, w.dX2, H + E, Tv * N, H + E, 4 * H, w.dXs, st, w.dXs_floats));
@@ -728,6 +817,25 @@ int s2vt_bptt_bwd_live(const s2vt_dims* d, const s2vt_params* p, const s2vt_para
             if (rc != S2VT_OK) return rc;
         }
     }
+    if (bf16) {
+        // dZ1 once: transposed over [encode steps | decode steps] (+ lstm1_b), and the encode rows by rows (dX1's A)
+        const int Re = Tv * B, Rd = Tc * B, ke = bf16_pad(Re), K1 = ke + bf16_pad(Rd);
+        HIP_TRY(tr(w.dZ1, 4 * H, nullptr, Re, 4 * H, bw.BT, K1, grads->lstm1_b, bw.L, K4));
+        HIP_TRY(tr(w.dZ1 + (size_t)Re * 4 * H, 4 * H, nullptr, Rd, 4 * H, bw.BT + ke, K1, grads->lstm1_b));
+        HIP_TRY(launch_cast_rows_bf16(p->lstm1_W, 4 * H, nullptr, E, 4 * H, bw.W, K4, st));
+        HIP_TRY(mm(bw.L, K4, bw.W, K4, w.dX1, E, Re, E, K4, 0));
+        HIP_TRY(tr(w.emb, E, w.encidx, Re, E, bw.AT, ke));                                          // the frame embedding, time-major
+        HIP_TRY(mm(bw.AT, ke, bw.BT, K1, grads->lstm1_W, 4 * H, E, 4 * H, ke, 1));
+        HIP_TRY(tr(w.H1, H, nullptr, Re, H, bw.AT, K1));
+        HIP_TRY(tr(w.H1 + (size_t)Re * H, H, nullptr, Rd, H, bw.AT + ke, K1));
+        HIP_TRY(mm(bw.AT, K1, bw.BT, K1, grads->lstm1_W + (size_t)E * 4 * H, 4 * H, H, 4 * H, K1, 1));
+        if (live_rows) HIP_TRY(launch_scatter_add_rows(w.dX2p + H, H + E, w.prevp, n_live, E, grads->Wemb, E, st));
+        else HIP_TRY(launch_scatter_add_rows(w.dX2 + (size_t)Tv * N * (H + E) + H, H + E, w.prev, Tc * N, E, grads->Wemb, E, st));
+        HIP_TRY(tr(video, D, w.encidx, Re, D, bw.AT, ke));
+        HIP_TRY(tr(w.dX1, E, nullptr, Re, E, bw.BT, ke, grads->encode_image_b));
+        HIP_TRY(mm(bw.AT, ke, bw.BT, ke, grads->encode_image_W, E, D, E, ke, 1));
+        return S2VT_OK;
+    }
     HIP_TRY(nn_bwd_slabs(w.dZ1, 4 * H, p->lstm1_W, 4 * H, w.dX1, E, Tv * B, E, 4 * H, w.dXs, st, w.dXs_floats));
 
     // ---- remaining weight gradients: one contraction over all unrolled steps per weight block
@@ -748,6 +856,60 @@ int s2vt_bptt_bwd_live(const s2vt_dims* d, const s2vt_params* p, const s2vt_para
         HIP_TRY(launch_gemm_tn(h, st));
     }
     if (sd != st) HIP_TRY(fork_to(sd, st, ss.ev[2]));        // join: the caller's stream waits for the side stream's gradients
+    return S2VT_OK;
+}
+
+int s2vt_bptt_bwd_live(const s2vt_dims* d, const s2vt_params* p, const s2vt_params* grads, const float* video, int32_t B,
+                       int32_t N, const float* dlogits, int32_t caption_steps, const int32_t* live_rows, int32_t n_live, float keep,
+                       uint64_t seed, const int32_t* video_id, const int32_t* sample_id, void* workspace, size_t workspace_bytes,
+                       int32_t phase, s2vt_stream stream)
+{
+    return bptt_bwd_body(d, p, grads, video, B, N, dlogits, caption_steps, live_rows, n_live, keep, seed, video_id, sample_id, workspace,
+                         workspace_bytes, phase, 0, nullptr, 0, stream);
+}
+
+size_t s2vt_bf16_grad_workspace_bytes(const s2vt_dims* d, int32_t B, int32_t N)
+{
+    if (!dims_ok(d) || B <= 0 || N <= 0 || N % B) return 0;
+    Carver c(nullptr, 0);
+    return carve_bf16(c, d, B, N, nullptr);
+}
+
+int s2vt_bptt_bwd_bf16(const s2vt_dims* d, const s2vt_params* p, const s2vt_params* grads, const float* video, int32_t B,
+                       int32_t N, const float* dlogits, int32_t caption_steps, const int32_t* live_rows, int32_t n_live, float keep,
+                       uint64_t seed, const int32_t* video_id, const int32_t* sample_id, void* workspace, size_t workspace_bytes,
+                       int32_t phase, void* bf16_ws, size_t bf16_ws_bytes, s2vt_stream stream)
+{
+    return bptt_bwd_body(d, p, grads, video, B, N, dlogits, caption_steps, live_rows, n_live, keep, seed, video_id, sample_id, workspace,
+                         workspace_bytes, phase, 1, bf16_ws, bf16_ws_bytes, stream);
+}
+
+int s2vt_cast_bf16(const float* src, int32_t ld, const int32_t* rowidx, int32_t R, int32_t C, int32_t transpose, uint16_t* dst, int32_t ldd,
+                   int32_t Rp, float* colsum, uint16_t* row_dst, int32_t row_ldd, void* scratch, size_t scratch_bytes, s2vt_stream stream)
+{
+    if (!src || !dst || R < 0 || C <= 0 || ld < C || transpose < 0 || transpose > 1) return S2VT_E_BADARG;
+    if (reinterpret_cast<uintptr_t>(dst) & 15) return S2VT_E_ALIGN;
+    if (!transpose) {
+        if (colsum || row_dst || ldd < bf16_pad(C) || (ldd & 7)) return S2VT_E_BADARG;
+        HIP_TRY(launch_cast_rows_bf16(src, ld, rowidx, R, C, dst, ldd, S(stream)));
+        return S2VT_OK;
+    }
+    if (Rp < R || Rp % kBf16K || ldd < Rp || (ldd & 7)) return S2VT_E_BADARG;
+    if (row_dst && (row_ldd < bf16_pad(C) || (row_ldd & 3))) return S2VT_E_BADARG;
+    if (row_dst && (reinterpret_cast<uintptr_t>(row_dst) & 7)) return S2VT_E_ALIGN;
+    if (colsum && (!scratch || scratch_bytes < cast_tr_part_floats(Rp, C) * 4)) return S2VT_E_WORKSPACE;
+    CastTrArgs a{src, ld, rowidx, R, C, dst, ldd, Rp, colsum, static_cast<float*>(scratch), row_dst, row_ldd};
+    HIP_TRY(launch_cast_tr_bf16(a, S(stream)));
+    return S2VT_OK;
+}
+
+int s2vt_gemm_bf16_nt(const uint16_t* A, int32_t lda, const uint16_t* Bm, int32_t ldb, float* C, int32_t ldc, int32_t M, int32_t N, int32_t Kp,
+                      int32_t accumulate, int32_t mfma, s2vt_stream stream)
+{
+    if (!A || !Bm || !C || M < 0 || N < 0 || Kp < 0 || Kp % kBf16K || lda < Kp || ldb < Kp || ldc < N || (lda & 7) || (ldb & 7)) return S2VT_E_BADARG;
+    if (accumulate < 0 || accumulate > 1 || (mfma != 0 && mfma != 16 && mfma != 32)) return S2VT_E_BADARG;
+    if ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(Bm)) & 15) return S2VT_E_ALIGN;
+    HIP_TRY(launch_gemm_bf16_nt(A, lda, Bm, ldb, C, ldc, M, N, Kp, accumulate, mfma, S(stream)));
     return S2VT_OK;
 }
 

@@ -266,6 +266,20 @@ class StepStats:
     mask_sum: torch.Tensor
 
 
+def grad_precision_from_env() -> str:
+    """The default of Video_Caption_Generator.grad_precision: S2VT_GRAD_PRECISION, unset = "fp32"; any value but "fp32" / "bf16"
+    raises ValueError."""
+    import os
+    v = os.environ.get("S2VT_GRAD_PRECISION")
+    return "fp32" if v is None else _check_grad_precision(v, "S2VT_GRAD_PRECISION")
+
+
+def _check_grad_precision(v, what="grad_precision") -> str:
+    if v not in ops.GRAD_PRECISIONS:
+        raise ValueError(f"{what} must be one of {ops.GRAD_PRECISIONS}, got {v!r}")
+    return v
+
+
 class Video_Caption_Generator:
     """Same constructor as the reference, positional order included: the twelve arguments of tf_s2vt.py:54-66, then
     `width, height, channels, feature_dim, label_dim, alpha` of the multitask / end-to-end classes
@@ -308,11 +322,22 @@ class Video_Caption_Generator:
         import os
         self.dp_overlap = os.environ.get("S2VT_DP_OVERLAP", "0") == "1"
         self._debug_checks = os.environ.get("S2VT_DEBUG_CHECKS", "0") == "1"
+        # "bf16": backward() runs its gradient contractions on bf16 operands with fp32 accumulation (ops.bptt_bwd(precision="bf16");
+        # non-parity, DESIGN.md §3: ids, logits, NLL and loss are unchanged, the gradients differ by a bounded amount)
+        self.grad_precision = grad_precision_from_env()
         self._applied = torch.zeros(1, dtype=torch.int32, device=self.device)   # step number of the last Adam update the device APPLIED
         self._row_id_cache = {}
         self._sumsq = torch.zeros(1, dtype=torch.float32, device=self.device)
         self._gscale = torch.ones(1, dtype=torch.float32, device=self.device)
         self._ascale = torch.ones(1, dtype=torch.float32, device=self.device)
+
+    @property
+    def grad_precision(self) -> str:
+        return self._grad_precision
+
+    @grad_precision.setter
+    def grad_precision(self, v):
+        self._grad_precision = _check_grad_precision(v)
 
     # -------------------------------------------------------------------------------- utilities
     def _dev(self, a, dtype):
@@ -605,21 +630,22 @@ class Video_Caption_Generator:
             def span(first, last):
                 return st.offsets[first], st.offsets[last] + (int(np.prod(st.shapes[last])) + 63) // 64 * 64
             args = (self.dims, st.params, st.grads, video, N, dlogits, ws, keep, seed, vid, sid)
-            ops.bptt_bwd(*args, phase=1, steps=steps, live=live)
+            ops.bptt_bwd(*args, phase=1, steps=steps, live=live, precision=self.grad_precision)
             lo1, hi1 = span("embed_word_W", "embed_word_b")
             self._pending.append(dp.allreduce_async(st.grad[lo1:hi1]))
             # From here RCCL's kernels run on the communicator's stream beside ours.  A persistent recurrence needs ~every CU
             # co-resident (csrc/chain.hip) and must not be started into a chip that is partly taken: while a slice is in
             # flight the two backward recurrences take their per-step form (same bits; ops.chain_hold).
             with ops.chain_hold():
-                ops.bptt_bwd(*args, phase=3, steps=steps, live=live)
+                ops.bptt_bwd(*args, phase=3, steps=steps, live=live, precision=self.grad_precision)
                 lo2, hi2 = span("lstm2_W", "lstm2_W")
                 assert hi2 == lo1, "bucket layout: lstm2_W sits right below embed_word_W"
                 self._pending.append(dp.allreduce_async(st.grad[lo2:hi2]))
                 self._early = (lo2, hi1)                       # [lo2, hi1) is already on its way
-                ops.bptt_bwd(*args, phase=4, steps=steps, live=live)
+                ops.bptt_bwd(*args, phase=4, steps=steps, live=live, precision=self.grad_precision)
         else:
-            ops.bptt_bwd(self.dims, st.params, st.grads, video, N, dlogits, ws, keep, seed, vid, sid, steps=steps, live=live)
+            ops.bptt_bwd(self.dims, st.params, st.grads, video, N, dlogits, ws, keep, seed, vid, sid, steps=steps, live=live,
+                         precision=self.grad_precision)
 
     def video_grad(self):
         """d(loss * sum(mask)) / d(video) [B, Tv, dim_image] of the pass backward() just ran -- the gradient the

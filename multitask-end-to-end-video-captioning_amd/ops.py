@@ -321,17 +321,82 @@ def softmax_unshifted_argmax(logits, want_probs=False):
     return ids, probs
 
 
+GRAD_PRECISIONS = ("fp32", "bf16")
+
+
+def bf16_grad_workspace(dims: Dims, B: int, N: int, device):
+    """The scratch of the bf16 backward (s2vt_bf16_grad_workspace_bytes), cached beside the train workspace."""
+    nbytes = lib().s2vt_bf16_grad_workspace_bytes(C.byref(dims), B, N)
+    assert nbytes > 0, "bad dims / B / N (N must be a multiple of B)"
+    return workspace(nbytes, device, "bf16_grad")
+
+
 def bptt_bwd(dims: Dims, params: Params, grads: Params, video, N: int, dlogits, ws, keep=1.0, seed=0, video_id=None,
-             sample_id=None, phase=0, steps=None, live=None):
+             sample_id=None, phase=0, steps=None, live=None, precision="fp32"):
     """phase 0 = the whole backward; 1 = vocab projection only; 2 = the rest (data-parallel overlap).
-    steps: what the forward call (teacher_forced_fwd) was given."""
+    steps: what the forward call (teacher_forced_fwd) was given.
+    precision "bf16": the gradient contractions on bf16 operands with fp32 accumulation (s2vt_bptt_bwd_bf16, non-parity:
+    only the gradients change)."""
     _chk_f32(video, dlogits)
+    if precision not in GRAD_PRECISIONS:
+        raise ValueError(f"precision must be one of {GRAD_PRECISIONS}, got {precision!r}")
     steps = dims.n_caption_lstm_step if steps is None else int(steps)
     assert dlogits.shape[0] == (steps * N if live is None else live.numel())
+    if precision == "bf16":
+        bws = bf16_grad_workspace(dims, video.shape[0], N, video.device)
+        check(lib().s2vt_bptt_bwd_bf16(C.byref(dims), C.byref(params), C.byref(grads), _ptr(video), video.shape[0], N, _ptr(dlogits),
+                                       steps, _ptr(live), 0 if live is None else live.numel(), float(keep), seed, _ptr(video_id),
+                                       _ptr(sample_id), _ptr(ws), ws.numel(), phase, _ptr(bws), bws.numel(), _stream()),
+              "s2vt_bptt_bwd_bf16")
+        return
     check(lib().s2vt_bptt_bwd_live(C.byref(dims), C.byref(params), C.byref(grads), _ptr(video), video.shape[0], N, _ptr(dlogits),
                                    steps, _ptr(live), 0 if live is None else live.numel(), float(keep), seed, _ptr(video_id),
                                    _ptr(sample_id), _ptr(ws), ws.numel(), phase, _stream()),
           "s2vt_bptt_bwd")
+
+
+def cast_bf16(src, rowidx=None, transpose=False, pad_rows=None, colsum=None, row_copy=False):
+    """s2vt_cast_bf16 on an fp32 [R, C] tensor (rows optionally gathered through the int32 `rowidx`, R = len(rowidx)).
+    transpose False: bf16 [R, Kp] (Kp = C rounded up to 64, zeros past C).  True: bf16 [C, Rp] (Rp = pad_rows, default R rounded
+    up to 64, zeros past R), plus (row_copy) the row form, and colsum[c] += the fp32 column sums of the rows.  Returns the bf16
+    tensor, or (transposed, rows) with row_copy."""
+    _chk_f32(src, colsum)
+    assert src.dim() == 2 and src.stride(1) == 1
+    if rowidx is not None:
+        assert rowidx.is_cuda and rowidx.dtype == torch.int32 and rowidx.is_contiguous()
+    R = src.shape[0] if rowidx is None else rowidx.numel()
+    Cc = src.shape[1]
+    Kp = (Cc + 63) // 64 * 64
+    dev = src.device
+    if not transpose:
+        out = torch.empty((R, Kp), dtype=torch.bfloat16, device=dev)
+        check(lib().s2vt_cast_bf16(_ptr(src), src.stride(0), _ptr(rowidx), R, Cc, 0, _ptr(out), Kp, 0, None, None, 0, None, 0, _stream()),
+              "s2vt_cast_bf16")
+        return out
+    Rp = (R + 63) // 64 * 64 if pad_rows is None else int(pad_rows)
+    out = torch.empty((Cc, Rp), dtype=torch.bfloat16, device=dev)
+    rows = torch.empty((R, Kp), dtype=torch.bfloat16, device=dev) if row_copy else None
+    scratch = workspace(4 * ((Rp + 255) // 256) * Cc, dev, "cast_bf16") if colsum is not None else None
+    check(lib().s2vt_cast_bf16(_ptr(src), src.stride(0), _ptr(rowidx), R, Cc, 1, _ptr(out), Rp, Rp, _ptr(colsum), _ptr(rows), Kp,
+                               _ptr(scratch), 0 if scratch is None else scratch.numel(), _stream()), "s2vt_cast_bf16")
+    return (out, rows) if row_copy else out
+
+
+def gemm_bf16_nt(A, B, out=None, accumulate=False, mfma=0, n=None):
+    """C[M, N] (+)= A[M, Kp] B[N, Kp]^T on bf16 operands (Kp % 64 == 0), fp32 accumulation (s2vt_gemm_bf16_nt).  `out` may be a
+    row-strided fp32 view; n: columns of C when B has more rows than are wanted."""
+    assert A.is_cuda and B.is_cuda and A.dtype == torch.bfloat16 and B.dtype == torch.bfloat16
+    assert A.stride(1) == 1 and B.stride(1) == 1 and A.shape[1] == B.shape[1]
+    M, Kp = A.shape
+    N = B.shape[0] if n is None else int(n)
+    if out is None:
+        assert not accumulate
+        out = torch.empty((M, N), dtype=torch.float32, device=A.device)
+    _chk_f32(out)
+    assert out.shape[0] == M and out.shape[1] == N and out.stride(1) == 1
+    check(lib().s2vt_gemm_bf16_nt(_ptr(A), A.stride(0), _ptr(B), B.stride(0), _ptr(out), out.stride(0), M, N, Kp, int(bool(accumulate)),
+                                  int(mfma), _stream()), "s2vt_gemm_bf16_nt")
+    return out
 
 
 def bptt_dvideo(dims: Dims, params: Params, B: int, N: int, ws):

@@ -50,7 +50,7 @@ def multilabel_eval(model, corpus, labels, batch_size, threshold=0.5):
 
 
 def train(cfg: Config, train_corpus: Corpus, test_corpus: Corpus | None = None, model=None, restore=None, log=print, resume=None,
-          attr_vocabulary=None):
+          attr_vocabulary=None, grad_precision=None):
     """attr_vocabulary (list of attribute words; None = the plain REINFORCE script): the multitask scripts on precomputed features
     (BASELINE configs[3]).  Labels = bag of words over all ground-truth captions of a video (get_multilabel, reinforce_multitask_e2e_attribute_loss.py
     :874-893), the model gets the attribute head (label_dim = len(attr_vocabulary), alpha = cfg.alpha) and the objective becomes
@@ -76,6 +76,8 @@ def train(cfg: Config, train_corpus: Corpus, test_corpus: Corpus | None = None, 
                                           cfg.n_video_lstm_step + cfg.n_caption_lstm_step, cfg.n_video_lstm_step,
                                           cfg.n_caption_lstm_step, bias_init_vector=None, seed=cfg.seed, multisample=K, device=par.device,
                                           label_dim=len(attr_vocabulary) if multitask else 0, alpha=cfg.alpha if multitask else 0.0)
+    if grad_precision is not None:
+        model.grad_precision = grad_precision          # (None: the model's default, S2VT_GRAD_PRECISION)
     par.attach(model)
     labels = test_labels = None
     if multitask:
@@ -187,13 +189,15 @@ def main():
     ap.add_argument("--stop-at-eos", action="store_true", help="samples leave the decode loop at their first <eos> (same update, shorter sampler loop)")
     ap.add_argument("--attr-vocab", help="multitask scripts: file with one attribute word per line (label_dim = its length)")
     ap.add_argument("--alpha", type=float, default=0.05); ap.add_argument("--lambda-loss", type=float, default=0.0)
+    ap.add_argument("--grad-precision", choices=("fp32", "bf16"), help="the backward's gradient contractions on bf16 operands (non-parity "
+                    "fast mode, DESIGN.md §3); default: S2VT_GRAD_PRECISION, else fp32")
     a = ap.parse_args()
     cfg = rl_config(n_epochs=a.epochs, batch_size=a.batch_size, multisample=a.samples, model_path=a.model_path, stop_at_eos=a.stop_at_eos,
                     alpha=a.alpha, lambda_loss=a.lambda_loss)
     tr = Corpus(a.train_sents, a.train_feats, vocabulary_file=a.vocab)
     te = Corpus(a.test_sents, a.test_feats, vocabulary=tr.vocabulary) if a.test_sents and a.test_feats else None
     attr = [l.strip() for l in open(a.attr_vocab)] if a.attr_vocab else None
-    train(cfg, tr, te, restore=a.restore, resume=a.resume, attr_vocabulary=attr)
+    train(cfg, tr, te, restore=a.restore, resume=a.resume, attr_vocabulary=attr, grad_precision=a.grad_precision)
 
 
 if __name__ == "__main__":

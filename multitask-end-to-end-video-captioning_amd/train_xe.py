@@ -19,7 +19,8 @@ from .train_common import (Config, Corpus, DataParallel, StepLog, epoch_batches,
                            run_step, save_checkpoint, save_checkpoint_checked)
 
 
-def train(cfg: Config, train_corpus: Corpus, test_corpus: Corpus | None = None, model=None, log=print, resume=None):
+def train(cfg: Config, train_corpus: Corpus, test_corpus: Corpus | None = None, model=None, log=print, resume=None,
+          grad_precision=None):
     """cfg.batch_size is the GLOBAL batch; data parallel as in train_rl.train (shards of each shuffled batch, Q1's per-step
     mask sums and the gradient bucket all-reduced inside xe_update, rank 0 logs and saves)."""
     from . import model as M
@@ -32,6 +33,8 @@ def train(cfg: Config, train_corpus: Corpus, test_corpus: Corpus | None = None, 
         model = M.Video_Caption_Generator(cfg.dim_image, len(wordtoix), cfg.word_dim, cfg.lstm_dim, B,
                                           cfg.n_video_lstm_step + cfg.n_caption_lstm_step, cfg.n_video_lstm_step,
                                           cfg.n_caption_lstm_step, bias_init_vector=None, seed=cfg.seed, device=par.device)
+    if grad_precision is not None:
+        model.grad_precision = grad_precision          # (None: the model's default, S2VT_GRAD_PRECISION)
     par.attach(model)
     if resume:
         log(f"resumed: {optimistic_restore(model, resume)} at step {model.global_step}")
@@ -98,11 +101,13 @@ def main():
     ap.add_argument("--vocab", required=True); ap.add_argument("--resume")
     ap.add_argument("--epochs", type=int, default=30); ap.add_argument("--batch-size", type=int, default=64)
     ap.add_argument("--model-path", default="./new_s2vt_models")
+    ap.add_argument("--grad-precision", choices=("fp32", "bf16"), help="the backward's gradient contractions on bf16 operands (non-parity "
+                    "fast mode, DESIGN.md §3); default: S2VT_GRAD_PRECISION, else fp32")
     a = ap.parse_args()
     cfg = Config(n_epochs=a.epochs, batch_size=a.batch_size, model_path=a.model_path, model_name=f"batch_size{a.batch_size}_s2vt_model")
     tr = Corpus(a.train_sents, a.train_feats, vocabulary_file=a.vocab)
     te = Corpus(a.test_sents, a.test_feats, vocabulary=tr.vocabulary) if a.test_sents and a.test_feats else None
-    train(cfg, tr, te, resume=a.resume)
+    train(cfg, tr, te, resume=a.resume, grad_precision=a.grad_precision)
 
 
 if __name__ == "__main__":
