@@ -344,6 +344,32 @@ int s2vt_cast_bf16(const float* src, int32_t ld, const int32_t* rowidx, int32_t 
 int s2vt_gemm_bf16_nt(const uint16_t* A, int32_t lda, const uint16_t* B, int32_t ldb, float* C, int32_t ldc, int32_t M, int32_t N,
                       int32_t Kp, int32_t accumulate, int32_t mfma, s2vt_stream stream);
 
+/* ---- split-bf16 products of the backward's gradient contractions (the default fp32 mode's arithmetic) ----------
+ * s2vt_bptt_bwd_split is s2vt_bptt_bwd_live with each gradient contraction A.B^T computed from split operands -- hi = bf16(x),
+ * lo = bf16(x - hi), both round to nearest even -- as Ahi.Bhi^T + Ahi.Blo^T + Alo.Bhi^T on bf16 MFMA with fp32 accumulation (about
+ * 3 x 2^-18 of |x.y| per product); the recurrences, dropout, the embedding scatter, the bias gradients (fp32 column sums), clip and
+ * Adam stay fp32, and ids, logits, NLL and loss are those of s2vt_bptt_bwd_live.  At N <= 256 rows it runs s2vt_bptt_bwd_live's
+ * fp32 body (the gated side-stream overlap); so does every shape when the environment sets S2VT_SPLIT_GRADS=0 (read once) -- then
+ * bit-identical to s2vt_bptt_bwd_live.  Deterministic, no atomics.  split_ws: a scratch of its own (256-byte aligned) of
+ * s2vt_split_grad_workspace_bytes(d, B, N) bytes (0 on bad arguments): about twice the bf16 mode's -- 0.7 GB at BASELINE
+ * configs[2], several GB at the reference defaults (B 256, K 8, 35 caption steps). */
+size_t s2vt_split_grad_workspace_bytes(const s2vt_dims* d, int32_t B, int32_t N);
+int s2vt_bptt_bwd_split(const s2vt_dims* d, const s2vt_params* p, const s2vt_params* grads, const float* video, int32_t B,
+                        int32_t N, const float* dlogits, int32_t caption_steps, const int32_t* live_rows, int32_t n_live, float keep,
+                        uint64_t seed, const int32_t* video_id, const int32_t* sample_id, void* workspace, size_t workspace_bytes,
+                        int32_t phase, void* split_ws, size_t split_ws_bytes, s2vt_stream stream);
+/* s2vt_cast_bf16 in split form: dst (row_dst) take hi = bf16(x), dst_lo (row_dst_lo) lo = bf16(x - hi), same layouts and rules
+ * (dst_lo 16-byte aligned, row_dst_lo 8-byte aligned, given together with row_dst).  NaN -> NaN / NaN; +-Inf -> +-Inf / NaN; a
+ * finite x that rounds to +-Inf in bf16 -> +-Inf / -+Inf. */
+int s2vt_cast_bf16_split(const float* src, int32_t ld, const int32_t* rowidx, int32_t R, int32_t C, int32_t transpose, uint16_t* dst,
+                         uint16_t* dst_lo, int32_t ldd, int32_t Rp, float* colsum, uint16_t* row_dst, uint16_t* row_dst_lo, int32_t row_ldd,
+                         void* scratch, size_t scratch_bytes, s2vt_stream stream);
+/* C[M,N] (+)= Ah.Bh^T + Ah.Bl^T + Al.Bh^T over Kp (the layout rules of s2vt_gemm_bf16_nt for all four planes), fp32 accumulation,
+ * no atomics.  scratch (optional): where the tiles do not fill the chip the reduction is split into up to 8 slabs, summed in slab
+ * order, when scratch holds them (4 x slabs x M x N bytes; 32 x M x N always suffices); with less it is not split. */
+int s2vt_gemm_bf16x3_nt(const uint16_t* Ah, const uint16_t* Al, int32_t lda, const uint16_t* Bh, const uint16_t* Bl, int32_t ldb, float* C,
+                        int32_t ldc, int32_t M, int32_t N, int32_t Kp, int32_t accumulate, void* scratch, size_t scratch_bytes, s2vt_stream stream);
+
 /* Gradient w.r.t. the frame features, for the end-to-end scripts where they are the CNN's output
  * (e2e_tf_s2vt.py:106-121,163-166: the optimizer differentiates through `video` into Inception-ResNet-v2):
  * d_video[B, Tv, dim_image] = d_emb @ encode_image_W^T, from the d_emb the preceding s2vt_bptt_bwd (phase 0 or 2)

@@ -1,7 +1,9 @@
-// bwd_bf16.hip -- the opt-in bf16 mode of the S2VT backward's gradient contractions (s2vt_bptt_bwd_bf16):
+// bwd_bf16.hip -- the bf16 MFMA forms of the S2VT backward's gradient contractions:
 // fp32 -> bf16 casts (a row form, and a transpose form through LDS that can also write the row form and add the fp32 column
-// sums of its input) and gemm_bf16_nt, C[M,N] (+)= A[M,Kp] B[N,Kp]^T on bf16 MFMA with fp32 accumulation.  Gradients only:
-// nothing here decides a token.  No atomics anywhere: two runs give the same bits.
+// sums of its input) and gemm_bf16_nt, C[M,N] (+)= A[M,Kp] B[N,Kp]^T on bf16 MFMA with fp32 accumulation -- the opt-in bf16
+// mode (s2vt_bptt_bwd_bf16); the split forms of the same casts (hi = bf16(x), lo = bf16(x - hi), one read of x) and
+// gemm_bf16x3_nt, C (+)= Ah Bh^T + Ah Bl^T + Al Bh^T -- the default fp32 mode's split-bf16 products (s2vt_bptt_bwd_split).
+// Gradients only: nothing here decides a token.  No atomics anywhere: two runs give the same bits.
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
@@ -25,11 +27,24 @@ __device__ __forceinline__ uint32_t pack2(float a, float b)
     return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
 }
 
+// split of two values: hi = bf16(x), lo = bf16(x - float(hi)), both RNE.  x - float(hi) is exact for finite x whose hi is
+// finite, so hi + lo carries 16 significant bits.  NaN: hi and lo NaN.  +-Inf, and finite x beyond the largest bf16 (x rounds to
+// +-Inf in hi): hi = +-Inf and lo = x - hi = NaN (Inf) / -+Inf (finite x) -- a product that takes such an element is NaN, where
+// fp32 arithmetic would give +-Inf or NaN (Inf) or a finite value (finite x).
+__device__ __forceinline__ void split2(float a, float b, uint32_t& hi, uint32_t& lo)
+{
+    hi = pack2(a, b);
+    lo = pack2(a - __uint_as_float(hi << 16), b - __uint_as_float(hi & 0xffff0000u));
+}
+
 // ---------------------------------------------------------------------------------------------
 // row form: dst[r][k] = bf16(src[row(r)][k]) for k < K, 0 for K <= k < bf16_pad(K).  One 16-byte store per 8 elements.
+// SPLIT: dst the hi plane, dst_lo the lo plane (same ldd).
 // ---------------------------------------------------------------------------------------------
+template <bool SPLIT>
 __global__ __launch_bounds__(256) void cast_rows_bf16_kernel(const float* __restrict__ src, int ld, const int32_t* __restrict__ rowidx,
-                                                             int R, int K, uint16_t* __restrict__ dst, int ldd, int vec)
+                                                             int R, int K, uint16_t* __restrict__ dst, int ldd, int vec,
+                                                             uint16_t* __restrict__ dst_lo)
 {
     const int cpr = bf16_pad(K) / 8;
     const long total = (long)R * cpr;
@@ -45,7 +60,13 @@ __global__ __launch_bounds__(256) void cast_rows_bf16_kernel(const float* __rest
             for (int j = 0; j < 8; ++j) v[j] = k0 + j < K ? s[j] : 0.0f;
         }
         uint4 o;
-        o.x = pack2(v[0], v[1]); o.y = pack2(v[2], v[3]); o.z = pack2(v[4], v[5]); o.w = pack2(v[6], v[7]);
+        if constexpr (SPLIT) {
+            uint4 l;
+            split2(v[0], v[1], o.x, l.x); split2(v[2], v[3], o.y, l.y); split2(v[4], v[5], o.z, l.z); split2(v[6], v[7], o.w, l.w);
+            *reinterpret_cast<uint4*>(dst_lo + (size_t)r * ldd + k0) = l;
+        } else {
+            o.x = pack2(v[0], v[1]); o.y = pack2(v[2], v[3]); o.z = pack2(v[4], v[5]); o.w = pack2(v[6], v[7]);
+        }
         *reinterpret_cast<uint4*>(dst + (size_t)r * ldd + k0) = o;
     }
 }
@@ -53,10 +74,12 @@ __global__ __launch_bounds__(256) void cast_rows_bf16_kernel(const float* __rest
 // ---------------------------------------------------------------------------------------------
 // transpose form: workgroup = 64 columns x kTrRows rows, 64 x 64 tiles through LDS.  dst[c][r] = bf16(src[row(r)][c]) for
 // r < R, 0 for R <= r < Rp; optional row-form copy rdst[r][c] (c < bf16_pad(C), zeros past C); optional column sums of the
-// fp32 input: part[blockIdx.y][c], summed in a fixed order by colsum_parts_kernel.
+// fp32 input: part[blockIdx.y][c], summed in a fixed order by colsum_parts_kernel.  SPLIT: dst / rdst the hi planes, dst_lo /
+// rdst_lo the lo planes.
 // ---------------------------------------------------------------------------------------------
 constexpr int kTrRows = 256;
 
+template <bool SPLIT>
 __global__ __launch_bounds__(256) void cast_tr_bf16_kernel(CastTrArgs a, int vec)
 {
     __shared__ float t[64][65];
@@ -81,7 +104,13 @@ __global__ __launch_bounds__(256) void cast_tr_bf16_kernel(CastTrArgs a, int vec
                 }
                 if (a.rdst) {
                     uint2 o;
-                    o.x = pack2(v[0], v[1]); o.y = pack2(v[2], v[3]);
+                    if constexpr (SPLIT) {
+                        uint2 l;
+                        split2(v[0], v[1], o.x, l.x); split2(v[2], v[3], o.y, l.y);
+                        *reinterpret_cast<uint2*>(a.rdst_lo + (size_t)r * a.rldd + c) = l;
+                    } else {
+                        o.x = pack2(v[0], v[1]); o.y = pack2(v[2], v[3]);
+                    }
                     *reinterpret_cast<uint2*>(a.rdst + (size_t)r * a.rldd + c) = o;
                 }
             }
@@ -95,8 +124,15 @@ __global__ __launch_bounds__(256) void cast_tr_bf16_kernel(CastTrArgs a, int vec
             const int cc = p * 32 + (tid >> 3), rr = (tid & 7) * 8;
             if (c0 + cc < a.C) {
                 uint4 o;
-                o.x = pack2(t[rr][cc], t[rr + 1][cc]); o.y = pack2(t[rr + 2][cc], t[rr + 3][cc]);
-                o.z = pack2(t[rr + 4][cc], t[rr + 5][cc]); o.w = pack2(t[rr + 6][cc], t[rr + 7][cc]);
+                if constexpr (SPLIT) {
+                    uint4 l;
+                    split2(t[rr][cc], t[rr + 1][cc], o.x, l.x); split2(t[rr + 2][cc], t[rr + 3][cc], o.y, l.y);
+                    split2(t[rr + 4][cc], t[rr + 5][cc], o.z, l.z); split2(t[rr + 6][cc], t[rr + 7][cc], o.w, l.w);
+                    *reinterpret_cast<uint4*>(a.dst_lo + (size_t)(c0 + cc) * a.ldd + r0 + rr) = l;
+                } else {
+                    o.x = pack2(t[rr][cc], t[rr + 1][cc]); o.y = pack2(t[rr + 2][cc], t[rr + 3][cc]);
+                    o.z = pack2(t[rr + 4][cc], t[rr + 5][cc]); o.w = pack2(t[rr + 6][cc], t[rr + 7][cc]);
+                }
                 *reinterpret_cast<uint4*>(a.dst + (size_t)(c0 + cc) * a.ldd + r0 + rr) = o;
             }
         }
@@ -241,15 +277,172 @@ __global__ __launch_bounds__(256) void gemm_bf16_nt_kernel(GemmBf16Args g)
             }
 }
 
+
+// ---------------------------------------------------------------------------------------------
+// gemm_bf16x3_nt: C[M,N] (+)= Ah Bh^T + Ah Bl^T + Al Bh^T over Kp, fp32 accumulation in one accumulator per output element.
+// 128 x 128 output tile per 512-thread workgroup: waves 0-3 are MFMA waves (2 x 2 of 64 x 64, v_mfma_f32_16x16x32_bf16, 4 x 4
+// per wave), waves 4-7 loader waves -- loader wave p moves plane p (Ah, Al, Bh, Bl) global -> LDS by LDS-DMA
+// (buffer_load_dwordx4 ... lds), 8 instructions of 16 rows x 32 k per K step, into a ring of kX3Slots K steps of 32.  Loaders keep
+// up to three K steps in flight and publish K step k + 1 at barrier k (counted vmcnt, raw s_barrier); the MFMA waves read K
+// step k + 1's fragments while they multiply K step k's, and free K step k's ring slot at barrier k.  LDS images are linear per
+// DMA instruction (16 rows x 64 bytes); the 16-byte k groups of a row are XOR-swizzled by (row >> 2) & 3 on the SOURCE address, so a
+// fragment read (16 rows, one k group each) covers all 64 banks.  Out-of-range rows load zeros (buffer range check).  Split-K
+// (blockIdx.y = slab of nk_slab K steps): slab s writes its partial tile to part + s * M * N, and reduce_slabs_kernel adds the
+// slabs in slab order -- deterministic, no atomics.
+// ---------------------------------------------------------------------------------------------
+struct GemmX3Args {
+    const uint16_t *Ah, *Al; int lda; const uint16_t *Bh, *Bl; int ldb; float* C; int ldc;
+    int M, N, nk, nk_slab, accumulate, tiles_m, tiles_n;
+    float* part;                                      // split-K slabs [slabs][M][N], or nullptr: the tile goes to C
+};
+
+constexpr int kX3BK = 32, kX3Slots = 4, kX3Plane = kTile * kX3BK;   // a plane's K step: 128 rows x 32 bf16 = 8 KB
+constexpr int kX3Lds = kX3Slots * 4 * kX3Plane * 2;                  // 128 KB: one workgroup per CU
+constexpr int kX3Dma = kTile / 16;                                   // DMA instructions per plane per K step (per loader wave)
+typedef __attribute__((address_space(3))) void* x3_lds_ptr;
+
+__global__ __launch_bounds__(512) void gemm_bf16x3_nt_kernel(GemmX3Args g)
+{
+    extern __shared__ __attribute__((aligned(16))) uint16_t x3lds[];   // [slot][plane][128 rows][32]
+    const int nwg = g.tiles_m * g.tiles_n, orig = blockIdx.x;
+    const int xcd = orig & 7, q = nwg >> 3, rem = nwg & 7;
+    const int wgid = (xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q) + (orig >> 3);
+    const int tm = wgid % g.tiles_m, tn = wgid / g.tiles_m;
+    const int m0 = tm * kTile, n0 = tn * kTile;
+    const int kbeg = blockIdx.y * g.nk_slab, nk = min(g.nk_slab, g.nk - kbeg);
+    const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+
+    if (w >= 4) {
+        // ================= loader wave: plane p, 8 DMA instructions per K step
+        const int p = w - 4;
+        const uint16_t* const plane = p == 0 ? g.Ah : p == 1 ? g.Al : p == 2 ? g.Bh : g.Bl;
+        const int r0 = p < 2 ? m0 : n0, rows = p < 2 ? g.M : g.N, ld = p < 2 ? g.lda : g.ldb;
+        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(plane + (size_t)r0 * ld), 0, (int)kOob, 0x00020000);
+        // lane -> (row lane >> 2 of a 16-row block, LDS 16-byte slot lane & 3): loads k group (lane & 3) ^ ((row >> 2) & 3)
+        const int rr = lane >> 2, kg = (lane & 3) ^ ((rr >> 2) & 3);
+        uint32_t voff[kX3Dma];
+#pragma unroll
+        for (int b = 0; b < kX3Dma; ++b) {
+            const int r = b * 16 + rr;
+            voff[b] = r0 + r < rows ? (uint32_t)(r * ld + kg * 8) * 2u : kOob;
+        }
+        auto issue = [&](int ks) __attribute__((always_inline)) {
+            uint16_t* const dst = x3lds + ((ks % kX3Slots) * 4 + p) * kX3Plane;
+            const uint32_t soff = (uint32_t)(kbeg + ks) * kX3BK * 2u;
+#pragma unroll
+            for (int b = 0; b < kX3Dma; ++b)
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (x3_lds_ptr)(dst + b * 16 * kX3BK), 16, voff[b], soff, 0, 0);
+        };
+        // K steps younger than the one that must have landed: 0, 1 or 2 (x 8 DMA instructions each)
+        auto wait_younger = [](int n) __attribute__((always_inline)) {
+            if (n >= 2) wait_vmcnt<2 * kX3Dma>();
+            else if (n == 1) wait_vmcnt<kX3Dma>();
+            else wait_vmcnt<0>();
+        };
+        const int pro = min(kX3Slots, nk);
+        for (int ks = 0; ks < pro; ++ks) issue(ks);
+        if (pro - 1 >= 3) wait_vmcnt<3 * kX3Dma>();                   // K step 0 has landed
+        else wait_younger(pro - 1);
+        asm volatile("" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        for (int k = 0; k < nk; ++k) {
+            wait_younger(min(k + 3, nk - 1) - (k + 1));                   // K step k + 1 has landed
+            asm volatile("" ::: "memory");
+            __builtin_amdgcn_s_barrier();                                 // barrier k: the MFMA waves are done reading K step k
+            asm volatile("" ::: "memory");
+            if (k + kX3Slots < nk) issue(k + kX3Slots);                   // into K step k's slot
+        }
+        return;
+    }
+
+    // ================= MFMA waves
+    const int wr = w >> 1, wc = w & 1;
+    const int fofs = (lane & 15) * kX3BK + (((lane >> 4) ^ ((lane >> 2) & 3)) << 3);   // + 16 rows per fragment repeat
+    f32x4 acc[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    // fragments of one K step: [plane][repeat]
+    auto read = [&](int ks, bf16x8 (&f)[4][4]) __attribute__((always_inline)) {
+        const uint16_t* const s = x3lds + (ks % kX3Slots) * 4 * kX3Plane;
+#pragma unroll
+        for (int pl = 0; pl < 4; ++pl)
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                f[pl][i] = *reinterpret_cast<const bf16x8*>(s + pl * kX3Plane + ((pl < 2 ? wr : wc) * 64 + i * 16) * kX3BK + fofs);
+    };
+    auto mul = [&](const bf16x8 (&f)[4][4]) __attribute__((always_inline)) {
+        // small products first, each pass over all 16 accumulators (no back-to-back dependent MFMAs)
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f[0][i], f[3][j], acc[i][j], 0, 0, 0);
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f[1][i], f[2][j], acc[i][j], 0, 0, 0);
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f[0][i], f[2][j], acc[i][j], 0, 0, 0);
+    };
+    bf16x8 fa[4][4], fb[4][4];
+    __syncthreads();                                                      // K step 0 has landed
+    if (nk > 0) read(0, fa);
+    // barrier k publishes K step k + 1 and frees K step k's slot (its fragments are in registers: lgkmcnt(0) first)
+    auto step = [&](int k, bf16x8 (&cur)[4][4], bf16x8 (&nxt)[4][4]) __attribute__((always_inline)) {
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __syncthreads();
+        if (k + 1 < nk) read(k + 1, nxt);
+        mul(cur);
+    };
+    for (int k = 0; k < nk; k += 2) {                                     // (nk is even: Kp % 64 == 0, slabs of an even count)
+        step(k, fa, fb);
+        step(k + 1, fb, fa);
+    }
+    float* const out = g.part ? g.part + (size_t)blockIdx.y * g.M * g.N : g.C;
+    const int ldo = g.part ? g.N : g.ldc;
+    const bool add = !g.part && g.accumulate;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int row = m0 + wr * 64 + i * 16 + (lane >> 4) * 4 + e, col = n0 + wc * 64 + j * 16 + (lane & 15);
+                if (row < g.M && col < g.N) {
+                    float* c = out + (size_t)row * ldo + col;
+                    *c = add ? *c + acc[i][j][e] : acc[i][j][e];
+                }
+            }
+}
+
+// C (+)= sum over slabs of part[s] (slab order)
+__global__ __launch_bounds__(256) void reduce_slabs_kernel(const float* __restrict__ part, int slabs, int M, int N, float* __restrict__ C, int ldc,
+                                                           int accumulate)
+{
+    const size_t MN = (size_t)M * N;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < MN; i += (size_t)gridDim.x * 256) {
+        float s = part[i];
+        for (int k = 1; k < slabs; ++k) s += part[(size_t)k * MN + i];
+        float* c = C + (i / N) * ldc + i % N;
+        *c = accumulate ? *c + s : s;
+    }
+}
 }  // namespace
 
-hipError_t launch_cast_rows_bf16(const float* src, int ld, const int32_t* rowidx, int R, int K, uint16_t* dst, int ldd, hipStream_t st)
+hipError_t launch_cast_rows_bf16(const float* src, int ld, const int32_t* rowidx, int R, int K, uint16_t* dst, int ldd, hipStream_t st,
+                                 uint16_t* dst_lo)
 {
     if (R <= 0 || K <= 0) return hipSuccess;
     const int vec = !((reinterpret_cast<uintptr_t>(src) & 15) || (ld & 3));
     const long chunks = (long)R * (bf16_pad(K) / 8);
     const long blocks = (chunks + 255) / 256;
-    hipLaunchKernelGGL(cast_rows_bf16_kernel, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(256), 0, st, src, ld, rowidx, R, K, dst, ldd, vec);
+    const dim3 grid((unsigned)(blocks < 8192 ? blocks : 8192));
+    if (dst_lo) hipLaunchKernelGGL(cast_rows_bf16_kernel<true>, grid, dim3(256), 0, st, src, ld, rowidx, R, K, dst, ldd, vec, dst_lo);
+    else hipLaunchKernelGGL(cast_rows_bf16_kernel<false>, grid, dim3(256), 0, st, src, ld, rowidx, R, K, dst, ldd, vec, dst_lo);
     return hipGetLastError();
 }
 
@@ -263,7 +456,8 @@ hipError_t launch_cast_tr_bf16(const CastTrArgs& a, hipStream_t st)
     if (a.C <= 0 || a.Rp <= 0) return hipSuccess;
     const int vec = !((reinterpret_cast<uintptr_t>(a.src) & 15) || (a.ld & 3));
     const int ny = (a.Rp + kTrRows - 1) / kTrRows;
-    hipLaunchKernelGGL(cast_tr_bf16_kernel, dim3((a.C + 63) / 64, ny), dim3(256), 0, st, a, vec);
+    if (a.dst_lo) hipLaunchKernelGGL(cast_tr_bf16_kernel<true>, dim3((a.C + 63) / 64, ny), dim3(256), 0, st, a, vec);
+    else hipLaunchKernelGGL(cast_tr_bf16_kernel<false>, dim3((a.C + 63) / 64, ny), dim3(256), 0, st, a, vec);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || !a.colsum) return e;
     hipLaunchKernelGGL(colsum_parts_kernel, dim3((a.C + 255) / 256), dim3(256), 0, st, (const float*)a.part, ny, a.C, a.colsum);
@@ -286,6 +480,62 @@ hipError_t launch_gemm_bf16_nt(const uint16_t* A, int lda, const uint16_t* B, in
     const dim3 grid((unsigned)(g.tiles_m * g.tiles_n));
     if ((mfma ? mfma : gemm_bf16_default_mfma()) == 32) hipLaunchKernelGGL(gemm_bf16_nt_kernel<32>, grid, dim3(256), 0, st, g);
     else hipLaunchKernelGGL(gemm_bf16_nt_kernel<16>, grid, dim3(256), 0, st, g);
+    return hipGetLastError();
+}
+
+int gemm_bf16x3_slabs(int M, int N, int Kp)
+{
+    // split-K where the tiles do not fill the chip (one workgroup per CU, one round): slabs of at least 16 K steps of 32
+    const int tiles = ((M + kTile - 1) / kTile) * ((N + kTile - 1) / kTile), nk = Kp / kX3BK;
+    static const int cus = [] {
+        int dev = 0, n = 256;
+        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
+        return n > 0 ? n : 256;
+    }();
+    int s = 1;
+    while (s < 8 && tiles * (s * 2) <= cus && nk / (s * 2) >= 16) s *= 2;
+    return s;
+}
+
+size_t gemm_bf16x3_part_floats(int M, int N, int Kp)
+{
+    const int s = gemm_bf16x3_slabs(M, N, Kp);
+    return s > 1 ? (size_t)s * M * N : 0;
+}
+
+hipError_t launch_gemm_bf16x3_nt(const uint16_t* Ah, const uint16_t* Al, int lda, const uint16_t* Bh, const uint16_t* Bl, int ldb, float* C, int ldc,
+                                 int M, int N, int Kp, int accumulate, float* part, size_t part_floats, int cls, hipStream_t st)
+{
+    if (M <= 0 || N <= 0) return hipSuccess;
+    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_bf16x3_nt_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kX3Lds);
+    if (attr != hipSuccess) return attr;
+    GemmX3Args g;
+    g.Ah = Ah; g.Al = Al; g.lda = lda; g.Bh = Bh; g.Bl = Bl; g.ldb = ldb; g.C = C; g.ldc = ldc; g.M = M; g.N = N;
+    g.nk = Kp / kX3BK; g.accumulate = accumulate;
+    g.tiles_m = (M + kTile - 1) / kTile; g.tiles_n = (N + kTile - 1) / kTile;
+    int slabs = part ? gemm_bf16x3_slabs(M, N, Kp) : 1;
+    if ((size_t)slabs * M * N > part_floats) slabs = 1;
+    g.nk_slab = ((g.nk + slabs - 1) / slabs + 1) & ~1;                    // >= nk / slabs (so no more slabs than the scratch holds), even:
+    slabs = g.nk_slab ? (g.nk + g.nk_slab - 1) / g.nk_slab : 1;           // the MFMA loop takes K steps in pairs
+    g.part = slabs > 1 ? part : nullptr;
+    const dim3 grid((unsigned)(g.tiles_m * g.tiles_n), (unsigned)slabs);
+    const bool prof = prof_wants(cls, 16);
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (prof) {
+        hipError_t pe = prof_events(&e0, &e1);
+        if (pe != hipSuccess) return pe;
+        (void)hipEventRecord(e0, st);
+    }
+    hipLaunchKernelGGL(gemm_bf16x3_nt_kernel, grid, dim3(512), kX3Lds, st, g);
+    if (slabs > 1) {
+        const size_t MN = (size_t)M * N, blocks = (MN + 255) / 256;
+        hipLaunchKernelGGL(reduce_slabs_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, st, (const float*)part, slabs, M, N, C, ldc,
+                           accumulate);
+    }
+    if (prof) {
+        (void)hipEventRecord(e1, st);
+        prof_record(cls, 16, cls == 3 ? "x3_128x128(dma) wgrad" : "x3_128x128(dma) dgrad", 2.0 * M * (double)N * Kp, e0, e1);
+    }
     return hipGetLastError();
 }
 

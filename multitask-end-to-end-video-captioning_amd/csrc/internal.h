@@ -272,7 +272,9 @@ hipError_t launch_attn_bwd_chain(const AttnBwdChainLaunch& a, hipStream_t st);
 constexpr int kBf16K = 64;                            // K step of gemm_bf16_nt: a bf16 operand row holds bf16_pad(K) elements, zeros past K
 __host__ __device__ inline int bf16_pad(int k) { return (k + kBf16K - 1) / kBf16K * kBf16K; }
 // dst[r][k] = bf16(src[row(r)][k]) (row(r) = rowidx ? rowidx[r] : r) for k < K, zeros up to bf16_pad(K); dst 16-byte aligned, ldd % 8 == 0
-hipError_t launch_cast_rows_bf16(const float* src, int ld, const int32_t* rowidx, int R, int K, uint16_t* dst, int ldd, hipStream_t st);
+// dst_lo (optional): the split form -- dst = bf16(x) (hi), dst_lo = bf16(x - hi) (lo), same ldd
+hipError_t launch_cast_rows_bf16(const float* src, int ld, const int32_t* rowidx, int R, int K, uint16_t* dst, int ldd, hipStream_t st,
+                                 uint16_t* dst_lo = nullptr);
 // dst[c][r] = bf16(src[row(r)][c]) for r < R, zeros for R <= r < Rp (Rp a multiple of 64; dst 16-byte aligned, ldd % 8 == 0).
 // rdst (optional): the row form as well, rdst[r][c] for c < bf16_pad(C) (8-byte aligned, rldd % 4 == 0).
 // colsum (optional): += the column sums of the fp32 input rows (fixed order, no atomics), through part[cast_tr_part_floats(Rp, C)].
@@ -281,6 +283,7 @@ struct CastTrArgs {
     uint16_t* dst; int ldd; int Rp;
     float* colsum; float* part;
     uint16_t* rdst; int rldd;
+    uint16_t* dst_lo; uint16_t* rdst_lo;             // (optional) the split form: dst / rdst take hi = bf16(x), these lo = bf16(x - hi)
 };
 hipError_t launch_cast_tr_bf16(const CastTrArgs& a, hipStream_t st);
 size_t cast_tr_part_floats(int Rp, int C);
@@ -288,6 +291,12 @@ size_t cast_tr_part_floats(int Rp, int C);
 // mfma: 16 (v_mfma_f32_16x16x32_bf16), 32 (v_mfma_f32_32x32x16_bf16), 0 = the library's choice
 hipError_t launch_gemm_bf16_nt(const uint16_t* A, int lda, const uint16_t* B, int ldb, float* C, int ldc, int M, int N, int Kp, int accumulate,
                                int mfma, hipStream_t st);
+// C[M,N] (+)= Ah Bh^T + Ah Bl^T + Al Bh^T: split-bf16 operands (hi / lo planes with the layout rules of launch_gemm_bf16_nt), fp32
+// accumulation, no atomics.  part: optional split-K scratch of part_floats floats (gemm_bf16x3_part_floats(M, N, Kp) for the full
+// split; fewer -> no split); cls: the launch profiler's class (3 weight gradients, 4 data gradients)
+hipError_t launch_gemm_bf16x3_nt(const uint16_t* Ah, const uint16_t* Al, int lda, const uint16_t* Bh, const uint16_t* Bl, int ldb, float* C, int ldc,
+                                 int M, int N, int Kp, int accumulate, float* part, size_t part_floats, int cls, hipStream_t st);
+size_t gemm_bf16x3_part_floats(int M, int N, int Kp);
 
 // order-free NN contraction for the backward data path with optional split-K slabs:
 // slab s (blockIdx.y) holds the partial over its K range at C + s * slab_stride.

@@ -203,9 +203,11 @@ size_t carve_train(Carver& c, const s2vt_dims* d, int B, int N, TrainWs* out)
 // in stream order -- L: the left operand of a data-gradient product in row form (dlogits, dZ2, dZ1 rows); W: the weight it multiplies;
 // BT / AT: both operands of a weight gradient transposed ([column][reduction row], the rows of two segments -- encode steps, decode
 // steps -- each padded to the K step, so that a product over the decode steps only starts at a padded column); part: column-sum partials.
-struct Bf16Ws { uint16_t *L, *W, *AT, *BT; float* part; };
+// Split mode (s2vt_bptt_bwd_split): the same four buffers hold the hi planes, followed by a copy of their whole region for the lo
+// planes (lo of a hi pointer = that pointer + lo_delta elements), and kpart: gemm_bf16x3_nt's split-K slabs.
+struct Bf16Ws { uint16_t *L, *W, *AT, *BT; float* part; size_t lo_delta; float* kpart; size_t kpart_floats; };
 
-size_t carve_bf16(Carver& c, const s2vt_dims* d, int B, int N, Bf16Ws* out)
+size_t carve_bf16(Carver& c, const s2vt_dims* d, int B, int N, Bf16Ws* out, bool split = false)
 {
     const size_t H = d->lstm_dim, E = d->word_dim, V = d->n_words, D = d->dim_image, Tv = d->n_video_lstm_step, Tc = d->n_caption_lstm_step;
     const size_t T = Tv + Tc;
@@ -214,10 +216,25 @@ size_t carve_bf16(Carver& c, const s2vt_dims* d, int B, int N, Bf16Ws* out)
     const size_t ke1 = bf16_pad((int)(Tv * B)), K1 = ke1 + bf16_pad((int)(Tc * B));                // LSTM1: encode | decode
     auto mx = [](std::initializer_list<size_t> l) { size_t m = 0; for (size_t v : l) m = v > m ? v : m; return m; };
     Bf16Ws w;
+    const size_t off0 = c.off;
     w.L = c.take<uint16_t>(mx({Tc * N * Kv, T * N * K4, Tv * B * K4}));
     w.W = c.take<uint16_t>(mx({H * Kv, (H + E) * K4, E * K4}));
     w.BT = c.take<uint16_t>(mx({V * Kr, 4 * H * Kt, 4 * H * K1, E * ke1}));
     w.AT = c.take<uint16_t>(mx({H * Kr, H * Kt, E * Kr, E * ke1, H * K1, D * ke1}));
+    w.lo_delta = 0; w.kpart = nullptr; w.kpart_floats = 0;
+    if (split) {
+        const size_t hi_bytes = c.off - off0;                    // (a multiple of 256: the lo region starts right behind)
+        c.take<char>(hi_bytes);
+        w.lo_delta = hi_bytes / sizeof(uint16_t);
+        const int Re = (int)(Tv * N), Rr = (int)(Tc * N), Re1 = (int)(Tv * B);
+        w.kpart_floats = mx({gemm_bf16x3_part_floats((int)H, (int)V, (int)Kr), gemm_bf16x3_part_floats(Rr, (int)H, (int)Kv),
+                             gemm_bf16x3_part_floats((int)H, (int)(4 * H), (int)Kt), gemm_bf16x3_part_floats((int)E, (int)(4 * H), (int)Kr),
+                             gemm_bf16x3_part_floats((int)(T * N), (int)(H + E), (int)K4), gemm_bf16x3_part_floats(Re, (int)(H + E), (int)K4),
+                             gemm_bf16x3_part_floats(Rr, (int)(H + E), (int)K4), gemm_bf16x3_part_floats(Re1, (int)E, (int)K4),
+                             gemm_bf16x3_part_floats((int)E, (int)(4 * H), (int)ke1), gemm_bf16x3_part_floats((int)H, (int)(4 * H), (int)K1),
+                             gemm_bf16x3_part_floats((int)D, (int)E, (int)ke1)});
+        w.kpart = c.take<float>(w.kpart_floats);
+    }
     w.part = c.take<float>(mx({cast_tr_part_floats((int)Kr, (int)V), cast_tr_part_floats((int)(ke > Kr ? ke : Kr), (int)(4 * H)),
                                cast_tr_part_floats((int)(K1 - ke1 > ke1 ? K1 - ke1 : ke1), (int)(4 * H)), cast_tr_part_floats((int)ke1, (int)E)}));
     if (out) *out = w;
@@ -578,12 +595,27 @@ int s2vt_bptt_bwd_steps(const s2vt_dims* d, const s2vt_params* p, const s2vt_par
                               workspace_bytes, phase, stream);
 }
 
-// The backward of s2vt_bptt_bwd_live; bf16 != 0: its gradient contractions on bf16 operands (s2vt_bptt_bwd_bf16), bf16_ws their scratch
+// Precision of the backward's gradient contractions: fp32 MFMA (s2vt_bptt_bwd_live), bf16 operands (s2vt_bptt_bwd_bf16), or
+// split-bf16 operands, three bf16 products per product (s2vt_bptt_bwd_split)
+enum GradMode { kGradFp32 = 0, kGradBf16 = 1, kGradSplit = 2 };
+
+// s2vt_bptt_bwd_split's dispatch: the split products where the unrolled rows exceed the gated side stream's 256 (all of that
+// step's contractions -- the REINFORCE shapes); at <= 256 rows the fp32 body with its side-stream overlap.  S2VT_SPLIT_GRADS=0: the
+// fp32 body at every shape (read once).
+static int split_grad_mode(int N)
+{
+    static const int on = [] { const char* e = getenv("S2VT_SPLIT_GRADS"); return e ? atoi(e) : 1; }();
+    return on && N > 256 ? kGradSplit : kGradFp32;
+}
+
+// The backward of s2vt_bptt_bwd_live; mode != kGradFp32: its gradient contractions on bf16 / split-bf16 operands, bf16_ws their scratch
 static int bptt_bwd_body(const s2vt_dims* d, const s2vt_params* p, const s2vt_params* grads, const float* video, int32_t B,
                          int32_t N, const float* dlogits, int32_t caption_steps, const int32_t* live_rows, int32_t n_live, float keep,
                          uint64_t seed, const int32_t* video_id, const int32_t* sample_id, void* workspace, size_t workspace_bytes,
-                         int32_t phase, int bf16, void* bf16_ws, size_t bf16_ws_bytes, s2vt_stream stream)
+                         int32_t phase, int mode, void* bf16_ws, size_t bf16_ws_bytes, s2vt_stream stream)
 {
+    const int bf16 = mode != kGradFp32;
+    const bool split = mode == kGradSplit;
     if ((live_rows == nullptr) != (n_live == 0) || n_live < 0) return S2VT_E_BADARG;
     if (bf16 && !bf16_ws) return S2VT_E_BADARG;
     if (phase < 0 || phase > 4) return S2VT_E_BADARG;
@@ -606,20 +638,28 @@ static int bptt_bwd_body(const s2vt_dims* d, const s2vt_params* p, const s2vt_pa
     Bf16Ws bw{};
     if (bf16) {
         Carver cb(bf16_ws, bf16_ws_bytes);
-        carve_bf16(cb, d, B, N, &bw);
+        carve_bf16(cb, d, B, N, &bw, split);
         if (!cb.ok()) return S2VT_E_WORKSPACE;
     }
     hipStream_t st = S(stream);
     const size_t NH = (size_t)N * H;
-    // bf16 mode: each operand of a gradient contraction is cast once (a shared one serves every product that reads it), then
-    // gemm_bf16_nt; the recurrences, dropout reductions and the embedding scatter stay as they are.  Everything on the caller's stream.
+    // bf16 / split mode: each operand of a gradient contraction is cast once (a shared one serves every product that reads it; split:
+    // its hi and lo planes from one read), then gemm_bf16_nt / gemm_bf16x3_nt; the recurrences, dropout reductions and the embedding
+    // scatter stay as they are.  Everything on the caller's stream.
     const int K4 = bf16_pad(4 * H);
+    auto lo = [&](uint16_t* hi) -> uint16_t* { return split && hi ? hi + bw.lo_delta : nullptr; };
     auto tr = [&](const float* src, int ld, const int32_t* idx, int R, int C, uint16_t* dst, int ldd, float* colsum = nullptr,
                   uint16_t* rdst = nullptr, int rldd = 0) -> hipError_t {
-        CastTrArgs a{src, ld, idx, R, C, dst, ldd, bf16_pad(R), colsum, bw.part, rdst, rldd};
+        CastTrArgs a{src, ld, idx, R, C, dst, ldd, bf16_pad(R), colsum, bw.part, rdst, rldd, lo(dst), lo(rdst)};
         return launch_cast_tr_bf16(a, st);
     };
-    auto mm = [&](const uint16_t* A, int lda, const uint16_t* Bm, int ldb, float* Cm, int ldc, int M, int Nn, int Kp, int acc) -> hipError_t {
+    auto rows = [&](const float* src, int ld, const int32_t* idx, int R, int K, uint16_t* dst, int ldd) -> hipError_t {
+        return launch_cast_rows_bf16(src, ld, idx, R, K, dst, ldd, st, lo(dst));
+    };
+    // (acc = 1: a weight gradient, accumulated into its buffer; 0: a data gradient)
+    auto mm = [&](uint16_t* A, int lda, uint16_t* Bm, int ldb, float* Cm, int ldc, int M, int Nn, int Kp, int acc) -> hipError_t {
+        if (split)
+            return launch_gemm_bf16x3_nt(A, lo(A), lda, Bm, lo(Bm), ldb, Cm, ldc, M, Nn, Kp, acc, bw.kpart, bw.kpart_floats, acc ? 3 : 4, st);
         return launch_gemm_bf16_nt(A, lda, Bm, ldb, Cm, ldc, M, Nn, Kp, acc, 0, st);
     };
 
@@ -660,7 +700,7 @@ static int bptt_bwd_body(const s2vt_dims* d, const s2vt_params* p, const s2vt_pa
             HIP_TRY(tr(dlogits, V, nullptr, R, V, bw.BT, Kr, grads->embed_word_b, bw.L, Kv));
             HIP_TRY(tr(w.O2 + (size_t)Tv * NH, H, live_rows, R, H, bw.AT, Kr));
             HIP_TRY(mm(bw.AT, Kr, bw.BT, Kr, grads->embed_word_W, V, H, V, Kr, 1));
-            HIP_TRY(launch_cast_rows_bf16(p->embed_word_W, V, nullptr, H, V, bw.W, Kv, st));
+            HIP_TRY(rows(p->embed_word_W, V, nullptr, H, V, bw.W, Kv));
             HIP_TRY(mm(bw.L, Kv, bw.W, Kv, dO2t, H, R, H, Kv, 0));
         } else {
         TnArgs a{w.O2 + (size_t)Tv * NH, live_rows, H, dlogits, V, grads->embed_word_W, V, R, H, V, 1};
@@ -776,10 +816,10 @@ static int bptt_bwd_body(const s2vt_dims* d, const s2vt_params* p, const s2vt_pa
     if (bf16) {
         const int Re = Tv * N, Rd = live_rows ? n_live : Tc * N;
         if (!do_l2) {                                        // (phase 4 alone: the row form phase 3 made in its fused cast, again)
-            HIP_TRY(launch_cast_rows_bf16(w.dZ2, 4 * H, nullptr, Re, 4 * H, bw.L, K4, st));
-            HIP_TRY(launch_cast_rows_bf16(live_rows ? w.dZ2p : w.dZ2 + (size_t)Tv * 4 * NH, 4 * H, nullptr, Rd, 4 * H, bw.L + (size_t)Re * K4, K4, st));
+            HIP_TRY(rows(w.dZ2, 4 * H, nullptr, Re, 4 * H, bw.L, K4));
+            HIP_TRY(rows(live_rows ? w.dZ2p : w.dZ2 + (size_t)Tv * 4 * NH, 4 * H, nullptr, Rd, 4 * H, bw.L + (size_t)Re * K4, K4));
         }
-        HIP_TRY(launch_cast_rows_bf16(p->lstm2_W, 4 * H, nullptr, H + E, 4 * H, bw.W, K4, st));
+        HIP_TRY(rows(p->lstm2_W, 4 * H, nullptr, H + E, 4 * H, bw.W, K4));
         if (!live_rows) {
             HIP_TRY(mm(bw.L, K4, bw.W, K4, w.dX2, H + E, T * N, H + E, K4, 0));
         } else {
@@ -817,12 +857,14 @@ static int bptt_bwd_body(const s2vt_dims* d, const s2vt_params* p, const s2vt_pa
             if (rc != S2VT_OK) return rc;
         }
     }
-    if (bf16) {
+    // (split mode: LSTM1's contractions -- B rows, not N: dX1 [Tv B, E], the weight gradients over (Tv + Tc) B rows -- stay on fp32
+    // MFMA, below)
+    if (bf16 && !split) {
         // dZ1 once: transposed over [encode steps | decode steps] (+ lstm1_b), and the encode rows by rows (dX1's A)
         const int Re = Tv * B, Rd = Tc * B, ke = bf16_pad(Re), K1 = ke + bf16_pad(Rd);
         HIP_TRY(tr(w.dZ1, 4 * H, nullptr, Re, 4 * H, bw.BT, K1, grads->lstm1_b, bw.L, K4));
         HIP_TRY(tr(w.dZ1 + (size_t)Re * 4 * H, 4 * H, nullptr, Rd, 4 * H, bw.BT + ke, K1, grads->lstm1_b));
-        HIP_TRY(launch_cast_rows_bf16(p->lstm1_W, 4 * H, nullptr, E, 4 * H, bw.W, K4, st));
+        HIP_TRY(rows(p->lstm1_W, 4 * H, nullptr, E, 4 * H, bw.W, K4));
         HIP_TRY(mm(bw.L, K4, bw.W, K4, w.dX1, E, Re, E, K4, 0));
         HIP_TRY(tr(w.emb, E, w.encidx, Re, E, bw.AT, ke));                                          // the frame embedding, time-major
         HIP_TRY(mm(bw.AT, ke, bw.BT, K1, grads->lstm1_W, 4 * H, E, 4 * H, ke, 1));
@@ -882,6 +924,56 @@ int s2vt_bptt_bwd_bf16(const s2vt_dims* d, const s2vt_params* p, const s2vt_para
 {
     return bptt_bwd_body(d, p, grads, video, B, N, dlogits, caption_steps, live_rows, n_live, keep, seed, video_id, sample_id, workspace,
                          workspace_bytes, phase, 1, bf16_ws, bf16_ws_bytes, stream);
+}
+
+size_t s2vt_split_grad_workspace_bytes(const s2vt_dims* d, int32_t B, int32_t N)
+{
+    if (!dims_ok(d) || B <= 0 || N <= 0 || N % B) return 0;
+    Carver c(nullptr, 0);
+    return carve_bf16(c, d, B, N, nullptr, true);
+}
+
+int s2vt_bptt_bwd_split(const s2vt_dims* d, const s2vt_params* p, const s2vt_params* grads, const float* video, int32_t B,
+                        int32_t N, const float* dlogits, int32_t caption_steps, const int32_t* live_rows, int32_t n_live, float keep,
+                        uint64_t seed, const int32_t* video_id, const int32_t* sample_id, void* workspace, size_t workspace_bytes,
+                        int32_t phase, void* split_ws, size_t split_ws_bytes, s2vt_stream stream)
+{
+    if (!split_ws) return S2VT_E_BADARG;
+    return bptt_bwd_body(d, p, grads, video, B, N, dlogits, caption_steps, live_rows, n_live, keep, seed, video_id, sample_id, workspace,
+                         workspace_bytes, phase, split_grad_mode(N), split_ws, split_ws_bytes, stream);
+}
+
+int s2vt_cast_bf16_split(const float* src, int32_t ld, const int32_t* rowidx, int32_t R, int32_t C, int32_t transpose, uint16_t* dst,
+                         uint16_t* dst_lo, int32_t ldd, int32_t Rp, float* colsum, uint16_t* row_dst, uint16_t* row_dst_lo, int32_t row_ldd,
+                         void* scratch, size_t scratch_bytes, s2vt_stream stream)
+{
+    if (!src || !dst || !dst_lo || R < 0 || C <= 0 || ld < C || transpose < 0 || transpose > 1) return S2VT_E_BADARG;
+    if ((reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(dst_lo)) & 15) return S2VT_E_ALIGN;
+    if (!transpose) {
+        if (colsum || row_dst || row_dst_lo || ldd < bf16_pad(C) || (ldd & 7)) return S2VT_E_BADARG;
+        HIP_TRY(launch_cast_rows_bf16(src, ld, rowidx, R, C, dst, ldd, S(stream), dst_lo));
+        return S2VT_OK;
+    }
+    if (Rp < R || Rp % kBf16K || ldd < Rp || (ldd & 7)) return S2VT_E_BADARG;
+    if (!row_dst != !row_dst_lo) return S2VT_E_BADARG;
+    if (row_dst && (row_ldd < bf16_pad(C) || (row_ldd & 3))) return S2VT_E_BADARG;
+    if (row_dst && ((reinterpret_cast<uintptr_t>(row_dst) | reinterpret_cast<uintptr_t>(row_dst_lo)) & 7)) return S2VT_E_ALIGN;
+    if (colsum && (!scratch || scratch_bytes < cast_tr_part_floats(Rp, C) * 4)) return S2VT_E_WORKSPACE;
+    CastTrArgs a{src, ld, rowidx, R, C, dst, ldd, Rp, colsum, static_cast<float*>(scratch), row_dst, row_ldd, dst_lo, row_dst_lo};
+    HIP_TRY(launch_cast_tr_bf16(a, S(stream)));
+    return S2VT_OK;
+}
+
+int s2vt_gemm_bf16x3_nt(const uint16_t* Ah, const uint16_t* Al, int32_t lda, const uint16_t* Bh, const uint16_t* Bl, int32_t ldb, float* C,
+                        int32_t ldc, int32_t M, int32_t N, int32_t Kp, int32_t accumulate, void* scratch, size_t scratch_bytes, s2vt_stream stream)
+{
+    if (!Ah || !Al || !Bh || !Bl || !C || M < 0 || N < 0 || Kp < 0 || Kp % kBf16K || lda < Kp || ldb < Kp || ldc < N || (lda & 7) || (ldb & 7))
+        return S2VT_E_BADARG;
+    if (accumulate < 0 || accumulate > 1 || (scratch_bytes && !scratch)) return S2VT_E_BADARG;
+    if ((reinterpret_cast<uintptr_t>(Ah) | reinterpret_cast<uintptr_t>(Al) | reinterpret_cast<uintptr_t>(Bh) | reinterpret_cast<uintptr_t>(Bl)) & 15)
+        return S2VT_E_ALIGN;
+    HIP_TRY(launch_gemm_bf16x3_nt(Ah, Al, lda, Bh, Bl, ldb, C, ldc, M, N, Kp, accumulate, static_cast<float*>(scratch), scratch_bytes / 4, 3, S(stream)));
+    return S2VT_OK;
 }
 
 int s2vt_cast_bf16(const float* src, int32_t ld, const int32_t* rowidx, int32_t R, int32_t C, int32_t transpose, uint16_t* dst, int32_t ldd,

@@ -331,6 +331,13 @@ def bf16_grad_workspace(dims: Dims, B: int, N: int, device):
     return workspace(nbytes, device, "bf16_grad")
 
 
+def split_grad_workspace(dims: Dims, B: int, N: int, device):
+    """The scratch of the split-bf16 backward (s2vt_split_grad_workspace_bytes), cached beside the train workspace."""
+    nbytes = lib().s2vt_split_grad_workspace_bytes(C.byref(dims), B, N)
+    assert nbytes > 0, "bad dims / B / N (N must be a multiple of B)"
+    return workspace(nbytes, device, "split_grad")
+
+
 def bptt_bwd(dims: Dims, params: Params, grads: Params, video, N: int, dlogits, ws, keep=1.0, seed=0, video_id=None,
              sample_id=None, phase=0, steps=None, live=None, precision="fp32"):
     """phase 0 = the whole backward; 1 = vocab projection only; 2 = the rest (data-parallel overlap).
@@ -349,10 +356,12 @@ def bptt_bwd(dims: Dims, params: Params, grads: Params, video, N: int, dlogits, 
                                        _ptr(sample_id), _ptr(ws), ws.numel(), phase, _ptr(bws), bws.numel(), _stream()),
               "s2vt_bptt_bwd_bf16")
         return
-    check(lib().s2vt_bptt_bwd_live(C.byref(dims), C.byref(params), C.byref(grads), _ptr(video), video.shape[0], N, _ptr(dlogits),
-                                   steps, _ptr(live), 0 if live is None else live.numel(), float(keep), seed, _ptr(video_id),
-                                   _ptr(sample_id), _ptr(ws), ws.numel(), phase, _stream()),
-          "s2vt_bptt_bwd")
+    # fp32: the split-bf16 products (s2vt_bptt_bwd_split; its fp32-MFMA body at <= 256 rows)
+    sws = split_grad_workspace(dims, video.shape[0], N, video.device)
+    check(lib().s2vt_bptt_bwd_split(C.byref(dims), C.byref(params), C.byref(grads), _ptr(video), video.shape[0], N, _ptr(dlogits),
+                                    steps, _ptr(live), 0 if live is None else live.numel(), float(keep), seed, _ptr(video_id),
+                                    _ptr(sample_id), _ptr(ws), ws.numel(), phase, _ptr(sws), sws.numel(), _stream()),
+          "s2vt_bptt_bwd_split")
 
 
 def cast_bf16(src, rowidx=None, transpose=False, pad_rows=None, colsum=None, row_copy=False):
@@ -380,6 +389,53 @@ def cast_bf16(src, rowidx=None, transpose=False, pad_rows=None, colsum=None, row
     check(lib().s2vt_cast_bf16(_ptr(src), src.stride(0), _ptr(rowidx), R, Cc, 1, _ptr(out), Rp, Rp, _ptr(colsum), _ptr(rows), Kp,
                                _ptr(scratch), 0 if scratch is None else scratch.numel(), _stream()), "s2vt_cast_bf16")
     return (out, rows) if row_copy else out
+
+
+def cast_bf16_split(src, rowidx=None, transpose=False, pad_rows=None, colsum=None, row_copy=False):
+    """cast_bf16 in split form (s2vt_cast_bf16_split): returns (hi, lo), or ((hi, lo), (row_hi, row_lo)) with row_copy."""
+    _chk_f32(src, colsum)
+    assert src.dim() == 2 and src.stride(1) == 1
+    if rowidx is not None:
+        assert rowidx.is_cuda and rowidx.dtype == torch.int32 and rowidx.is_contiguous()
+    R = src.shape[0] if rowidx is None else rowidx.numel()
+    Cc = src.shape[1]
+    Kp = (Cc + 63) // 64 * 64
+    dev = src.device
+    if not transpose:
+        hi = torch.empty((R, Kp), dtype=torch.bfloat16, device=dev)
+        lo = torch.empty_like(hi)
+        check(lib().s2vt_cast_bf16_split(_ptr(src), src.stride(0), _ptr(rowidx), R, Cc, 0, _ptr(hi), _ptr(lo), Kp, 0, None, None, None, 0,
+                                         None, 0, _stream()), "s2vt_cast_bf16_split")
+        return hi, lo
+    Rp = (R + 63) // 64 * 64 if pad_rows is None else int(pad_rows)
+    hi = torch.empty((Cc, Rp), dtype=torch.bfloat16, device=dev)
+    lo = torch.empty_like(hi)
+    rh = torch.empty((R, Kp), dtype=torch.bfloat16, device=dev) if row_copy else None
+    rl = torch.empty((R, Kp), dtype=torch.bfloat16, device=dev) if row_copy else None
+    scratch = workspace(4 * ((Rp + 255) // 256) * Cc, dev, "cast_bf16") if colsum is not None else None
+    check(lib().s2vt_cast_bf16_split(_ptr(src), src.stride(0), _ptr(rowidx), R, Cc, 1, _ptr(hi), _ptr(lo), Rp, Rp, _ptr(colsum), _ptr(rh),
+                                     _ptr(rl), Kp, _ptr(scratch), 0 if scratch is None else scratch.numel(), _stream()), "s2vt_cast_bf16_split")
+    return ((hi, lo), (rh, rl)) if row_copy else (hi, lo)
+
+
+def gemm_bf16x3_nt(Ah, Al, Bh, Bl, out=None, accumulate=False, split_k=True):
+    """C[M, N] (+)= Ah Bh^T + Ah Bl^T + Al Bh^T on split-bf16 operands [M | N, Kp] (Kp % 64 == 0), fp32 accumulation
+    (s2vt_gemm_bf16x3_nt).  split_k: give it the scratch that lets it split the reduction where its tiles do not fill the chip."""
+    for t in (Ah, Al, Bh, Bl):
+        assert t.is_cuda and t.dtype == torch.bfloat16 and t.stride(1) == 1
+    assert Ah.shape == Al.shape and Bh.shape == Bl.shape and Ah.stride(0) == Al.stride(0) and Bh.stride(0) == Bl.stride(0)
+    M, Kp = Ah.shape
+    N = Bh.shape[0]
+    if out is None:
+        assert not accumulate
+        out = torch.empty((M, N), dtype=torch.float32, device=Ah.device)
+    _chk_f32(out)
+    assert out.shape[0] == M and out.shape[1] == N and out.stride(1) == 1
+    scratch = workspace(32 * M * N, Ah.device, "gemm_bf16x3") if split_k and M * N else None
+    check(lib().s2vt_gemm_bf16x3_nt(_ptr(Ah), _ptr(Al), Ah.stride(0), _ptr(Bh), _ptr(Bl), Bh.stride(0), _ptr(out), out.stride(0), M, N, Kp,
+                                    int(bool(accumulate)), _ptr(scratch), 0 if scratch is None else scratch.numel(), _stream()),
+          "s2vt_gemm_bf16x3_nt")
+    return out
 
 
 def gemm_bf16_nt(A, B, out=None, accumulate=False, mfma=0, n=None):
