@@ -347,8 +347,8 @@ int s2vt_gemm_bf16_nt(const uint16_t* A, int32_t lda, const uint16_t* B, int32_t
 /* ---- split-bf16 products of the backward's gradient contractions (the default fp32 mode's arithmetic) ----------
  * s2vt_bptt_bwd_split is s2vt_bptt_bwd_live with each gradient contraction A.B^T computed from split operands -- hi = bf16(x),
  * lo = bf16(x - hi), both round to nearest even -- as Ahi.Bhi^T + Ahi.Blo^T + Alo.Bhi^T on bf16 MFMA with fp32 accumulation (about
- * 3 x 2^-18 of |x.y| per product); the recurrences, dropout, the embedding scatter, the bias gradients (fp32 column sums), clip and
- * Adam stay fp32, and ids, logits, NLL and loss are those of s2vt_bptt_bwd_live.  At N <= 256 rows it runs s2vt_bptt_bwd_live's
+ * 3 x 2^-18 of |x.y| per product); the recurrences, dropout, the embedding scatter, the other bias gradients (fp32 column sums), clip
+ * and Adam stay fp32, and ids, logits, NLL and loss are those of s2vt_bptt_bwd_live.  At N <= 256 rows it runs s2vt_bptt_bwd_live's
  * fp32 body (the gated side-stream overlap); so does every shape when the environment sets S2VT_SPLIT_GRADS=0 (read once) -- then
  * bit-identical to s2vt_bptt_bwd_live.  Deterministic, no atomics.  split_ws: a scratch of its own (256-byte aligned) of
  * s2vt_split_grad_workspace_bytes(d, B, N) bytes (0 on bad arguments): about twice the bf16 mode's -- 0.7 GB at BASELINE
@@ -369,6 +369,38 @@ int s2vt_cast_bf16_split(const float* src, int32_t ld, const int32_t* rowidx, in
  * order, when scratch holds them (4 x slabs x M x N bytes; 32 x M x N always suffices); with less it is not split. */
 int s2vt_gemm_bf16x3_nt(const uint16_t* Ah, const uint16_t* Al, int32_t lda, const uint16_t* Bh, const uint16_t* Bl, int32_t ldb, float* C,
                         int32_t ldc, int32_t M, int32_t N, int32_t Kp, int32_t accumulate, void* scratch, size_t scratch_bytes, s2vt_stream stream);
+
+/* The K-major form of s2vt_gemm_bf16x3_nt, for products that sum over the ROW index of both operands (weight gradients) without
+ * transposed copies: C[M,N] (+)= sum over k < K of A[k][m].B[k][n] with the same three products, planes stored by rows -- A as
+ * [K][lda], B as [K][ldb] (lda >= M, ldb >= N, both % 8 == 0, 16-byte aligned; K is any count: rows >= K are never read; the
+ * columns of a row up to the next multiple of 128 may be read, which stays inside the planes or reads zeros; (K + 65).ld.2 bytes
+ * must stay below 2 GiB).  The same K steps and accumulation order as the NT form: on planes that are each other's transposes the two
+ * return the same bits.  bias (optional, [N]): the caller has put ones into column M of A's hi plane and zeros into that of its lo
+ * plane (lda > M); the product's row M -- the column sums of B -- is ADDED to bias, whatever `accumulate` says.  scratch as for the
+ * NT form, counting M + 1 rows with a bias. */
+int s2vt_gemm_bf16x3_tn(const uint16_t* Ah, const uint16_t* Al, int32_t lda, const uint16_t* Bh, const uint16_t* Bl, int32_t ldb, float* C,
+                        int32_t ldc, int32_t M, int32_t N, int32_t K, int32_t accumulate, float* bias, void* scratch, size_t scratch_bytes,
+                        s2vt_stream stream);
+/* The fused form of the split mode (the default; S2VT_SPLIT_FUSED=0, read once, restores transposed casts + NT products everywhere):
+ * every weight gradient runs K-major on operands cast by rows, the bias gradients embed_word_b and lstm2_b ride in their weight's
+ * product as a row of ones (sums of hi + lo, 2^-17 relative per term, fixed order), and dlogits can reach the backward as planes:
+ *  - s2vt_split_grad_active(N): 1 when s2vt_bptt_bwd_split at N unrolled rows runs this form (N > 256, both knobs on), else 0.
+ *  - s2vt_softmax_nll_fwd_bwd_split: s2vt_softmax_nll_fwd_bwd (smoothing_rows == NULL) or _rows (smoothing_rows given, `smoothing`
+ *    ignored) with the same nll / lp_target bits, but dlogits -- the same fp32 values -- is written as hi / lo planes
+ *    [R][bf16_pad(V)] (pad columns zero) into split_ws, where s2vt_bptt_bwd_split(d, ..., B, N, ...) of the same d, B, N reads it,
+ *    and `logits` is left unchanged.  Returns 0 then.  Returns 1 where the shape is not the in-register softmax kernel's (V % 4,
+ *    V > 12288, ld % 4, alignment): dlogits is then written in place as fp32, exactly as the unfused entries do, and must be passed
+ *    to the backward.  Requires s2vt_split_grad_active(N), V == d->n_words and R <= n_caption_lstm_step x N.
+ *  - s2vt_bptt_bwd_split with dlogits == NULL: "the planes are in split_ws".  They are read by phase 0 and phase 1 only, with the R
+ *    rows (all unrolled rows, or n_live) the softmax call wrote; phases 3 and 4 reuse that region of split_ws, so the vocabulary
+ *    phase runs first -- and nothing else may use split_ws between the softmax call and it.  (Phases 2, 3 and 4 do not read dlogits
+ *    and accept the same NULL.)  NULL where this form is not active (s2vt_split_grad_active(N) == 0) is a bad argument.
+ *  - s2vt_split_grad_dlogits_planes: where in split_ws those planes lie (byte offsets of the hi and lo plane, elements per row). */
+int s2vt_split_grad_active(int32_t N);
+int s2vt_split_grad_dlogits_planes(const s2vt_dims* d, int32_t B, int32_t N, size_t* hi_offset, size_t* lo_offset, int32_t* ld);
+int s2vt_softmax_nll_fwd_bwd_split(float* logits, int32_t ld, int32_t R, int32_t V, const int32_t* target, const float* coef, float smoothing,
+                                   const float* smoothing_rows, float* nll, float* lp_target, const s2vt_dims* d, int32_t B, int32_t N,
+                                   void* split_ws, size_t split_ws_bytes, s2vt_stream stream);
 
 /* Gradient w.r.t. the frame features, for the end-to-end scripts where they are the CNN's output
  * (e2e_tf_s2vt.py:106-121,163-166: the optimizer differentiates through `video` into Inception-ResNet-v2):

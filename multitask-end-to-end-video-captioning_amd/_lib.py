@@ -99,6 +99,10 @@ SIGNATURES = {
     "s2vt_bptt_bwd_split": (C.c_int, [_DP, _PP, _PP, _vp, _i32, _i32, _vp, _i32, _vp, _i32, _f32, _u64, _vp, _vp, _vp, _sz, _i32, _vp, _sz, _vp]),
     "s2vt_cast_bf16_split": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _sz, _vp]),
     "s2vt_gemm_bf16x3_nt": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _sz, _vp]),
+    "s2vt_gemm_bf16x3_tn": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _sz, _vp]),
+    "s2vt_split_grad_active": (C.c_int, [_i32]),
+    "s2vt_split_grad_dlogits_planes": (C.c_int, [_DP, _i32, _i32, C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_i32)]),
+    "s2vt_softmax_nll_fwd_bwd_split": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _f32, _vp, _vp, _vp, _DP, _i32, _i32, _vp, _sz, _vp]),
     "s2vt_bptt_bwd_steps": (C.c_int, [_DP, _PP, _PP, _vp, _i32, _i32, _vp, _i32, _f32, _u64, _vp, _vp, _vp, _sz, _i32, _vp]),
     "s2vt_softmax_nll_fwd_bwd": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _f32, _vp, _vp, _vp]),
     "s2vt_softmax_unshifted_argmax": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _vp]),

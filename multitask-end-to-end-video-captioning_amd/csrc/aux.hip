@@ -312,10 +312,13 @@ __global__ __launch_bounds__(256) void softmax_nll_kernel(float* logits, int ld,
 // The same arithmetic, in the same per-thread order, with the row held in REGISTERS: thread t owns the float4s
 // t, t+256, ... (NV4 of them, V <= 1024*NV4), loads them once, keeps exp(l - max) from the sum pass for the gradient
 // pass -- HBM and L2 see one read and one write of the row, and each element costs one exp instead of two.
-template <int NV4>
+// SPLIT: the same loads, reductions and gradient arithmetic (nll, lp_t and every dlogits value keep their bits), but the gradient
+// leaves as the split-bf16 planes the backward's products read -- hi[row][c] = bf16(d), lo[row][c] = bf16(d - hi), rows ldp apart,
+// columns V .. bf16_pad(V) - 1 zeroed -- and the logits are left as they were.
+template <int NV4, bool SPLIT>
 __global__ __launch_bounds__(256) void softmax_nll_reg_kernel(float* logits, int ld, int V, const int32_t* target,
                                                               const float* coef, float smoothing_all, const float* smooth_rows,
-                                                              float* nll, float* lp_t)
+                                                              float* nll, float* lp_t, uint16_t* hi, uint16_t* lo, int ldp)
 {
     const float smoothing = smooth_rows ? smooth_rows[blockIdx.x] : smoothing_all;
     __shared__ float sh[8];
@@ -375,9 +378,42 @@ __global__ __launch_bounds__(256) void softmax_nll_reg_kernel(float* logits, int
                 const float d = cf * (1.0f - smoothing);
                 if (tg == b) v.x -= d; else if (tg == b + 1) v.y -= d; else if (tg == b + 2) v.z -= d; else v.w -= d;
             }
-            reinterpret_cast<float4*>(l)[i] = v;
+            if constexpr (SPLIT) {
+                uint2 h, w;
+                split2(v.x, v.y, h.x, w.x); split2(v.z, v.w, h.y, w.y);
+                reinterpret_cast<uint2*>(hi + (size_t)row * ldp)[i] = h;
+                reinterpret_cast<uint2*>(lo + (size_t)row * ldp)[i] = w;
+            } else {
+                reinterpret_cast<float4*>(l)[i] = v;
+            }
         }
     }
+    if constexpr (SPLIT) {
+        const int i = V4 + tid;                   // (at most 15 groups of 4 pad columns)
+        if (i < bf16_pad(V) / 4) {
+            reinterpret_cast<uint2*>(hi + (size_t)row * ldp)[i] = make_uint2(0u, 0u);
+            reinterpret_cast<uint2*>(lo + (size_t)row * ldp)[i] = make_uint2(0u, 0u);
+        }
+    }
+}
+
+bool softmax_nll_split_ok(const float* logits, int ld, int V, const uint16_t* hi, const uint16_t* lo, int ldp)
+{
+    return (ld & 3) == 0 && (V & 3) == 0 && V > 0 && V <= 1024 * 12 && (reinterpret_cast<uintptr_t>(logits) & 15) == 0 && ldp >= bf16_pad(V) &&
+           (ldp & 3) == 0 && ((reinterpret_cast<uintptr_t>(hi) | reinterpret_cast<uintptr_t>(lo)) & 7) == 0;
+}
+
+hipError_t launch_softmax_nll_split(const float* logits, int ld, int R, int V, const int32_t* target, const float* coef, float smoothing, float* nll,
+                                    float* lp_t, uint16_t* hi, uint16_t* lo, int ldp, hipStream_t st, const float* smooth_rows)
+{
+    if (R <= 0) return hipSuccess;
+    if (!softmax_nll_split_ok(logits, ld, V, hi, lo, ldp)) return hipErrorInvalidValue;
+    float* const l = const_cast<float*>(logits);  // (never written on this path)
+    if (V <= 1024 * 4)
+        hipLaunchKernelGGL((softmax_nll_reg_kernel<4, true>), dim3(R), dim3(256), 0, st, l, ld, V, target, coef, smoothing, smooth_rows, nll, lp_t, hi, lo, ldp);
+    else
+        hipLaunchKernelGGL((softmax_nll_reg_kernel<12, true>), dim3(R), dim3(256), 0, st, l, ld, V, target, coef, smoothing, smooth_rows, nll, lp_t, hi, lo, ldp);
+    return hipGetLastError();
 }
 
 hipError_t launch_softmax_nll(float* logits, int ld, int R, int V, const int32_t* target, const float* coef,
@@ -386,9 +422,11 @@ hipError_t launch_softmax_nll(float* logits, int ld, int R, int V, const int32_t
     if (R <= 0) return hipSuccess;
     const bool vec = (ld & 3) == 0 && (V & 3) == 0 && (reinterpret_cast<uintptr_t>(logits) & 15) == 0;
     if (vec && V <= 1024 * 4)
-        hipLaunchKernelGGL(softmax_nll_reg_kernel<4>, dim3(R), dim3(256), 0, st, logits, ld, V, target, coef, smoothing, smooth_rows, nll, lp_t);
+        hipLaunchKernelGGL((softmax_nll_reg_kernel<4, false>), dim3(R), dim3(256), 0, st, logits, ld, V, target, coef, smoothing, smooth_rows, nll, lp_t,
+                           (uint16_t*)nullptr, (uint16_t*)nullptr, 0);
     else if (vec && V <= 1024 * 12)
-        hipLaunchKernelGGL(softmax_nll_reg_kernel<12>, dim3(R), dim3(256), 0, st, logits, ld, V, target, coef, smoothing, smooth_rows, nll, lp_t);
+        hipLaunchKernelGGL((softmax_nll_reg_kernel<12, false>), dim3(R), dim3(256), 0, st, logits, ld, V, target, coef, smoothing, smooth_rows, nll, lp_t,
+                           (uint16_t*)nullptr, (uint16_t*)nullptr, 0);
     else
         hipLaunchKernelGGL(softmax_nll_kernel, dim3(R), dim3(256), 0, st, logits, ld, V, target, coef, smoothing, smooth_rows, nll, lp_t);
     return hipGetLastError();

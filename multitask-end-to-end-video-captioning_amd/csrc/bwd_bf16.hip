@@ -14,39 +14,21 @@
 namespace s2vt {
 namespace {
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-// RNE, NaN kept (v_cvt_pk_bf16_f32)
-__device__ __forceinline__ uint32_t pack2(float a, float b)
-{
-    const f32x2 v = {a, b};
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
-}
-
-// split of two values: hi = bf16(x), lo = bf16(x - float(hi)), both RNE.  x - float(hi) is exact for finite x whose hi is
-// finite, so hi + lo carries 16 significant bits.  NaN: hi and lo NaN.  +-Inf, and finite x beyond the largest bf16 (x rounds to
-// +-Inf in hi): hi = +-Inf and lo = x - hi = NaN (Inf) / -+Inf (finite x) -- a product that takes such an element is NaN, where
-// fp32 arithmetic would give +-Inf or NaN (Inf) or a finite value (finite x).
-__device__ __forceinline__ void split2(float a, float b, uint32_t& hi, uint32_t& lo)
-{
-    hi = pack2(a, b);
-    lo = pack2(a - __uint_as_float(hi << 16), b - __uint_as_float(hi & 0xffff0000u));
-}
-
 // ---------------------------------------------------------------------------------------------
 // row form: dst[r][k] = bf16(src[row(r)][k]) for k < K, 0 for K <= k < bf16_pad(K).  One 16-byte store per 8 elements.
-// SPLIT: dst the hi plane, dst_lo the lo plane (same ldd).
+// SPLIT: dst the hi plane, dst_lo the lo plane (same ldd).  ones: the row is bf16_pad(K + 1) wide and column K holds 1 (hi 1, lo 0) -- as
+// the K-major operand A of gemm_bf16x3_tn it makes output row K the column sums of B (a bias gradient riding in the product).
 // ---------------------------------------------------------------------------------------------
 template <bool SPLIT>
 __global__ __launch_bounds__(256) void cast_rows_bf16_kernel(const float* __restrict__ src, int ld, const int32_t* __restrict__ rowidx,
                                                              int R, int K, uint16_t* __restrict__ dst, int ldd, int vec,
-                                                             uint16_t* __restrict__ dst_lo)
+                                                             uint16_t* __restrict__ dst_lo, int ones)
 {
-    const int cpr = bf16_pad(K) / 8;
+    const int cpr = bf16_pad(K + ones) / 8;
     const long total = (long)R * cpr;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
         const int r = (int)(i / cpr), k0 = (int)(i % cpr) * 8;
@@ -57,7 +39,7 @@ __global__ __launch_bounds__(256) void cast_rows_bf16_kernel(const float* __rest
             v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
         } else {
 #pragma unroll
-            for (int j = 0; j < 8; ++j) v[j] = k0 + j < K ? s[j] : 0.0f;
+            for (int j = 0; j < 8; ++j) v[j] = k0 + j < K ? s[j] : ones && k0 + j == K ? 1.0f : 0.0f;
         }
         uint4 o;
         if constexpr (SPLIT) {
@@ -286,22 +268,39 @@ __global__ __launch_bounds__(256) void gemm_bf16_nt_kernel(GemmBf16Args g)
 // up to three K steps in flight and publish K step k + 1 at barrier k (counted vmcnt, raw s_barrier); the MFMA waves read K
 // step k + 1's fragments while they multiply K step k's, and free K step k's ring slot at barrier k.  LDS images are linear per
 // DMA instruction (16 rows x 64 bytes); the 16-byte k groups of a row are XOR-swizzled by (row >> 2) & 3 on the SOURCE address, so a
-// fragment read (16 rows, one k group each) covers all 64 banks.  Out-of-range rows load zeros (buffer range check).  Split-K
+// fragment read (16 rows, one k group each) covers all 64 banks.  (The LDS serves a ds_read_b128 in four 16-lane groups that mix two k
+// groups, and this swizzle is 2-way there: SQ_LDS_BANK_CONFLICT = 4 cycles per read.  The swizzle -(row >> 2) & 3 measured 0 conflicts
+// and the same kernel times -- the reads are not what the kernel waits for, profiles/NOTES.md -- so it stays as it was.)  Out-of-range rows load zeros (buffer range check).  Split-K
 // (blockIdx.y = slab of nk_slab K steps): slab s writes its partial tile to part + s * M * N, and reduce_slabs_kernel adds the
 // slabs in slab order -- deterministic, no atomics.
+//
+// TN = true, gemm_bf16x3_tn: C[M,N] (+)= sum_k A[k][m] B[k][n], the planes stored by rows of the REDUCTION index ([K][lda], [K][ldb]: a
+// weight gradient's operands as they lie in memory, no transposed copies).  Same tile, ring, waits, K steps and MFMA order -- on planes
+// that are each other's transposes TN and NT give the same bits.  A plane's K step is the LDS image [32 k][128 m] (256-byte k rows, one
+// DMA instruction = 4 k rows); the MFMA waves take a 16x16x32 operand with two transposed reads (ds_read_b64_tr_b16: a 16-lane group
+// g reads k rows 8g .. 8g+3, then 8g+4 .. 8g+7, of its 16 columns).  The 32-byte column blocks of k row k are XOR-permuted by
+// (k & 3) | ((k >> 1) & 4) on the SOURCE address: the 8 k rows a 32-lane half reads lie in 8 distinct blocks = all 64 banks.  k rows
+// past K load zeros (buffer range check: the descriptor ends behind row K - 1); a tile's columns past lda / ldb come from the next
+// row and only reach outputs that are not stored.  bias (optional): output row M -- the product of A's column M, which the caller
+// filled with ones (cast_rows_bf16 ones) -- is added to bias[n] instead of a C row: the column sums of B.
 // ---------------------------------------------------------------------------------------------
 struct GemmX3Args {
     const uint16_t *Ah, *Al; int lda; const uint16_t *Bh, *Bl; int ldb; float* C; int ldc;
     int M, N, nk, nk_slab, accumulate, tiles_m, tiles_n;
-    float* part;                                      // split-K slabs [slabs][M][N], or nullptr: the tile goes to C
+    float* part;                                      // split-K slabs [slabs][Mo][N], or nullptr: the tile goes to C
+    int K;                                            // TN: rows of the planes
+    float* bias; int Mo;                              // TN: optional [N] += output row M; Mo = M + (bias ? 1 : 0) output rows (NT: Mo = M)
 };
 
 constexpr int kX3BK = 32, kX3Slots = 4, kX3Plane = kTile * kX3BK;   // a plane's K step: 128 rows x 32 bf16 = 8 KB
 constexpr int kX3Lds = kX3Slots * 4 * kX3Plane * 2;                  // 128 KB: one workgroup per CU
 constexpr int kX3Dma = kTile / 16;                                   // DMA instructions per plane per K step (per loader wave)
 typedef __attribute__((address_space(3))) void* x3_lds_ptr;
+typedef short i16x4 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(3))) i16x4* x3_tr_ptr;
 
-__global__ __launch_bounds__(512) void gemm_bf16x3_nt_kernel(GemmX3Args g)
+template <bool TN>
+__global__ __launch_bounds__(512) void gemm_bf16x3_kernel(GemmX3Args g)
 {
     extern __shared__ __attribute__((aligned(16))) uint16_t x3lds[];   // [slot][plane][128 rows][32]
     const int nwg = g.tiles_m * g.tiles_n, orig = blockIdx.x;
@@ -317,21 +316,40 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_nt_kernel(GemmX3Args g)
         const int p = w - 4;
         const uint16_t* const plane = p == 0 ? g.Ah : p == 1 ? g.Al : p == 2 ? g.Bh : g.Bl;
         const int r0 = p < 2 ? m0 : n0, rows = p < 2 ? g.M : g.N, ld = p < 2 ? g.lda : g.ldb;
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(plane + (size_t)r0 * ld), 0, (int)kOob, 0x00020000);
-        // lane -> (row lane >> 2 of a 16-row block, LDS 16-byte slot lane & 3): loads k group (lane & 3) ^ ((row >> 2) & 3)
-        const int rr = lane >> 2, kg = (lane & 3) ^ ((rr >> 2) & 3);
+        // NT: the descriptor starts at the tile's first row; TN: at its first column, and ends behind k row K - 1
+        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(plane + (TN ? (size_t)r0 : (size_t)r0 * ld)), 0,
+                                                                            TN ? (int)(((uint32_t)g.K * (uint32_t)ld - (uint32_t)r0) * 2u) : (int)kOob, 0x00020000);
         uint32_t voff[kX3Dma];
+        if constexpr (TN) {
+            // lane -> (k row lane >> 4 of a 4-row block, LDS 16-byte slot s = lane & 15): loads the 16-byte piece s & 1 of column block
+            // (s >> 1) ^ swz(k), swz(k) = (k & 3) | ((k >> 1) & 4) = kr | ((b & 2) << 1) for k = 4 b + kr
+            const int kr = lane >> 4, s = lane & 15;
 #pragma unroll
-        for (int b = 0; b < kX3Dma; ++b) {
-            const int r = b * 16 + rr;
-            voff[b] = r0 + r < rows ? (uint32_t)(r * ld + kg * 8) * 2u : kOob;
+            for (int b = 0; b < kX3Dma; ++b)
+                voff[b] = (uint32_t)((b * 4 + kr) * ld + ((((s >> 1) ^ (kr | ((b & 2) << 1))) << 1) | (s & 1)) * 8) * 2u;
+        } else {
+            // lane -> (row lane >> 2 of a 16-row block, LDS 16-byte slot lane & 3): loads k group (lane & 3) ^ ((row >> 2) & 3)
+            const int rr = lane >> 2, kg = (lane & 3) ^ ((rr >> 2) & 3);
+#pragma unroll
+            for (int b = 0; b < kX3Dma; ++b) {
+                const int r = b * 16 + rr;
+                voff[b] = r0 + r < rows ? (uint32_t)(r * ld + kg * 8) * 2u : kOob;
+            }
         }
         auto issue = [&](int ks) __attribute__((always_inline)) {
             uint16_t* const dst = x3lds + ((ks % kX3Slots) * 4 + p) * kX3Plane;
-            const uint32_t soff = (uint32_t)(kbeg + ks) * kX3BK * 2u;
+            if constexpr (TN) {
+                // (the K step goes into the VECTOR offset: that is the part of the address the range check sees)
+                const uint32_t koff = (uint32_t)(kbeg + ks) * kX3BK * (uint32_t)ld * 2u;
 #pragma unroll
-            for (int b = 0; b < kX3Dma; ++b)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (x3_lds_ptr)(dst + b * 16 * kX3BK), 16, voff[b], soff, 0, 0);
+                for (int b = 0; b < kX3Dma; ++b)
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (x3_lds_ptr)(dst + b * 4 * kTile), 16, voff[b] + koff, 0, 0, 0);
+            } else {
+                const uint32_t soff = (uint32_t)(kbeg + ks) * kX3BK * 2u;
+#pragma unroll
+                for (int b = 0; b < kX3Dma; ++b)
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (x3_lds_ptr)(dst + b * 16 * kX3BK), 16, voff[b], soff, 0, 0);
+            }
         };
         // K steps younger than the one that must have landed: 0, 1 or 2 (x 8 DMA instructions each)
         auto wait_younger = [](int n) __attribute__((always_inline)) {
@@ -359,6 +377,9 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_nt_kernel(GemmX3Args g)
     // ================= MFMA waves
     const int wr = w >> 1, wc = w & 1;
     const int fofs = (lane & 15) * kX3BK + (((lane >> 4) ^ ((lane >> 2) & 3)) << 3);   // + 16 rows per fragment repeat
+    // TN: lane 4 q + pp of group gq addresses k row 8 gq + q (second read: + 4 rows, the same swz), elements 4 pp .. 4 pp + 3 of its block
+    const int gq = lane >> 4, tq = (lane >> 2) & 3, tswz = tq | ((gq & 1) << 2);
+    const int tofs = (gq * 8 + tq) * kTile + (lane & 3) * 4;                           // + ((column block ^ tswz) << 4) elements
     f32x4 acc[4][4];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
@@ -371,7 +392,14 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_nt_kernel(GemmX3Args g)
         for (int pl = 0; pl < 4; ++pl)
 #pragma unroll
             for (int i = 0; i < 4; ++i)
-                f[pl][i] = *reinterpret_cast<const bf16x8*>(s + pl * kX3Plane + ((pl < 2 ? wr : wc) * 64 + i * 16) * kX3BK + fofs);
+                if constexpr (TN) {
+                    const uint16_t* const a = s + pl * kX3Plane + tofs + ((((pl < 2 ? wr : wc) * 4 + i) ^ tswz) << 4);
+                    const i16x4 lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((x3_tr_ptr)a);
+                    const i16x4 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((x3_tr_ptr)(a + 4 * kTile));
+                    f[pl][i] = __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo4, hi4, 0, 1, 2, 3, 4, 5, 6, 7));
+                } else {
+                    f[pl][i] = *reinterpret_cast<const bf16x8*>(s + pl * kX3Plane + ((pl < 2 ? wr : wc) * 64 + i * 16) * kX3BK + fofs);
+                }
     };
     auto mul = [&](const bf16x8 (&f)[4][4]) __attribute__((always_inline)) {
         // small products first, each pass over all 16 accumulators (no back-to-back dependent MFMAs)
@@ -402,7 +430,7 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_nt_kernel(GemmX3Args g)
         step(k, fa, fb);
         step(k + 1, fb, fa);
     }
-    float* const out = g.part ? g.part + (size_t)blockIdx.y * g.M * g.N : g.C;
+    float* const out = g.part ? g.part + (size_t)blockIdx.y * g.Mo * g.N : g.C;
     const int ldo = g.part ? g.N : g.ldc;
     const bool add = !g.part && g.accumulate;
 #pragma unroll
@@ -415,34 +443,43 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_nt_kernel(GemmX3Args g)
                 if (row < g.M && col < g.N) {
                     float* c = out + (size_t)row * ldo + col;
                     *c = add ? *c + acc[i][j][e] : acc[i][j][e];
+                } else if (TN && row == g.M && g.bias && col < g.N) {
+                    if (g.part) out[(size_t)row * ldo + col] = acc[i][j][e];
+                    else g.bias[col] += acc[i][j][e];                      // (a bias gradient accumulates, as its weight's)
                 }
             }
 }
 
-// C (+)= sum over slabs of part[s] (slab order)
+// C (+)= sum over slabs of part[s] (slab order); slab row M (Mo = M + 1 rows, gemm_bf16x3_tn's bias row) is ADDED to bias
 __global__ __launch_bounds__(256) void reduce_slabs_kernel(const float* __restrict__ part, int slabs, int M, int N, float* __restrict__ C, int ldc,
-                                                           int accumulate)
+                                                           int accumulate, int Mo, float* __restrict__ bias)
 {
-    const size_t MN = (size_t)M * N;
+    const size_t MN = (size_t)Mo * N;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < MN; i += (size_t)gridDim.x * 256) {
         float s = part[i];
         for (int k = 1; k < slabs; ++k) s += part[(size_t)k * MN + i];
-        float* c = C + (i / N) * ldc + i % N;
-        *c = accumulate ? *c + s : s;
+        const size_t r = i / N;
+        if (r < (size_t)M) {
+            float* c = C + r * ldc + i % N;
+            *c = accumulate ? *c + s : s;
+        } else {
+            bias[i % N] += s;
+        }
     }
 }
 }  // namespace
 
 hipError_t launch_cast_rows_bf16(const float* src, int ld, const int32_t* rowidx, int R, int K, uint16_t* dst, int ldd, hipStream_t st,
-                                 uint16_t* dst_lo)
+                                 uint16_t* dst_lo, int ones)
 {
     if (R <= 0 || K <= 0) return hipSuccess;
+    ones = ones ? 1 : 0;
     const int vec = !((reinterpret_cast<uintptr_t>(src) & 15) || (ld & 3));
-    const long chunks = (long)R * (bf16_pad(K) / 8);
+    const long chunks = (long)R * (bf16_pad(K + ones) / 8);
     const long blocks = (chunks + 255) / 256;
     const dim3 grid((unsigned)(blocks < 8192 ? blocks : 8192));
-    if (dst_lo) hipLaunchKernelGGL(cast_rows_bf16_kernel<true>, grid, dim3(256), 0, st, src, ld, rowidx, R, K, dst, ldd, vec, dst_lo);
-    else hipLaunchKernelGGL(cast_rows_bf16_kernel<false>, grid, dim3(256), 0, st, src, ld, rowidx, R, K, dst, ldd, vec, dst_lo);
+    if (dst_lo) hipLaunchKernelGGL(cast_rows_bf16_kernel<true>, grid, dim3(256), 0, st, src, ld, rowidx, R, K, dst, ldd, vec, dst_lo, ones);
+    else hipLaunchKernelGGL(cast_rows_bf16_kernel<false>, grid, dim3(256), 0, st, src, ld, rowidx, R, K, dst, ldd, vec, dst_lo, ones);
     return hipGetLastError();
 }
 
@@ -503,18 +540,23 @@ size_t gemm_bf16x3_part_floats(int M, int N, int Kp)
     return s > 1 ? (size_t)s * M * N : 0;
 }
 
-hipError_t launch_gemm_bf16x3_nt(const uint16_t* Ah, const uint16_t* Al, int lda, const uint16_t* Bh, const uint16_t* Bl, int ldb, float* C, int ldc,
-                                 int M, int N, int Kp, int accumulate, float* part, size_t part_floats, int cls, hipStream_t st)
+namespace {
+// the launch of either form (TN: Kp = the planes' K rows, any count; NT: Kp % 64 == 0)
+template <bool TN>
+hipError_t launch_x3(const uint16_t* Ah, const uint16_t* Al, int lda, const uint16_t* Bh, const uint16_t* Bl, int ldb, float* C, int ldc, int M, int N,
+                     int Kp, int accumulate, float* bias, float* part, size_t part_floats, int cls, hipStream_t st)
 {
     if (M <= 0 || N <= 0) return hipSuccess;
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_bf16x3_nt_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kX3Lds);
+    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_bf16x3_kernel<TN>), hipFuncAttributeMaxDynamicSharedMemorySize, kX3Lds);
     if (attr != hipSuccess) return attr;
     GemmX3Args g;
     g.Ah = Ah; g.Al = Al; g.lda = lda; g.Bh = Bh; g.Bl = Bl; g.ldb = ldb; g.C = C; g.ldc = ldc; g.M = M; g.N = N;
-    g.nk = Kp / kX3BK; g.accumulate = accumulate;
-    g.tiles_m = (M + kTile - 1) / kTile; g.tiles_n = (N + kTile - 1) / kTile;
-    int slabs = part ? gemm_bf16x3_slabs(M, N, Kp) : 1;
-    if ((size_t)slabs * M * N > part_floats) slabs = 1;
+    g.K = Kp; g.bias = bias; g.Mo = M + (bias ? 1 : 0);
+    const int Kr = bf16_pad(Kp);
+    g.nk = Kr / kX3BK; g.accumulate = accumulate;
+    g.tiles_m = (g.Mo + kTile - 1) / kTile; g.tiles_n = (N + kTile - 1) / kTile;
+    int slabs = part ? gemm_bf16x3_slabs(g.Mo, N, Kr) : 1;
+    if ((size_t)slabs * g.Mo * N > part_floats) slabs = 1;
     g.nk_slab = ((g.nk + slabs - 1) / slabs + 1) & ~1;                    // >= nk / slabs (so no more slabs than the scratch holds), even:
     slabs = g.nk_slab ? (g.nk + g.nk_slab - 1) / g.nk_slab : 1;           // the MFMA loop takes K steps in pairs
     g.part = slabs > 1 ? part : nullptr;
@@ -526,17 +568,38 @@ hipError_t launch_gemm_bf16x3_nt(const uint16_t* Ah, const uint16_t* Al, int lda
         if (pe != hipSuccess) return pe;
         (void)hipEventRecord(e0, st);
     }
-    hipLaunchKernelGGL(gemm_bf16x3_nt_kernel, grid, dim3(512), kX3Lds, st, g);
+    hipLaunchKernelGGL(gemm_bf16x3_kernel<TN>, grid, dim3(512), kX3Lds, st, g);
     if (slabs > 1) {
-        const size_t MN = (size_t)M * N, blocks = (MN + 255) / 256;
+        const size_t MN = (size_t)g.Mo * N, blocks = (MN + 255) / 256;
         hipLaunchKernelGGL(reduce_slabs_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, st, (const float*)part, slabs, M, N, C, ldc,
-                           accumulate);
+                           accumulate, g.Mo, bias);
     }
     if (prof) {
         (void)hipEventRecord(e1, st);
         prof_record(cls, 16, cls == 3 ? "x3_128x128(dma) wgrad" : "x3_128x128(dma) dgrad", 2.0 * M * (double)N * Kp, e0, e1);
     }
     return hipGetLastError();
+}
+}  // namespace
+
+hipError_t launch_gemm_bf16x3_nt(const uint16_t* Ah, const uint16_t* Al, int lda, const uint16_t* Bh, const uint16_t* Bl, int ldb, float* C, int ldc,
+                                 int M, int N, int Kp, int accumulate, float* part, size_t part_floats, int cls, hipStream_t st)
+{
+    return launch_x3<false>(Ah, Al, lda, Bh, Bl, ldb, C, ldc, M, N, Kp, accumulate, nullptr, part, part_floats, cls, st);
+}
+
+bool gemm_bf16x3_tn_ok(int lda, int ldb, int K)
+{
+    // the loader forms byte offsets of the planes in 32 bits (K steps up to bf16_pad(K) rows, a tile's 256 bytes behind them)
+    const unsigned long long ld = (unsigned long long)(lda > ldb ? lda : ldb);
+    return K >= 0 && lda > 0 && ldb > 0 && ((unsigned long long)bf16_pad(K) + 1) * ld * 2ull + 512ull < (1ull << 31);
+}
+
+hipError_t launch_gemm_bf16x3_tn(const uint16_t* Ah, const uint16_t* Al, int lda, const uint16_t* Bh, const uint16_t* Bl, int ldb, float* C, int ldc,
+                                 int M, int N, int K, int accumulate, float* bias, float* part, size_t part_floats, int cls, hipStream_t st)
+{
+    if (!gemm_bf16x3_tn_ok(lda, ldb, K)) return hipErrorInvalidValue;
+    return launch_x3<true>(Ah, Al, lda, Bh, Bl, ldb, C, ldc, M, N, K, accumulate, bias, part, part_floats, cls, st);
 }
 
 }  // namespace s2vt

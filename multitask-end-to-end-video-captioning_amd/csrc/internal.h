@@ -271,10 +271,29 @@ hipError_t launch_attn_bwd_chain(const AttnBwdChainLaunch& a, hipStream_t st);
 // ---- the opt-in bf16 mode of the S2VT backward's gradient contractions (bwd_bf16.hip): operands cast to bf16, fp32 accumulation
 constexpr int kBf16K = 64;                            // K step of gemm_bf16_nt: a bf16 operand row holds bf16_pad(K) elements, zeros past K
 __host__ __device__ inline int bf16_pad(int k) { return (k + kBf16K - 1) / kBf16K * kBf16K; }
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+// RNE, NaN kept (v_cvt_pk_bf16_f32)
+__device__ __forceinline__ uint32_t pack2(float a, float b)
+{
+    const f32x2 v = {a, b};
+    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
+}
+
+// split of two values: hi = bf16(x), lo = bf16(x - float(hi)), both RNE.  x - float(hi) is exact for finite x whose hi is
+// finite, so hi + lo carries 16 significant bits.  NaN: hi and lo NaN.  +-Inf, and finite x beyond the largest bf16 (x rounds to
+// +-Inf in hi): hi = +-Inf and lo = x - hi = NaN (Inf) / -+Inf (finite x) -- a product that takes such an element is NaN, where
+// fp32 arithmetic would give +-Inf or NaN (Inf) or a finite value (finite x).
+__device__ __forceinline__ void split2(float a, float b, uint32_t& hi, uint32_t& lo)
+{
+    hi = pack2(a, b);
+    lo = pack2(a - __uint_as_float(hi << 16), b - __uint_as_float(hi & 0xffff0000u));
+}
 // dst[r][k] = bf16(src[row(r)][k]) (row(r) = rowidx ? rowidx[r] : r) for k < K, zeros up to bf16_pad(K); dst 16-byte aligned, ldd % 8 == 0
 // dst_lo (optional): the split form -- dst = bf16(x) (hi), dst_lo = bf16(x - hi) (lo), same ldd
+// ones: rows bf16_pad(K + 1) wide with column K = 1 -- the operand A of launch_gemm_bf16x3_tn with a bias row
 hipError_t launch_cast_rows_bf16(const float* src, int ld, const int32_t* rowidx, int R, int K, uint16_t* dst, int ldd, hipStream_t st,
-                                 uint16_t* dst_lo = nullptr);
+                                 uint16_t* dst_lo = nullptr, int ones = 0);
 // dst[c][r] = bf16(src[row(r)][c]) for r < R, zeros for R <= r < Rp (Rp a multiple of 64; dst 16-byte aligned, ldd % 8 == 0).
 // rdst (optional): the row form as well, rdst[r][c] for c < bf16_pad(C) (8-byte aligned, rldd % 4 == 0).
 // colsum (optional): += the column sums of the fp32 input rows (fixed order, no atomics), through part[cast_tr_part_floats(Rp, C)].
@@ -297,6 +316,18 @@ hipError_t launch_gemm_bf16_nt(const uint16_t* A, int lda, const uint16_t* B, in
 hipError_t launch_gemm_bf16x3_nt(const uint16_t* Ah, const uint16_t* Al, int lda, const uint16_t* Bh, const uint16_t* Bl, int ldb, float* C, int ldc,
                                  int M, int N, int Kp, int accumulate, float* part, size_t part_floats, int cls, hipStream_t st);
 size_t gemm_bf16x3_part_floats(int M, int N, int Kp);
+// The K-major form: C[M,N] (+)= sum_k A[k][m] B[k][n] over K rows of planes stored by rows ([K][lda], [K][ldb]; lda, ldb % 8 == 0, 16-byte
+// aligned; rows >= K are never read, columns up to the next multiple of 128 may be -- they lie inside the planes or read zeros).  The
+// same K steps and MFMA order as the NT form: equal bits on transposed planes.  bias (optional): A's column M holds ones (lda > M),
+// and bias[n] += the product's row M, the column sums of B; the split-K scratch then counts M + 1 rows.
+bool gemm_bf16x3_tn_ok(int lda, int ldb, int K);     // the planes' byte offsets fit the loader's 32 bits
+hipError_t launch_gemm_bf16x3_tn(const uint16_t* Ah, const uint16_t* Al, int lda, const uint16_t* Bh, const uint16_t* Bl, int ldb, float* C, int ldc,
+                                 int M, int N, int K, int accumulate, float* bias, float* part, size_t part_floats, int cls, hipStream_t st);
+// the split softmax (aux.hip): as launch_softmax_nll, but dlogits leaves as hi / lo planes [R][ldp] (ldp >= bf16_pad(V), pad columns zero)
+// and the logits stay; false: the shape is not the register kernel's (V % 4, V > 12288, alignment) -- nothing launched
+bool softmax_nll_split_ok(const float* logits, int ld, int V, const uint16_t* hi, const uint16_t* lo, int ldp);
+hipError_t launch_softmax_nll_split(const float* logits, int ld, int R, int V, const int32_t* target, const float* coef, float smoothing, float* nll,
+                                    float* lp_t, uint16_t* hi, uint16_t* lo, int ldp, hipStream_t st, const float* smooth_rows = nullptr);
 
 // order-free NN contraction for the backward data path with optional split-K slabs:
 // slab s (blockIdx.y) holds the partial over its K range at C + s * slab_stride.

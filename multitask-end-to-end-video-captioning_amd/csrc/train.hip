@@ -204,7 +204,16 @@ size_t carve_train(Carver& c, const s2vt_dims* d, int B, int N, TrainWs* out)
 // BT / AT: both operands of a weight gradient transposed ([column][reduction row], the rows of two segments -- encode steps, decode
 // steps -- each padded to the K step, so that a product over the decode steps only starts at a padded column); part: column-sum partials.
 // Split mode (s2vt_bptt_bwd_split): the same four buffers hold the hi planes, followed by a copy of their whole region for the lo
-// planes (lo of a hi pointer = that pointer + lo_delta elements), and kpart: gemm_bf16x3_nt's split-K slabs.
+// planes (lo of a hi pointer = that pointer + lo_delta elements), and kpart: gemm_bf16x3_nt's split-K slabs.  The fused form of the
+// split mode (split_fused(), the default) keeps no transposed operand: BT stays unused and AT holds the A operand of a weight gradient by
+// rows ([reduction row][bf16_pad(width + 1)], the encode rows followed by the decode rows) for gemm_bf16x3_tn, whose B operand is L.
+// S2VT_SPLIT_FUSED=0 (read once): the transposed casts and gemm_bf16x3_nt for every product, dlogits always as fp32.
+static bool split_fused()
+{
+    static const int on = [] { const char* e = getenv("S2VT_SPLIT_FUSED"); return e ? atoi(e) : 1; }();
+    return on != 0;
+}
+
 struct Bf16Ws { uint16_t *L, *W, *AT, *BT; float* part; size_t lo_delta; float* kpart; size_t kpart_floats; };
 
 size_t carve_bf16(Carver& c, const s2vt_dims* d, int B, int N, Bf16Ws* out, bool split = false)
@@ -219,14 +228,25 @@ size_t carve_bf16(Carver& c, const s2vt_dims* d, int B, int N, Bf16Ws* out, bool
     const size_t off0 = c.off;
     w.L = c.take<uint16_t>(mx({Tc * N * Kv, T * N * K4, Tv * B * K4}));
     w.W = c.take<uint16_t>(mx({H * Kv, (H + E) * K4, E * K4}));
+    const bool fused = split && split_fused();
+    const size_t Hp1 = bf16_pad((int)H + 1), Ep = bf16_pad((int)E);
+    // (BT is carved in the fused form too, though nothing is written there: the scratch size is part of the interface -- callers and
+    //  tests size buffers by "two planes of everything the bf16 mode holds" -- and S2VT_SPLIT_FUSED must not change it)
     w.BT = c.take<uint16_t>(mx({V * Kr, 4 * H * Kt, 4 * H * K1, E * ke1}));
-    w.AT = c.take<uint16_t>(mx({H * Kr, H * Kt, E * Kr, E * ke1, H * K1, D * ke1}));
+    w.AT = c.take<uint16_t>(mx({H * Kr, H * Kt, E * Kr, E * ke1, H * K1, D * ke1, fused ? T * N * Hp1 : 0, fused ? Tc * N * Ep : 0}));
     w.lo_delta = 0; w.kpart = nullptr; w.kpart_floats = 0;
     if (split) {
         const size_t hi_bytes = c.off - off0;                    // (a multiple of 256: the lo region starts right behind)
         c.take<char>(hi_bytes);
         w.lo_delta = hi_bytes / sizeof(uint16_t);
         const int Re = (int)(Tv * N), Rr = (int)(Tc * N), Re1 = (int)(Tv * B);
+        if (fused)                                               // (weight gradients: K-major, a bias row where one rides)
+            w.kpart_floats = mx({gemm_bf16x3_part_floats((int)H + 1, (int)V, (int)Kr), gemm_bf16x3_part_floats(Rr, (int)H, (int)Kv),
+                                 gemm_bf16x3_part_floats((int)H + 1, (int)(4 * H), bf16_pad((int)(T * N))),
+                                 gemm_bf16x3_part_floats((int)E, (int)(4 * H), (int)Kr),
+                                 gemm_bf16x3_part_floats((int)(T * N), (int)(H + E), (int)K4), gemm_bf16x3_part_floats(Re, (int)(H + E), (int)K4),
+                                 gemm_bf16x3_part_floats(Rr, (int)(H + E), (int)K4)});
+        else
         w.kpart_floats = mx({gemm_bf16x3_part_floats((int)H, (int)V, (int)Kr), gemm_bf16x3_part_floats(Rr, (int)H, (int)Kv),
                              gemm_bf16x3_part_floats((int)H, (int)(4 * H), (int)Kt), gemm_bf16x3_part_floats((int)E, (int)(4 * H), (int)Kr),
                              gemm_bf16x3_part_floats((int)(T * N), (int)(H + E), (int)K4), gemm_bf16x3_part_floats(Re, (int)(H + E), (int)K4),
@@ -619,7 +639,11 @@ static int bptt_bwd_body(const s2vt_dims* d, const s2vt_params* p, const s2vt_pa
     if ((live_rows == nullptr) != (n_live == 0) || n_live < 0) return S2VT_E_BADARG;
     if (bf16 && !bf16_ws) return S2VT_E_BADARG;
     if (phase < 0 || phase > 4) return S2VT_E_BADARG;
-    if (!dims_ok(d) || !params_ok(p) || !params_ok(grads) || !video || !dlogits || !workspace || B <= 0 || N <= 0 || N % B)
+    const bool fused = split && split_fused();               // no transposed operands: K-major weight gradients (carve_bf16)
+    // (fused split mode: dlogits == NULL = its planes are in bf16_ws already, s2vt_softmax_nll_fwd_bwd_split -- read by the vocabulary
+    //  phase only; phases 2 to 4 never look at dlogits and take the same NULL from a caller that runs the phases one by one)
+    if (!dlogits && !fused) return S2VT_E_BADARG;
+    if (!dims_ok(d) || !params_ok(p) || !params_ok(grads) || !video || !workspace || B <= 0 || N <= 0 || N % B)
         return S2VT_E_BADARG;
     if (reinterpret_cast<uintptr_t>(workspace) & 255u) return S2VT_E_ALIGN;
     if (bf16 && (reinterpret_cast<uintptr_t>(bf16_ws) & 255u)) return S2VT_E_ALIGN;
@@ -662,6 +686,14 @@ static int bptt_bwd_body(const s2vt_dims* d, const s2vt_params* p, const s2vt_pa
             return launch_gemm_bf16x3_nt(A, lo(A), lda, Bm, lo(Bm), ldb, Cm, ldc, M, Nn, Kp, acc, bw.kpart, bw.kpart_floats, acc ? 3 : 4, st);
         return launch_gemm_bf16_nt(A, lda, Bm, ldb, Cm, ldc, M, Nn, Kp, acc, 0, st);
     };
+    // fused split mode: a weight gradient from operands by rows, C[M, Nn] += A[K rows][M]^T B[K rows][Nn] (+ bias += B's column sums through
+    // the ones column that rows1 puts behind A's M columns)
+    auto rows1 = [&](const float* src, int ld, const int32_t* idx, int R, int K, uint16_t* dst, int ldd) -> hipError_t {
+        return launch_cast_rows_bf16(src, ld, idx, R, K, dst, ldd, st, lo(dst), 1);
+    };
+    auto mmt = [&](uint16_t* A, int lda, uint16_t* Bm, int ldb, float* Cm, int ldc, int M, int Nn, int K, float* bias) -> hipError_t {
+        return launch_gemm_bf16x3_tn(A, lo(A), lda, Bm, lo(Bm), ldb, Cm, ldc, M, Nn, K, 1, bias, bw.kpart, bw.kpart_floats, 3, st);
+    };
 
     // Phases, for data-parallel callers that start a slice's all-reduce as soon as its gradients are final:
     //   1 = the vocab projection (embed_word_W / _b final);  3 = LSTM2's recurrence + its weight gradients (lstm2_W / _b
@@ -694,7 +726,19 @@ static int bptt_bwd_body(const s2vt_dims* d, const s2vt_params* p, const s2vt_pa
         // form, so leaving them out of the reductions changes nothing and their dO2 rows are the zeros written below)
         const int R = live_rows ? n_live : Tc * N;
         float* const dO2t = live_rows ? w.dO2p : w.dO2;     // where the product lands: packed rows are scattered afterwards
-        if (bf16) {
+        // (planes too large for the K-major loader's 32-bit offsets: the transposed form, which needs dlogits as fp32 -- the split
+        //  softmax entry applies the same rule and leaves them so)
+        const bool fused_v = fused && gemm_bf16x3_tn_ok(bf16_pad(H + 1), bf16_pad(V), R);
+        if (!fused_v && !dlogits) return S2VT_E_BADARG;
+        if (fused_v) {
+            // dlogits by rows, once (or there already): dWout's B (K-major; + the bias gradient) and dO2's A
+            const int Kv = bf16_pad(V), Hp1 = bf16_pad(H + 1);
+            if (dlogits) HIP_TRY(rows(dlogits, V, nullptr, R, V, bw.L, Kv));
+            HIP_TRY(rows1(w.O2 + (size_t)Tv * NH, H, live_rows, R, H, bw.AT, Hp1));
+            HIP_TRY(mmt(bw.AT, Hp1, bw.L, Kv, grads->embed_word_W, V, H, V, R, grads->embed_word_b));
+            HIP_TRY(rows(p->embed_word_W, V, nullptr, H, V, bw.W, Kv));
+            HIP_TRY(mm(bw.L, Kv, bw.W, Kv, dO2t, H, R, H, Kv, 0));
+        } else if (bf16) {
             // dlogits once, in both forms: transposed (dWout's B, + the bias gradient) and by rows (dO2's A)
             const int Kr = bf16_pad(R), Kv = bf16_pad(V);
             HIP_TRY(tr(dlogits, V, nullptr, R, V, bw.BT, Kr, grads->embed_word_b, bw.L, Kv));
@@ -758,7 +802,23 @@ static int bptt_bwd_body(const s2vt_dims* d, const s2vt_params* p, const s2vt_pa
     // only -- launched from the lambda below once that grid is resident; dX2 keeps the chip to itself)
     if (sd != st) HIP_TRY(fork_to(st, sd, ss.ev[1]));
     auto l2_weight_grads = [&]() -> int {
-    if (bf16) {
+    if (fused && gemm_bf16x3_tn_ok(bf16_pad(H + 1) > bf16_pad(E) ? bf16_pad(H + 1) : bf16_pad(E), K4, Tv * N + (live_rows ? n_live : Tc * N))) {
+        // dZ2 once, by rows, [encode steps | decode steps (live: the packed live rows)]: the B operand of all three products (+ lstm2_b
+        // with the last) and dX2's A (phase 4); out1 / h2 by rows over the same two segments, the embedding rows over the decode one
+        const int Re = Tv * N, Rd = live_rows ? n_live : Tc * N, Hp = bf16_pad(H), Hp1 = bf16_pad(H + 1), Ep = bf16_pad(E);
+        const float* const dzd = live_rows ? w.dZ2p : w.dZ2 + (size_t)Tv * 4 * NH;
+        uint16_t* const dzd16 = bw.L + (size_t)Re * K4;
+        HIP_TRY(rows(w.dZ2, 4 * H, nullptr, Re, 4 * H, bw.L, K4));
+        HIP_TRY(rows(dzd, 4 * H, nullptr, Rd, 4 * H, dzd16, K4));
+        HIP_TRY(rows(w.O1, H, nullptr, Re, H, bw.AT, Hp));
+        HIP_TRY(rows(w.O1 + (size_t)Tv * NH, H, live_rows, Rd, H, bw.AT + (size_t)Re * Hp, Hp));
+        HIP_TRY(mmt(bw.AT, Hp, bw.L, K4, grads->lstm2_W, 4 * H, H, 4 * H, Re + Rd, nullptr));
+        HIP_TRY(rows(p->Wemb, E, live_rows ? w.prevp : w.prev, Rd, E, bw.AT, Ep));                  // Wemb [V, E] rows of the previous words
+        HIP_TRY(mmt(bw.AT, Ep, dzd16, K4, grads->lstm2_W + (size_t)H * 4 * H, 4 * H, E, 4 * H, Rd, nullptr));
+        HIP_TRY(rows1(w.H2, H, nullptr, Re, H, bw.AT, Hp1));
+        HIP_TRY(rows1(w.H2 + (size_t)Tv * NH, H, live_rows, Rd, H, bw.AT + (size_t)Re * Hp1, Hp1));
+        HIP_TRY(mmt(bw.AT, Hp1, bw.L, K4, grads->lstm2_W + (size_t)(H + E) * 4 * H, 4 * H, H, 4 * H, Re + Rd, grads->lstm2_b));
+    } else if (bf16) {
         // dZ2 once: transposed over [encode steps | decode steps (live: the packed live rows)] -- the B operand of all three products,
         // + lstm2_b -- and by rows (dX2's A, phase 4); out1 / h2 take the same two segments, the embedding rows the decode segment only
         const int Re = Tv * N, Rd = live_rows ? n_live : Tc * N, ke = bf16_pad(Re), Kd = bf16_pad(Rd), Kt = ke + Kd;
@@ -941,6 +1001,58 @@ int s2vt_bptt_bwd_split(const s2vt_dims* d, const s2vt_params* p, const s2vt_par
     if (!split_ws) return S2VT_E_BADARG;
     return bptt_bwd_body(d, p, grads, video, B, N, dlogits, caption_steps, live_rows, n_live, keep, seed, video_id, sample_id, workspace,
                          workspace_bytes, phase, split_grad_mode(N), split_ws, split_ws_bytes, stream);
+}
+
+int s2vt_split_grad_active(int32_t N)
+{
+    return split_grad_mode(N) == kGradSplit && split_fused();
+}
+
+int s2vt_softmax_nll_fwd_bwd_split(float* logits, int32_t ld, int32_t R, int32_t V, const int32_t* target, const float* coef, float smoothing,
+                                   const float* smoothing_rows, float* nll, float* lp_target, const s2vt_dims* d, int32_t B, int32_t N,
+                                   void* split_ws, size_t split_ws_bytes, s2vt_stream stream)
+{
+    if (!logits || !target || !coef || R < 0 || V <= 0 || ld < V || !dims_ok(d) || B <= 0 || N <= 0 || N % B || !split_ws) return S2VT_E_BADARG;
+    if (V != d->n_words || (size_t)R > (size_t)d->n_caption_lstm_step * N || !s2vt_split_grad_active(N)) return S2VT_E_BADARG;
+    if (reinterpret_cast<uintptr_t>(split_ws) & 255u) return S2VT_E_ALIGN;
+    Carver cb(split_ws, split_ws_bytes);
+    Bf16Ws bw{};
+    carve_bf16(cb, d, B, N, &bw, true);
+    if (!cb.ok()) return S2VT_E_WORKSPACE;
+    const int Kv = bf16_pad(V);
+    if (!softmax_nll_split_ok(logits, ld, V, bw.L, bw.L + bw.lo_delta, Kv) || !gemm_bf16x3_tn_ok(bf16_pad(d->lstm_dim + 1), Kv, R)) {
+        // not the register kernel's shape (or planes beyond the K-major product's reach): fp32 dlogits in place, for the backward to cast
+        HIP_TRY(launch_softmax_nll(logits, ld, R, V, target, coef, smoothing_rows ? 0.0f : smoothing, nll, lp_target, S(stream), smoothing_rows));
+        return 1;
+    }
+    HIP_TRY(launch_softmax_nll_split(logits, ld, R, V, target, coef, smoothing_rows ? 0.0f : smoothing, nll, lp_target, bw.L, bw.L + bw.lo_delta, Kv,
+                                     S(stream), smoothing_rows));
+    return S2VT_OK;
+}
+
+int s2vt_split_grad_dlogits_planes(const s2vt_dims* d, int32_t B, int32_t N, size_t* hi_offset, size_t* lo_offset, int32_t* ld)
+{
+    if (!dims_ok(d) || B <= 0 || N <= 0 || N % B || !hi_offset || !lo_offset || !ld) return S2VT_E_BADARG;
+    Carver cb(nullptr, 0);
+    Bf16Ws bw{};
+    carve_bf16(cb, d, B, N, &bw, true);
+    *hi_offset = 0;                                            // (L is the first region of the carve)
+    *lo_offset = bw.lo_delta * sizeof(uint16_t);
+    *ld = bf16_pad(d->n_words);
+    return S2VT_OK;
+}
+
+int s2vt_gemm_bf16x3_tn(const uint16_t* Ah, const uint16_t* Al, int32_t lda, const uint16_t* Bh, const uint16_t* Bl, int32_t ldb, float* C,
+                        int32_t ldc, int32_t M, int32_t N, int32_t K, int32_t accumulate, float* bias, void* scratch, size_t scratch_bytes,
+                        s2vt_stream stream)
+{
+    if (!Ah || !Al || !Bh || !Bl || !C || M < 0 || N < 0 || K < 0 || lda < M + (bias ? 1 : 0) || ldb < N || ldc < N || (lda & 7) || (ldb & 7))
+        return S2VT_E_BADARG;
+    if (accumulate < 0 || accumulate > 1 || (scratch_bytes && !scratch) || !gemm_bf16x3_tn_ok(lda, ldb, K)) return S2VT_E_BADARG;
+    if ((reinterpret_cast<uintptr_t>(Ah) | reinterpret_cast<uintptr_t>(Al) | reinterpret_cast<uintptr_t>(Bh) | reinterpret_cast<uintptr_t>(Bl)) & 15)
+        return S2VT_E_ALIGN;
+    HIP_TRY(launch_gemm_bf16x3_tn(Ah, Al, lda, Bh, Bl, ldb, C, ldc, M, N, K, accumulate, bias, static_cast<float*>(scratch), scratch_bytes / 4, 3, S(stream)));
+    return S2VT_OK;
 }
 
 int s2vt_cast_bf16_split(const float* src, int32_t ld, const int32_t* rowidx, int32_t R, int32_t C, int32_t transpose, uint16_t* dst,

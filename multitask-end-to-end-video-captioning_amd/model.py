@@ -266,6 +266,29 @@ class StepStats:
     mask_sum: torch.Tensor
 
 
+class _PlanesDlogits:
+    """The dlogits slot of a pass whose softmax wrote them as split-bf16 planes for the backward (ops.softmax_nll_fwd_bwd_split): the
+    backward consumes the planes and later overwrites them.  Whoever else asks for the fp32 values gets them from the untouched logits
+    -- the same arithmetic, the values the planes were split from -- computed on first use; every tensor attribute is the fp32
+    tensor's."""
+
+    def __init__(self, logits, target, coef, smoothing):
+        self._src = (logits, target, coef, smoothing)
+        self._t = None
+
+    def materialize(self):
+        if self._t is None:
+            logits, target, coef, smoothing = self._src
+            self._t = logits.clone()
+            ops.softmax_nll_fwd_bwd(self._t, target, coef, smoothing)
+        return self._t
+
+    def __getattr__(self, name):
+        if name.startswith("__"):
+            raise AttributeError(name)
+        return getattr(self.materialize(), name)
+
+
 def grad_precision_from_env() -> str:
     """The default of Video_Caption_Generator.grad_precision: S2VT_GRAD_PRECISION, unset = "fp32"; any value but "fp32" / "bf16"
     raises ValueError."""
@@ -605,9 +628,17 @@ class Video_Caption_Generator:
             target, coef = target[ix].contiguous(), coef[ix].contiguous()
             if isinstance(smoothing, torch.Tensor):
                 smoothing = smoothing[ix].contiguous()
-        nll, lp = ops.softmax_nll_fwd_bwd(logits, target, coef, smoothing)
+        dlogits = logits
+        if self.grad_precision == "fp32" and ops.split_grad_active(N):
+            # the fused split backward: dlogits leaves the softmax as the planes its products read, in the split workspace (backward()
+            # runs the vocabulary phase first, and nothing else touches that workspace in between); `logits` keeps the logits
+            nll, lp, in_planes = ops.softmax_nll_fwd_bwd_split(logits, target, coef, smoothing, self.dims, B, N)
+            if in_planes:
+                dlogits = _PlanesDlogits(logits, target, coef, smoothing)
+        else:
+            nll, lp = ops.softmax_nll_fwd_bwd(logits, target, coef, smoothing)
         self._coef_used = coef
-        self._ctx = (video, N, logits, ws, keep, seed, vid, sid, steps, live)
+        self._ctx = (video, N, dlogits, ws, keep, seed, vid, sid, steps, live)
         return nll, lp
 
     def backward(self, accumulate=False, overlap=None, keep_tail=False):
@@ -621,6 +652,8 @@ class Video_Caption_Generator:
         if overlap is None:
             overlap = self.dp_overlap
         video, N, dlogits, ws, keep, seed, vid, sid, steps, live = self._ctx
+        if isinstance(dlogits, _PlanesDlogits):
+            dlogits = None                                     # ops.bptt_bwd: "the planes are in the split workspace"
         st = self.store
         if not accumulate:
             ops.zero_(st.grad[:st.numel] if keep_tail else st.grad)    # keep_tail: sum(mask) already sits in the tail slot (ops.caption_mask)

@@ -310,6 +310,44 @@ def softmax_nll_fwd_bwd(logits, target, coef, smoothing=0.0):
     return nll, lp
 
 
+def split_grad_active(N: int) -> bool:
+    """Whether the fp32-mode backward at N unrolled rows runs the fused split form (s2vt_split_grad_active): then
+    softmax_nll_fwd_bwd_split can hand it dlogits as planes."""
+    return bool(lib().s2vt_split_grad_active(int(N)))
+
+
+def softmax_nll_fwd_bwd_split(logits, target, coef, smoothing, dims: Dims, B: int, N: int):
+    """softmax_nll_fwd_bwd for an update whose backward is the fused split form (split_grad_active(N)): the same nll / lp, but
+    dlogits goes as split-bf16 planes into the split-gradient workspace of (dims, B, N), where bptt_bwd(..., dlogits=None) reads
+    it, and `logits` stays as it was.  Returns (nll, lp, in_planes); in_planes False: the shape is not the fused kernel's and
+    `logits` now holds the fp32 dlogits, as after softmax_nll_fwd_bwd."""
+    _chk_f32(logits, coef)
+    R, V = logits.shape
+    assert target.dtype == torch.int32 and target.is_cuda and target.numel() == R and coef.numel() == R
+    nll = torch.empty(R, dtype=torch.float32, device=logits.device)
+    lp = torch.empty_like(nll)
+    rows = None
+    if isinstance(smoothing, torch.Tensor):
+        _chk_f32(smoothing)
+        assert smoothing.numel() == R and smoothing.is_contiguous()
+        rows, smoothing = smoothing, 0.0
+    sws = split_grad_workspace(dims, B, N, logits.device)
+    rc = lib().s2vt_softmax_nll_fwd_bwd_split(_ptr(logits), logits.stride(0), R, V, _ptr(target), _ptr(coef), float(smoothing), _ptr(rows),
+                                              _ptr(nll), _ptr(lp), C.byref(dims), B, N, _ptr(sws), sws.numel(), _stream())
+    if rc != 1:
+        check(rc, "s2vt_softmax_nll_fwd_bwd_split")
+    return nll, lp, rc == 0
+
+
+def split_grad_dlogits_planes(dims: Dims, B: int, N: int, R: int, device):
+    """Views (hi, lo), bf16 [R, bf16_pad(V)], of the dlogits planes softmax_nll_fwd_bwd_split left in the split workspace."""
+    hi_off, lo_off, ld = C.c_size_t(), C.c_size_t(), C.c_int32()
+    check(lib().s2vt_split_grad_dlogits_planes(C.byref(dims), B, N, C.byref(hi_off), C.byref(lo_off), C.byref(ld)), "s2vt_split_grad_dlogits_planes")
+    sws = split_grad_workspace(dims, B, N, device)
+    n = R * ld.value * 2
+    return tuple(sws[o.value:o.value + n].view(torch.bfloat16).view(R, ld.value) for o in (hi_off, lo_off))
+
+
 def softmax_unshifted_argmax(logits, want_probs=False):
     """tf_s2vt.py:208-209 as written: argmax(exp(l) / sum(exp(l))) in fp32 without a max shift (ids int32 [R], probs)."""
     _chk_f32(logits)
@@ -343,12 +381,15 @@ def bptt_bwd(dims: Dims, params: Params, grads: Params, video, N: int, dlogits, 
     """phase 0 = the whole backward; 1 = vocab projection only; 2 = the rest (data-parallel overlap).
     steps: what the forward call (teacher_forced_fwd) was given.
     precision "bf16": the gradient contractions on bf16 operands with fp32 accumulation (s2vt_bptt_bwd_bf16, non-parity:
-    only the gradients change)."""
+    only the gradients change).
+    dlogits None (fp32 precision): softmax_nll_fwd_bwd_split has left it as planes in the split workspace, where the vocabulary phase
+    (phase 0 or 1) reads it; the later phases do not use dlogits."""
     _chk_f32(video, dlogits)
     if precision not in GRAD_PRECISIONS:
         raise ValueError(f"precision must be one of {GRAD_PRECISIONS}, got {precision!r}")
     steps = dims.n_caption_lstm_step if steps is None else int(steps)
-    assert dlogits.shape[0] == (steps * N if live is None else live.numel())
+    assert dlogits is None or dlogits.shape[0] == (steps * N if live is None else live.numel())
+    assert dlogits is not None or precision == "fp32"
     if precision == "bf16":
         bws = bf16_grad_workspace(dims, video.shape[0], N, video.device)
         check(lib().s2vt_bptt_bwd_bf16(C.byref(dims), C.byref(params), C.byref(grads), _ptr(video), video.shape[0], N, _ptr(dlogits),
@@ -389,6 +430,28 @@ def cast_bf16(src, rowidx=None, transpose=False, pad_rows=None, colsum=None, row
     check(lib().s2vt_cast_bf16(_ptr(src), src.stride(0), _ptr(rowidx), R, Cc, 1, _ptr(out), Rp, Rp, _ptr(colsum), _ptr(rows), Kp,
                                _ptr(scratch), 0 if scratch is None else scratch.numel(), _stream()), "s2vt_cast_bf16")
     return (out, rows) if row_copy else out
+
+
+def gemm_bf16x3_tn(Ah, Al, Bh, Bl, M=None, N=None, out=None, accumulate=False, split_k=True, bias=None):
+    """C[M, N] (+)= sum_k A[k, m] B[k, n] as Ah^T Bh + Ah^T Bl + Al^T Bh on split-bf16 planes stored by rows, [K, lda] and [K, ldb]
+    (s2vt_gemm_bf16x3_tn; M, N default to the planes' widths).  bias [N]: += the product's row M -- column M of Ah must hold ones."""
+    for t in (Ah, Al, Bh, Bl):
+        assert t.is_cuda and t.dtype == torch.bfloat16 and t.stride(1) == 1
+    assert Ah.shape == Al.shape and Bh.shape == Bl.shape and Ah.stride(0) == Al.stride(0) and Bh.stride(0) == Bl.stride(0)
+    K = Ah.shape[0]
+    assert Bh.shape[0] == K
+    M = Ah.shape[1] if M is None else int(M)
+    N = Bh.shape[1] if N is None else int(N)
+    if out is None:
+        assert not accumulate
+        out = torch.empty((M, N), dtype=torch.float32, device=Ah.device)
+    _chk_f32(out, bias)
+    assert out.shape[0] == M and out.shape[1] == N and out.stride(1) == 1
+    scratch = workspace(32 * (M + 1) * N, Ah.device, "gemm_bf16x3") if split_k and M * N else None
+    check(lib().s2vt_gemm_bf16x3_tn(_ptr(Ah), _ptr(Al), Ah.stride(0), _ptr(Bh), _ptr(Bl), Bh.stride(0), _ptr(out), out.stride(0), M, N, K,
+                                    int(bool(accumulate)), _ptr(bias), _ptr(scratch), 0 if scratch is None else scratch.numel(), _stream()),
+          "s2vt_gemm_bf16x3_tn")
+    return out
 
 
 def cast_bf16_split(src, rowidx=None, transpose=False, pad_rows=None, colsum=None, row_copy=False):
