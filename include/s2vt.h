@@ -533,6 +533,30 @@ int s2vt_attn_bptt_bwd(const s2vt_dims* d, const s2vt_attn_params* p, const s2vt
 int s2vt_attn_decode_greedy(const s2vt_dims* d, const s2vt_attn_params* p, const float* video, int32_t B, int32_t video_base, int32_t* ids_out,
                             float* alphas_out, void* workspace, size_t workspace_bytes, s2vt_stream stream);
 
+/* ---- batched beam search for the attention captioner: the decode step of build_generator / build_sampler
+ * (original_attention.py:155-251) under the beam bookkeeping of final_beam_search.py:201-294, for B videos at once.  Same division of
+ * work as s2vt_beam_*: one call per decode step advances every live hypothesis of every video, the heaps stay on the host.
+ *
+ * Workspace of a decoder for B videos and up to beam hypotheses per video (1 <= beam <= 16): the frame embeddings and the hoisted
+ * image part for B videos -- ONE [Tv, H] block each per video, shared by its hypotheses, never copied per hypothesis -- plus two
+ * LSTM3 state buffers, the step's activations and logits for B * beam rows.  0 on bad arguments (n_video_lstm_step <= 64). */
+size_t s2vt_attn_beam_workspace_bytes(const s2vt_dims* d, int32_t B, int32_t beam);
+/* Frame embedding V = video @ encode_image_W + b (time-major, :159-162) and the hoisted image part V @ Ua + ba (:171) of the B videos:
+ * everything of a decode step that does not depend on a word. */
+int s2vt_attn_beam_encode(const s2vt_dims* d, const s2vt_attn_params* p, const float* video, int32_t B, int32_t beam, void* workspace,
+                          size_t workspace_bytes, s2vt_stream stream);
+/* Decode step t (0 <= t < Tc) for R <= B * beam live hypotheses, no host synchronisation; steps are issued in order t = 0, 1, ...
+ * Hypothesis m continues video video_of_row[m] from row parent[m] of step t - 1 with word[m]; at t = 0 it starts from the zero state
+ * with no word (state1 = h_prev = current_embed = 0, :164-169: parent and word are ignored -- this model feeds no <bos>).  The step is query h @ Wa ->
+ * score / softmax / context over the video's block (row -> video: the image blocks are indexed through video_of_row) -> LSTM3 ->
+ * tanh([embed ; atten ; output1] @ Wp + bp) -> vocabulary logits, no dropout (:188), each chain in the block order of the numeric
+ * contract above: the logits of a hypothesis are bit-identical to what s2vt_attn_teacher_forced_fwd (keep = 1) gives at step t for
+ * that hypothesis' word prefix.  The three int32 [R] arrays are device pointers; indices out of range are clamped, not reported.
+ * Writes top_ids / top_logp [R, k] (s2vt_vocab_topk of the step's logits) and, when given, logits_out [R, V] and alphas_out [Tv][R]. */
+int s2vt_attn_beam_step(const s2vt_dims* d, const s2vt_attn_params* p, int32_t B, int32_t beam, int32_t t, int32_t R,
+                        const int32_t* video_of_row, const int32_t* parent, const int32_t* word, int32_t k, int32_t* top_ids, float* top_logp,
+                        float* logits_out, float* alphas_out, void* workspace, size_t workspace_bytes, s2vt_stream stream);
+
 /* ---- multitask attribute head (reinforce_multitask_e2e_attribute_loss.py:375-380, 606-626) -----
  * mean_feat[b,:] = mean_t video[b,t,:]; z = mean_feat @ attr_W + attr_b;
  * bce = max(z,0) - z*y + log(1+exp(-|z|))  (tf.nn.sigmoid_cross_entropy_with_logits); labels/bce optional.

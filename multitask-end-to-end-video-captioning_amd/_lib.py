@@ -127,6 +127,9 @@ SIGNATURES = {
     "s2vt_attn_step_scalars": (C.c_int, [_vp, _vp, _i64, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _DP, _i32, _vp, _sz, _vp]),
     "s2vt_attn_bptt_bwd": (C.c_int, [_DP, _AP, _AP, _vp, _i32, _vp, _i32, _vp, _f32, _f32, _u64, _vp, _vp, _vp, _sz, _vp]),
     "s2vt_attn_decode_greedy": (C.c_int, [_DP, _AP, _vp, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "s2vt_attn_beam_workspace_bytes": (_sz, [_DP, _i32, _i32]),
+    "s2vt_attn_beam_encode": (C.c_int, [_DP, _AP, _vp, _i32, _i32, _vp, _sz, _vp]),
+    "s2vt_attn_beam_step": (C.c_int, [_DP, _AP, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "s2vt_attr_head_fwd": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "s2vt_attr_head_bwd": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp]),
     "s2vt_attr_head_scores": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),

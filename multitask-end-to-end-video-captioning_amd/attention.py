@@ -6,8 +6,8 @@ the arithmetic restated here is original_attention.py:95-147.  The class keeps t
 ``build_*`` surface: the methods return the same tuples of placeholders / fetches, ``model.Session(m).run(fetches, feed)``
 evaluates them, and ``exponential_decay`` / ``minimize`` stand for the nodes the reference's train() adds (:430-441), so
 that loop translates statement by statement (tests/test_gpu_attention_model.py replays it).  All arithmetic is in
-libs2vt_hip.so (csrc/attn_model.hip: the whole unroll, its backward and the greedy decode loop are library calls; csrc/attn.hip:
-score -> softmax -> context in one launch per step); torch supplies device memory and streams.  No CPU fallback.
+libs2vt_hip.so (csrc/attn_model.hip: the whole unroll, its backward, the greedy decode loop and the beam-search step are library
+calls; csrc/attn.hip: score -> softmax -> context in one launch per step); torch supplies device memory and streams.  No CPU fallback.
 """
 from __future__ import annotations
 
@@ -67,6 +67,15 @@ class Attention_Caption_Generator:
         self._gscale = torch.ones(1, dtype=torch.float32, device=self.device)
         self._applied = torch.zeros(1, dtype=torch.int32, device=self.device)   # step number of the last Adam update the device APPLIED
         self._row_ids_cache = {}
+
+    # the S2VT class's spelling of the two step counts: what train_common.beam_eval and beam_generator.BatchedBeamSearch read
+    @property
+    def n_caption_lstm_step(self):
+        return self.n_caption_lstm_steps
+
+    @property
+    def n_video_lstm_step(self):
+        return self.n_video_lstm_steps
 
     # ------------------------------------------------------------------------------------------ utilities
     def _dev(self, a, dtype):
@@ -193,6 +202,23 @@ class Attention_Caption_Generator:
         ids, _ = ops.attn_decode_greedy(self.dims, self.store.params, self._dev(video, torch.float32), video_base)
         return None, ids
 
+    def _beam_decoder(self, B, beam):
+        """The device half of beam_generator.BatchedBeamSearch for this model: encode(params, video) / step(params, t, rows, k)."""
+        return ops.AttnBeamDecoder(self.dims, B, beam, self.device)
+
+    def beam_search(self, video, beam_size=3, length_normalization_factor=0.0, batch_size=64):
+        """Beam search over a block of videos [n, Tv, dim_image]: the decode step of build_generator (original_attention.py:155-199)
+        under the beam bookkeeping of final_beam_search.py:201-294, which is how the reference's test scripts report results,
+        batch_size videos at once (beam_generator.BatchedBeamSearch over ops.AttnBeamDecoder).  Returns [(sentence ids, logprob,
+        score)] * n, as Video_Caption_Generator.beam_search."""
+        from .beam_generator import BatchedBeamSearch
+        gen = BatchedBeamSearch(self, beam_size, length_normalization_factor)
+        n = video.shape[0] if hasattr(video, "shape") else len(video)
+        out = []
+        for a in range(0, n, batch_size):
+            out += gen.generate(video[a:a + batch_size])
+        return out
+
     def set_step(self, global_step, adam_t=None):
         self.global_step = int(global_step)
         self.adam_t = int(global_step if adam_t is None else adam_t)
@@ -229,11 +255,19 @@ class Attention_Caption_Generator:
             return {"loss": float(self.loss(v, c, m))}
         return Output("loss", fn, [video, caption, caption_mask]), video, caption, caption_mask
 
-    def build_generator(self):
-        """(video, generated_words) as :155-199: greedy words [B, Tc] int64 for a batch_size block of videos."""
+    def build_generator(self, beam_size=1, length_normalization_factor=0.5):
+        """(video, generated_words) as :155-199: greedy words [B, Tc] int64 for a batch_size block of videos.  beam_size > 1 (the
+        arguments of final_beam_search.py's build_generator, :201): each video's best beam caption, padded with 0 to Tc."""
         video = Placeholder("video", (self.batch_size, self.n_video_lstm_steps, self.dim_image), np.float32)
+        Tc = self.n_caption_lstm_steps
 
         def fn(v):
+            if beam_size > 1:
+                res = self.beam_search(v, beam_size, length_normalization_factor, max(1, len(v)))
+                ids = np.zeros((len(res), Tc), np.int64)
+                for i, (sent, _, _) in enumerate(res):
+                    ids[i, :min(len(sent), Tc)] = sent[:Tc]
+                return {"generated_words": ids}
             ids, _ = ops.attn_decode_greedy(self.dims, self.store.params, self._dev(v, torch.float32))
             return {"generated_words": ids.cpu().numpy().astype(np.int64)}
         return video, Output("generated_words", fn, [video])

@@ -1,10 +1,11 @@
 """Beam-search captions for a test set from a checkpoint (the test() of final_beam_search.py:504-545 / e2e_beam_search.py, batched):
 
     python -m s2vt_amd.beam_eval --checkpoint CKPT --test-sents SENTS --test-feats FEATS --vocab VOCAB \
-        [--beam 3] [--lnf 0.0] [--batch-size 64] [--n-caption-lstm-step 35] [--out captions.txt]
+        [--beam 3] [--lnf 0.0] [--batch-size 64] [--n-caption-lstm-step 35] [--out captions.txt] [--model auto|s2vt|attention]
 
 The checkpoint is loaded with optimistic_restore (an .npz dump or a TensorFlow checkpoint); the model's dimensions are read from
-its variables, Tv from the feature file.  Writes one `video_id<TAB>sentence` line per test video, as the reference does (the
+its variables, Tv from the feature file.  The model class is read off the variable names too: a checkpoint that holds embed_att_Wa
+is the temporal-attention captioner (original_attention.py:64-86), any other the S2VT model; --model overrides the detection.  Writes one `video_id<TAB>sentence` line per test video, as the reference does (the
 caption cut at its first <eos>, <bos> / <eos> dropped), and prints the mean CIDEr-D against the test set's references."""
 from __future__ import annotations
 
@@ -42,6 +43,16 @@ def read_captions(path) -> dict:
     return out
 
 
+def model_kind(variable_names, choice="auto") -> str:
+    """"attention" or "s2vt" for a checkpoint's variable names (any iterable of names, e.g. the dict read_checkpoint returns):
+    embed_att_Wa exists only in the temporal-attention captioner.  `choice` other than "auto" wins."""
+    if choice != "auto":
+        if choice not in ("s2vt", "attention"):
+            raise ValueError(f"model: {choice!r} (auto, s2vt or attention)")
+        return choice
+    return "attention" if "embed_att_Wa" in set(variable_names) else "s2vt"
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--checkpoint", required=True)
@@ -51,6 +62,7 @@ def main(argv=None):
     ap.add_argument("--batch-size", type=int, default=64)
     ap.add_argument("--n-caption-lstm-step", type=int, default=35)
     ap.add_argument("--out", default="beam_captions.txt")
+    ap.add_argument("--model", choices=("auto", "s2vt", "attention"), default="auto")
     a = ap.parse_args(argv)
 
     from . import hostglue, reward, tfckpt
@@ -66,7 +78,11 @@ def main(argv=None):
         raise SystemExit(f"checkpoint vocabulary has {V} words, {a.vocab} gives {len(wordtoix)}")
     Tv = corpus.features.features.shape[1]
     Tc = a.n_caption_lstm_step
-    model = M.Video_Caption_Generator(D, V, E, H, a.batch_size, Tv + Tc, Tv, Tc, bias_init_vector=None)
+    if model_kind(raw, a.model) == "attention":
+        from . import attention as A
+        model = A.Attention_Caption_Generator(D, V, E, a.batch_size, Tv, Tc, 1.0, bias_init_vector=None)    # dim_hidden = Wemb.shape[1] (:65)
+    else:
+        model = M.Video_Caption_Generator(D, V, E, H, a.batch_size, Tv + Tc, Tv, Tc, bias_init_vector=None)
     optimistic_restore(model, a.checkpoint)
     scorer = reward.CiderD(corpus.index.refs_by_video(), wordtoix)
     decoded, cider = beam_eval(model, corpus, ixtoword, scorer, a.batch_size, a.beam, a.lnf)

@@ -158,16 +158,20 @@ class BatchedBeamSearch:
     bookkeeping per video is BeamSearchGenerator.generate's, statement for statement -- the same BestK(k*k) / BestK(k) heaps, the
     `exclude` counter, the length normalisation, the final_captions fallback.  A video whose loop would break (no mid captions,
     or exclude == k) leaves the row list; the step's rows never depend on other videos', so a video decodes to the same bits
-    whatever batch it is in."""
+    whatever batch it is in.
+
+    The search knows nothing of the model's arithmetic: the model hands out its decoder (`model._beam_decoder(B, beam)`: encode /
+    step of ops.BeamDecoder for the S2VT model, ops.AttnBeamDecoder for the temporal-attention captioner) and its dimensions
+    (n_video_lstm_step, n_caption_lstm_step, dim_image).  The step-0 word row is <bos> = 1, which the S2VT decoder feeds; the
+    attention decoder ignores it (that model starts from current_embed = 0, original_attention.py:169)."""
 
     def __init__(self, model, beam_size=3, length_normalization_factor=0.0):
         self.m, self.beam_size, self.lnf = model, beam_size, length_normalization_factor
         self._dec = None
 
     def _decoder(self, B):
-        m = self.m
         if self._dec is None or self._dec.max_B < B:
-            self._dec = ops.BeamDecoder(m.dims, B, self.beam_size, m.device)
+            self._dec = self.m._beam_decoder(B, self.beam_size)
         return self._dec
 
     def generate(self, video):

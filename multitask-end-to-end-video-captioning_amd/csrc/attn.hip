@@ -33,6 +33,12 @@ typedef float v4f __attribute__((ext_vector_type(4)));
 constexpr int kAttnMaxTv = 64;
 constexpr int kAttnChunkRows = 32;       // frames whose tanh rows are resident in LDS at a time (32 x 1004 floats = 126 KB at H = 1000)
 
+// ROWMAP (beam search): workgroup b is hypothesis b of B and reads the image block of video sv = row_video[b] out of n_video --
+// P[t][sv] and Vt[t][sv] with the VIDEO count as the row stride -- so the hypotheses of a video share its one [Tv, H] block and
+// nothing is copied per hypothesis; the query row hWa[b], alpha[t][b] (row stride B) and ctx[b] stay per hypothesis.  The index
+// is device data: clamped into [0, n_video).  ROWMAP = false is the kernel as it always was (sv == b, stride B): the same
+// arithmetic in the same order -- the chains above are the contract.
+template <bool ROWMAP>
 __global__ __launch_bounds__(256) void attn_fwd_kernel(const AttnFwdArgs a)
 {
     extern __shared__ float sm[];
@@ -43,6 +49,12 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const AttnFwdArgs a)
     float* xv = ev + kAttnMaxTv;                     // [64] exp(e), then alpha
     float* sc = xv + kAttnMaxTv;                     // [4] scalars
     const int b = blockIdx.x, tid = threadIdx.x;
+    int sv = b, Bs = B;                              // image block of this row and the blocks per frame
+    if constexpr (ROWMAP) {
+        Bs = a.n_video;
+        sv = a.row_video[b];
+        sv = sv < 0 ? 0 : (sv >= Bs ? Bs - 1 : sv);
+    }
     const float* __restrict__ hp = a.hWa ? a.hWa + (size_t)b * H : nullptr;
     const float* __restrict__ Pp = a.P;
     const float* __restrict__ Vp = a.Vt;
@@ -60,7 +72,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const AttnFwdArgs a)
                     float4 pv[8];
 #pragma unroll
                     for (int j = 0; j < 8; ++j)
-                        if (r0 + j < nr) pv[j] = *reinterpret_cast<const float4*>(Pp + ((size_t)(c0 + r0 + j) * B + b) * H + 4 * q);
+                        if (r0 + j < nr) pv[j] = *reinterpret_cast<const float4*>(Pp + ((size_t)(c0 + r0 + j) * Bs + sv) * H + 4 * q);
 #pragma unroll
                     for (int j = 0; j < 8; ++j)
                         if (r0 + j < nr) {
@@ -73,7 +85,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const AttnFwdArgs a)
         } else {
             for (int i = tid; i < nr * H; i += 256) {
                 const int r = i / H, h = i - r * H;
-                Tt[(size_t)r * ldT + h] = dm_tanhf((hp ? hp[h] : 0.f) + Pp[((size_t)(c0 + r) * B + b) * H + h]);
+                Tt[(size_t)r * ldT + h] = dm_tanhf((hp ? hp[h] : 0.f) + Pp[((size_t)(c0 + r) * Bs + sv) * H + h]);
             }
         }
         __syncthreads();
@@ -113,7 +125,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const AttnFwdArgs a)
                 float4 v[8];
 #pragma unroll
                 for (int j = 0; j < 8; ++j)
-                    if (t0 + j < Tv) v[j] = *reinterpret_cast<const float4*>(Vp + ((size_t)(t0 + j) * B + b) * H + 4 * q);
+                    if (t0 + j < Tv) v[j] = *reinterpret_cast<const float4*>(Vp + ((size_t)(t0 + j) * Bs + sv) * H + 4 * q);
 #pragma unroll
                 for (int j = 0; j < 8; ++j)
                     if (t0 + j < Tv) {
@@ -127,7 +139,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const AttnFwdArgs a)
     } else {
         for (int h = tid; h < H; h += 256) {
             float c = 0.f;
-            for (int t = 0; t < Tv; ++t) c = __builtin_fmaf(ev[t], Vp[((size_t)t * B + b) * H + h], c);
+            for (int t = 0; t < Tv; ++t) c = __builtin_fmaf(ev[t], Vp[((size_t)t * Bs + sv) * H + h], c);
             a.ctx[(size_t)b * H + h] = c;
         }
     }
@@ -313,25 +325,32 @@ hipError_t launch_attn_fwd(const AttnFwdArgs& a0, hipStream_t st)
     const auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; };
     a.vec = (!(a.H & 3) && al16(a.P) && al16(a.Vt) && al16(a.ctx) && (!a.hWa || al16(a.hWa))) ? 1 : 0;
     const size_t lds = ((size_t)(a.RC + 1) * a.ldT + 2 * kAttnMaxTv + 4) * sizeof(float);
+    if (a.row_video && a.n_video <= 0) return hipErrorInvalidValue;
     static std::once_flag once;
     static hipError_t attr_err = hipSuccess;
     std::call_once(once, [] {
-        attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (attr_err == hipSuccess)
+            attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     });
     if (attr_err != hipSuccess) return attr_err;
     if (lds > 160 * 1024) return hipErrorInvalidValue;
+    const auto launch = [&] {
+        if (a.row_video) hipLaunchKernelGGL(attn_fwd_kernel<true>, dim3(a.B), dim3(256), lds, st, a);
+        else hipLaunchKernelGGL(attn_fwd_kernel<false>, dim3(a.B), dim3(256), lds, st, a);
+    };
     // launch profiler class 7: attention forward (flops = the score and context chains, 2 x 2 Tv B H; HBM-bound by P and V)
     if (!prof_wants(7, 0)) {
-        hipLaunchKernelGGL(attn_fwd_kernel, dim3(a.B), dim3(256), lds, st, a);
+        launch();
         return hipGetLastError();
     }
     hipEvent_t e0, e1;
     hipError_t pe = prof_events(&e0, &e1);
     if (pe != hipSuccess) return pe;
     (void)hipEventRecord(e0, st);
-    hipLaunchKernelGGL(attn_fwd_kernel, dim3(a.B), dim3(256), lds, st, a);
+    launch();
     (void)hipEventRecord(e1, st);
-    prof_record(7, 0, "attn_fwd(score+softmax+ctx)", 4.0 * a.Tv * a.B * (double)a.H, e0, e1);
+    prof_record(7, 0, a.row_video ? "attn_fwd(row->video)" : "attn_fwd(score+softmax+ctx)", 4.0 * a.Tv * a.B * (double)a.H, e0, e1);
     return hipGetLastError();
 }
 

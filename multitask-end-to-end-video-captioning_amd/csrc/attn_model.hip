@@ -14,6 +14,7 @@
 // backward.  Forward activations are bit-identical to oracle/s2vt_oracle.py::attention_forward; gradients are order-free.
 #include <hip/hip_runtime.h>
 
+#include <climits>
 #include <cstring>
 
 #include <mutex>
@@ -253,6 +254,63 @@ hipError_t attn_step(const s2vt_attn_params* p, const AttnWs& w, int t, int Tv, 
     a.alpha = w.alpha + (size_t)t * Tv * B; a.asum = w.asum + (size_t)t * B; a.ctx = w.ctx + t * BH;
     a.Tv = Tv; a.B = B; a.H = H;
     return launch_attn_fwd(a, st);
+}
+
+
+// ---- batched beam search (final_beam_search.py:201-294 over the decode step of original_attention.py:155-251) ----------------
+// Beam step, stage 1: what the R live hypotheses continue from.  The parent's LSTM3 cell state is copied into dense rows (the cell
+// kernel reads c_prev by row number); its h is NOT copied -- the query projection and the cell's recurrent segment gather it through
+// the clamped parent index (ASeg::rowidx), as the word's embedding rows are gathered through the clamped word.  Step 0 starts from
+// the zero state (:164-165).  Indices are device data the host does not see here: out-of-range values are clamped into range
+// (nothing is read outside the workspace or the embedding table), as beam_gather_kernel (beam.hip) clamps.
+__global__ __launch_bounds__(256) void attn_beam_gather_kernel(const int32_t* parent, const int32_t* word, int t, int Rmax, int H, int V,
+                                                               const float* c_prev, float* c_out, int32_t* par_out, int32_t* word_out)
+{
+    const int m = blockIdx.x;
+    int par = 0;
+    if (t > 0) {
+        par = parent[m];
+        par = par < 0 ? 0 : (par >= Rmax ? Rmax - 1 : par);
+    }
+    const float* cs = c_prev + (size_t)par * H;
+    for (int i = threadIdx.x; i < H; i += 256) c_out[(size_t)m * H + i] = t > 0 ? cs[i] : 0.f;
+    if (threadIdx.x == 0) {
+        const int wd = word[m];
+        par_out[m] = par;
+        word_out[m] = wd < 0 ? 0 : (wd >= V ? V - 1 : wd);
+    }
+}
+
+constexpr int kBeamTopkMax = 16;
+
+struct AttnBeamWs {
+    AttnWs img;                        // encidx, Vt, P [Tv*B, H] of the B videos (attn_prologue); nothing else of it is carved
+    float *c[2], *h[2];                // LSTM3 state [Rmax][H]: step t writes slot t & 1 and reads the other (rows are permuted between steps)
+    float* cg;                         // the parents' cell state, gathered [Rmax][H]
+    int32_t *par, *word;               // clamped parent rows / words [Rmax]
+    float *hWa, *alpha, *ctx, *Y;      // [Rmax][H], [Tv][Rmax], [Rmax][H], [Rmax][H]
+    float* logits;                     // [Rmax][V] (when the caller does not ask for them)
+};
+
+size_t carve_attn_beam(Carver& c, const s2vt_dims* d, int B, int beam, AttnBeamWs* out)
+{
+    const size_t H = d->lstm_dim, V = d->n_words, Tv = d->n_video_lstm_step, b = B, Rmax = (size_t)B * beam;
+    AttnBeamWs w;
+    std::memset(&w, 0, sizeof(w));
+    w.img.encidx = c.take<int32_t>(Tv * b);
+    w.img.Vt = c.take<float>(Tv * b * H); w.img.P = c.take<float>(Tv * b * H);
+    for (int i = 0; i < 2; ++i) { w.c[i] = c.take<float>(Rmax * H); w.h[i] = c.take<float>(Rmax * H); }
+    w.cg = c.take<float>(Rmax * H);
+    w.par = c.take<int32_t>(Rmax); w.word = c.take<int32_t>(Rmax);
+    w.hWa = c.take<float>(Rmax * H); w.alpha = c.take<float>(Tv * Rmax); w.ctx = c.take<float>(Rmax * H); w.Y = c.take<float>(Rmax * H);
+    w.logits = c.take<float>(Rmax * V);
+    if (out) *out = w;
+    return c.off;
+}
+
+bool attn_beam_shape_ok(const s2vt_dims* d, int B, int beam)
+{
+    return attn_dims_ok(d) && B > 0 && beam >= 1 && beam <= kBeamTopkMax && (int64_t)B * beam <= INT_MAX / 4;
 }
 
 }  // namespace
@@ -579,6 +637,84 @@ int s2vt_attn_decode_greedy(const s2vt_dims* d, const s2vt_attn_params* p, const
         if (cl.add(alphas_out, w.alpha, (size_t)Tc * Tv * B * 4)) HIP_TRY(launch_copy_regions(cl, st));
         else HIP_TRY(hipMemcpyAsync(alphas_out, w.alpha, (size_t)Tc * Tv * B * 4, hipMemcpyDeviceToDevice, st));
     }
+    return S2VT_OK;
+}
+
+
+size_t s2vt_attn_beam_workspace_bytes(const s2vt_dims* d, int32_t B, int32_t beam)
+{
+    if (!attn_beam_shape_ok(d, B, beam)) return 0;
+    Carver c(nullptr, 0);
+    return carve_attn_beam(c, d, B, beam, nullptr);
+}
+
+int s2vt_attn_beam_encode(const s2vt_dims* d, const s2vt_attn_params* p, const float* video, int32_t B, int32_t beam, void* workspace,
+                          size_t workspace_bytes, s2vt_stream stream)
+{
+    if (!attn_beam_shape_ok(d, B, beam) || !attn_params_ok(p) || !video || !workspace) return S2VT_E_BADARG;
+    if (reinterpret_cast<uintptr_t>(workspace) & 255u) return S2VT_E_ALIGN;
+    Carver c(workspace, workspace_bytes);
+    AttnBeamWs w;
+    carve_attn_beam(c, d, B, beam, &w);
+    if (!c.ok()) return S2VT_E_WORKSPACE;
+    return attn_prologue(d, p, video, B, w.img, S(stream));
+}
+
+int s2vt_attn_beam_step(const s2vt_dims* d, const s2vt_attn_params* p, int32_t B, int32_t beam, int32_t t, int32_t R, const int32_t* video_of_row,
+                        const int32_t* parent, const int32_t* word, int32_t k, int32_t* top_ids, float* top_logp, float* logits_out,
+                        float* alphas_out, void* workspace, size_t workspace_bytes, s2vt_stream stream)
+{
+    if (!attn_beam_shape_ok(d, B, beam) || !attn_params_ok(p) || !video_of_row || !parent || !word || !top_ids || !top_logp || !workspace)
+        return S2VT_E_BADARG;
+    if (t < 0 || t >= d->n_caption_lstm_step || R < 0 || R > B * beam || k < 1 || k > kBeamTopkMax || k > d->n_words) return S2VT_E_BADARG;
+    if (reinterpret_cast<uintptr_t>(workspace) & 255u) return S2VT_E_ALIGN;
+    Carver c(workspace, workspace_bytes);
+    AttnBeamWs w;
+    carve_attn_beam(c, d, B, beam, &w);
+    if (!c.ok()) return S2VT_E_WORKSPACE;
+    if (R == 0) return S2VT_OK;
+    const int H = d->lstm_dim, V = d->n_words, Tv = d->n_video_lstm_step;
+    hipStream_t st = S(stream);
+    const float *c_prev = w.c[(t & 1) ^ 1], *h_prev = w.h[(t & 1) ^ 1];
+    float *c_new = w.c[t & 1], *h_new = w.h[t & 1];
+    // 1. gather: the parents' cell state (zeros at step 0), the clamped parent rows and words
+    hipLaunchKernelGGL(attn_beam_gather_kernel, dim3(R), dim3(256), 0, st, parent, word, (int)t, (int)(B * beam), H, V, c_prev, w.cg, w.par, w.word);
+    HIP_TRY(hipGetLastError());
+    // 2. query projection of the parent's clean h (no dropout in the samplers, :188), gathered through the parent index
+    //    (step 0: the query is the zero state, h_prev @ Wa = 0)
+    if (t > 0) {
+        ASeg sq = make_seg(h_prev, H, H, 0, 0, w.par);
+        HIP_TRY(store_call(&sq, 1, p->embed_att_Wa, H, nullptr, w.hWa, H, R, H, 0, -1, st));
+    }
+    // 3. score -> softmax -> context, row -> video: hypothesis m reads its video's one [Tv, H] block of P and Vt
+    {
+        AttnFwdArgs a;
+        std::memset(&a, 0, sizeof(a));
+        a.hWa = t > 0 ? w.hWa : nullptr; a.P = w.img.P; a.Vt = w.img.Vt; a.w = p->embed_att_w;
+        a.alpha = alphas_out ? alphas_out : w.alpha; a.ctx = w.ctx;
+        a.Tv = Tv; a.B = R; a.H = H;
+        a.row_video = video_of_row; a.n_video = B;
+        HIP_TRY(launch_attn_fwd(a, st));
+    }
+    // 4. LSTM3: one chain over the word's embedding rows (none at step 0: current_embed = 0, :169), the parent's h, the context;
+    // 5. output layer tanh([embed ; atten ; output1] @ Wp + bp) in the order [2H:3H], [H:2H], [0:H]
+    NoiseIds none{nullptr, nullptr, 0};
+    if (t == 0) {
+        ASeg s3 = make_seg(w.ctx, H, H, 0);
+        HIP_TRY(lstm_call(&s3, 1, p->lstm3_W, p->lstm3_b, w.cg, 0, c_new, h_new, nullptr, nullptr, R, H, 1.0f, none, 0, -1, st));
+        ASeg sy[2] = {make_seg(w.ctx, H, H, H), make_seg(h_new, H, H, 0)};
+        HIP_TRY(store_call(sy, 2, p->embed_nn_Wp, H, p->embed_nn_bp, w.Y, H, R, H, 1, -1, st));
+    } else {
+        ASeg s3[3] = {make_seg(p->Wemb, H, H, H, 0, w.word), make_seg(h_prev, H, H, 2 * H, 0, w.par), make_seg(w.ctx, H, H, 0)};
+        HIP_TRY(lstm_call(s3, 3, p->lstm3_W, p->lstm3_b, w.cg, 0, c_new, h_new, nullptr, nullptr, R, H, 1.0f, none, 0, -1, st));
+        ASeg sy[3] = {make_seg(p->Wemb, H, H, 2 * H, 0, w.word), make_seg(w.ctx, H, H, H), make_seg(h_new, H, H, 0)};
+        HIP_TRY(store_call(sy, 3, p->embed_nn_Wp, H, p->embed_nn_bp, w.Y, H, R, H, 1, -1, st));
+    }
+    // 6. vocabulary logits on the store tile, 7. top-k words and their log-probabilities
+    float* logits = logits_out ? logits_out : w.logits;
+    ASeg so = make_seg(w.Y, H, H, 0);
+    HIP_TRY(store_call(&so, 1, p->embed_word_W, V, p->embed_word_b, logits, V, R, V, 0, -1, st));
+    HIP_TRY(launch_vocab_topk(logits, V, R, V, k, top_ids, top_logp, st));
     return S2VT_OK;
 }
 

@@ -212,6 +212,11 @@ struct AttnFwdArgs {
     float* ctx;                  // [B, H]
     int Tv, B, H;
     int RC, ldT, vec;            // (set by the launcher) frames per LDS chunk, LDS row stride, 16-byte path
+    // the row -> video form (beam search: the B rows are hypotheses that share their video's image block).  row_video == NULL:
+    // row b reads block b of P / Vt, which hold B blocks per frame -- the form above, and the same kernel as before.  Else row b
+    // reads block clamp(row_video[b], 0, n_video - 1) of P / Vt [Tv, n_video, H]; hWa, alpha, asum, ctx stay per row (stride B).
+    const int32_t* row_video;    // [B] device, or NULL
+    int n_video;
 };
 hipError_t launch_attn_fwd(const AttnFwdArgs& a, hipStream_t st);
 struct AttnBwdArgs {
@@ -229,6 +234,9 @@ struct AttnBwdArgs {
     int vec;                                           // (set by the launcher) 16-byte path
 };
 hipError_t launch_attn_bwd(const AttnBwdArgs& a, hipStream_t st);
+
+// ---- vocabulary top-k with log-probabilities (beam.hip): ids / logp [R, k] of logits [R, V] (row stride ld), 1 <= k <= 16
+hipError_t launch_vocab_topk(const float* logits, int ld, int R, int V, int k, int32_t* ids, float* logp, hipStream_t st);
 
 // ---- the attention captioner's whole forward recurrence in one persistent launch (attn_chain.hip)
 struct AttnChainLaunch {

@@ -521,6 +521,10 @@ class Video_Caption_Generator:
         sentence = [Output(f"word_{t}", fn, [video]) for t in range(Tc)]
         return video, sentence, []
 
+    def _beam_decoder(self, B, beam):
+        """The device half of beam_generator.BatchedBeamSearch for this model: encode(params, video) / step(params, t, rows, k)."""
+        return ops.BeamDecoder(self.dims, B, beam, self.device)
+
     def beam_search(self, video, beam_size=3, length_normalization_factor=0.0, batch_size=64):
         """Beam search over a block of videos (features [n, Tv, dim_image], or frames once a CNN is attached): the captions
         build_generator(beam_size, length_normalization_factor) returns one video at a time (final_beam_search.py:504-545,

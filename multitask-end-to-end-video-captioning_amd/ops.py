@@ -890,6 +890,49 @@ class BeamDecoder:
         return (ids, logp, logits) if want_logits else (ids, logp)
 
 
+class AttnBeamDecoder:
+    """s2vt_attn_beam_workspace_bytes / s2vt_attn_beam_encode / s2vt_attn_beam_step: BeamDecoder for the temporal-attention captioner
+    (same interface).  encode embeds the frames and hoists the image part once per batch; a step's hypotheses read their video's
+    block in place.  Steps are issued in order t = 0, 1, ...; at t = 0 the parent and word rows are ignored (zero state, no <bos>)."""
+
+    def __init__(self, dims: Dims, max_B: int, beam: int, device="cuda"):
+        self.dims, self.max_B, self.beam, self.device = dims, int(max_B), int(beam), torch.device(device)
+        nbytes = lib().s2vt_attn_beam_workspace_bytes(C.byref(dims), self.max_B, self.beam)
+        if not nbytes:
+            raise ValueError(f"attention beam decoder: bad shape (B={max_B}, beam={beam}; 1 <= beam <= 16, n_video_lstm_step <= 64)")
+        self.ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        assert self.ws.data_ptr() % 256 == 0
+        self._B = 0
+
+    def encode(self, params: AttnParams, video):
+        _chk_f32(video)
+        assert video.is_contiguous() and video.shape[0] <= self.max_B
+        self._B = video.shape[0]
+        check(lib().s2vt_attn_beam_encode(C.byref(self.dims), C.byref(params), _ptr(video), self._B, self.beam, _ptr(self.ws), self.ws.numel(),
+                                          _stream()), "s2vt_attn_beam_encode")
+
+    def step(self, params: AttnParams, t: int, rows, k: int, want_logits=False, want_alphas=False):
+        """rows: int32 [3, R] host array (video of each row, parent row of step t - 1, word).  Returns numpy (ids [R, k],
+        logp [R, k]), then -- when asked for -- the step's logits [R, V] and alphas [Tv, R] on the device."""
+        import numpy as np
+        rows = np.ascontiguousarray(rows, dtype=np.int32)
+        R = rows.shape[1]
+        dev = torch.from_numpy(rows).to(self.device)                            # the one host-to-device copy
+        out = torch.empty((2, R, k), dtype=torch.int32, device=self.device)    # ids, then the bits of logp
+        logits = torch.empty((R, self.dims.n_words), dtype=torch.float32, device=self.device) if want_logits else None
+        alphas = torch.empty((self.dims.n_video_lstm_step, R), dtype=torch.float32, device=self.device) if want_alphas else None
+        check(lib().s2vt_attn_beam_step(C.byref(self.dims), C.byref(params), self._B, self.beam, int(t), R, _ptr(dev[0]), _ptr(dev[1]),
+                                        _ptr(dev[2]), int(k), _ptr(out[0]), _ptr(out[1]), _ptr(logits), _ptr(alphas), _ptr(self.ws),
+                                        self.ws.numel(), _stream()), "s2vt_attn_beam_step")
+        host = out.cpu().numpy()                                                # the one device-to-host copy
+        res = (host[0], host[1].view(np.float32))
+        if want_logits:
+            res += (logits,)
+        if want_alphas:
+            res += (alphas,)
+        return res
+
+
 def pack_weights(W_tf, in_dim: int):
     _chk_f32(W_tf)
     H = W_tf.shape[1] // 4

@@ -16,8 +16,8 @@ import numpy as np
 import torch
 
 from . import hostglue, reward
-from .train_common import (Config, Corpus, DataParallel, StepLog, epoch_batches, greedy_eval, learning_rate, lookahead, optimistic_restore,
-                           run_step, save_checkpoint_checked)
+from .train_common import (Config, Corpus, DataParallel, StepLog, beam_eval, epoch_batches, greedy_eval, learning_rate, lookahead,
+                           optimistic_restore, run_step, save_checkpoint_checked)
 
 
 def attention_config(**kw):
@@ -28,8 +28,11 @@ def attention_config(**kw):
     return Config(**base)
 
 
-def train(cfg: Config, train_corpus: Corpus, test_corpus: Corpus | None = None, model=None, log=print, resume=None, m=0.5, beta=10.0):
-    """cfg.batch_size is the GLOBAL batch; cfg.lstm_dim is dim_hidden (the word embedding has the same width, :65)."""
+def train(cfg: Config, train_corpus: Corpus, test_corpus: Corpus | None = None, model=None, log=print, resume=None, m=0.5, beta=10.0,
+          eval_beam=0, eval_lnf=0.0):
+    """cfg.batch_size is the GLOBAL batch; cfg.lstm_dim is dim_hidden (the word embedding has the same width, :65).  eval_beam > 0:
+    the per-epoch evaluation decodes with a beam of that size and length normalisation eval_lnf (train_common.beam_eval) instead of
+    greedily."""
     from . import attention as A
     par = DataParallel(model.device if model is not None else None)
     if not par.chief:
@@ -85,7 +88,10 @@ def train(cfg: Config, train_corpus: Corpus, test_corpus: Corpus | None = None, 
             pending()
         entry = {"epoch": epoch, "loss": float(np.mean(losses)) if losses else None}
         if test_corpus is not None:
-            _, entry["ciderD"] = greedy_eval(model, test_corpus, ixtoword, scorer, B, par)
+            if eval_beam > 0:
+                _, entry["ciderD"] = beam_eval(model, test_corpus, ixtoword, scorer, B, eval_beam, eval_lnf, par)
+            else:
+                _, entry["ciderD"] = greedy_eval(model, test_corpus, ixtoword, scorer, B, par)
         ck = save_checkpoint_checked(model, cfg, epoch, step_name="Variable", chief=par.chief)
         if par.chief:
             entry["checkpoint"] = ck
@@ -104,12 +110,14 @@ def main():
     ap.add_argument("--epochs", type=int, default=20); ap.add_argument("--batch-size", type=int, default=64)
     ap.add_argument("--frames", type=int, default=5, help="n_video_lstm_steps (the feature file's frames per video; up to 64)")
     ap.add_argument("--model-path", default="./attention_models")
+    ap.add_argument("--eval-beam", type=int, default=0, help="per-epoch evaluation with a beam of this size (1..16) instead of greedy decoding")
+    ap.add_argument("--eval-lnf", type=float, default=0.0, help="length normalisation factor of the evaluation beam search")
     a = ap.parse_args()
     cfg = attention_config(n_epochs=a.epochs, batch_size=a.batch_size, model_path=a.model_path, n_video_lstm_step=a.frames,
                            model_name=f"batch_size{a.batch_size}_beta10_m05_{a.frames}img_attention_model")
     tr = Corpus(a.train_sents, a.train_feats, vocabulary_file=a.vocab)
     te = Corpus(a.test_sents, a.test_feats, vocabulary=tr.vocabulary) if a.test_sents and a.test_feats else None
-    train(cfg, tr, te, resume=a.resume)
+    train(cfg, tr, te, resume=a.resume, eval_beam=a.eval_beam, eval_lnf=a.eval_lnf)
 
 
 if __name__ == "__main__":
