@@ -997,6 +997,15 @@ def embed_gather(Wemb, idx):
     return out
 
 
+def embed_scatter_add(dE, idx, dWemb):
+    """dWemb[idx[r], :] += dE[r, :] (s2vt_embed_scatter_add): dE [R, E] may be a row-strided view, dWemb [V, E] is contiguous."""
+    _chk_f32(dE, dWemb)
+    assert idx.dtype == torch.int32 and idx.is_cuda and idx.numel() == dE.shape[0]
+    assert dE.dim() == 2 and dE.stride(1) == 1 and dWemb.is_contiguous() and dWemb.shape[1] == dE.shape[1]
+    check(lib().s2vt_embed_scatter_add(_ptr(dE), dE.stride(0), _ptr(idx), dE.shape[0], dE.shape[1], _ptr(dWemb), _stream()),
+          "s2vt_embed_scatter_add")
+
+
 def global_norm_clip(g, clip_norm: float):
     _chk_f32(g)
     sumsq = torch.empty(1, dtype=torch.float32, device=g.device)

@@ -1,0 +1,87 @@
+"""Guard bands for kernel tests: a [rows, cols] window with row stride ld inside ONE flat allocation whose every other element --
+the lead in front of the window, the tail behind it and the ld - cols pad of every row -- holds a NaN sentinel written through
+an integer view.  A kernel that stores outside its output changes a sentinel and assert_intact() names the first such element; a
+kernel that loads outside its input reads a NaN, which poisons the result the test compares with its reference.
+
+    out = Guarded(R, V, ld=V + 5, lead=65, device="cuda")     # lead % 4 == 1: 4-byte, not 16-byte aligned
+    rc = L.s2vt_...(src.ptr, ..., out.ptr, out.ld, ...)
+    got = out.numpy(); out.assert_intact()
+
+A plain module (not a conftest, no fixtures); works on CPU tensors as well, where tests/test_guardband_cpu.py checks it."""
+import ctypes
+
+import numpy as np
+import torch
+
+SENTINEL32 = 0x7FC5A5A5          # an fp32 quiet NaN with a payload; the same bits serve int32 outputs
+SENTINEL16 = 0x7FC5              # a bf16 (and fp16) quiet NaN with a payload
+MIN_GUARD = 64                   # elements in front of and behind the window, at least
+
+_INT_VIEW = {4: (torch.int32, SENTINEL32), 2: (torch.int16, SENTINEL16)}
+
+
+class Guarded:
+    def __init__(self, rows, cols, ld=None, dtype=torch.float32, lead=MIN_GUARD, tail=MIN_GUARD, device="cuda", name="buffer"):
+        ld = cols if ld is None else int(ld)
+        assert rows >= 1 and cols >= 1 and ld >= cols, (rows, cols, ld)
+        assert lead >= MIN_GUARD and tail >= MIN_GUARD, "guards are at least 64 elements"
+        self.rows, self.cols, self.ld, self.lead, self.tail, self.dtype, self.name = rows, cols, ld, int(lead), int(tail), dtype, name
+        self._itype, self._sentinel = _INT_VIEW[torch.empty(0, dtype=dtype).element_size()]
+        n = self.lead + rows * ld + self.tail
+        self._buf = torch.empty(n, dtype=dtype, device=device)
+        assert self._buf.data_ptr() % 16 == 0, "the allocator's base is 16-byte aligned: `lead` alone sets the window's alignment"
+        self._ibuf = self._buf.view(self._itype)
+        self._ibuf.fill_(self._sentinel)
+        self.view = self._buf[self.lead:self.lead + rows * ld].view(rows, ld)[:, :cols]
+        self._iview = self._ibuf[self.lead:self.lead + rows * ld].view(rows, ld)[:, :cols]
+
+    @classmethod
+    def of(cls, array, ld=None, **kw):
+        """A guarded copy of a 1-D ([1, n] window) or 2-D array / tensor (inputs are guarded the same way as outputs)."""
+        t = torch.as_tensor(np.ascontiguousarray(array) if isinstance(array, np.ndarray) else array)
+        t = t.reshape(1, -1) if t.dim() <= 1 else t.reshape(t.shape[0], -1)
+        g = cls(t.shape[0], t.shape[1], ld=ld, dtype=kw.pop("dtype", t.dtype), **kw)
+        g.fill(t)
+        return g
+
+    @property
+    def ptr(self):
+        return ctypes.c_void_p(self.view.data_ptr())
+
+    @property
+    def aligned16(self):
+        return self.view.data_ptr() % 16 == 0
+
+    def fill(self, array):
+        """Write the window only."""
+        t = torch.as_tensor(np.ascontiguousarray(array) if isinstance(array, np.ndarray) else array)
+        self.view.copy_(t.reshape(self.rows, self.cols).to(self.dtype))
+        return self
+
+    def numpy(self):
+        """The window as a host array (bf16 as its uint16 bits)."""
+        if self.dtype == torch.bfloat16:
+            return self._iview.cpu().numpy().view(np.uint16)
+        return self.view.cpu().numpy()
+
+    def bits(self):
+        """The window's bit patterns as a host integer array."""
+        return self._iview.cpu().numpy()
+
+    def _where(self, off):
+        if off < self.lead:
+            return f"lead guard, {self.lead - off} element(s) in front of the window"
+        rel = off - self.lead
+        if rel >= self.rows * self.ld:
+            return f"tail guard, {rel - self.rows * self.ld} element(s) behind the last row's pad"
+        return f"pad of row {rel // self.ld}, column {rel % self.ld} (cols = {self.cols}, ld = {self.ld})"
+
+    def assert_intact(self):
+        """Every element outside the window still holds the sentinel bits."""
+        changed = self._ibuf != self._sentinel
+        changed[self.lead:self.lead + self.rows * self.ld].view(self.rows, self.ld)[:, :self.cols] = False
+        if bool(changed.any()):
+            off = int(changed.nonzero()[0, 0])
+            got = int(self._ibuf[off]) & (0xFFFFFFFF if self._itype == torch.int32 else 0xFFFF)
+            raise AssertionError(f"{self.name}: write outside the window at flat offset {off} (window starts at {self.lead}): "
+                                 f"{self._where(off)}; bits {got:#x}, sentinel {self._sentinel:#x}; {int(changed.sum())} element(s) changed")

@@ -1,0 +1,82 @@
+"""tests/guardband.py on CPU tensors: an untouched buffer passes, one planted element in the lead, the tail or a row pad fails and is
+located, the window round-trips, and lead % 4 == 1 really gives a 4-byte but not 16-byte aligned window."""
+import numpy as np
+import pytest
+import torch
+
+from guardband import SENTINEL16, SENTINEL32, Guarded
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.int32, torch.bfloat16])
+def test_untouched_buffer_is_intact_and_holds_the_sentinel(dtype):
+    g = Guarded(5, 7, ld=10, dtype=dtype, lead=65, tail=70, device="cpu")
+    g.assert_intact()
+    assert g._buf.numel() == 65 + 5 * 10 + 70
+    if dtype == torch.bfloat16:
+        assert (g._ibuf == SENTINEL16).all() and torch.isnan(g._buf.float()).all()
+    else:
+        assert (g._ibuf == SENTINEL32).all()
+    if dtype == torch.float32:
+        assert torch.isnan(g._buf).all()                              # an out-of-window read poisons a result
+
+
+def test_writes_inside_the_window_are_not_reported():
+    g = Guarded(4, 6, ld=9, device="cpu")
+    g.view.zero_()
+    g.view[3, 5] = float("nan")
+    g.assert_intact()
+
+
+@pytest.mark.parametrize("where", ["lead", "tail", "pad", "last_pad", "first", "last"])
+def test_one_planted_element_is_found(where):
+    g = Guarded(4, 6, ld=9, lead=64, tail=64, device="cpu")
+    g.fill(np.arange(24, dtype=np.float32).reshape(4, 6))
+    off = {"lead": 63, "tail": 64 + 4 * 9 + 5, "pad": 64 + 2 * 9 + 6, "last_pad": 64 + 3 * 9 + 8, "first": 0, "last": 64 + 36 + 63}[where]
+    g._buf[off] = 1.0
+    with pytest.raises(AssertionError) as e:
+        g.assert_intact()
+    msg = str(e.value)
+    assert f"flat offset {off} " in msg
+    assert {"lead": "lead guard, 1 element", "first": "lead guard, 64 element", "tail": "tail guard, 5 element", "last": "tail guard, 63 element",
+            "pad": "pad of row 2, column 6", "last_pad": "pad of row 3, column 8"}[where] in msg
+
+
+def test_a_changed_nan_payload_is_a_write():
+    """The comparison is on bits: another NaN in a guard is a write, too."""
+    g = Guarded(2, 3, device="cpu")
+    g._ibuf[10] = 0x7FC00000
+    with pytest.raises(AssertionError):
+        g.assert_intact()
+    h = Guarded(2, 3, dtype=torch.int32, device="cpu")
+    h._ibuf[64 + 6] = 0
+    with pytest.raises(AssertionError):
+        h.assert_intact()
+
+
+def test_window_round_trips():
+    rng = np.random.default_rng(0)
+    a = rng.standard_normal((5, 7)).astype(np.float32)
+    g = Guarded.of(a, ld=12, lead=65, device="cpu")
+    assert g.view.shape == (5, 7) and g.view.stride() == (12, 1) and g.ld == 12
+    assert np.array_equal(g.numpy(), a) and np.array_equal(g.bits(), a.view(np.int32))
+    g.assert_intact()
+    i = Guarded.of(np.arange(9, dtype=np.int32), device="cpu")
+    assert i.view.shape == (1, 9) and i.dtype == torch.int32 and i.numpy().tolist() == [list(range(9))]
+    b = Guarded.of(torch.tensor([[1.0, -2.5], [0.0, 3.0]], dtype=torch.bfloat16), ld=4, device="cpu")
+    assert b.view.float().tolist() == [[1.0, -2.5], [0.0, 3.0]] and b.numpy().dtype == np.uint16
+    b.assert_intact()
+
+
+def test_lead_sets_the_alignment():
+    a = Guarded(3, 4, lead=64, device="cpu")
+    m = Guarded(3, 4, lead=65, device="cpu")
+    assert a.view.data_ptr() % 16 == 0 and a.aligned16
+    assert m.view.data_ptr() % 16 == 4 and m.view.data_ptr() % 4 == 0 and not m.aligned16
+    assert m.ptr.value == m.view.data_ptr() == m._buf.data_ptr() + 65 * 4
+
+
+def test_guards_have_a_minimum():
+    with pytest.raises(AssertionError):
+        Guarded(2, 2, lead=8, device="cpu")
+    with pytest.raises(AssertionError):
+        Guarded(2, 2, ld=1, device="cpu")
