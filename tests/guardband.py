@@ -7,6 +7,11 @@ kernel that loads outside its input reads a NaN, which poisons the result the te
     rc = L.s2vt_...(src.ptr, ..., out.ptr, out.ld, ...)
     got = out.numpy(); out.assert_intact()
 
+Index arrays that a kernel follows to an address (rowidx, video_id, sample_id) take `fill=<a valid index>`: their guards then hold
+that in-range integer instead of the NaN bits, so that a read past the array can never become a wild address; assert_intact()
+compares with the same value.  int64 windows (the packed pick words) are guarded with the 32-bit sentinel in both halves.
+reset() puts the sentinel back into the window as well, for an output that several launches write in turn.
+
 A plain module (not a conftest, no fixtures); works on CPU tensors as well, where tests/test_guardband_cpu.py checks it."""
 import ctypes
 
@@ -15,18 +20,22 @@ import torch
 
 SENTINEL32 = 0x7FC5A5A5          # an fp32 quiet NaN with a payload; the same bits serve int32 outputs
 SENTINEL16 = 0x7FC5              # a bf16 (and fp16) quiet NaN with a payload
+SENTINEL64 = (SENTINEL32 << 32) | SENTINEL32      # 8-byte elements: the 32-bit sentinel twice
 MIN_GUARD = 64                   # elements in front of and behind the window, at least
 
-_INT_VIEW = {4: (torch.int32, SENTINEL32), 2: (torch.int16, SENTINEL16)}
+_INT_VIEW = {8: (torch.int64, SENTINEL64), 4: (torch.int32, SENTINEL32), 2: (torch.int16, SENTINEL16)}
 
 
 class Guarded:
-    def __init__(self, rows, cols, ld=None, dtype=torch.float32, lead=MIN_GUARD, tail=MIN_GUARD, device="cuda", name="buffer"):
+    def __init__(self, rows, cols, ld=None, dtype=torch.float32, lead=MIN_GUARD, tail=MIN_GUARD, device="cuda", name="buffer", fill=None):
         ld = cols if ld is None else int(ld)
         assert rows >= 1 and cols >= 1 and ld >= cols, (rows, cols, ld)
         assert lead >= MIN_GUARD and tail >= MIN_GUARD, "guards are at least 64 elements"
         self.rows, self.cols, self.ld, self.lead, self.tail, self.dtype, self.name = rows, cols, ld, int(lead), int(tail), dtype, name
         self._itype, self._sentinel = _INT_VIEW[torch.empty(0, dtype=dtype).element_size()]
+        if fill is not None:                                             # an index array: guards of a valid index, not of NaN bits
+            assert dtype in (torch.int32, torch.int64) and int(fill) == fill, "fill= is for integer index arrays"
+            self._sentinel = int(fill)
         n = self.lead + rows * ld + self.tail
         self._buf = torch.empty(n, dtype=dtype, device=device)
         assert self._buf.data_ptr() % 16 == 0, "the allocator's base is 16-byte aligned: `lead` alone sets the window's alignment"
@@ -58,6 +67,11 @@ class Guarded:
         self.view.copy_(t.reshape(self.rows, self.cols).to(self.dtype))
         return self
 
+    def reset(self):
+        """The sentinel everywhere, the window included: an element the next launch does not write then shows in bits()."""
+        self._ibuf.fill_(self._sentinel)
+        return self
+
     def numpy(self):
         """The window as a host array (bf16 as its uint16 bits)."""
         if self.dtype == torch.bfloat16:
@@ -82,6 +96,6 @@ class Guarded:
         changed[self.lead:self.lead + self.rows * self.ld].view(self.rows, self.ld)[:, :self.cols] = False
         if bool(changed.any()):
             off = int(changed.nonzero()[0, 0])
-            got = int(self._ibuf[off]) & (0xFFFFFFFF if self._itype == torch.int32 else 0xFFFF)
+            got = int(self._ibuf[off]) & {torch.int64: 0xFFFFFFFFFFFFFFFF, torch.int32: 0xFFFFFFFF, torch.int16: 0xFFFF}[self._itype]
             raise AssertionError(f"{self.name}: write outside the window at flat offset {off} (window starts at {self.lead}): "
                                  f"{self._where(off)}; bits {got:#x}, sentinel {self._sentinel:#x}; {int(changed.sum())} element(s) changed")

@@ -4,7 +4,7 @@ import numpy as np
 import pytest
 import torch
 
-from guardband import SENTINEL16, SENTINEL32, Guarded
+from guardband import SENTINEL16, SENTINEL32, SENTINEL64, Guarded
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.int32, torch.bfloat16])
@@ -80,3 +80,42 @@ def test_guards_have_a_minimum():
         Guarded(2, 2, lead=8, device="cpu")
     with pytest.raises(AssertionError):
         Guarded(2, 2, ld=1, device="cpu")
+
+
+def test_index_arrays_are_guarded_by_a_valid_index():
+    """fill=: the guards of an index array hold an in-range index, a change of one of them is still found, and reset() restores it."""
+    idx = np.array([3, 0, 6, 6, 1], np.int32)
+    g = Guarded.of(idx, tail=256, fill=6, device="cpu")
+    assert g._buf.numel() == 64 + 5 + 256 and g.numpy().tolist() == [idx.tolist()]
+    outside = torch.cat([g._buf[:64], g._buf[64 + 5:]])
+    assert (outside == 6).all() and int(g._buf.min()) >= 0 and int(g._buf.max()) <= 6       # nothing a kernel could follow out of range
+    g.assert_intact()
+    g._buf[64 + 5 + 200] = 7
+    with pytest.raises(AssertionError) as e:
+        g.assert_intact()
+    assert "tail guard, 200 element" in str(e.value)
+    g.reset()
+    g.assert_intact()
+    assert (g._buf == 6).all()
+    with pytest.raises(AssertionError):
+        Guarded(1, 4, fill=1, device="cpu")                           # float windows keep the NaN sentinel
+
+
+def test_eight_byte_windows():
+    """int64 (the packed pick words): both halves of every guard element hold the 32-bit sentinel, and a write of either half is found."""
+    g = Guarded(1, 5, dtype=torch.int64, device="cpu", name="packed")
+    assert (g._ibuf == SENTINEL64).all() and (g._buf.view(torch.int32) == SENTINEL32).all()
+    g.view.zero_()
+    g.assert_intact()
+    assert g.bits().tolist() == [[0] * 5] and g.view.data_ptr() % 16 == 0
+    g._buf.view(torch.int32)[2 * (64 + 5) + 1] = 0                    # the high half of the first tail element
+    with pytest.raises(AssertionError) as e:
+        g.assert_intact()
+    assert "tail guard, 0 element" in str(e.value) and "packed" in str(e.value)
+
+
+def test_reset_poisons_the_window():
+    g = Guarded.of(np.ones((2, 3), np.float32), ld=5, device="cpu")
+    g.reset()
+    assert (g.bits() == SENTINEL32).all() and np.isnan(g.numpy()).all()
+    g.assert_intact()
