@@ -480,6 +480,19 @@ int s2vt_attention_bwd(const float* hWa, const float* P, const float* Vt, const 
                        const float* dctx, float* de_scratch, float* dhWa, float* dP, float* dVt, float* dw, int32_t Tv,
                        int32_t B, int32_t H, s2vt_stream stream);
 
+/* The row -> video forms of the two calls above, for rows that share image blocks (the K samples of a video in self-critical
+ * REINFORCE): N = n_video * samples rows, sample-major -- row s * n_video + j is sample s of video j -- over P / Vt [Tv, n_video, H],
+ * ONE block per video.  hWa, dctx, dhWa, ctx [N, H] and scores, alpha [Tv, N] stay per row.  Forward: the same chains as
+ * s2vt_attention_fwd, so bit-identical to it on P / Vt tiled `samples` times; row_video_scratch: [N] int32.  Backward: dP / dVt
+ * [Tv, n_video, H] take the SUM over the video's rows (acc != 0: added to what is there), with no atomics -- every element has one
+ * owning thread that adds the rows in ascending s, so two runs give equal bits; dw [H] is accumulated with atomicAdd as above.
+ * de_scratch: [N * Tv] floats. */
+int s2vt_attention_fwd_rows(const float* hWa, const float* P, const float* Vt, const float* w, float* scores, float* alpha, float* ctx,
+                            int32_t* row_video_scratch, int32_t Tv, int32_t n_video, int32_t samples, int32_t H, s2vt_stream stream);
+int s2vt_attention_bwd_rows(const float* hWa, const float* P, const float* Vt, const float* w, const float* alpha, const float* dctx,
+                            float* de_scratch, float* dhWa, float* dP, float* dVt, float* dw, int32_t Tv, int32_t n_video,
+                            int32_t samples, int32_t H, int32_t acc, s2vt_stream stream);
+
 /* ---- the temporal-attention captioner as a whole model (original_attention.py:53-251) -----------
  * Variables of original_attention.py:55-86 in the reference's own layouts (names = the TF variable names; LSTM3 lives under
  * s2vt/LSTM3/basic_lstm_cell).  The word embedding has dim_hidden columns (:65); s2vt_dims.word_dim is ignored here.
@@ -532,6 +545,41 @@ int s2vt_attn_bptt_bwd(const s2vt_dims* d, const s2vt_attn_params* p, const s2vt
  * t-1 is the gather index of step t's embedding operand); ids_out [B, Tc] int32, alphas_out optional [Tc][Tv][B] (saved_alphas). */
 int s2vt_attn_decode_greedy(const s2vt_dims* d, const s2vt_attn_params* p, const float* video, int32_t B, int32_t video_base, int32_t* ids_out,
                             float* alphas_out, void* workspace, size_t workspace_bytes, s2vt_stream stream);
+
+/* ---- self-critical REINFORCE on the attention captioner: rows that share image blocks ---------------------------------------
+ * Rows are sample-major everywhere: row s * B + j is sample s of video j (as on the S2VT path); a greedy block comes last with
+ * sample id -1.  These forms run the per-step launches: the persistent recurrences (attn_chain*.hip) hold one image block per row and
+ * at most 64 rows, and are not used here.
+ *
+ * s2vt_attn_sample: K multinomial captions per video (+ the greedy one) -- ONE prologue (frame embedding, V @ Ua + ba) for the B
+ * videos, then the decode loop of s2vt_attn_decode_greedy on (K + with_greedy) * B rows with the attention step in its row -> video
+ * form.  Gumbel-max over Philox with counters (video_base + j, s, step) and `seed`; the greedy block takes the argmax.  No dropout, no
+ * <bos>, no host round trip per step.  ids_out [K*B, Tc] (NULL when K = 0), greedy_out [B, Tc] (NULL without with_greedy), int32.
+ * K = 0 with with_greedy gives the ids of s2vt_attn_decode_greedy.  ..._workspace_bytes: 0 on bad arguments. */
+size_t s2vt_attn_sample_workspace_bytes(const s2vt_dims* d, int32_t B, int32_t K, int32_t with_greedy);
+int s2vt_attn_sample(const s2vt_dims* d, const s2vt_attn_params* p, const float* video, int32_t B, int32_t K, int32_t with_greedy, uint64_t seed,
+                     int32_t video_base, int32_t* ids_out, int32_t* greedy_out, void* workspace, size_t workspace_bytes, s2vt_stream stream);
+/* Workspace of the three calls below for N = n_video * samples rows over n_video image blocks (0 on bad arguments). */
+size_t s2vt_attn_rows_workspace_bytes(const s2vt_dims* d, int32_t n_video, int32_t samples);
+/* s2vt_attn_teacher_forced_fwd on N rows that share n_video image blocks: caption [N, Tc], video [n_video, Tv, D], video_id / sample_id
+ * [N] for LSTM3's dropout stream (code 768 + step); logits [caption_steps*N, V], alphas_out [caption_steps][Tv][N], the first-8-frames
+ * sums per row.  The chains of the numeric contract in the same block order: logits and alphas are bit-identical to
+ * s2vt_attn_teacher_forced_fwd on the feature block tiled `samples` times. */
+int s2vt_attn_teacher_forced_fwd_rows(const s2vt_dims* d, const s2vt_attn_params* p, const float* video, int32_t n_video, int32_t samples,
+                                      const int32_t* caption, int32_t caption_steps, float keep, uint64_t seed, const int32_t* video_id,
+                                      const int32_t* sample_id, float* logits, float* alphas_out, void* workspace, size_t workspace_bytes,
+                                      s2vt_stream stream);
+/* s2vt_attn_step_scalars after s2vt_attn_teacher_forced_fwd_rows on the same workspace (R <= Tc * N). */
+int s2vt_attn_step_scalars_rows(const float* coef, const float* nll, int64_t R, const float* reg_coef, float reg_m, const float* mask_sum_local,
+                                const float* mask_sum_global, float* loss, float* gscale, float* sumsq, const s2vt_dims* d, int32_t n_video,
+                                int32_t samples, void* workspace, size_t workspace_bytes, s2vt_stream stream);
+/* s2vt_attn_bptt_bwd through that unroll: dlogits [caption_steps*N, V], reg_coef [caption_steps*N] or NULL; ACCUMULATES into `grads`.
+ * The gradients of the image blocks are [Tv, n_video, H], summed over the video's rows and the steps without atomics
+ * (s2vt_attention_bwd_rows); the Ua / ba / encode_image products run on Tv * n_video rows. */
+int s2vt_attn_bptt_bwd_rows(const s2vt_dims* d, const s2vt_attn_params* p, const s2vt_attn_params* grads, const float* video, int32_t n_video,
+                            int32_t samples, const float* dlogits, int32_t caption_steps, const float* reg_coef, float reg_m, float keep,
+                            uint64_t seed, const int32_t* video_id, const int32_t* sample_id, void* workspace, size_t workspace_bytes,
+                            s2vt_stream stream);
 
 /* ---- batched beam search for the attention captioner: the decode step of build_generator / build_sampler
  * (original_attention.py:155-251) under the beam bookkeeping of final_beam_search.py:201-294, for B videos at once.  Same division of

@@ -121,6 +121,14 @@ SIGNATURES = {
     "s2vt_adam_tf": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _f32, _f32, _i64, _f32, _f32, _f32, _vp]),
     "s2vt_attention_fwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "s2vt_attention_bwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
+    "s2vt_attention_fwd_rows": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
+    "s2vt_attention_bwd_rows": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "s2vt_attn_sample_workspace_bytes": (_sz, [_DP, _i32, _i32, _i32]),
+    "s2vt_attn_sample": (C.c_int, [_DP, _AP, _vp, _i32, _i32, _i32, _u64, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "s2vt_attn_rows_workspace_bytes": (_sz, [_DP, _i32, _i32]),
+    "s2vt_attn_teacher_forced_fwd_rows": (C.c_int, [_DP, _AP, _vp, _i32, _i32, _vp, _i32, _f32, _u64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "s2vt_attn_step_scalars_rows": (C.c_int, [_vp, _vp, _i64, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _DP, _i32, _i32, _vp, _sz, _vp]),
+    "s2vt_attn_bptt_bwd_rows": (C.c_int, [_DP, _AP, _AP, _vp, _i32, _i32, _vp, _i32, _vp, _f32, _f32, _u64, _vp, _vp, _vp, _sz, _vp]),
     "s2vt_attn_workspace_bytes": (_sz, [_DP, _i32]),
     "s2vt_attn_teacher_forced_fwd": (C.c_int, [_DP, _AP, _vp, _i32, _vp, _i32, _f32, _u64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "s2vt_attn_loss_inputs": (C.c_int, [_vp, _vp, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp]),

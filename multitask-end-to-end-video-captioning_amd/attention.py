@@ -8,6 +8,11 @@ evaluates them, and ``exponential_decay`` / ``minimize`` stand for the nodes the
 that loop translates statement by statement (tests/test_gpu_attention_model.py replays it).  All arithmetic is in
 libs2vt_hip.so (csrc/attn_model.hip: the whole unroll, its backward, the greedy decode loop and the beam-search step are library
 calls; csrc/attn.hip: score -> softmax -> context in one launch per step); torch supplies device memory and streams.  No CPU fallback.
+
+Beyond the reference script, which trains this model with cross entropy only, the class carries the self-critical REINFORCE stage that
+every reinforcement_* script applies to its model: sample() draws K multinomial captions per video (+ the greedy one),
+reinforce_update() is the reward-scaled update, and build_multinomial_sampler / build_loss / reinforce_train_op are the graph
+surface of reinforcement_multisampling_tf_s2vt.py's train().  The K sample rows of a video share its one image block on the device.
 """
 from __future__ import annotations
 
@@ -39,10 +44,11 @@ class Attention_Caption_Generator:
     regulariser constants (:299-300), `device` / `seed` additions."""
 
     def __init__(self, dim_image, n_words, dim_hidden, batch_size, n_video_lstm_steps, n_caption_lstm_steps, drop_out_rate,
-                 bias_init_vector=None, m=0.5, beta=10.0, device="cuda", seed=1234):
+                 bias_init_vector=None, m=0.5, beta=10.0, device="cuda", seed=1234, multisample=1):
         self.dim_image, self.n_words, self.dim_hidden, self.batch_size = dim_image, n_words, dim_hidden, batch_size
         self.n_video_lstm_steps, self.n_caption_lstm_steps, self.drop_out_rate = n_video_lstm_steps, n_caption_lstm_steps, drop_out_rate
         self.m, self.beta = float(m), float(beta)
+        self.multisample = int(multisample)            # K of the REINFORCE graphs (build_loss's feed is the K-times tiled feature block)
         self.device = torch.device(device)
         H = dim_hidden
         self.dims = ops.make_dims(dim_image, n_words, H, H, n_video_lstm_steps, n_caption_lstm_steps)
@@ -63,6 +69,7 @@ class Attention_Caption_Generator:
         self.global_step = 0
         self.adam_t = 0
         self.world_size, self.rank, self.dp_overlap = 1, 0, False        # data parallel: one all-reduce of the flat bucket (dist.py)
+        self.sample_seed = seed
         self.dropout_seed = seed + 1
         self._gscale = torch.ones(1, dtype=torch.float32, device=self.device)
         self._applied = torch.zeros(1, dtype=torch.int32, device=self.device)   # step number of the last Adam update the device APPLIED
@@ -83,12 +90,16 @@ class Attention_Caption_Generator:
             return a.to(device=self.device, dtype=dtype).contiguous()
         return torch.as_tensor(np.ascontiguousarray(a)).to(device=self.device, dtype=dtype).contiguous()
 
-    def _row_ids(self, B, video_base=0):
-        key = (B, int(video_base))
+    def _row_ids(self, B, video_base=0, rep=1):
+        """(video_id, sample_id) of rep * B sample-major rows: row s * B + j is sample s of video video_base + j."""
+        key = (B, int(video_base)) if rep == 1 else (B, int(video_base), int(rep))
         hit = self._row_ids_cache.get(key)
         if hit is None:
-            hit = self._row_ids_cache[key] = ((torch.arange(B, dtype=torch.int32, device=self.device) + video_base).contiguous(),
-                                              torch.zeros(B, dtype=torch.int32, device=self.device))
+            if len(self._row_ids_cache) > 64:
+                self._row_ids_cache.clear()
+            vid = (torch.arange(B, dtype=torch.int32, device=self.device) + video_base).repeat(rep)
+            sid = torch.arange(rep, dtype=torch.int32, device=self.device).repeat_interleave(B)
+            hit = self._row_ids_cache[key] = (vid.contiguous(), sid.contiguous())
         return hit
 
     def load(self, arrays):
@@ -196,11 +207,95 @@ class Attention_Caption_Generator:
         return self._active_steps(mask, self.n_caption_lstm_steps)
 
     def sample(self, video, K=0, with_greedy=True, seed=None, video_base=0):
-        """(None, greedy ids [B, Tc]) -- the greedy sampler in the shape train_common.greedy_eval expects (this model has no
-        multinomial sampler: original_attention.py trains with cross entropy only)."""
-        assert K == 0 and with_greedy
-        ids, _ = ops.attn_decode_greedy(self.dims, self.store.params, self._dev(video, torch.float32), video_base)
-        return None, ids
+        """K multinomial captions per video (+ the greedy caption): (sampled [K*B, Tc], greedy [B, Tc]) int32 device tensors, sample-major
+        rows (row s * B + j is sample s of video j) -- the contract of Video_Caption_Generator.sample.  One prologue for the B videos, the
+        decode loop on (K + greedy) * B rows that share the B image blocks, Gumbel-max over Philox with counters (video_base + j, s, step):
+        no host round trip per step, no dropout, no <bos> (the sampler graphs of original_attention.py:155-251 with tf.multinomial in
+        place of the argmax, as reinforcement_multisampling_tf_s2vt.py:294-339 does for its model).
+        K = 0: (None, greedy ids [B, Tc]) -- the greedy sampler in the shape train_common.greedy_eval expects."""
+        video = self._dev(video, torch.float32)
+        if K == 0:
+            assert with_greedy
+            ids, _ = ops.attn_decode_greedy(self.dims, self.store.params, video, video_base)
+            return None, ids
+        return ops.attn_sample(self.dims, self.store.params, video, int(K), self.sample_seed if seed is None else seed, video_base, with_greedy)
+
+    def _pg_forward(self, video, cap, keep, steps, video_base, share):
+        """The teacher-forced unroll of the N = S * B sample rows: on the B shared image blocks, or (share False) through the plain entry
+        point on the S-times tiled feature block -- the same chains, bit-identical logits."""
+        B, N = video.shape[0], cap.shape[0]
+        S = N // B
+        vid, sid = self._row_ids(B, video_base, S)
+        seed = self.dropout_seed + 104729 * self.global_step
+        if share:
+            logits, _, ws = ops.attn_teacher_forced_fwd_rows(self.dims, self.store.params, video, cap, keep, seed, vid, sid, steps=steps)
+            feats = video
+        else:
+            feats = video.repeat(S, 1, 1).contiguous() if S > 1 else video
+            logits, _, ws = ops.attn_teacher_forced_fwd(self.dims, self.store.params, feats, cap, keep, seed, vid, sid, steps=steps)
+        return dict(logits=logits, ws=ws, feats=feats, S=S, B=B, N=N, vid=vid, sid=sid, seed=seed, keep=keep, steps=steps, share=share)
+
+    def reinforce_update(self, video, sampled, mask, rewards, baseline, lr, clip_norm=5.0, keep=None, video_base=0, reward_fn=None,
+                         active_steps="auto", share_image_blocks=True, beta1=0.9, beta2=0.999, eps=1e-8):
+        """One self-critical REINFORCE step (build_loss + train_op of reinforcement_multisampling_tf_s2vt.py:227-292, 633-652, on this
+        model): video [B, Tv, D], sampled [N, Tc] ids with N = S * B sample-major rows, rewards / baseline [N].  The objective is
+
+            ( - sum_{n,t} lp[n,t] mask[n,t] (r[n] - b[n])  +  sum_{n,t} beta max(0, m - sum(alpha[t, 0:8, n])) mask[n,t] ) / sum(mask)
+
+        lp = the log-probability of the sampled word under the teacher-forced unroll with LSTM3's dropout (keep; None: the model's);
+        the alpha regulariser of build_model (original_attention.py:118-123,144) is kept, weighted by the policy-gradient mask -- it is
+        identically zero while Tv <= 8.  mask None: derived from the ids on the device (s2vt_caption_mask: 1 up to and including the
+        first <eos> = 0).  reward_fn: callable() -> (rewards [N], baseline [N]) evaluated on the host AFTER the forward has been queued,
+        so a host-side scorer (CIDEr-D) runs under it; `rewards` / `baseline` are ignored then.  active_steps: "auto" (a host-resident
+        mask: only the steps up to the batch's longest sample are unrolled), an int, or None (all Tc) -- exact, the skipped steps add
+        zeros.  Then as xe_update: all-reduce of the bucket, 1 / sum(mask), clip_by_global_norm, TF-form Adam, the step counters.
+        share_image_blocks: the S rows of a video read its ONE [Tv, H] block in the forward, and the backward sums their image
+        gradients per video without atomics (s2vt_attn_*_rows); False runs the same update through the plain entry points on the
+        S-times tiled feature block (the A/B switch; profiles/NOTES.md has the figures)."""
+        keep = self.drop_out_rate if keep is None else keep
+        Tc = self.n_caption_lstm_steps
+        steps = Tc
+        if active_steps == "auto":
+            s = self._active_steps(mask, Tc) if (mask is not None and not dp.active()) else None
+            steps = Tc if s is None else s
+        elif active_steps:
+            steps = max(1, min(Tc, int(active_steps)))
+        video = self._dev(video, torch.float32)
+        cap = self._dev(sampled, torch.int32)
+        if mask is None:
+            mask, target, msum = ops.caption_mask(cap)
+        else:
+            mask = self._dev(mask, torch.float32)
+            target, msum = cap.t().contiguous().view(-1), mask.sum().reshape(1)
+        c = self._pg_forward(video, cap, keep, steps, video_base, share_image_blocks)
+        N, S, B = c["N"], c["S"], c["B"]
+        R = steps * N
+        r, b = reward_fn() if reward_fn is not None else (rewards, baseline)
+        coef = ops.pg_coef(mask, self._dev(r, torch.float32), self._dev(b, torch.float32), 1.0)[:R]
+        reg = None
+        if self.n_video_lstm_steps > 8 and self.beta != 0.0:
+            reg = (mask * self.beta).t().contiguous().view(-1)[:R]
+        nll, _ = ops.softmax_nll_fwd_bwd(c["logits"], target[:R], coef, 0.0)      # logits <- coef * (softmax - onehot)
+        st = self.store
+        ops.zero_(st.grad)
+        if share_image_blocks:
+            ops.attn_bptt_bwd_rows(self.dims, st.params, st.grads, video, S, c["logits"], c["ws"], steps, reg, self.m, keep, c["seed"], c["vid"], c["sid"])
+        else:
+            ops.attn_bptt_bwd(self.dims, st.params, st.grads, c["feats"], c["logits"], c["ws"], steps, reg, self.m, keep, c["seed"], c["vid"], c["sid"])
+        gsum = dp.allreduce_bucket(st.grad, st.numel, msum)
+        loss = torch.empty(1, dtype=torch.float32, device=self.device)
+        sumsq = torch.empty(1, dtype=torch.float32, device=self.device)
+        if share_image_blocks:
+            ops.attn_step_scalars_rows(self.dims, B, S, c["ws"], coef, nll, reg, self.m, msum, gsum, loss, self._gscale, sumsq)
+        else:
+            ops.attn_step_scalars(self.dims, N, c["ws"], coef, nll, reg, self.m, msum, gsum, loss, self._gscale, sumsq)
+        ops.grad_finalize(st.grad[:st.numel], st.theta, self._gscale, 0.0, sumsq)
+        self.global_step += 1
+        self.adam_t += 1
+        ops.adam_tf(st.theta, st.grad[:st.numel], st.m, st.v, sumsq, clip_norm, lr, self.adam_t, beta1, beta2, eps, applied_step=self._applied)
+        out = StepStats(loss[0], sumsq, msum[0])
+        out.mask = mask
+        return out
 
     def _beam_decoder(self, B, beam):
         """The device half of beam_generator.BatchedBeamSearch for this model: encode(params, video) / step(params, t, rows, k)."""
@@ -281,6 +376,76 @@ class Attention_Caption_Generator:
             ids, al = ops.attn_decode_greedy(self.dims, self.store.params, self._dev(v, torch.float32), want_alphas=True)
             return {"sampled_captions": ids.cpu().numpy().astype(np.int64), "saved_alphas": al.cpu().numpy()}
         return Output("sampled_captions", fn, [video]), video, Output("saved_alphas", fn, [video])
+
+    # ---- the REINFORCE graphs (reinforcement_multisampling_tf_s2vt.py's surface on this model)
+    def placeholder(self, name, shape=(None,), dtype=np.float32):
+        """tf.placeholder: `rewards` / `base_line` of reinforcement_multisampling_tf_s2vt.py:628-629."""
+        return Placeholder(name, shape, dtype)
+
+    def build_multinomial_sampler(self):
+        """(sampled_captions, video): one multinomial caption per video (reinforcement_multisampling_tf_s2vt.py:294-339).  Every run
+        draws from a fresh Philox stream (the TF op is stateful too); the stream is a function of the model's seed and the run count."""
+        video = Placeholder("video", (self.batch_size, self.n_video_lstm_steps, self.dim_image), np.float32)
+        state = {"calls": 0}
+
+        def fn(v):
+            state["calls"] += 1
+            s, _ = self.sample(v, 1, False, seed=self.sample_seed + 7919 * state["calls"])
+            return {"sampled_captions": s.cpu().numpy().astype(np.int64)}
+        return Output("sampled_captions", fn, [video]), video
+
+    def _untile(self, v, N):
+        """build_loss's video feed -> the B distinct videos on the device.  The reference feeds the feature block tiled K times, rows
+        k*B + j = video j (reinforcement_multisampling_tf_s2vt.py:779-782): with multisample = K > 1 and N % K == 0 such a feed is
+        recognised (compared on the host when it arrives there; a device tensor is taken at the feed contract's word) and the K copies
+        are never made on the device.  Any other [N, ...] block is N videos."""
+        K = self.multisample
+        host = None if isinstance(v, torch.Tensor) else np.asarray(v, np.float32)
+        n = (v if host is None else host).shape[0]
+        if n == N and K > 1 and N % K == 0:
+            B = N // K
+            if host is not None:
+                hb = host.reshape(K, B, -1)
+                if all(np.array_equal(hb[0], hb[k]) for k in range(1, K)):
+                    return self._dev(host[:B], torch.float32)
+            else:
+                return v[:B].to(device=self.device, dtype=torch.float32).contiguous()
+        return self._dev(v if host is None else host, torch.float32)
+
+    def build_loss(self):
+        """(loss, video, caption, caption_mask) as reinforcement_multisampling_tf_s2vt.py:227-292 on this model's unroll: the reference
+        returns the dense [N, Tc, V] tensor log_softmax * onehot * mask, which has one non-zero per (n, t) -- the fetch here is the
+        [N, Tc] array of those values, lp * mask (as Video_Caption_Generator.build_loss)."""
+        N, Tc = self.batch_size * self.multisample, self.n_caption_lstm_steps
+        video = Placeholder("video", (N, self.n_video_lstm_steps, self.dim_image), np.float32)
+        caption = Placeholder("caption", (N, Tc), np.int32)
+        caption_mask = Placeholder("caption_mask", (N, Tc), np.float32)
+
+        def fn(v, c, m):
+            c = self._dev(c, torch.int32); m = self._dev(m, torch.float32)
+            f = self._pg_forward(self._untile(v, c.shape[0]), c, self.drop_out_rate, Tc, 0, True)
+            zero = torch.zeros(f["logits"].shape[0], dtype=torch.float32, device=self.device)
+            _, lp = ops.softmax_nll_fwd_bwd(f["logits"], c.t().contiguous().view(-1), zero, 0.0)
+            return {"loss": (lp.view(Tc, -1).t() * m).cpu().numpy()}
+        loss = Output("loss", fn, [video, caption, caption_mask])
+        loss.graph = {"kind": "build_loss"}
+        return loss, video, caption, caption_mask
+
+    def reinforce_train_op(self, build_loss_outputs, rewards, base_line, learning_rate, clip_norm=5.0):
+        """(train_op, sum_loss) of reinforcement_multisampling_tf_s2vt.py:641-652:
+            norm = sum(loss_masks); sum_loss = -sum(loss * (rewards - base_line)) / norm  (+ this model's alpha regulariser, see
+            reinforce_update); clip_by_global_norm(tf.gradients(sum_loss), 5); Adam.apply_gradients(global_step).
+        Fed as there (:821-823): {loss_masks, loss_captions, loss_features (the K-times tiled block), rewards, base_line}.  sum_loss
+        fetched beside train_op is the pre-update value the update differentiated."""
+        video, caption, caption_mask = build_loss_outputs[1:4]
+        lr = learning_rate.value if hasattr(learning_rate, "value") else (lambda: float(learning_rate))
+        inputs = [video, caption, caption_mask, rewards, base_line]
+
+        def fn(v, c, m, r, b):
+            r = np.asarray(r, np.float32).reshape(-1); b = np.asarray(b, np.float32).reshape(-1)
+            st = self.reinforce_update(self._untile(v, np.shape(c)[0]), c, m, r, b, lr(), clip_norm=clip_norm)
+            return {"train_op": None, "sum_loss": float(st.loss)}
+        return Output("train_op", fn, inputs), Output("sum_loss", fn, inputs)
 
     # ---- the nodes train() adds around the model's graph (:430-441)
     def exponential_decay(self, start_learning_rate, decay_steps, decay_rate=0.5):

@@ -6,8 +6,12 @@
 // fixed sequences of detmath.h, the context is an ascending-t fmaf chain: bit-identical to the oracle's
 // orc_attention_step.  One launch per decode step does score -> softmax -> context (one workgroup per batch row).
 // Backward is order-free fp32, one launch per step as well.  The whole-model entry points are in attn_model.hip.
+// The row -> video forms serve rows that share image blocks (the hypotheses of a beam search, the K samples of a video in self-critical
+// REINFORCE): the forward reads P / Vt [Tv, n_video, H] through a row -> video index; the shared-block backward sums dP / dVt per video
+// over its rows in two launches and without atomics (launch_attn_bwd_rows).  The plain forms are the kernels they always were.
 #include <hip/hip_runtime.h>
 
+#include <cstdint>
 #include <cstring>
 #include <mutex>
 
@@ -282,6 +286,104 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const AttnBwdArgs a)
     }
 }
 
+// ---- backward on shared image blocks (internal.h AttnBwdRowsArgs): rows sample-major, row -> video = row % n_video ---------------
+// Launch 1, one workgroup per row: the first half of attn_bwd_kernel -- dctx, dalpha (V read from the video's block), hinge, de.
+__global__ __launch_bounds__(256) void attn_bwd_rows_de_kernel(const AttnBwdRowsArgs r)
+{
+    extern __shared__ float sm[];
+    const AttnBwdArgs& a = r.a;
+    const int H = a.H, Tv = a.Tv, B = a.B, NV = r.n_video;
+    float* dc = sm;                      // [H]
+    float* dal = sm + ((H + 3) & ~3);    // [64]
+    float* al = dal + kAttnMaxTv;        // [64]
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int sv = b % NV;
+    const float* __restrict__ Vp = a.Vt;
+    const float* __restrict__ sl = a.slabs;
+    if (tid < Tv) al[tid] = a.alpha[tid * B + b];
+    for (int h = tid; h < H; h += 256) {
+        float v = a.dctx ? a.dctx[(size_t)b * a.ld_dctx + h] : 0.f;
+        for (int s = 0; s < a.nslab; ++s) v += sl[(size_t)s * a.slab_stride + (size_t)b * a.ld_slab + a.ctx_col0 + h];
+        dc[h] = v;
+        if (r.dctx_rows) r.dctx_rows[(size_t)b * H + h] = v;
+        if (a.demb_out) {
+            float u = a.demb_dense ? a.demb_dense[(size_t)b * a.ld_demb + h] : 0.f;
+            for (int s = 0; s < a.nslab; ++s) u += sl[(size_t)s * a.slab_stride + (size_t)b * a.ld_slab + a.emb_col0 + h];
+            a.demb_out[(size_t)b * H + h] = u;
+        }
+    }
+    __syncthreads();
+    for (int t = wv; t < Tv; t += 4) {
+        const float* vp = Vp + ((size_t)t * NV + sv) * H;
+        float s = 0.f;
+        for (int h = lane; h < H; h += 64) s += dc[h] * vp[h];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+        if (lane == 0) dal[t] = s;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        if (a.reg_coef && (a.reg_m - a.asum[b]) > 0.f) {
+            const int n8 = Tv < 8 ? Tv : 8;
+            const float rc = a.reg_coef[b];
+            for (int t = 0; t < n8; ++t) dal[t] -= rc;
+        }
+        float dot = 0.f;
+        for (int t = 0; t < Tv; ++t) dot += al[t] * dal[t];
+        for (int t = 0; t < Tv; ++t) r.de_rows[(size_t)b * Tv + t] = al[t] * (dal[t] - dot);
+    }
+}
+
+// Launch 2, one workgroup per (video, 256-column slice), one column per thread: the video's rows in ascending s.  The thread is the
+// only writer of dhWa[row][h] and of dP / dVt[t][video][h]; CAP >= Tv frames of the two sums live in registers.
+template <int CAP>
+__global__ __launch_bounds__(256) void attn_bwd_rows_acc_kernel(const AttnBwdRowsArgs r)
+{
+    const AttnBwdArgs& a = r.a;
+    const int H = a.H, Tv = a.Tv, N = a.B, NV = r.n_video;
+    const int v = blockIdx.x, h = blockIdx.y * 256 + threadIdx.x;
+    if (h >= H) return;
+    const float* __restrict__ Pp = a.P;
+    float sP[CAP], sV[CAP];
+#pragma unroll
+    for (int t = 0; t < CAP; ++t) { sP[t] = 0.f; sV[t] = 0.f; }
+    const float wh = a.w[h];
+    float dwl = 0.f;
+    for (int s = 0; s < r.samples; ++s) {
+        const int row = s * NV + v;
+        const float hv = a.hWa ? a.hWa[(size_t)row * H + h] : 0.f;
+        const float dch = r.dctx_rows ? r.dctx_rows[(size_t)row * H + h] : a.dctx[(size_t)row * a.ld_dctx + h];
+        const float* __restrict__ de = r.de_rows + (size_t)row * Tv;
+        float acc = 0.f;
+#pragma unroll
+        for (int t = 0; t < CAP; ++t)
+            if (t < Tv) {
+                const float T = dm_tanhf(hv + Pp[((size_t)t * NV + v) * H + h]);
+                const float d = de[t];
+                const float ds = d * wh * (1.f - T * T);
+                sP[t] += ds;
+                sV[t] += a.alpha[t * N + row] * dch;
+                acc += ds;
+                dwl += d * T;
+            }
+        if (a.dhWa) a.dhWa[(size_t)row * H + h] = acc;
+    }
+#pragma unroll
+    for (int t = 0; t < CAP; ++t)
+        if (t < Tv) {
+            const size_t o = ((size_t)t * NV + v) * H + h;
+            if (a.acc) { a.dP[o] += sP[t]; a.dVt[o] += sV[t]; }
+            else { a.dP[o] = sP[t]; a.dVt[o] = sV[t]; }
+        }
+    atomicAdd(a.dw + h, dwl);
+}
+
+__global__ void attn_row_video_kernel(int32_t* row_video, int rows, int n_video)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < rows) row_video[i] = i % n_video;
+}
+
 // ---- attribute head ---------------------------------------------------------------------------
 __global__ void mean_frames_kernel(const float* video, float* out, int B, int Tv, int D)
 {
@@ -381,9 +483,65 @@ hipError_t launch_attn_bwd(const AttnBwdArgs& a0, hipStream_t st)
     return hipGetLastError();
 }
 
+hipError_t launch_attn_bwd_rows(const AttnBwdRowsArgs& r, hipStream_t st)
+{
+    const AttnBwdArgs& a = r.a;
+    if (a.Tv <= 0 || a.Tv > kAttnMaxTv || a.B <= 0 || a.H <= 0 || r.n_video <= 0 || r.samples <= 0) return hipErrorInvalidValue;
+    if ((int64_t)r.n_video * r.samples != a.B || !r.de_rows || (!r.dctx_rows && (!a.dctx || a.nslab > 0))) return hipErrorInvalidValue;
+    const size_t lds = ((size_t)((a.H + 3) & ~3) + 2 * kAttnMaxTv) * sizeof(float);
+    hipLaunchKernelGGL(attn_bwd_rows_de_kernel, dim3(a.B), dim3(256), lds, st, r);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const dim3 grid(r.n_video, (a.H + 255) / 256);
+    if (a.Tv <= 8) hipLaunchKernelGGL(attn_bwd_rows_acc_kernel<8>, grid, dim3(256), 0, st, r);
+    else if (a.Tv <= 32) hipLaunchKernelGGL(attn_bwd_rows_acc_kernel<32>, grid, dim3(256), 0, st, r);
+    else hipLaunchKernelGGL(attn_bwd_rows_acc_kernel<kAttnMaxTv>, grid, dim3(256), 0, st, r);
+    return hipGetLastError();
+}
+
+hipError_t launch_attn_row_video(int32_t* row_video, int rows, int n_video, hipStream_t st)
+{
+    if (rows <= 0 || n_video <= 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(attn_row_video_kernel, dim3((rows + 255) / 256), dim3(256), 0, st, row_video, rows, n_video);
+    return hipGetLastError();
+}
+
 }  // namespace s2vt
 
 extern "C" {
+
+int s2vt_attention_fwd_rows(const float* hWa, const float* P, const float* Vt, const float* w, float* scores, float* alpha, float* ctx,
+                            int32_t* row_video_scratch, int32_t Tv, int32_t n_video, int32_t samples, int32_t H, s2vt_stream stream)
+{
+    if (!hWa || !P || !Vt || !w || !scores || !alpha || !ctx || !row_video_scratch || Tv <= 0 || Tv > kAttnMaxTv || n_video <= 0 ||
+        samples <= 0 || H <= 0 || (int64_t)n_video * samples > INT32_MAX / 64)
+        return S2VT_E_BADARG;
+    const int N = n_video * samples;
+    HIP_TRY(launch_attn_row_video(row_video_scratch, N, n_video, S(stream)));
+    AttnFwdArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.hWa = hWa; a.P = P; a.Vt = Vt; a.w = w; a.scores = scores; a.alpha = alpha; a.ctx = ctx; a.Tv = Tv; a.B = N; a.H = H;
+    a.row_video = row_video_scratch; a.n_video = n_video;
+    HIP_TRY(launch_attn_fwd(a, S(stream)));
+    return S2VT_OK;
+}
+
+int s2vt_attention_bwd_rows(const float* hWa, const float* P, const float* Vt, const float* w, const float* alpha, const float* dctx,
+                            float* de_scratch, float* dhWa, float* dP, float* dVt, float* dw, int32_t Tv, int32_t n_video,
+                            int32_t samples, int32_t H, int32_t acc, s2vt_stream stream)
+{
+    if (!hWa || !P || !Vt || !w || !alpha || !dctx || !de_scratch || !dhWa || !dP || !dVt || !dw || Tv <= 0 || Tv > kAttnMaxTv ||
+        n_video <= 0 || samples <= 0 || H <= 0 || (int64_t)n_video * samples > INT32_MAX / 64)
+        return S2VT_E_BADARG;
+    AttnBwdRowsArgs r;
+    std::memset(&r, 0, sizeof(r));
+    AttnBwdArgs& a = r.a;
+    a.hWa = hWa; a.P = P; a.Vt = Vt; a.w = w; a.alpha = alpha; a.dctx = dctx; a.ld_dctx = H;
+    a.dhWa = dhWa; a.dP = dP; a.dVt = dVt; a.dw = dw; a.Tv = Tv; a.B = n_video * samples; a.H = H; a.acc = acc ? 1 : 0;
+    r.n_video = n_video; r.samples = samples; r.de_rows = de_scratch;
+    HIP_TRY(launch_attn_bwd_rows(r, S(stream)));
+    return S2VT_OK;
+}
 
 int s2vt_attention_fwd(const float* hWa, const float* P, const float* Vt, const float* w, float* scores, float* alpha,
                        float* ctx, int32_t Tv, int32_t B, int32_t H, s2vt_stream stream)

@@ -12,6 +12,12 @@
 // product for all steps: the chain's first block), the output layer tanh([emb ; ctx ; out] @ Wp + bp) and the vocabulary
 // logits after the loop, every weight gradient and the [out | ctx | emb] data gradient of the output layer in the
 // backward.  Forward activations are bit-identical to oracle/s2vt_oracle.py::attention_forward; gradients are order-free.
+//
+// Self-critical REINFORCE (s2vt_attn_sample, s2vt_attn_teacher_forced_fwd_rows, s2vt_attn_bptt_bwd_rows): N = samples * B sample-major rows
+// (row s * B + j = sample s of video j) share the B image blocks -- one prologue, the attention step in its row -> video form, the
+// shared-block attention backward of attn.hip, the image-side gradient products on Tv * B rows.  Scope: these forms run the PER-STEP
+// launches; the persistent recurrences (attn_chain*.hip: one image block per row, B <= 64) are not used by them and are unchanged -- at
+// the working shape N = 320 they would not be eligible anyway.
 #include <hip/hip_runtime.h>
 
 #include <climits>
@@ -174,15 +180,19 @@ struct AttnWs {
     float* aimg; unsigned* async_; // persistent forward recurrence (attn_chain.hip): fragment images, hand-off counters
     float *bimg, *bex, *brow_; unsigned* bsync;   // persistent backward recurrence (attn_chain_bwd.hip)
     float* deh;                                   // ... its d(score) history [Tc][Tv][B] (more than 5 frames: dP / dV are accumulated behind the launch)
+    int32_t* rowvid; float* dctxr;                // the shared-block form only: row -> video [rows], the assembled d(ctx) of one step [rows][H]
 };
 
-size_t carve_attn(Carver& c, const s2vt_dims* d, int B, AttnWs* out)
+// n_video > 0: the shared-block form -- B rows (sample-major) over n_video image blocks: the image arrays (encidx, Vt, P and their gradients)
+// count n_video blocks per frame, everything else B rows, and rowvid / dctxr follow at the end.  n_video = 0: one block per row, the
+// layout as it always was.
+size_t carve_attn(Carver& c, const s2vt_dims* d, int B, AttnWs* out, int n_video = 0)
 {
-    const size_t H = d->lstm_dim, V = d->n_words, Tv = d->n_video_lstm_step, Tc = d->n_caption_lstm_step, b = B;
+    const size_t H = d->lstm_dim, V = d->n_words, Tv = d->n_video_lstm_step, Tc = d->n_caption_lstm_step, b = B, nv = n_video > 0 ? n_video : B;
     AttnWs w;
-    w.encidx = c.take<int32_t>(Tv * b); w.prev = c.take<int32_t>(Tc * b); w.tgt = c.take<int32_t>(Tc * b);
+    w.encidx = c.take<int32_t>(Tv * nv); w.prev = c.take<int32_t>(Tc * b); w.tgt = c.take<int32_t>(Tc * b);
     w.vid = c.take<int32_t>(b); w.sid = c.take<int32_t>(b);
-    w.Vt = c.take<float>(Tv * b * H); w.P = c.take<float>(Tv * b * H);
+    w.Vt = c.take<float>(Tv * nv * H); w.P = c.take<float>(Tv * nv * H);
     w.hWa = c.take<float>(Tc * b * H); w.alpha = c.take<float>(Tc * Tv * b); w.asum = c.take<float>(Tc * b); w.ctx = c.take<float>(Tc * b * H);
     w.G3 = c.take<float>(Tc * b * 4 * H); w.C3 = c.take<float>((Tc + 1) * b * H); w.H3 = c.take<float>((Tc + 1) * b * H);
     w.O3 = c.take<float>((Tc + 1) * b * H);
@@ -190,7 +200,7 @@ size_t carve_attn(Carver& c, const s2vt_dims* d, int B, AttnWs* out)
     w.dY = c.take<float>(Tc * b * H); w.dcat = c.take<float>(Tc * b * 3 * H); w.dZ3 = c.take<float>(Tc * b * 4 * H);
     w.dxs = c.take<float>((size_t)kXSlabs * b * 3 * H); w.dqs = c.take<float>((size_t)kQSlabs * b * H); w.dc = c.take<float>(b * H);
     w.dhWa = c.take<float>(Tc * b * H); w.dEmb = c.take<float>(Tc * b * H);
-    w.dPt = c.take<float>(Tv * b * H); w.dVtt = c.take<float>(Tv * b * H); w.dEv = c.take<float>(Tv * b * H);
+    w.dPt = c.take<float>(Tv * nv * H); w.dVtt = c.take<float>(Tv * nv * H); w.dEv = c.take<float>(Tv * nv * H);
     w.deh = c.take<float>(Tc * Tv * b);
     {
         // dY = dlogits @ Wout^T ([Tc B, H], K = |V|) and dcat = dpre @ Wp^T ([Tc B, 3H], K = H) when they are short of tiles
@@ -211,6 +221,8 @@ size_t carve_attn(Carver& c, const s2vt_dims* d, int B, AttnWs* out)
         attn_bwd_chain_scratch((int)H, &imgf, &exf, &rowf, &syncb);
         w.bimg = c.take<float>(imgf); w.bex = c.take<float>(exf); w.brow_ = c.take<float>(rowf); w.bsync = c.take<unsigned>(syncb / 4);
     }
+    w.rowvid = nullptr; w.dctxr = nullptr;
+    if (n_video > 0) { w.rowvid = c.take<int32_t>(b); w.dctxr = c.take<float>(b * H); }
     if (out) *out = w;
     return c.off;
 }
@@ -240,7 +252,7 @@ int attn_prologue(const s2vt_dims* d, const s2vt_attn_params* p, const float* vi
     return S2VT_OK;
 }
 
-hipError_t attn_step(const s2vt_attn_params* p, const AttnWs& w, int t, int Tv, int B, int H, const float* query, hipStream_t st)
+hipError_t attn_step(const s2vt_attn_params* p, const AttnWs& w, int t, int Tv, int B, int H, const float* query, hipStream_t st, int n_video = 0)
 {
     const size_t BH = (size_t)B * H;
     if (t > 0) {       // (step 0: the query is the zero state, h_prev @ Wa = 0, :102)
@@ -253,6 +265,7 @@ hipError_t attn_step(const s2vt_attn_params* p, const AttnWs& w, int t, int Tv, 
     a.hWa = t > 0 ? w.hWa + t * BH : nullptr; a.P = w.P; a.Vt = w.Vt; a.w = p->embed_att_w;
     a.alpha = w.alpha + (size_t)t * Tv * B; a.asum = w.asum + (size_t)t * B; a.ctx = w.ctx + t * BH;
     a.Tv = Tv; a.B = B; a.H = H;
+    if (n_video > 0) { a.row_video = w.rowvid; a.n_video = n_video; }       // the B rows share n_video image blocks (row -> video form)
     return launch_attn_fwd(a, st);
 }
 
@@ -308,6 +321,54 @@ size_t carve_attn_beam(Carver& c, const s2vt_dims* d, int B, int beam, AttnBeamW
     return c.off;
 }
 
+// The multinomial sampler's workspace: the image blocks of the B videos and one step's worth of per-row state for R = (K + greedy) B rows.
+struct AttnSampleWs {
+    int32_t *encidx, *vid, *sid, *rowvid;
+    float *Vt, *P;                     // [Tv*B, H]
+    float *c[2], *h[2];                // LSTM3 state [R][H]: step t reads slot t & 1 and writes the other
+    float *hWa, *alpha, *ctx, *Y;      // [R][H], [Tv][R], [R][H], [R][H]
+    unsigned long long* packed;        // picks [Tc][R][kPickStride]
+};
+
+size_t carve_attn_sample(Carver& c, const s2vt_dims* d, int B, int R, AttnSampleWs* out)
+{
+    const size_t H = d->lstm_dim, Tv = d->n_video_lstm_step, Tc = d->n_caption_lstm_step, b = B, r = R;
+    AttnSampleWs w;
+    w.encidx = c.take<int32_t>(Tv * b); w.vid = c.take<int32_t>(r); w.sid = c.take<int32_t>(r); w.rowvid = c.take<int32_t>(r);
+    w.Vt = c.take<float>(Tv * b * H); w.P = c.take<float>(Tv * b * H);
+    for (int i = 0; i < 2; ++i) { w.c[i] = c.take<float>(r * H); w.h[i] = c.take<float>(r * H); }
+    w.hWa = c.take<float>(r * H); w.alpha = c.take<float>(Tv * r); w.ctx = c.take<float>(r * H); w.Y = c.take<float>(r * H);
+    w.packed = c.take<unsigned long long>(Tc * r * kPickStride);
+    if (out) *out = w;
+    return c.off;
+}
+
+// rows = n_video * samples of the shared-block forms (the sampler, the _rows unroll and its backward)
+bool attn_rows_shape_ok(const s2vt_dims* d, int n_video, int samples)
+{
+    return attn_dims_ok(d) && n_video > 0 && samples > 0 && (int64_t)n_video * samples <= INT_MAX / 64 / d->n_caption_lstm_step;
+}
+
+// noise ids of the sampler's rows (sample-major): video = video_base + row % B, sample = row / B for the K multinomial blocks, -1
+// (argmax, no noise) for the greedy block behind them; and the row -> video map of the attention step
+__global__ void attn_sample_rows_kernel(int32_t* vid, int32_t* sid, int32_t* rowvid, int R, int B, int K, int video_base)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= R) return;
+    vid[i] = video_base + i % B;
+    sid[i] = i / B < K ? i / B : -1;
+    rowvid[i] = i % B;
+}
+
+// ids[m][t] for rows m0 .. m0 + n - 1 of the R packed rows
+__global__ void attn_unpack_rows_kernel(const unsigned long long* packed, int32_t* ids, int R, int m0, int n, int T, int stride)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n * T) return;
+    const int m = i / T, t = i % T;
+    ids[i] = (int32_t)(~(uint32_t)packed[((size_t)t * R + m0 + m) * stride]);
+}
+
 bool attn_beam_shape_ok(const s2vt_dims* d, int B, int beam)
 {
     return attn_dims_ok(d) && B > 0 && beam >= 1 && beam <= kBeamTopkMax && (int64_t)B * beam <= INT_MAX / 4;
@@ -324,9 +385,11 @@ size_t s2vt_attn_workspace_bytes(const s2vt_dims* d, int32_t B)
     return carve_attn(c, d, B, nullptr);
 }
 
-int s2vt_attn_teacher_forced_fwd(const s2vt_dims* d, const s2vt_attn_params* p, const float* video, int32_t B, const int32_t* caption,
-                                 int32_t caption_steps, float keep, uint64_t seed, const int32_t* video_id, const int32_t* sample_id,
-                                 float* logits, float* alphas_out, void* workspace, size_t workspace_bytes, s2vt_stream stream)
+// n_video = 0: the unroll on B videos.  n_video > 0 (s2vt_attn_teacher_forced_fwd_rows): B = n_video * samples sample-major rows over
+// n_video image blocks -- one prologue for the n_video videos, the attention step in its row -> video form, per-step launches.
+static int attn_tf_fwd_impl(const s2vt_dims* d, const s2vt_attn_params* p, const float* video, int32_t B, const int32_t* caption,
+                            int32_t caption_steps, float keep, uint64_t seed, const int32_t* video_id, const int32_t* sample_id,
+                            float* logits, float* alphas_out, void* workspace, size_t workspace_bytes, s2vt_stream stream, int n_video)
 {
     if (!attn_dims_ok(d) || !attn_params_ok(p) || !video || !caption || !logits || !workspace || B <= 0) return S2VT_E_BADARG;
     if (!(keep > 0.0f) || (keep < 1.0f && (!video_id || !sample_id))) return S2VT_E_BADARG;
@@ -336,18 +399,19 @@ int s2vt_attn_teacher_forced_fwd(const s2vt_dims* d, const s2vt_attn_params* p, 
     const int H = d->lstm_dim, V = d->n_words, Tv = d->n_video_lstm_step, Tc = caption_steps;
     Carver c(workspace, workspace_bytes);
     AttnWs w;
-    carve_attn(c, d, B, &w);
+    carve_attn(c, d, B, &w, n_video);
     if (!c.ok()) return S2VT_E_WORKSPACE;
     hipStream_t st = S(stream);
     const size_t BH = (size_t)B * H;
 
+    if (n_video > 0) HIP_TRY(launch_attn_row_video(w.rowvid, B, n_video, st));
     HIP_TRY(launch_prep_caption(caption, w.prev, w.tgt, B, d->n_caption_lstm_step, st));      // prev[t*B + b] = caption[b][t-1] for t >= 1
     {
         ZeroList z;     // zero initial state (:100-101), the zero partial of step 0 (current_embed = 0, :105)
         z.add(w.C3, BH * 4); z.add(w.H3, BH * 4); z.add(w.O3, BH * 4); z.add(w.G3, BH * 4 * 4);
         HIP_TRY(launch_zero_regions(z, st));
     }
-    int rc = attn_prologue(d, p, video, B, w, st);
+    int rc = attn_prologue(d, p, video, n_video > 0 ? n_video : B, w, st);
     if (rc != S2VT_OK) return rc;
     // the embedding rows of W3 for every step >= 1 in one product, written where the step's gates will go: the first block of
     // each pre-activation chain (the word fed at step t is caption[:, t-1], :141-142)
@@ -356,7 +420,7 @@ int s2vt_attn_teacher_forced_fwd(const s2vt_dims* d, const s2vt_attn_params* p, 
         HIP_TRY(store_call(&se, 1, p->lstm3_W, 4 * H, nullptr, w.G3 + 4 * BH, 4 * H, (Tc - 1) * B, 4 * H, 0, -1, st));
     }
     NoiseIds ids{video_id, sample_id, seed};
-    if (attn_chain_eligible(B, H, Tv) && !chain_fault() && !(reinterpret_cast<uintptr_t>(p->lstm3_W) & 15) && !(reinterpret_cast<uintptr_t>(p->embed_att_Wa) & 15)) {
+    if (n_video == 0 && attn_chain_eligible(B, H, Tv) && !chain_fault() && !(reinterpret_cast<uintptr_t>(p->lstm3_W) & 15) && !(reinterpret_cast<uintptr_t>(p->embed_att_Wa) & 15)) {
         // the whole recurrence -- query projection, score / softmax / context, LSTM3, all Tc steps -- in ONE persistent launch
         AttnChainLaunch a;
         std::memset(&a, 0, sizeof(a));
@@ -372,7 +436,7 @@ int s2vt_attn_teacher_forced_fwd(const s2vt_dims* d, const s2vt_attn_params* p, 
         HIP_TRY(launch_attn_chain(a, st));
     } else {
         for (int t = 0; t < Tc; ++t) {
-            HIP_TRY(attn_step(p, w, t, Tv, B, H, w.O3 + t * BH, st));                                     // (:113-128)
+            HIP_TRY(attn_step(p, w, t, Tv, B, H, w.O3 + t * BH, st, n_video));                            // (:113-128)
             // LSTM3 (:131): the chain continues from the hoisted partial with the recurrent rows, then the context rows
             ASeg s3[2] = {make_seg(w.H3 + t * BH, H, H, 2 * H), make_seg(w.ctx + t * BH, H, H, 0)};
             HIP_TRY(lstm_call(s3, 2, p->lstm3_W, p->lstm3_b, w.C3 + t * BH, 0, w.C3 + (t + 1) * BH, w.H3 + (t + 1) * BH, w.O3 + (t + 1) * BH,
@@ -397,6 +461,24 @@ int s2vt_attn_teacher_forced_fwd(const s2vt_dims* d, const s2vt_attn_params* p, 
         else HIP_TRY(hipMemcpyAsync(alphas_out, w.alpha, (size_t)Tc * Tv * B * 4, hipMemcpyDeviceToDevice, st));
     }
     return S2VT_OK;
+}
+
+int s2vt_attn_teacher_forced_fwd(const s2vt_dims* d, const s2vt_attn_params* p, const float* video, int32_t B, const int32_t* caption,
+                                 int32_t caption_steps, float keep, uint64_t seed, const int32_t* video_id, const int32_t* sample_id,
+                                 float* logits, float* alphas_out, void* workspace, size_t workspace_bytes, s2vt_stream stream)
+{
+    return attn_tf_fwd_impl(d, p, video, B, caption, caption_steps, keep, seed, video_id, sample_id, logits, alphas_out, workspace, workspace_bytes,
+                            stream, 0);
+}
+
+int s2vt_attn_teacher_forced_fwd_rows(const s2vt_dims* d, const s2vt_attn_params* p, const float* video, int32_t n_video, int32_t samples,
+                                      const int32_t* caption, int32_t caption_steps, float keep, uint64_t seed, const int32_t* video_id,
+                                      const int32_t* sample_id, float* logits, float* alphas_out, void* workspace, size_t workspace_bytes,
+                                      s2vt_stream stream)
+{
+    if (!attn_rows_shape_ok(d, n_video, samples)) return S2VT_E_BADARG;
+    return attn_tf_fwd_impl(d, p, video, n_video * samples, caption, caption_steps, keep, seed, video_id, sample_id, logits, alphas_out, workspace,
+                            workspace_bytes, stream, n_video);
 }
 
 int s2vt_attn_loss_inputs(const int32_t* caption, const float* mask, int32_t B, int32_t Tc, float beta, int32_t* target_tm, float* coef_tm,
@@ -424,9 +506,12 @@ int s2vt_attn_step_scalars(const float* coef, const float* nll, int64_t R, const
     return S2VT_OK;
 }
 
-int s2vt_attn_bptt_bwd(const s2vt_dims* d, const s2vt_attn_params* p, const s2vt_attn_params* grads, const float* video, int32_t B,
-                       const float* dlogits, int32_t caption_steps, const float* reg_coef, float reg_m, float keep, uint64_t seed,
-                       const int32_t* video_id, const int32_t* sample_id, void* workspace, size_t workspace_bytes, s2vt_stream stream)
+// n_video as attn_tf_fwd_impl: > 0 is the shared-block form -- per-step launches, the attention backward of launch_attn_bwd_rows (dP / dVt
+// one block per video, summed over its rows), the image-side products on Tv * n_video rows.
+static int attn_bptt_bwd_impl(const s2vt_dims* d, const s2vt_attn_params* p, const s2vt_attn_params* grads, const float* video, int32_t B,
+                              const float* dlogits, int32_t caption_steps, const float* reg_coef, float reg_m, float keep, uint64_t seed,
+                              const int32_t* video_id, const int32_t* sample_id, void* workspace, size_t workspace_bytes, s2vt_stream stream,
+                              int n_video)
 {
     if (!attn_dims_ok(d) || !attn_params_ok(p) || !attn_params_ok(grads) || !video || !dlogits || !workspace || B <= 0) return S2VT_E_BADARG;
     if (!(keep > 0.0f) || (keep < 1.0f && (!video_id || !sample_id))) return S2VT_E_BADARG;
@@ -436,13 +521,14 @@ int s2vt_attn_bptt_bwd(const s2vt_dims* d, const s2vt_attn_params* p, const s2vt
     const int H = d->lstm_dim, V = d->n_words, D = d->dim_image, Tv = d->n_video_lstm_step, Tc = caption_steps;
     Carver c(workspace, workspace_bytes);
     AttnWs w;
-    carve_attn(c, d, B, &w);
+    carve_attn(c, d, B, &w, n_video);
     if (!c.ok()) return S2VT_E_WORKSPACE;
     hipStream_t st = S(stream);
     const size_t BH = (size_t)B * H;
     const int R = Tc * B, R1 = (Tc - 1) * B;
+    const int NV = n_video > 0 ? n_video : B;                 // image blocks per frame
 
-    const bool persistent = attn_bwd_chain_eligible(B, H, Tv) && !chain_fault() && !(reinterpret_cast<uintptr_t>(p->lstm3_W) & 15) &&
+    const bool persistent = n_video == 0 && attn_bwd_chain_eligible(B, H, Tv) && !chain_fault() && !(reinterpret_cast<uintptr_t>(p->lstm3_W) & 15) &&
                             !(reinterpret_cast<uintptr_t>(p->embed_att_Wa) & 15);
     // Gated overlap (S2VT_OVERLAP=0 switches it off): the weight gradients of the vocabulary projection and of the output layer feed
     // nothing in the recurrence -- with the persistent backward recurrence they are launched on the side stream once its grid is resident and
@@ -480,7 +566,7 @@ int s2vt_attn_bptt_bwd(const s2vt_dims* d, const s2vt_attn_params* p, const s2vt
     HIP_TRY(nn_bwd_slabs(w.dY, H, p->embed_nn_Wp, H, w.dcat, 3 * H, R, 3 * H, H, w.bslab, st, w.bslab_floats));
     {
         ZeroList z;
-        z.add(w.dPt, (size_t)Tv * BH * 4); z.add(w.dVtt, (size_t)Tv * BH * 4);
+        z.add(w.dPt, (size_t)Tv * NV * H * 4); z.add(w.dVtt, (size_t)Tv * NV * H * 4);
         HIP_TRY(launch_zero_regions(z, st));
     }
     // ---- the recurrence, back through time
@@ -550,7 +636,14 @@ int s2vt_attn_bptt_bwd(const s2vt_dims* d, const s2vt_attn_params* p, const s2vt
             if (reg_coef) { g.reg_coef = reg_coef + (size_t)t * B; g.asum = w.asum + (size_t)t * B; g.reg_m = reg_m; }
             g.dhWa = t > 0 ? w.dhWa + t * BH : nullptr; g.dP = w.dPt; g.dVt = w.dVtt; g.acc = 1; g.dw = grads->embed_att_w;
             g.Tv = Tv; g.B = B; g.H = H;
-            HIP_TRY(launch_attn_bwd(g, st));
+            if (n_video > 0) {
+                AttnBwdRowsArgs r;
+                std::memset(&r, 0, sizeof(r));
+                r.a = g; r.n_video = n_video; r.samples = B / n_video; r.de_rows = w.deh; r.dctx_rows = w.dctxr;
+                HIP_TRY(launch_attn_bwd_rows(r, st));
+            } else {
+                HIP_TRY(launch_attn_bwd(g, st));
+            }
             // gradient w.r.t. the previous step's dropped output through this step's query: dhWa @ Wa^T (slabs, summed by the cell backward)
             if (t > 0) HIP_TRY(nn_bwd(w.dhWa + t * BH, H, p->embed_att_Wa, H, w.dqs, H, B, H, H, sq, BH, st, sq > 1 ? kSlabTileCfg : -1));
         }
@@ -573,18 +666,52 @@ int s2vt_attn_bptt_bwd(const s2vt_dims* d, const s2vt_attn_params* p, const s2vt
     }
     // ---- image part P = V @ Ua + ba and the frame embedding V = video @ encode_image_W + b
     {
-        TnArgs u{w.Vt, nullptr, H, w.dPt, H, grads->embed_att_Ua, H, Tv * B, H, H, 1};
+        TnArgs u{w.Vt, nullptr, H, w.dPt, H, grads->embed_att_Ua, H, Tv * NV, H, H, 1};
         u.colsum = grads->embed_att_ba;
         HIP_TRY(launch_gemm_tn(u, st));
         ASeg sp = make_seg(w.dPt, H, H, 0);
-        HIP_TRY(store_call(&sp, 1, p->embed_att_Ua, H, nullptr, w.dEv, H, Tv * B, H, 0, -1, st, w.dVtt, H, true));     // dV = dV(ctx path) + dP @ Ua^T
-        TnArgs v{video, w.encidx, D, w.dEv, H, grads->encode_image_W, H, Tv * B, D, H, 1};
-        v.gather_rows = Tv * B;
+        HIP_TRY(store_call(&sp, 1, p->embed_att_Ua, H, nullptr, w.dEv, H, Tv * NV, H, 0, -1, st, w.dVtt, H, true));     // dV = dV(ctx path) + dP @ Ua^T
+        TnArgs v{video, w.encidx, D, w.dEv, H, grads->encode_image_W, H, Tv * NV, D, H, 1};
+        v.gather_rows = Tv * NV;
         v.colsum = grads->encode_image_b;
         HIP_TRY(launch_gemm_tn(v, st));
     }
     if (gated) HIP_TRY(fork_to(ss.s, st, ss.ev[2]));        // join: the caller's stream waits for the side stream's gradients
     return S2VT_OK;
+}
+
+int s2vt_attn_bptt_bwd(const s2vt_dims* d, const s2vt_attn_params* p, const s2vt_attn_params* grads, const float* video, int32_t B,
+                       const float* dlogits, int32_t caption_steps, const float* reg_coef, float reg_m, float keep, uint64_t seed,
+                       const int32_t* video_id, const int32_t* sample_id, void* workspace, size_t workspace_bytes, s2vt_stream stream)
+{
+    return attn_bptt_bwd_impl(d, p, grads, video, B, dlogits, caption_steps, reg_coef, reg_m, keep, seed, video_id, sample_id, workspace,
+                              workspace_bytes, stream, 0);
+}
+
+int s2vt_attn_step_scalars_rows(const float* coef, const float* nll, int64_t R, const float* reg_coef, float reg_m, const float* mask_sum_local,
+                                const float* mask_sum_global, float* loss, float* gscale, float* sumsq, const s2vt_dims* d, int32_t n_video,
+                                int32_t samples, void* workspace, size_t workspace_bytes, s2vt_stream stream)
+{
+    if (!coef || !nll || R < 0 || !mask_sum_local || !mask_sum_global || !attn_rows_shape_ok(d, n_video, samples) || !workspace) return S2VT_E_BADARG;
+    if (R > (int64_t)d->n_caption_lstm_step * n_video * samples) return S2VT_E_BADARG;
+    Carver c(workspace, workspace_bytes);
+    AttnWs w;
+    carve_attn(c, d, n_video * samples, &w, n_video);
+    if (!c.ok()) return S2VT_E_WORKSPACE;
+    hipLaunchKernelGGL(attn_step_scalars_kernel, dim3(1), dim3(256), 0, S(stream), coef, nll, reg_coef, w.asum, reg_m, (int)R, mask_sum_local,
+                       mask_sum_global, loss, gscale, sumsq);
+    HIP_TRY(hipGetLastError());
+    return S2VT_OK;
+}
+
+int s2vt_attn_bptt_bwd_rows(const s2vt_dims* d, const s2vt_attn_params* p, const s2vt_attn_params* grads, const float* video, int32_t n_video,
+                            int32_t samples, const float* dlogits, int32_t caption_steps, const float* reg_coef, float reg_m, float keep,
+                            uint64_t seed, const int32_t* video_id, const int32_t* sample_id, void* workspace, size_t workspace_bytes,
+                            s2vt_stream stream)
+{
+    if (!attn_rows_shape_ok(d, n_video, samples)) return S2VT_E_BADARG;
+    return attn_bptt_bwd_impl(d, p, grads, video, n_video * samples, dlogits, caption_steps, reg_coef, reg_m, keep, seed, video_id, sample_id,
+                              workspace, workspace_bytes, stream, n_video);
 }
 
 int s2vt_attn_decode_greedy(const s2vt_dims* d, const s2vt_attn_params* p, const float* video, int32_t B, int32_t video_base, int32_t* ids_out,
@@ -640,6 +767,90 @@ int s2vt_attn_decode_greedy(const s2vt_dims* d, const s2vt_attn_params* p, const
     return S2VT_OK;
 }
 
+size_t s2vt_attn_rows_workspace_bytes(const s2vt_dims* d, int32_t n_video, int32_t samples)
+{
+    if (!attn_rows_shape_ok(d, n_video, samples)) return 0;
+    Carver c(nullptr, 0);
+    return carve_attn(c, d, n_video * samples, nullptr, n_video);
+}
+
+size_t s2vt_attn_sample_workspace_bytes(const s2vt_dims* d, int32_t B, int32_t K, int32_t with_greedy)
+{
+    if (K < 0 || (K == 0 && !with_greedy) || !attn_rows_shape_ok(d, B, K + (with_greedy ? 1 : 0))) return 0;
+    Carver c(nullptr, 0);
+    return carve_attn_sample(c, d, B, (K + (with_greedy ? 1 : 0)) * B, nullptr);
+}
+
+// K multinomial captions per video and (with_greedy) the greedy one: the decode loop of s2vt_attn_decode_greedy on R = (K + greedy) B
+// sample-major rows that share the B image blocks (one prologue; the attention step in its row -> video form).  The PICK epilogue
+// draws Gumbel-max noise from the Philox counters (video_base + j, s, step) for sample s >= 0 and takes the argmax for the greedy
+// block (sample id -1); the packed pick of step t-1 is the embedding gather index of step t.  No dropout, no <bos>, no host round
+// trip.  Per-step launches: the persistent recurrences (attn_chain*.hip) hold one image block per row and at most 64 rows.
+int s2vt_attn_sample(const s2vt_dims* d, const s2vt_attn_params* p, const float* video, int32_t B, int32_t K, int32_t with_greedy, uint64_t seed,
+                     int32_t video_base, int32_t* ids_out, int32_t* greedy_out, void* workspace, size_t workspace_bytes, s2vt_stream stream)
+{
+    const int g = with_greedy ? 1 : 0;
+    if (K < 0 || (K == 0 && !g) || !attn_rows_shape_ok(d, B, K + g) || !attn_params_ok(p) || !video || !workspace) return S2VT_E_BADARG;
+    if ((K > 0 && !ids_out) || (g && !greedy_out)) return S2VT_E_BADARG;
+    if (reinterpret_cast<uintptr_t>(workspace) & 255u) return S2VT_E_ALIGN;
+    const int H = d->lstm_dim, V = d->n_words, Tv = d->n_video_lstm_step, Tc = d->n_caption_lstm_step, R = (K + g) * B;
+    Carver c(workspace, workspace_bytes);
+    AttnSampleWs w;
+    carve_attn_sample(c, d, B, R, &w);
+    if (!c.ok()) return S2VT_E_WORKSPACE;
+    hipStream_t st = S(stream);
+    {
+        ZeroList z;     // the zero state (:164-165); the pick words are combined with atomicMax from zero
+        z.add(w.c[0], (size_t)R * H * 4); z.add(w.h[0], (size_t)R * H * 4); z.add(w.packed, (size_t)Tc * R * kPickStride * 8);
+        HIP_TRY(launch_zero_regions(z, st));
+    }
+    hipLaunchKernelGGL(attn_sample_rows_kernel, dim3((R + 255) / 256), dim3(256), 0, st, w.vid, w.sid, w.rowvid, R, (int)B, (int)K, (int)video_base);
+    HIP_TRY(hipGetLastError());
+    {
+        AttnWs img;
+        std::memset(&img, 0, sizeof(img));
+        img.encidx = w.encidx; img.Vt = w.Vt; img.P = w.P;
+        const int rc = attn_prologue(d, p, video, B, img, st);
+        if (rc != S2VT_OK) return rc;
+    }
+    NoiseIds none{nullptr, nullptr, 0};
+    NoiseIds ids{w.vid, w.sid, seed};
+    for (int t = 0; t < Tc; ++t) {
+        const float *c_prev = w.c[t & 1], *h_prev = w.h[t & 1];
+        float *c_new = w.c[(t & 1) ^ 1], *h_new = w.h[(t & 1) ^ 1];
+        if (t > 0) {       // the query is the clean h (no dropout in the samplers, :188,:235); step 0: the zero state
+            ASeg sq = make_seg(h_prev, H, H, 0);
+            HIP_TRY(store_call(&sq, 1, p->embed_att_Wa, H, nullptr, w.hWa, H, R, H, 0, -1, st));
+        }
+        AttnFwdArgs a;
+        std::memset(&a, 0, sizeof(a));
+        a.hWa = t > 0 ? w.hWa : nullptr; a.P = w.P; a.Vt = w.Vt; a.w = p->embed_att_w; a.alpha = w.alpha; a.ctx = w.ctx;
+        a.Tv = Tv; a.B = R; a.H = H; a.row_video = w.rowvid; a.n_video = B;
+        HIP_TRY(launch_attn_fwd(a, st));
+        const unsigned long long* tok = t > 0 ? w.packed + (size_t)(t - 1) * R * kPickStride : nullptr;    // the word picked at step t-1 (:196-197)
+        if (t == 0) {
+            ASeg s3 = make_seg(w.ctx, H, H, 0);
+            HIP_TRY(lstm_call(&s3, 1, p->lstm3_W, p->lstm3_b, c_prev, 0, c_new, h_new, nullptr, nullptr, R, H, 1.0f, none, 0, -1, st));
+            ASeg sy[2] = {make_seg(w.ctx, H, H, H), make_seg(h_new, H, H, 0)};
+            HIP_TRY(store_call(sy, 2, p->embed_nn_Wp, H, p->embed_nn_bp, w.Y, H, R, H, 1, -1, st));
+        } else {
+            ASeg s3[3] = {make_seg(p->Wemb, H, H, H, 0, nullptr, tok, kPickStride), make_seg(h_prev, H, H, 2 * H), make_seg(w.ctx, H, H, 0)};
+            HIP_TRY(lstm_call(s3, 3, p->lstm3_W, p->lstm3_b, c_prev, 0, c_new, h_new, nullptr, nullptr, R, H, 1.0f, none, 0, -1, st));
+            ASeg sy[3] = {make_seg(p->Wemb, H, H, 2 * H, 0, nullptr, tok, kPickStride), make_seg(w.ctx, H, H, H), make_seg(h_new, H, H, 0)};
+            HIP_TRY(store_call(sy, 3, p->embed_nn_Wp, H, p->embed_nn_bp, w.Y, H, R, H, 1, -1, st));
+        }
+        HIP_TRY(pick_call(w.Y, H, p->embed_word_W, p->embed_word_b, R, H, V, ids, t, w.packed + (size_t)t * R * kPickStride, nullptr, -1, st, kPickStride));
+    }
+    if (K > 0) {
+        hipLaunchKernelGGL(attn_unpack_rows_kernel, dim3((K * B * Tc + 255) / 256), dim3(256), 0, st, w.packed, ids_out, R, 0, (int)(K * B), Tc, kPickStride);
+        HIP_TRY(hipGetLastError());
+    }
+    if (g) {
+        hipLaunchKernelGGL(attn_unpack_rows_kernel, dim3((B * Tc + 255) / 256), dim3(256), 0, st, w.packed, greedy_out, R, (int)(K * B), (int)B, Tc, kPickStride);
+        HIP_TRY(hipGetLastError());
+    }
+    return S2VT_OK;
+}
 
 size_t s2vt_attn_beam_workspace_bytes(const s2vt_dims* d, int32_t B, int32_t beam)
 {

@@ -234,6 +234,21 @@ struct AttnBwdArgs {
     int vec;                                           // (set by the launcher) 16-byte path
 };
 hipError_t launch_attn_bwd(const AttnBwdArgs& a, hipStream_t st);
+// The shared-block backward (self-critical REINFORCE on the attention captioner): the a.B = n_video * samples rows are sample-major
+// (row s * n_video + j is sample s of video j) and the samples of a video share its one block of P / Vt, so dP / dVt are
+// [Tv, n_video, H] and take the SUM over the video's rows.  Two launches, no atomics on dP / dVt:
+//   1. one workgroup per row: dctx (dense part + slabs), dalpha, the open-hinge term, de[Tv] -> de_rows / dctx_rows (and demb_out)
+//   2. one workgroup per (video, 256-column slice): the video's rows in ascending s -- T = tanh(hWa[row] + P[t][video]) once, dhWa[row]
+//      written, dP[t] / dVt[t] / dw summed in registers -- then ONE add into the video's block (every element has one owner; two runs
+//      give equal bits there).  dw keeps its atomicAdd.
+struct AttnBwdRowsArgs {
+    AttnBwdArgs a;               // as above with B = rows; P / Vt / dP / dVt hold n_video blocks per frame
+    int n_video, samples;
+    float* de_rows;              // [rows][Tv] scratch
+    float* dctx_rows;            // [rows][H] scratch: the assembled d(ctx); NULL = a.dctx is complete (no slabs) and is read in place
+};
+hipError_t launch_attn_bwd_rows(const AttnBwdRowsArgs& r, hipStream_t st);
+hipError_t launch_attn_row_video(int32_t* row_video, int rows, int n_video, hipStream_t st);   // row_video[i] = i % n_video (sample-major rows)
 
 // ---- vocabulary top-k with log-probabilities (beam.hip): ids / logp [R, k] of logits [R, V] (row stride ld), 1 <= k <= 16
 hipError_t launch_vocab_topk(const float* logits, int ld, int R, int V, int k, int32_t* ids, float* logp, hipStream_t st);

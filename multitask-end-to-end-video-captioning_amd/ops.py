@@ -762,6 +762,100 @@ def attn_decode_greedy(dims: Dims, params: AttnParams, video, video_base=0, want
     return ids, al
 
 
+# ---- rows that share image blocks (self-critical REINFORCE on the attention captioner): N = n_video * samples, sample-major
+def attention_fwd_rows(hWa, P, Vt, w):
+    """s2vt_attention_fwd for hWa [N,H] over P/Vt [Tv,n_video,H], N = samples * n_video (row s*n_video + j reads block j)
+    -> (scores [Tv,N], alpha [Tv,N], ctx [N,H])."""
+    _chk_f32(hWa, P, Vt, w)
+    Tv, nv, H = P.shape
+    N = hWa.shape[0]
+    assert N % nv == 0
+    sc = torch.empty((Tv, N), dtype=torch.float32, device=P.device)
+    al = torch.empty_like(sc)
+    ctx = torch.empty((N, H), dtype=torch.float32, device=P.device)
+    rv = torch.empty(N, dtype=torch.int32, device=P.device)
+    check(lib().s2vt_attention_fwd_rows(_ptr(hWa), _ptr(P), _ptr(Vt), _ptr(w), _ptr(sc), _ptr(al), _ptr(ctx), _ptr(rv), Tv, nv, N // nv, H,
+                                        _stream()), "s2vt_attention_fwd_rows")
+    return sc, al, ctx
+
+
+def attention_bwd_rows(hWa, P, Vt, w, alpha, dctx, dw, dP=None, dVt=None):
+    """Returns (dhWa [N,H], dP, dVt [Tv,n_video,H] summed over each video's rows); accumulates into dw [H], and into dP / dVt when given."""
+    _chk_f32(hWa, P, Vt, w, alpha, dctx, dw, dP, dVt)
+    Tv, nv, H = P.shape
+    N = hWa.shape[0]
+    assert N % nv == 0 and (dP is None) == (dVt is None)
+    acc = dP is not None
+    de = torch.empty(N * Tv, dtype=torch.float32, device=P.device)
+    dh = torch.empty_like(hWa)
+    if not acc:
+        dP = torch.empty_like(P); dVt = torch.empty_like(Vt)
+    check(lib().s2vt_attention_bwd_rows(_ptr(hWa), _ptr(P), _ptr(Vt), _ptr(w), _ptr(alpha), _ptr(dctx), _ptr(de), _ptr(dh), _ptr(dP),
+                                        _ptr(dVt), _ptr(dw), Tv, nv, N // nv, H, int(acc), _stream()), "s2vt_attention_bwd_rows")
+    return dh, dP, dVt
+
+
+def attn_sample(dims: Dims, params: AttnParams, video, K: int, seed: int, video_base: int = 0, with_greedy: bool = True):
+    """K multinomial captions per video (+ greedy) from the attention captioner: (sampled [K*B,Tc] | None, greedy [B,Tc] | None) int32."""
+    _chk_f32(video)
+    assert video.is_contiguous()
+    B = video.shape[0]
+    g = 1 if with_greedy else 0
+    nbytes = lib().s2vt_attn_sample_workspace_bytes(C.byref(dims), B, K, g)
+    assert nbytes > 0, "bad dims / B / K (n_video_lstm_step <= 64, K >= 0, K > 0 or with_greedy)"
+    ws = workspace(nbytes, video.device, "attn_sample")
+    Tc = dims.n_caption_lstm_step
+    ids = torch.empty((K * B, Tc), dtype=torch.int32, device=video.device) if K > 0 else None
+    gr = torch.empty((B, Tc), dtype=torch.int32, device=video.device) if g else None
+    check(lib().s2vt_attn_sample(C.byref(dims), C.byref(params), _ptr(video), B, K, g, seed, int(video_base), _ptr(ids), _ptr(gr), _ptr(ws),
+                                 ws.numel(), _stream()), "s2vt_attn_sample")
+    return ids, gr
+
+
+def attn_rows_workspace(dims: Dims, n_video: int, samples: int, device):
+    nbytes = lib().s2vt_attn_rows_workspace_bytes(C.byref(dims), n_video, samples)
+    assert nbytes > 0, "bad dims / n_video / samples (n_video_lstm_step <= 64)"
+    return workspace(nbytes, device, "attn_rows")
+
+
+def attn_teacher_forced_fwd_rows(dims: Dims, params: AttnParams, video, caption, keep=1.0, seed=0, video_id=None, sample_id=None, steps=None,
+                                 ws=None, want_alphas=False):
+    """attn_teacher_forced_fwd on N = caption.shape[0] sample-major rows that share the n_video = video.shape[0] image blocks.
+    Returns (time-major logits [steps*N, V], alphas [steps,Tv,N] | None, ws)."""
+    _chk_f32(video)
+    nv, N = video.shape[0], caption.shape[0]
+    assert video.is_contiguous() and caption.is_cuda and caption.dtype == torch.int32 and caption.is_contiguous()
+    assert N % nv == 0 and caption.shape == (N, dims.n_caption_lstm_step)
+    steps = dims.n_caption_lstm_step if steps is None else int(steps)
+    if ws is None:
+        ws = attn_rows_workspace(dims, nv, N // nv, video.device)
+    logits = torch.empty((steps * N, dims.n_words), dtype=torch.float32, device=video.device)
+    al = torch.empty((steps, dims.n_video_lstm_step, N), dtype=torch.float32, device=video.device) if want_alphas else None
+    check(lib().s2vt_attn_teacher_forced_fwd_rows(C.byref(dims), C.byref(params), _ptr(video), nv, N // nv, _ptr(caption), steps, float(keep), seed,
+                                                  _ptr(video_id), _ptr(sample_id), _ptr(logits), _ptr(al), _ptr(ws), ws.numel(), _stream()),
+          "s2vt_attn_teacher_forced_fwd_rows")
+    return logits, al, ws
+
+
+def attn_step_scalars_rows(dims: Dims, n_video: int, samples: int, ws, coef, nll, reg_coef, reg_m, msum_local, gsum_global, loss, gscale, sumsq):
+    _chk_f32(coef, nll, reg_coef, msum_local, gsum_global, loss, gscale, sumsq)
+    check(lib().s2vt_attn_step_scalars_rows(_ptr(coef), _ptr(nll), coef.numel(), _ptr(reg_coef), float(reg_m), _ptr(msum_local), _ptr(gsum_global),
+                                            _ptr(loss), _ptr(gscale), _ptr(sumsq), C.byref(dims), n_video, samples, _ptr(ws), ws.numel(), _stream()),
+          "s2vt_attn_step_scalars_rows")
+
+
+def attn_bptt_bwd_rows(dims: Dims, params: AttnParams, grads: AttnParams, video, samples, dlogits, ws, steps=None, reg_coef=None, reg_m=0.5,
+                       keep=1.0, seed=0, video_id=None, sample_id=None):
+    _chk_f32(video, dlogits, reg_coef)
+    nv = video.shape[0]
+    N = nv * int(samples)
+    steps = dims.n_caption_lstm_step if steps is None else int(steps)
+    assert dlogits.shape[0] == steps * N and (reg_coef is None or reg_coef.numel() == steps * N)
+    check(lib().s2vt_attn_bptt_bwd_rows(C.byref(dims), C.byref(params), C.byref(grads), _ptr(video), nv, int(samples), _ptr(dlogits), steps,
+                                        _ptr(reg_coef), float(reg_m), float(keep), seed, _ptr(video_id), _ptr(sample_id), _ptr(ws), ws.numel(),
+                                        _stream()), "s2vt_attn_bptt_bwd_rows")
+
+
 def attr_head_fwd(video, attr_W, attr_b, labels=None):
     _chk_f32(video, attr_W, attr_b, labels)
     B, Tv, D = video.shape

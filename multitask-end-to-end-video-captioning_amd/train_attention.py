@@ -5,7 +5,13 @@
 Per step the reference runs sess.run([train_op, tf_loss]) on build_model (cross entropy on the ground-truth caption + the alpha
 regulariser, clip 10, Adam, lr 1e-4 halved every 10000 steps, :430-441); here that is Attention_Caption_Generator.xe_update.  Every
 epoch: greedy captions of the test videos through the sampler graph (:483-497) and a checkpoint under the TF variable names (:519).
-One process per GPU under torch.distributed.run for data parallel (every rank walks the same shuffled epoch and takes its shard)."""
+One process per GPU under torch.distributed.run for data parallel (every rank walks the same shuffled epoch and takes its shard).
+
+    python -m s2vt_amd.train_attention ... --reinforce --samples 5 --restore XE_CHECKPOINT
+
+is the CIDEr fine-tuning stage the reinforcement_* scripts apply to their models, on this one: the loop of train_rl.train -- K multinomial
+samples + the greedy caption per video in one sampler call, CIDEr-D on the ids (reward.py) on the host under the queued teacher-forced
+forward, then Attention_Caption_Generator.reinforce_update (clip 5, lr 1e-6 halved every 1000 steps unless the config says otherwise)."""
 from __future__ import annotations
 
 import argparse
@@ -28,11 +34,21 @@ def attention_config(**kw):
     return Config(**base)
 
 
+def reinforce_config(**kw):
+    """The REINFORCE stage's "Train Parameters" (reinforcement_multisampling_tf_s2vt.py:505-517) on this model's dimensions."""
+    return attention_config(**dict(dict(start_learning_rate=1e-6, decay_steps=1000, clip_norm=5.0, model_name="attention_reinforce_model"), **kw))
+
+
 def train(cfg: Config, train_corpus: Corpus, test_corpus: Corpus | None = None, model=None, log=print, resume=None, m=0.5, beta=10.0,
-          eval_beam=0, eval_lnf=0.0):
+          eval_beam=0, eval_lnf=0.0, reinforce=False, samples=5, restore=None):
     """cfg.batch_size is the GLOBAL batch; cfg.lstm_dim is dim_hidden (the word embedding has the same width, :65).  eval_beam > 0:
     the per-epoch evaluation decodes with a beam of that size and length normalisation eval_lnf (train_common.beam_eval) instead of
-    greedily."""
+    greedily.
+    reinforce: the self-critical stage instead of cross entropy -- per step `samples` multinomial captions and the greedy one per video
+    (model.sample, global video indices in the noise counters), CIDEr-D of both against the training references, and
+    model.reinforce_update with reward = the samples' scores and baseline = the greedy caption's; logging, checkpoints and the
+    per-epoch evaluation are the same.  restore: variables (and Adam slots) of an XE checkpoint, the step counter starting at 0;
+    resume: a checkpoint of this driver, counters included."""
     from . import attention as A
     par = DataParallel(model.device if model is not None else None)
     if not par.chief:
@@ -43,9 +59,13 @@ def train(cfg: Config, train_corpus: Corpus, test_corpus: Corpus | None = None, 
         model = A.Attention_Caption_Generator(cfg.dim_image, len(wordtoix), cfg.lstm_dim, B, cfg.n_video_lstm_step, cfg.n_caption_lstm_step, 0.9,
                                               bias_init_vector=None, m=m, beta=beta, seed=cfg.seed, device=par.device)
     par.attach(model)
+    if restore:
+        log(f"restored: {optimistic_restore(model, restore, step_names=('g_step',))}")
     if resume:
         log(f"resumed: {optimistic_restore(model, resume)} at step {model.global_step}")
     scorer = reward.CiderD(test_corpus.index.refs_by_video(), wordtoix) if test_corpus is not None else None
+    K = int(samples)
+    train_scorer = reward.CiderD(train_corpus.index.refs_by_video(), wordtoix) if reinforce else None
     rng = random.Random(cfg.seed)
     caps = train_corpus.captions
     history = []
@@ -54,6 +74,9 @@ def train(cfg: Config, train_corpus: Corpus, test_corpus: Corpus | None = None, 
     def prepare(gidx):
         idx, lo = par.shard(gidx)
         vid = caps[idx, 0]
+        if reinforce:
+            return dict(lo=lo, feats=model._dev(train_corpus.features.batch(vid), torch.float32),
+                        rows=np.asarray([train_corpus.index.row[v] for v in vid], np.int32))
         g_ind, g_mask = hostglue.sentence_padding_toix(caps[gidx, 1].tolist(), wordtoix, cfg.n_caption_lstm_step)
         g_mask = np.asarray(g_mask, np.float32)
         return dict(lo=lo, ind=np.asarray(g_ind, np.int32)[lo:lo + len(idx)], mask=g_mask[lo:lo + len(idx)],
@@ -74,13 +97,36 @@ def train(cfg: Config, train_corpus: Corpus, test_corpus: Corpus | None = None, 
                 if pending is not None:
                     pending()
             b = cur
-            st, loss = run_step(model, lambda: model.xe_update(b["feats"], b["ind"], b["mask"], lr=learning_rate(cfg, model.global_step),
-                                                               clip_norm=cfg.clip_norm, video_base=b["lo"], active_steps=b["steps"]),
-                                log, overlap=overlap)
+            rb = {}
+
+            def rl_step():
+                sampled, greedy = model.sample(b["feats"], K, True, seed=cfg.seed + 7919 * (model.global_step + 1), video_base=b["lo"])
+                s_host, g_host = sampled.cpu().numpy(), greedy.cpu().numpy()
+
+                def rewards():              # on the host while the GPU runs the teacher-forced forward
+                    rb["r"] = train_scorer.score_ids(s_host, np.tile(b["rows"], K))      # [K*B], sample-major like the ids
+                    rb["b"] = train_scorer.score_ids(g_host, b["rows"])                  # [B]
+                    return rb["r"], hostglue.tile_baseline(rb["b"], K)
+                # the ids are on the host anyway: behind the longest sample (its first <eos> included) every position is masked
+                eos = s_host == 0
+                steps = int(np.where(eos.any(1), eos.argmax(1) + 1, s_host.shape[1]).max())
+                return model.reinforce_update(b["feats"], sampled, None, None, None, lr=learning_rate(cfg, model.global_step), clip_norm=cfg.clip_norm,
+                                              video_base=b["lo"], reward_fn=rewards, active_steps=steps)
+            if reinforce:
+                st, loss = run_step(model, rl_step, log, overlap=overlap)
+            else:
+                st, loss = run_step(model, lambda: model.xe_update(b["feats"], b["ind"], b["mask"], lr=learning_rate(cfg, model.global_step),
+                                                                   clip_norm=cfg.clip_norm, video_base=b["lo"], active_steps=b["steps"]),
+                                    log, overlap=overlap)
             losses.append(loss)
             t1 = time.time()
+            rm, bm = (float(rb["r"].mean()), float(rb["b"].mean())) if reinforce else (None, None)
 
-            def pending(it=it, loss=loss, lr=learning_rate(cfg, model.global_step), step=model.global_step, secs=t1 - t0):
+            def pending(it=it, loss=loss, lr=learning_rate(cfg, model.global_step), step=model.global_step, secs=t1 - t0, rm=rm, bm=bm):
+                if reinforce:
+                    log(f"idx: {it * cfg.batch_size} rate: {lr:g} Epoch: {epoch} loss: {loss:.5f} r: {rm:.4f} b: {bm:.4f} Elapsed time: {secs:.3f}")
+                    steplog.write(kind="step", epoch=epoch, step=step, lr=lr, loss=loss, reward=rm, baseline=bm, seconds=secs)
+                    return
                 log(f"idx: {it * cfg.batch_size} rate: {lr:g} Epoch: {epoch} loss: {loss:.5f} Elapsed time: {secs:.3f}")
                 steplog.write(kind="step", epoch=epoch, step=step, lr=lr, loss=loss, seconds=secs)
             t0, cur = t1, (nxt if gnext is not None else None)
@@ -92,7 +138,7 @@ def train(cfg: Config, train_corpus: Corpus, test_corpus: Corpus | None = None, 
                 _, entry["ciderD"] = beam_eval(model, test_corpus, ixtoword, scorer, B, eval_beam, eval_lnf, par)
             else:
                 _, entry["ciderD"] = greedy_eval(model, test_corpus, ixtoword, scorer, B, par)
-        ck = save_checkpoint_checked(model, cfg, epoch, step_name="Variable", chief=par.chief)
+        ck = save_checkpoint_checked(model, cfg, epoch, step_name="g_step" if reinforce else "Variable", chief=par.chief)
         if par.chief:
             entry["checkpoint"] = ck
         history.append(entry)
@@ -112,12 +158,16 @@ def main():
     ap.add_argument("--model-path", default="./attention_models")
     ap.add_argument("--eval-beam", type=int, default=0, help="per-epoch evaluation with a beam of this size (1..16) instead of greedy decoding")
     ap.add_argument("--eval-lnf", type=float, default=0.0, help="length normalisation factor of the evaluation beam search")
+    ap.add_argument("--reinforce", action="store_true", help="the self-critical REINFORCE stage (CIDEr-D reward) instead of cross entropy")
+    ap.add_argument("--samples", type=int, default=5, help="multinomial samples per video and step of --reinforce (K)")
+    ap.add_argument("--restore", help="--reinforce: the XE checkpoint to start from (variables and Adam slots; the step counter starts at 0)")
     a = ap.parse_args()
-    cfg = attention_config(n_epochs=a.epochs, batch_size=a.batch_size, model_path=a.model_path, n_video_lstm_step=a.frames,
-                           model_name=f"batch_size{a.batch_size}_beta10_m05_{a.frames}img_attention_model")
+    make = reinforce_config if a.reinforce else attention_config
+    cfg = make(n_epochs=a.epochs, batch_size=a.batch_size, model_path=a.model_path, n_video_lstm_step=a.frames,
+               model_name=f"batch_size{a.batch_size}_beta10_m05_{a.frames}img_attention_{'reinforce_' if a.reinforce else ''}model")
     tr = Corpus(a.train_sents, a.train_feats, vocabulary_file=a.vocab)
     te = Corpus(a.test_sents, a.test_feats, vocabulary=tr.vocabulary) if a.test_sents and a.test_feats else None
-    train(cfg, tr, te, resume=a.resume, eval_beam=a.eval_beam, eval_lnf=a.eval_lnf)
+    train(cfg, tr, te, resume=a.resume, eval_beam=a.eval_beam, eval_lnf=a.eval_lnf, reinforce=a.reinforce, samples=a.samples, restore=a.restore)
 
 
 if __name__ == "__main__":
