@@ -4,7 +4,6 @@
 // global-norm clip + TF-form Adam.
 #include <hip/hip_runtime.h>
 
-#include <functional>
 #include <mutex>
 
 #include <cstdlib>
@@ -628,7 +627,252 @@ static int split_grad_mode(int N)
     return on && N > 256 ? kGradSplit : kGradFp32;
 }
 
-// The backward of s2vt_bptt_bwd_live; mode != kGradFp32: its gradient contractions on bf16 / split-bf16 operands, bf16_ws their scratch
+// Phases of the backward (the ABI's `phase`, 0 to 4), for data-parallel callers that start a slice's all-reduce as soon as its gradients
+// are final:  kVocab = the vocab projection (embed_word_W / _b final);  kLstm2 = LSTM2's recurrence + its weight gradients (lstm2_W / _b
+// final);  kRest = everything after (dX2, LSTM1, Wemb, frame embedding);  kLstm2AndRest = kLstm2 + kRest;  kAll = all.
+enum BwdPhase { kAll = 0, kVocab = 1, kLstm2AndRest = 2, kLstm2 = 3, kRest = 4 };
+
+// (inside a stage: hand a failed launch's error to the driver, whose HIP_TRY records it)
+#define HIP_CHECK(expr) do { const hipError_t _e = (expr); if (_e != hipSuccess) return _e; } while (0)
+
+// A weight gradient C[M, N] += A[rows, M]^T B[rows, N] (+ colsum += B's column sums); idx: A's rows gathered out of a table of gather_rows
+// rows (0 = not stated)
+static TnArgs tn(const float* A, const int32_t* idx, int gather_rows, int lda, const float* B, int ldb, float* C, int ldc, int rows, int M, int N,
+                 float* colsum = nullptr)
+{
+    return TnArgs{A, idx, lda, B, ldb, C, ldc, rows, M, N, 1, colsum, gather_rows};
+}
+
+// One backward call: what every stage reads (filled once by bptt_bwd_body, which is the driver) and the stages themselves.  Each of the
+// four product stages -- vocab projection, LSTM2's weight gradients, dX2, LSTM1's tail -- has one straight-line function per
+// implementation: *_fp32 (fp32 MFMA; the live-row list, when given, cuts the decode steps down to a second, packed contraction),
+// *_tr (bf16 / split-bf16 on transposed operands: tr + mm) and *_fused (split-bf16 on operands by rows: rows / rows1 + mmt).  The bf16
+// scratch is reused in stream order, so the order of casts and products inside a stage is part of it.
+struct BpttBwd {
+    SideStream& ss;
+    int H, E, V, D, Tv, Tc, T, B, N;     // (Tc, T: the steps the forward call unrolled)
+    int K4, Re, Rd;                      // bf16_pad(4 H); rows of the N-row products: encode steps | decode steps (the live rows when listed)
+    size_t NH; TrainWs w; Bf16Ws bw;
+    const s2vt_params *p, *grads; const float *video, *dlogits; const int32_t* live_rows; int n_live;
+    float keep; uint64_t seed; const int32_t *video_id, *sample_id;
+    bool bf16, split, fused;             // bf16: either bf16 mode; fused: the split mode without transposed operands (carve_bf16)
+    hipStream_t st, sd, sv;              // the caller's; LSTM2's weight gradients' and the deferred dWout's; the vocab stage's dWout's
+    bool gate1, gate2;                   // gated overlap beside LSTM1's / LSTM2's recurrence
+
+    // the decode rows of dZ2 (live: the packed copy the LSTM2 phase left in the workspace)
+    const float* dzd() const { return live_rows ? w.dZ2p : w.dZ2 + (size_t)Tv * 4 * NH; }
+
+    // ---- bf16 / split mode: each operand of a gradient contraction is cast once (a shared one serves every product that reads it; split:
+    // its hi and lo planes from one read), then gemm_bf16_nt / gemm_bf16x3_nt; the recurrences, dropout reductions and the embedding
+    // scatter stay as they are.  Everything on the caller's stream.
+    uint16_t* lo(uint16_t* hi) const { return split && hi ? hi + bw.lo_delta : nullptr; }
+    hipError_t tr(const float* src, int ld, const int32_t* idx, int R, int C, uint16_t* dst, int ldd, float* colsum = nullptr,
+                  uint16_t* rdst = nullptr, int rldd = 0) const
+    {
+        CastTrArgs a{src, ld, idx, R, C, dst, ldd, bf16_pad(R), colsum, bw.part, rdst, rldd, lo(dst), lo(rdst)};
+        return launch_cast_tr_bf16(a, st);
+    }
+    hipError_t rows(const float* src, int ld, const int32_t* idx, int R, int K, uint16_t* dst, int ldd) const
+    {
+        return launch_cast_rows_bf16(src, ld, idx, R, K, dst, ldd, st, lo(dst));
+    }
+    // (acc = 1: a weight gradient, accumulated into its buffer; 0: a data gradient)
+    hipError_t mm(uint16_t* A, int lda, uint16_t* Bm, int ldb, float* Cm, int ldc, int M, int Nn, int Kp, int acc) const
+    {
+        if (split)
+            return launch_gemm_bf16x3_nt(A, lo(A), lda, Bm, lo(Bm), ldb, Cm, ldc, M, Nn, Kp, acc, bw.kpart, bw.kpart_floats, acc ? 3 : 4, st);
+        return launch_gemm_bf16_nt(A, lda, Bm, ldb, Cm, ldc, M, Nn, Kp, acc, 0, st);
+    }
+    // fused split mode: a weight gradient from operands by rows, C[M, Nn] += A[K rows][M]^T B[K rows][Nn] (+ bias += B's column sums through
+    // the ones column that rows1 puts behind A's M columns)
+    hipError_t rows1(const float* src, int ld, const int32_t* idx, int R, int K, uint16_t* dst, int ldd) const
+    {
+        return launch_cast_rows_bf16(src, ld, idx, R, K, dst, ldd, st, lo(dst), 1);
+    }
+    hipError_t mmt(uint16_t* A, int lda, uint16_t* Bm, int ldb, float* Cm, int ldc, int M, int Nn, int K, float* bias) const
+    {
+        return launch_gemm_bf16x3_tn(A, lo(A), lda, Bm, lo(Bm), ldb, Cm, ldc, M, Nn, K, 1, bias, bw.kpart, bw.kpart_floats, 3, st);
+    }
+
+    // ---- steps shared between stages
+    // n packed rows (row r belonging to row live_rows[r] of dst) into dst, every other row of it zero
+    hipError_t scatter_into_zeroed(const float* packed, int ld, int n, float* dst, size_t bytes) const
+    {
+        ZeroList z;
+        z.add(dst, bytes);
+        const hipError_t e = launch_zero_regions(z, st);
+        return e != hipSuccess ? e : launch_scatter_rows(packed, ld, live_rows, n, ld, dst, ld, st);
+    }
+    // embedding rows (gradient of tf.nn.embedding_lookup): scatter-add of the embed slice of dX2
+    hipError_t wemb_scatter_add() const
+    {
+        if (live_rows) return launch_scatter_add_rows(w.dX2p + H, H + E, w.prevp, n_live, E, grads->Wemb, E, st);
+        return launch_scatter_add_rows(w.dX2 + (size_t)Tv * N * (H + E) + H, H + E, w.prev, Tc * N, E, grads->Wemb, E, st);
+    }
+    // dZ2 by rows into L, [encode steps | decode steps]: the B operand of the fused LSTM2 products and dX2's A
+    hipError_t cast_dz2_rows() const
+    {
+        HIP_CHECK(rows(w.dZ2, 4 * H, nullptr, Re, 4 * H, bw.L, K4));
+        return rows(dzd(), 4 * H, nullptr, Rd, 4 * H, bw.L + (size_t)Re * K4, K4);
+    }
+
+    // ---- vocab projection: dWout (+ the bias gradient) = O2^T dlogits and dO2 = dlogits Wout^T -> dO2t.  R rows: every unrolled
+    // (step, row) pair, or the LIVE ones only (dlogits is then [n_live, V], row r belonging to row live_rows[r] of the unroll; the masked
+    // rows' dlogits are exact zeros in the full form, so leaving them out of the reductions changes nothing and their dO2 rows are the
+    // zeros the driver writes)
+    hipError_t vocab_fused(int R, float* dO2t) const
+    {
+        // dlogits by rows, once (or there already): dWout's B (K-major; + the bias gradient) and dO2's A
+        const int Kv = bf16_pad(V), Hp1 = bf16_pad(H + 1);
+        if (dlogits) HIP_CHECK(rows(dlogits, V, nullptr, R, V, bw.L, Kv));
+        HIP_CHECK(rows1(w.O2 + (size_t)Tv * NH, H, live_rows, R, H, bw.AT, Hp1));
+        HIP_CHECK(mmt(bw.AT, Hp1, bw.L, Kv, grads->embed_word_W, V, H, V, R, grads->embed_word_b));
+        HIP_CHECK(rows(p->embed_word_W, V, nullptr, H, V, bw.W, Kv));
+        return mm(bw.L, Kv, bw.W, Kv, dO2t, H, R, H, Kv, 0);
+    }
+    hipError_t vocab_tr(int R, float* dO2t) const
+    {
+        // dlogits once, in both forms: transposed (dWout's B, + the bias gradient) and by rows (dO2's A)
+        const int Kr = bf16_pad(R), Kv = bf16_pad(V);
+        HIP_CHECK(tr(dlogits, V, nullptr, R, V, bw.BT, Kr, grads->embed_word_b, bw.L, Kv));
+        HIP_CHECK(tr(w.O2 + (size_t)Tv * NH, H, live_rows, R, H, bw.AT, Kr));
+        HIP_CHECK(mm(bw.AT, Kr, bw.BT, Kr, grads->embed_word_W, V, H, V, Kr, 1));
+        HIP_CHECK(rows(p->embed_word_W, V, nullptr, H, V, bw.W, Kv));
+        return mm(bw.L, Kv, bw.W, Kv, dO2t, H, R, H, Kv, 0);
+    }
+    // (deferred != NULL: dWout is handed back for the driver to launch behind LSTM2's recurrence instead)
+    hipError_t vocab_fp32(int R, float* dO2t, TnArgs* deferred) const
+    {
+        // the bias gradient rides in the same pass over dlogits
+        const TnArgs a = tn(w.O2 + (size_t)Tv * NH, live_rows, live_rows ? Tc * N : 0, H, dlogits, V, grads->embed_word_W, V, R, H, V, grads->embed_word_b);
+        if (deferred) *deferred = a;
+        else HIP_CHECK(launch_gemm_tn(a, sv));
+        int s2 = w.dO2s ? do2_splits(R, H, V) : 1;
+        if ((size_t)s2 * R > w.dO2s_rows) s2 = 1;            // (a live-row count between two step counts the carve did not see)
+        if (s2 > 1) {
+            const size_t stride = (size_t)R * H;
+            HIP_CHECK(nn_bwd(dlogits, V, p->embed_word_W, V, w.dO2s, H, R, H, V, s2, stride, st, kSlabTileCfg));
+            const int kper = ((V + s2 - 1) / s2 + BK - 1) / BK * BK;       // what nn_bwd made of `splits`
+            return launch_sum_slabs(dO2t, w.dO2s, (V + kper - 1) / kper, stride, stride, st);
+        }
+        return nn_bwd(dlogits, V, p->embed_word_W, V, dO2t, H, R, H, V, 1, 0, st);
+    }
+
+    // ---- LSTM2's weight gradients over [encode steps | decode steps (live: the packed live rows)]: out1, the embedding rows of the previous
+    // words (decode segment only) and h2 against dZ2, lstm2_b with the last.  On sd: beside dX2 and LSTM1's recurrence, or (gated) launched
+    // by the driver behind LSTM1's recurrence.
+    hipError_t l2_grads_fused() const
+    {
+        // dZ2 once, by rows: the B operand of all three products (+ lstm2_b with the last) and dX2's A (phase 4); out1 / h2 by rows over
+        // the same two segments, the embedding rows over the decode one
+        const int Hp = bf16_pad(H), Hp1 = bf16_pad(H + 1), Ep = bf16_pad(E);
+        HIP_CHECK(cast_dz2_rows());
+        HIP_CHECK(rows(w.O1, H, nullptr, Re, H, bw.AT, Hp));
+        HIP_CHECK(rows(w.O1 + (size_t)Tv * NH, H, live_rows, Rd, H, bw.AT + (size_t)Re * Hp, Hp));
+        HIP_CHECK(mmt(bw.AT, Hp, bw.L, K4, grads->lstm2_W, 4 * H, H, 4 * H, Re + Rd, nullptr));
+        HIP_CHECK(rows(p->Wemb, E, live_rows ? w.prevp : w.prev, Rd, E, bw.AT, Ep));                  // Wemb [V, E] rows of the previous words
+        HIP_CHECK(mmt(bw.AT, Ep, bw.L + (size_t)Re * K4, K4, grads->lstm2_W + (size_t)H * 4 * H, 4 * H, E, 4 * H, Rd, nullptr));
+        HIP_CHECK(rows1(w.H2, H, nullptr, Re, H, bw.AT, Hp1));
+        HIP_CHECK(rows1(w.H2 + (size_t)Tv * NH, H, live_rows, Rd, H, bw.AT + (size_t)Re * Hp1, Hp1));
+        return mmt(bw.AT, Hp1, bw.L, K4, grads->lstm2_W + (size_t)(H + E) * 4 * H, 4 * H, H, 4 * H, Re + Rd, grads->lstm2_b);
+    }
+    hipError_t l2_grads_tr() const
+    {
+        // dZ2 once: transposed -- the B operand of all three products, + lstm2_b -- and by rows (dX2's A, phase 4)
+        const int ke = bf16_pad(Re), Kd = bf16_pad(Rd), Kt = ke + Kd;
+        HIP_CHECK(tr(w.dZ2, 4 * H, nullptr, Re, 4 * H, bw.BT, Kt, grads->lstm2_b, bw.L, K4));
+        HIP_CHECK(tr(dzd(), 4 * H, nullptr, Rd, 4 * H, bw.BT + ke, Kt, grads->lstm2_b, bw.L + (size_t)Re * K4, K4));
+        HIP_CHECK(tr(w.O1, H, nullptr, Re, H, bw.AT, Kt));
+        HIP_CHECK(tr(w.O1 + (size_t)Tv * NH, H, live_rows, Rd, H, bw.AT + ke, Kt));
+        HIP_CHECK(mm(bw.AT, Kt, bw.BT, Kt, grads->lstm2_W, 4 * H, H, 4 * H, Kt, 1));
+        HIP_CHECK(tr(p->Wemb, E, live_rows ? w.prevp : w.prev, Rd, E, bw.AT, Kd));                    // Wemb [V, E] rows of the previous words
+        HIP_CHECK(mm(bw.AT, Kd, bw.BT + ke, Kt, grads->lstm2_W + (size_t)H * 4 * H, 4 * H, E, 4 * H, Kd, 1));
+        HIP_CHECK(tr(w.H2, H, nullptr, Re, H, bw.AT, Kt));
+        HIP_CHECK(tr(w.H2 + (size_t)Tv * NH, H, live_rows, Rd, H, bw.AT + ke, Kt));
+        return mm(bw.AT, Kt, bw.BT, Kt, grads->lstm2_W + (size_t)(H + E) * 4 * H, 4 * H, H, 4 * H, Kt, 1);
+    }
+    hipError_t l2_grads_fp32() const
+    {
+        float* const gO1 = grads->lstm2_W, *const gEmb = gO1 + (size_t)H * 4 * H, *const gH2 = gO1 + (size_t)(H + E) * 4 * H;
+        if (!live_rows) {
+            HIP_CHECK(launch_gemm_tn(tn(w.O1, nullptr, 0, H, w.dZ2, 4 * H, gO1, 4 * H, T * N, H, 4 * H), sd));
+            HIP_CHECK(launch_gemm_tn(tn(p->Wemb, w.prev, V, E, dzd(), 4 * H, gEmb, 4 * H, Tc * N, E, 4 * H), sd));
+            return launch_gemm_tn(tn(w.H2, nullptr, 0, H, w.dZ2, 4 * H, gH2, 4 * H, T * N, H, 4 * H, grads->lstm2_b), sd);
+        }
+        // Live rows: behind its first <eos> a row's dZ2 is an exact zero at every later step (zero upstream gradient, zero carried
+        // dh / dc), so the weight gradients are reduced over the Tv encode steps (every row) plus the LIVE decode rows -- their
+        // dZ2 rows as a packed copy, the matching activation rows gathered through the same list.
+        HIP_CHECK(launch_gemm_tn(tn(w.O1, nullptr, 0, H, w.dZ2, 4 * H, gO1, 4 * H, Re, H, 4 * H), sd));
+        HIP_CHECK(launch_gemm_tn(tn(w.O1 + (size_t)Tv * NH, live_rows, Tc * N, H, w.dZ2p, 4 * H, gO1, 4 * H, Rd, H, 4 * H), sd));
+        HIP_CHECK(launch_gemm_tn(tn(p->Wemb, w.prevp, V, E, w.dZ2p, 4 * H, gEmb, 4 * H, Rd, E, 4 * H), sd));
+        HIP_CHECK(launch_gemm_tn(tn(w.H2, nullptr, 0, H, w.dZ2, 4 * H, gH2, 4 * H, Re, H, 4 * H, grads->lstm2_b), sd));
+        return launch_gemm_tn(tn(w.H2 + (size_t)Tv * NH, live_rows, Tc * N, H, w.dZ2p, 4 * H, gH2, 4 * H, Rd, H, 4 * H, grads->lstm2_b), sd);
+    }
+    // (one name for the driver's two call sites: at once, or deferred behind LSTM1's recurrence)
+    hipError_t l2_grads() const
+    {
+        // (planes too large for the K-major loader's 32-bit offsets: the transposed form)
+        if (fused && gemm_bf16x3_tn_ok(bf16_pad(H + 1) > bf16_pad(E) ? bf16_pad(H + 1) : bf16_pad(E), K4, Re + Rd)) return l2_grads_fused();
+        return bf16 ? l2_grads_tr() : l2_grads_fp32();
+    }
+
+    // ---- d[out1 ; embed] for every step at once -- with live rows: the encode steps, then the live decode rows (from the packed dZ2
+    // of the LSTM2 phase), scattered into the zeroed decode part
+    // (one function for the three bf16 forms: mm picks the product.  recast: phase 4 alone -- the row form phase 3 made, again)
+    hipError_t dx2_bf16(bool recast) const
+    {
+        if (recast) HIP_CHECK(cast_dz2_rows());
+        HIP_CHECK(rows(p->lstm2_W, 4 * H, nullptr, H + E, 4 * H, bw.W, K4));
+        if (!live_rows) return mm(bw.L, K4, bw.W, K4, w.dX2, H + E, T * N, H + E, K4, 0);
+        HIP_CHECK(mm(bw.L, K4, bw.W, K4, w.dX2, H + E, Re, H + E, K4, 0));
+        HIP_CHECK(mm(bw.L + (size_t)Re * K4, K4, bw.W, K4, w.dX2p, H + E, Rd, H + E, K4, 0));
+        return scatter_into_zeroed(w.dX2p, H + E, n_live, w.dX2 + (size_t)Tv * N * (H + E), (size_t)Tc * N * (H + E) * 4);
+    }
+    hipError_t dx2_fp32() const
+    {
+        if (!live_rows) return nn_bwd_slabs(w.dZ2, 4 * H, p->lstm2_W, 4 * H, w.dX2, H + E, T * N, H + E, 4 * H, w.dXs, st, w.dXs_floats);
+        HIP_CHECK(nn_bwd_slabs(w.dZ2, 4 * H, p->lstm2_W, 4 * H, w.dX2, H + E, Tv * N, H + E, 4 * H, w.dXs, st, w.dXs_floats));
+        HIP_CHECK(nn_bwd_slabs(w.dZ2p, 4 * H, p->lstm2_W, 4 * H, w.dX2p, H + E, n_live, H + E, 4 * H, w.dXs, st, w.dXs_floats));
+        return scatter_into_zeroed(w.dX2p, H + E, n_live, w.dX2 + (size_t)Tv * N * (H + E), (size_t)Tc * N * (H + E) * 4);
+    }
+
+    // ---- LSTM1's tail: dX1, LSTM1's weight gradients over all unrolled steps, the embedding scatter-add, the frame embedding
+    hipError_t lstm1_tail_bf16() const
+    {
+        // dZ1 once: transposed over [encode steps | decode steps] (+ lstm1_b), and the encode rows by rows (dX1's A)
+        const int Re1 = Tv * B, Rd1 = Tc * B, ke = bf16_pad(Re1), K1 = ke + bf16_pad(Rd1);
+        HIP_CHECK(tr(w.dZ1, 4 * H, nullptr, Re1, 4 * H, bw.BT, K1, grads->lstm1_b, bw.L, K4));
+        HIP_CHECK(tr(w.dZ1 + (size_t)Re1 * 4 * H, 4 * H, nullptr, Rd1, 4 * H, bw.BT + ke, K1, grads->lstm1_b));
+        HIP_CHECK(rows(p->lstm1_W, 4 * H, nullptr, E, 4 * H, bw.W, K4));
+        HIP_CHECK(mm(bw.L, K4, bw.W, K4, w.dX1, E, Re1, E, K4, 0));
+        HIP_CHECK(tr(w.emb, E, w.encidx, Re1, E, bw.AT, ke));                                         // the frame embedding, time-major
+        HIP_CHECK(mm(bw.AT, ke, bw.BT, K1, grads->lstm1_W, 4 * H, E, 4 * H, ke, 1));
+        HIP_CHECK(tr(w.H1, H, nullptr, Re1, H, bw.AT, K1));
+        HIP_CHECK(tr(w.H1 + (size_t)Re1 * H, H, nullptr, Rd1, H, bw.AT + ke, K1));
+        HIP_CHECK(mm(bw.AT, K1, bw.BT, K1, grads->lstm1_W + (size_t)E * 4 * H, 4 * H, H, 4 * H, K1, 1));
+        HIP_CHECK(wemb_scatter_add());
+        HIP_CHECK(tr(video, D, w.encidx, Re1, D, bw.AT, ke));
+        HIP_CHECK(tr(w.dX1, E, nullptr, Re1, E, bw.BT, ke, grads->encode_image_b));
+        return mm(bw.AT, ke, bw.BT, ke, grads->encode_image_W, E, D, E, ke, 1);
+    }
+    // (the split mode's too: LSTM1's contractions -- B rows, not N: dX1 [Tv B, E], the weight gradients over (Tv + Tc) B rows -- stay on
+    // fp32 MFMA)
+    hipError_t lstm1_tail_fp32() const
+    {
+        HIP_CHECK(nn_bwd_slabs(w.dZ1, 4 * H, p->lstm1_W, 4 * H, w.dX1, E, Tv * B, E, 4 * H, w.dXs, st, w.dXs_floats));
+        HIP_CHECK(launch_gemm_tn(tn(w.emb, w.encidx, Tv * B, E, w.dZ1, 4 * H, grads->lstm1_W, 4 * H, Tv * B, E, 4 * H), st));
+        HIP_CHECK(launch_gemm_tn(tn(w.H1, nullptr, 0, H, w.dZ1, 4 * H, grads->lstm1_W + (size_t)E * 4 * H, 4 * H, T * B, H, 4 * H, grads->lstm1_b), st));
+        HIP_CHECK(wemb_scatter_add());
+        return launch_gemm_tn(tn(video, w.encidx, Tv * B, D, w.dX1, E, grads->encode_image_W, E, Tv * B, D, E, grads->encode_image_b), st);
+    }
+};
+
+// The backward of s2vt_bptt_bwd_live; mode != kGradFp32: its gradient contractions on bf16 / split-bf16 operands, bf16_ws their scratch.
+// The driver only: validate and carve; streams, gates and the side-stream lock; then the stages of BpttBwd in the order of the phases --
+// vocab projection | LSTM2's recurrence (the deferred dWout beside it), live-row gathers, LSTM2's weight gradients (now, or deferred
+// beside LSTM1's recurrence) | dX2, dropout reduction + LSTM1's recurrence, LSTM1's tail -- and ONE successful exit, through the join.
+// The bf16 and split modes never fork (their SideStream is a local one with ok = false, so sd == sv == st): for them, and for the
+// single-phase calls, `sd != st` makes the join nothing.
 static int bptt_bwd_body(const s2vt_dims* d, const s2vt_params* p, const s2vt_params* grads, const float* video, int32_t B,
                          int32_t N, const float* dlogits, int32_t caption_steps, const int32_t* live_rows, int32_t n_live, float keep,
                          uint64_t seed, const int32_t* video_id, const int32_t* sample_id, void* workspace, size_t workspace_bytes,
@@ -638,7 +882,7 @@ static int bptt_bwd_body(const s2vt_dims* d, const s2vt_params* p, const s2vt_pa
     const bool split = mode == kGradSplit;
     if ((live_rows == nullptr) != (n_live == 0) || n_live < 0) return S2VT_E_BADARG;
     if (bf16 && !bf16_ws) return S2VT_E_BADARG;
-    if (phase < 0 || phase > 4) return S2VT_E_BADARG;
+    if (phase < kAll || phase > kRest) return S2VT_E_BADARG;
     const bool fused = split && split_fused();               // no transposed operands: K-major weight gradients (carve_bf16)
     // (fused split mode: dlogits == NULL = its planes are in bf16_ws already, s2vt_softmax_nll_fwd_bwd_split -- read by the vocabulary
     //  phase only; phases 2 to 4 never look at dlogits and take the same NULL from a caller that runs the phases one by one)
@@ -652,9 +896,7 @@ static int bptt_bwd_body(const s2vt_dims* d, const s2vt_params* p, const s2vt_pa
     if (live_rows && (n_live > caption_steps * N || ((d->lstm_dim | d->word_dim) & 3))) return S2VT_E_BADARG;
     // the steps the forward call unrolled (s2vt_teacher_forced_fwd_steps): later steps carry no gradient, so the
     // recurrences start from zero at step T - 1 and every contraction covers the leading T (Tc) steps only
-    const int H = d->lstm_dim, E = d->word_dim, V = d->n_words, D = d->dim_image, Tv = d->n_video_lstm_step,
-              Tc = caption_steps;
-    const int T = Tv + Tc;
+    const int H = d->lstm_dim, E = d->word_dim, V = d->n_words, Tv = d->n_video_lstm_step, Tc = caption_steps, T = Tv + Tc;
     Carver c(workspace, workspace_bytes);
     TrainWs w;
     carve_train(c, d, B, N, &w);
@@ -667,115 +909,51 @@ static int bptt_bwd_body(const s2vt_dims* d, const s2vt_params* p, const s2vt_pa
     }
     hipStream_t st = S(stream);
     const size_t NH = (size_t)N * H;
-    // bf16 / split mode: each operand of a gradient contraction is cast once (a shared one serves every product that reads it; split:
-    // its hi and lo planes from one read), then gemm_bf16_nt / gemm_bf16x3_nt; the recurrences, dropout reductions and the embedding
-    // scatter stay as they are.  Everything on the caller's stream.
-    const int K4 = bf16_pad(4 * H);
-    auto lo = [&](uint16_t* hi) -> uint16_t* { return split && hi ? hi + bw.lo_delta : nullptr; };
-    auto tr = [&](const float* src, int ld, const int32_t* idx, int R, int C, uint16_t* dst, int ldd, float* colsum = nullptr,
-                  uint16_t* rdst = nullptr, int rldd = 0) -> hipError_t {
-        CastTrArgs a{src, ld, idx, R, C, dst, ldd, bf16_pad(R), colsum, bw.part, rdst, rldd, lo(dst), lo(rdst)};
-        return launch_cast_tr_bf16(a, st);
-    };
-    auto rows = [&](const float* src, int ld, const int32_t* idx, int R, int K, uint16_t* dst, int ldd) -> hipError_t {
-        return launch_cast_rows_bf16(src, ld, idx, R, K, dst, ldd, st, lo(dst));
-    };
-    // (acc = 1: a weight gradient, accumulated into its buffer; 0: a data gradient)
-    auto mm = [&](uint16_t* A, int lda, uint16_t* Bm, int ldb, float* Cm, int ldc, int M, int Nn, int Kp, int acc) -> hipError_t {
-        if (split)
-            return launch_gemm_bf16x3_nt(A, lo(A), lda, Bm, lo(Bm), ldb, Cm, ldc, M, Nn, Kp, acc, bw.kpart, bw.kpart_floats, acc ? 3 : 4, st);
-        return launch_gemm_bf16_nt(A, lda, Bm, ldb, Cm, ldc, M, Nn, Kp, acc, 0, st);
-    };
-    // fused split mode: a weight gradient from operands by rows, C[M, Nn] += A[K rows][M]^T B[K rows][Nn] (+ bias += B's column sums through
-    // the ones column that rows1 puts behind A's M columns)
-    auto rows1 = [&](const float* src, int ld, const int32_t* idx, int R, int K, uint16_t* dst, int ldd) -> hipError_t {
-        return launch_cast_rows_bf16(src, ld, idx, R, K, dst, ldd, st, lo(dst), 1);
-    };
-    auto mmt = [&](uint16_t* A, int lda, uint16_t* Bm, int ldb, float* Cm, int ldc, int M, int Nn, int K, float* bias) -> hipError_t {
-        return launch_gemm_bf16x3_tn(A, lo(A), lda, Bm, lo(Bm), ldb, Cm, ldc, M, Nn, K, 1, bias, bw.kpart, bw.kpart_floats, 3, st);
-    };
+    const bool do_vocab = phase == kAll || phase == kVocab, do_l2 = phase == kAll || phase == kLstm2AndRest || phase == kLstm2,
+               do_rest = phase == kAll || phase == kLstm2AndRest || phase == kRest;
 
-    // Phases, for data-parallel callers that start a slice's all-reduce as soon as its gradients are final:
-    //   1 = the vocab projection (embed_word_W / _b final);  3 = LSTM2's recurrence + its weight gradients (lstm2_W / _b
-    //   final);  4 = everything after (dX2, LSTM1, Wemb, frame embedding);  2 = 3 + 4;  0 = all.
-    const bool do_vocab = phase == 0 || phase == 1, do_l2 = phase == 0 || phase == 2 || phase == 3,
-               do_rest = phase == 0 || phase == 2 || phase == 4;
+    // ---- streams, gates, the side-stream lock
     SideStream one_stream;                                   // (ok = false: the bf16 mode keeps to the caller's stream)
     SideStream& ss = bf16 ? one_stream : side_stream();
+    BpttBwd x{ss};
     // gated overlap (mode 2): only beside recurrences that run as ONE-part persistent grids (<= 256 rows: room for a second wave per SIMD)
-    const bool gate2 = ss.ok && ss.mode == 2 && phase == 0 && N <= 256 && bwd_chain_auto(N, H) && !(reinterpret_cast<uintptr_t>(p->lstm2_W) & 15);
+    x.gate2 = ss.ok && ss.mode == 2 && phase == kAll && N <= 256 && bwd_chain_auto(N, H) && !(reinterpret_cast<uintptr_t>(p->lstm2_W) & 15);
     // (LSTM1's recurrence is gated only where LSTM2's is: at N > 256 rows -- the REINFORCE step's 320 -- LSTM2's three contractions are 0.6 ms
     //  each and lose more beside the 64-row recurrence than it gains: 12.26 -> 12.28 ms measured, profiles/r05_overlap_ab.jsonl)
-    const bool gate1 = ss.ok && ss.mode == 2 && phase == 0 && N <= 256 && B <= 256 && bwd_chain_auto(B, H) && !(reinterpret_cast<uintptr_t>(p->lstm1_W) & 15);
-    const bool side_on = ss.ok && phase == 0 && (ss.mode == 1 || gate1 || gate2);
+    x.gate1 = ss.ok && ss.mode == 2 && phase == kAll && N <= 256 && B <= 256 && bwd_chain_auto(B, H) && !(reinterpret_cast<uintptr_t>(p->lstm1_W) & 15);
+    const bool side_on = ss.ok && phase == kAll && (ss.mode == 1 || x.gate1 || x.gate2);
     hipStream_t sd = side_on ? ss.s : st;                    // weight-gradient work that may run beside a recurrence (whole-pass calls only)
+    x.H = H; x.E = E; x.V = V; x.D = d->dim_image; x.Tv = Tv; x.Tc = Tc; x.T = T; x.B = B; x.N = N;
+    x.K4 = bf16_pad(4 * H); x.Re = Tv * N; x.Rd = live_rows ? n_live : Tc * N; x.NH = NH;
+    x.w = w; x.bw = bw; x.p = p; x.grads = grads; x.video = video; x.dlogits = dlogits; x.live_rows = live_rows; x.n_live = n_live;
+    x.keep = keep; x.seed = seed; x.video_id = video_id; x.sample_id = sample_id; x.bf16 = bf16; x.split = split; x.fused = fused;
+    x.st = st; x.sd = sd; x.sv = (phase == kAll && ss.ok && ss.mode == 1) ? sd : st;   // (phase 1: its gradients must be final on the caller's stream)
     // The side stream and its events are ONE per process: two host threads driving distinct workspaces must not interleave their
     // record / wait pairs (a wait enqueued after the OTHER thread's record of the same event would order this call's side work behind
     // the wrong point).  The lock covers this call's enqueueing only -- the launches themselves are asynchronous as ever.
     std::unique_lock<std::mutex> side_lk(side_stream_mutex(), std::defer_lock);
     if (side_on) side_lk.lock();
     ChainGate gate{ss.s, ss.ev[3], false};
+    const BwdScratch sc{w.slab, w.dc, w.bimg, w.bex, w.bsync};
+
+    // ---- vocab projection
     TnArgs dwout;                                            // (mode 2: the vocabulary projection's weight gradient is launched behind LSTM2's recurrence)
-    bool dwout_deferred = false;
+    const bool dwout_deferred = x.gate2 && do_l2;            // (a gate means a whole pass on fp32 products: the vocab stage runs, and takes its fp32 form)
     if (do_vocab) {
-        // transposed weight copy for the data-gradient product + the vocab projection
-        hipStream_t sv = (phase == 0 && ss.ok && ss.mode == 1) ? sd : st;     // (phase 1: its gradients must be final on the caller's stream)
-        if (sv != st) HIP_TRY(fork_to(st, sv, ss.ev[0]));
-        // rows of the vocabulary-side products: every unrolled (step, row) pair, or the LIVE ones only (dlogits is then
-        // [n_live, V], row r belonging to row live_rows[r] of the unroll; the masked rows' dlogits are exact zeros in the full
-        // form, so leaving them out of the reductions changes nothing and their dO2 rows are the zeros written below)
-        const int R = live_rows ? n_live : Tc * N;
-        float* const dO2t = live_rows ? w.dO2p : w.dO2;     // where the product lands: packed rows are scattered afterwards
+        if (x.sv != st) HIP_TRY(fork_to(st, x.sv, ss.ev[0]));
+        float* const dO2t = live_rows ? w.dO2p : w.dO2;     // where dO2 lands: packed rows are scattered afterwards
         // (planes too large for the K-major loader's 32-bit offsets: the transposed form, which needs dlogits as fp32 -- the split
         //  softmax entry applies the same rule and leaves them so)
-        const bool fused_v = fused && gemm_bf16x3_tn_ok(bf16_pad(H + 1), bf16_pad(V), R);
+        const bool fused_v = fused && gemm_bf16x3_tn_ok(bf16_pad(H + 1), bf16_pad(V), x.Rd);
         if (!fused_v && !dlogits) return S2VT_E_BADARG;
-        if (fused_v) {
-            // dlogits by rows, once (or there already): dWout's B (K-major; + the bias gradient) and dO2's A
-            const int Kv = bf16_pad(V), Hp1 = bf16_pad(H + 1);
-            if (dlogits) HIP_TRY(rows(dlogits, V, nullptr, R, V, bw.L, Kv));
-            HIP_TRY(rows1(w.O2 + (size_t)Tv * NH, H, live_rows, R, H, bw.AT, Hp1));
-            HIP_TRY(mmt(bw.AT, Hp1, bw.L, Kv, grads->embed_word_W, V, H, V, R, grads->embed_word_b));
-            HIP_TRY(rows(p->embed_word_W, V, nullptr, H, V, bw.W, Kv));
-            HIP_TRY(mm(bw.L, Kv, bw.W, Kv, dO2t, H, R, H, Kv, 0));
-        } else if (bf16) {
-            // dlogits once, in both forms: transposed (dWout's B, + the bias gradient) and by rows (dO2's A)
-            const int Kr = bf16_pad(R), Kv = bf16_pad(V);
-            HIP_TRY(tr(dlogits, V, nullptr, R, V, bw.BT, Kr, grads->embed_word_b, bw.L, Kv));
-            HIP_TRY(tr(w.O2 + (size_t)Tv * NH, H, live_rows, R, H, bw.AT, Kr));
-            HIP_TRY(mm(bw.AT, Kr, bw.BT, Kr, grads->embed_word_W, V, H, V, Kr, 1));
-            HIP_TRY(rows(p->embed_word_W, V, nullptr, H, V, bw.W, Kv));
-            HIP_TRY(mm(bw.L, Kv, bw.W, Kv, dO2t, H, R, H, Kv, 0));
-        } else {
-        TnArgs a{w.O2 + (size_t)Tv * NH, live_rows, H, dlogits, V, grads->embed_word_W, V, R, H, V, 1};
-        a.gather_rows = live_rows ? Tc * N : 0;
-        a.colsum = grads->embed_word_b;                     // the bias gradient rides in the same pass over dlogits
-        if (gate2 && do_l2) { dwout = a; dwout_deferred = true; }
-        else HIP_TRY(launch_gemm_tn(a, sv));
-        int s2 = w.dO2s ? do2_splits(R, H, V) : 1;
-        if ((size_t)s2 * R > w.dO2s_rows) s2 = 1;            // (a live-row count between two step counts the carve did not see)
-        if (s2 > 1) {
-            const size_t stride = (size_t)R * H;
-            HIP_TRY(nn_bwd(dlogits, V, p->embed_word_W, V, w.dO2s, H, R, H, V, s2, stride, st, kSlabTileCfg));
-            const int kper = ((V + s2 - 1) / s2 + BK - 1) / BK * BK;       // what nn_bwd made of `splits`
-            HIP_TRY(launch_sum_slabs(dO2t, w.dO2s, (V + kper - 1) / kper, stride, stride, st));
-        } else {
-            HIP_TRY(nn_bwd(dlogits, V, p->embed_word_W, V, dO2t, H, R, H, V, 1, 0, st));
-        }
-        }
-        if (live_rows) {
-            ZeroList z;
-            z.add(w.dO2, (size_t)Tc * N * H * 4);
-            HIP_TRY(launch_zero_regions(z, st));
-            HIP_TRY(launch_scatter_rows(w.dO2p, H, live_rows, R, H, w.dO2, H, st));
-        }
+        if (fused_v) HIP_TRY(x.vocab_fused(x.Rd, dO2t));
+        else if (bf16) HIP_TRY(x.vocab_tr(x.Rd, dO2t));
+        else HIP_TRY(x.vocab_fp32(x.Rd, dO2t, dwout_deferred ? &dwout : nullptr));
+        if (live_rows) HIP_TRY(x.scatter_into_zeroed(w.dO2p, H, x.Rd, w.dO2, (size_t)Tc * N * H * 4));
     }
-    bool l2_deferred = false;
-    std::function<int()> l2_grads_fn;
+    const bool l2_deferred = x.gate1 && do_rest && sd != st;
     if (do_l2) {
-    // ---- LSTM2 back through time (one persistent launch up to 128 rows: chain.hip)
-    {
-        BwdScratch sc{w.slab, w.dc, w.bimg, w.bex, w.bsync};
+        // ---- LSTM2 back through time (one persistent launch up to 128 rows: chain.hip)
         // (live rows: the forward pass of this workspace stopped the rows behind their <eos>, see there -- the same order here)
         const bool rec_live = live_rows && Tc <= 128 && chain_live_capable(N, H);
         if (live_rows && Tc <= 128 && N <= 1024) HIP_TRY(launch_row_order(live_rows, n_live, N, Tv, Tc, w.perm, w.nlive, st));
@@ -791,171 +969,28 @@ static int bptt_bwd_body(const s2vt_dims* d, const s2vt_params* p, const s2vt_pa
             if (!gate.fired) HIP_TRY(fork_to(st, sd, ss.ev[3]));
             HIP_TRY(launch_gemm_tn(dwout, sd));
         }
-    }
-    // Live rows: the packed copies of the live dZ2 rows / previous words are read on BOTH streams (weight gradients on the side
-    // stream, dX2 and the embedding scatter on the caller's), so they are made on the caller's stream, ahead of the fork
-    if (live_rows) {
-        HIP_TRY(launch_gather_rows(w.dZ2 + (size_t)Tv * 4 * NH, 4 * H, live_rows, n_live, 4 * H, w.dZ2p, 4 * H, st));
-        HIP_TRY(launch_gather_i32(w.prev, live_rows, n_live, w.prevp, st));
-    }
-    // dZ2 is complete: LSTM2's weight gradients go to the side stream, beside dX2 and LSTM1's recurrence (mode 2: beside LSTM1's recurrence
-    // only -- launched from the lambda below once that grid is resident; dX2 keeps the chip to itself)
-    if (sd != st) HIP_TRY(fork_to(st, sd, ss.ev[1]));
-    auto l2_weight_grads = [&]() -> int {
-    if (fused && gemm_bf16x3_tn_ok(bf16_pad(H + 1) > bf16_pad(E) ? bf16_pad(H + 1) : bf16_pad(E), K4, Tv * N + (live_rows ? n_live : Tc * N))) {
-        // dZ2 once, by rows, [encode steps | decode steps (live: the packed live rows)]: the B operand of all three products (+ lstm2_b
-        // with the last) and dX2's A (phase 4); out1 / h2 by rows over the same two segments, the embedding rows over the decode one
-        const int Re = Tv * N, Rd = live_rows ? n_live : Tc * N, Hp = bf16_pad(H), Hp1 = bf16_pad(H + 1), Ep = bf16_pad(E);
-        const float* const dzd = live_rows ? w.dZ2p : w.dZ2 + (size_t)Tv * 4 * NH;
-        uint16_t* const dzd16 = bw.L + (size_t)Re * K4;
-        HIP_TRY(rows(w.dZ2, 4 * H, nullptr, Re, 4 * H, bw.L, K4));
-        HIP_TRY(rows(dzd, 4 * H, nullptr, Rd, 4 * H, dzd16, K4));
-        HIP_TRY(rows(w.O1, H, nullptr, Re, H, bw.AT, Hp));
-        HIP_TRY(rows(w.O1 + (size_t)Tv * NH, H, live_rows, Rd, H, bw.AT + (size_t)Re * Hp, Hp));
-        HIP_TRY(mmt(bw.AT, Hp, bw.L, K4, grads->lstm2_W, 4 * H, H, 4 * H, Re + Rd, nullptr));
-        HIP_TRY(rows(p->Wemb, E, live_rows ? w.prevp : w.prev, Rd, E, bw.AT, Ep));                  // Wemb [V, E] rows of the previous words
-        HIP_TRY(mmt(bw.AT, Ep, dzd16, K4, grads->lstm2_W + (size_t)H * 4 * H, 4 * H, E, 4 * H, Rd, nullptr));
-        HIP_TRY(rows1(w.H2, H, nullptr, Re, H, bw.AT, Hp1));
-        HIP_TRY(rows1(w.H2 + (size_t)Tv * NH, H, live_rows, Rd, H, bw.AT + (size_t)Re * Hp1, Hp1));
-        HIP_TRY(mmt(bw.AT, Hp1, bw.L, K4, grads->lstm2_W + (size_t)(H + E) * 4 * H, 4 * H, H, 4 * H, Re + Rd, grads->lstm2_b));
-    } else if (bf16) {
-        // dZ2 once: transposed over [encode steps | decode steps (live: the packed live rows)] -- the B operand of all three products,
-        // + lstm2_b -- and by rows (dX2's A, phase 4); out1 / h2 take the same two segments, the embedding rows the decode segment only
-        const int Re = Tv * N, Rd = live_rows ? n_live : Tc * N, ke = bf16_pad(Re), Kd = bf16_pad(Rd), Kt = ke + Kd;
-        const float* const dzd = live_rows ? w.dZ2p : w.dZ2 + (size_t)Tv * 4 * NH;
-        HIP_TRY(tr(w.dZ2, 4 * H, nullptr, Re, 4 * H, bw.BT, Kt, grads->lstm2_b, bw.L, K4));
-        HIP_TRY(tr(dzd, 4 * H, nullptr, Rd, 4 * H, bw.BT + ke, Kt, grads->lstm2_b, bw.L + (size_t)Re * K4, K4));
-        HIP_TRY(tr(w.O1, H, nullptr, Re, H, bw.AT, Kt));
-        HIP_TRY(tr(w.O1 + (size_t)Tv * NH, H, live_rows, Rd, H, bw.AT + ke, Kt));
-        HIP_TRY(mm(bw.AT, Kt, bw.BT, Kt, grads->lstm2_W, 4 * H, H, 4 * H, Kt, 1));
-        HIP_TRY(tr(p->Wemb, E, live_rows ? w.prevp : w.prev, Rd, E, bw.AT, Kd));                    // Wemb [V, E] rows of the previous words
-        HIP_TRY(mm(bw.AT, Kd, bw.BT + ke, Kt, grads->lstm2_W + (size_t)H * 4 * H, 4 * H, E, 4 * H, Kd, 1));
-        HIP_TRY(tr(w.H2, H, nullptr, Re, H, bw.AT, Kt));
-        HIP_TRY(tr(w.H2 + (size_t)Tv * NH, H, live_rows, Rd, H, bw.AT + ke, Kt));
-        HIP_TRY(mm(bw.AT, Kt, bw.BT, Kt, grads->lstm2_W + (size_t)(H + E) * 4 * H, 4 * H, H, 4 * H, Kt, 1));
-    } else if (!live_rows) {
-        TnArgs a{w.O1, nullptr, H, w.dZ2, 4 * H, grads->lstm2_W, 4 * H, T * N, H, 4 * H, 1};
-        HIP_TRY(launch_gemm_tn(a, sd));
-        TnArgs b{p->Wemb, w.prev, E, w.dZ2 + (size_t)Tv * 4 * NH, 4 * H, grads->lstm2_W + (size_t)H * 4 * H, 4 * H, Tc * N, E,
-                 4 * H, 1};
-        b.gather_rows = V;                                  // Wemb [V, E]
-        HIP_TRY(launch_gemm_tn(b, sd));
-        TnArgs e{w.H2, nullptr, H, w.dZ2, 4 * H, grads->lstm2_W + (size_t)(H + E) * 4 * H, 4 * H, T * N, H, 4 * H, 1};
-        e.colsum = grads->lstm2_b;
-        HIP_TRY(launch_gemm_tn(e, sd));
-    } else {
-        // Live rows: behind its first <eos> a row's dZ2 is an exact zero at every later step (zero upstream gradient, zero carried
-        // dh / dc), so the weight gradients are reduced over the Tv encode steps (every row) plus the LIVE decode rows -- their
-        // dZ2 rows as a packed copy, the matching activation rows gathered through the same list.
-        const int R = n_live;
-        TnArgs a0{w.O1, nullptr, H, w.dZ2, 4 * H, grads->lstm2_W, 4 * H, Tv * N, H, 4 * H, 1};
-        HIP_TRY(launch_gemm_tn(a0, sd));
-        TnArgs a1{w.O1 + (size_t)Tv * NH, live_rows, H, w.dZ2p, 4 * H, grads->lstm2_W, 4 * H, R, H, 4 * H, 1};
-        a1.gather_rows = Tc * N;
-        HIP_TRY(launch_gemm_tn(a1, sd));
-        TnArgs b{p->Wemb, w.prevp, E, w.dZ2p, 4 * H, grads->lstm2_W + (size_t)H * 4 * H, 4 * H, R, E, 4 * H, 1};
-        b.gather_rows = V;                                  // Wemb [V, E]
-        HIP_TRY(launch_gemm_tn(b, sd));
-        TnArgs e0{w.H2, nullptr, H, w.dZ2, 4 * H, grads->lstm2_W + (size_t)(H + E) * 4 * H, 4 * H, Tv * N, H, 4 * H, 1};
-        e0.colsum = grads->lstm2_b;
-        HIP_TRY(launch_gemm_tn(e0, sd));
-        TnArgs e1{w.H2 + (size_t)Tv * NH, live_rows, H, w.dZ2p, 4 * H, grads->lstm2_W + (size_t)(H + E) * 4 * H, 4 * H, R, H, 4 * H, 1};
-        e1.gather_rows = Tc * N;
-        e1.colsum = grads->lstm2_b;
-        HIP_TRY(launch_gemm_tn(e1, sd));
-    }
-    return S2VT_OK;
-    };
-    l2_deferred = gate1 && do_rest && sd != st;
-    if (!l2_deferred) { const int rc = l2_weight_grads(); if (rc != S2VT_OK) return rc; }
-    else l2_grads_fn = l2_weight_grads;
-    }
-    if (!do_rest) return S2VT_OK;
-    // d[out1 ; embed] for every step at once -- with live rows: the encode steps, then the live decode rows (from the packed dZ2
-    // of the LSTM2 phase), scattered into the zeroed decode part
-    if (bf16) {
-        const int Re = Tv * N, Rd = live_rows ? n_live : Tc * N;
-        if (!do_l2) {                                        // (phase 4 alone: the row form phase 3 made in its fused cast, again)
-            HIP_TRY(rows(w.dZ2, 4 * H, nullptr, Re, 4 * H, bw.L, K4));
-            HIP_TRY(rows(live_rows ? w.dZ2p : w.dZ2 + (size_t)Tv * 4 * NH, 4 * H, nullptr, Rd, 4 * H, bw.L + (size_t)Re * K4, K4));
+        // Live rows: the packed copies of the live dZ2 rows / previous words are read on BOTH streams (weight gradients on the side
+        // stream, dX2 and the embedding scatter on the caller's), so they are made on the caller's stream, ahead of the fork
+        if (live_rows) {
+            HIP_TRY(launch_gather_rows(w.dZ2 + (size_t)Tv * 4 * NH, 4 * H, live_rows, n_live, 4 * H, w.dZ2p, 4 * H, st));
+            HIP_TRY(launch_gather_i32(w.prev, live_rows, n_live, w.prevp, st));
         }
-        HIP_TRY(rows(p->lstm2_W, 4 * H, nullptr, H + E, 4 * H, bw.W, K4));
-        if (!live_rows) {
-            HIP_TRY(mm(bw.L, K4, bw.W, K4, w.dX2, H + E, T * N, H + E, K4, 0));
-        } else {
-            HIP_TRY(mm(bw.L, K4, bw.W, K4, w.dX2, H + E, Re, H + E, K4, 0));
-            HIP_TRY(mm(bw.L + (size_t)Re * K4, K4, bw.W, K4, w.dX2p, H + E, Rd, H + E, K4, 0));
-            float* const dec = w.dX2 + (size_t)Tv * N * (H + E);
-            ZeroList z;
-            z.add(dec, (size_t)Tc * N * (H + E) * 4);
-            HIP_TRY(launch_zero_regions(z, st));
-            HIP_TRY(launch_scatter_rows(w.dX2p, H + E, live_rows, n_live, H + E, dec, H + E, st));
-        }
-    } else if (!live_rows) {
-        HIP_TRY(nn_bwd_slabs(w.dZ2, 4 * H, p->lstm2_W, 4 * H, w.dX2, H + E, T * N, H + E, 4 * H, w.dXs, st, w.dXs_floats));
-    } else {
-        HIP_TRY(nn_bwd_slabs(w.dZ2, 4 * H, p->lstm2_W, 4 * H, w.dX2, H + E, Tv * N, H + E, 4 * H, w.dXs, st, w.dXs_floats));
-        HIP_TRY(nn_bwd_slabs(w.dZ2p, 4 * H, p->lstm2_W, 4 * H, w.dX2p, H + E, n_live, H + E, 4 * H, w.dXs, st, w.dXs_floats));
-        float* const dec = w.dX2 + (size_t)Tv * N * (H + E);
-        ZeroList z;
-        z.add(dec, (size_t)Tc * N * (H + E) * 4);
-        HIP_TRY(launch_zero_regions(z, st));
-        HIP_TRY(launch_scatter_rows(w.dX2p, H + E, live_rows, n_live, H + E, dec, H + E, st));
+        // dZ2 is complete: LSTM2's weight gradients go to the side stream, beside dX2 and LSTM1's recurrence (mode 2: beside LSTM1's
+        // recurrence only -- launched below once that grid is resident; dX2 keeps the chip to itself)
+        if (sd != st) HIP_TRY(fork_to(st, sd, ss.ev[1]));
+        if (!l2_deferred) HIP_TRY(x.l2_grads());
     }
-    // ---- LSTM1 back through time, on the B per-video rows: the gradient w.r.t. its dropped output is
-    // first reduced over the rep sample rows of each video (with their dropout masks)
-    const size_t BH = (size_t)B * H;
-    HIP_TRY(launch_reduce_dropout(w.dX2, H + E, w.dH1, T, B, N, H, keep, seed, 256u, video_id, sample_id, st));
-    {
-        BwdScratch sc{w.slab, w.dc, w.bimg, w.bex, w.bsync};
+    if (do_rest) {
+        HIP_TRY(bf16 ? x.dx2_bf16(!do_l2) : x.dx2_fp32());
+        // ---- LSTM1 back through time, on the B per-video rows: the gradient w.r.t. its dropped output is
+        // first reduced over the rep sample rows of each video (with their dropout masks)
+        HIP_TRY(launch_reduce_dropout(w.dX2, H + E, w.dH1, T, B, N, H, keep, seed, 256u, video_id, sample_id, st));
         if (l2_deferred) chain_gate_arm(&gate);
-        const hipError_t re = lstm_recurrence_bwd(p->lstm1_W, E, w.G1, w.C1, w.dH1, BH, H, 0, w.dZ1, B, H, T, 1.0f, seed, 0u, nullptr, nullptr, sc, -1, st);
+        const hipError_t re = lstm_recurrence_bwd(p->lstm1_W, E, w.G1, w.C1, w.dH1, (size_t)B * H, H, 0, w.dZ1, B, H, T, 1.0f, seed, 0u, nullptr, nullptr, sc, -1, st);
         chain_gate_arm(nullptr);
         HIP_TRY(re);
-        if (l2_deferred) {                                   // LSTM2's three weight-gradient contractions, beside LSTM1's recurrence (they read dZ2: final since ev[1])
-            const int rc = l2_grads_fn();
-            if (rc != S2VT_OK) return rc;
-        }
-    }
-    // (split mode: LSTM1's contractions -- B rows, not N: dX1 [Tv B, E], the weight gradients over (Tv + Tc) B rows -- stay on fp32
-    // MFMA, below)
-    if (bf16 && !split) {
-        // dZ1 once: transposed over [encode steps | decode steps] (+ lstm1_b), and the encode rows by rows (dX1's A)
-        const int Re = Tv * B, Rd = Tc * B, ke = bf16_pad(Re), K1 = ke + bf16_pad(Rd);
-        HIP_TRY(tr(w.dZ1, 4 * H, nullptr, Re, 4 * H, bw.BT, K1, grads->lstm1_b, bw.L, K4));
-        HIP_TRY(tr(w.dZ1 + (size_t)Re * 4 * H, 4 * H, nullptr, Rd, 4 * H, bw.BT + ke, K1, grads->lstm1_b));
-        HIP_TRY(rows(p->lstm1_W, 4 * H, nullptr, E, 4 * H, bw.W, K4));
-        HIP_TRY(mm(bw.L, K4, bw.W, K4, w.dX1, E, Re, E, K4, 0));
-        HIP_TRY(tr(w.emb, E, w.encidx, Re, E, bw.AT, ke));                                          // the frame embedding, time-major
-        HIP_TRY(mm(bw.AT, ke, bw.BT, K1, grads->lstm1_W, 4 * H, E, 4 * H, ke, 1));
-        HIP_TRY(tr(w.H1, H, nullptr, Re, H, bw.AT, K1));
-        HIP_TRY(tr(w.H1 + (size_t)Re * H, H, nullptr, Rd, H, bw.AT + ke, K1));
-        HIP_TRY(mm(bw.AT, K1, bw.BT, K1, grads->lstm1_W + (size_t)E * 4 * H, 4 * H, H, 4 * H, K1, 1));
-        if (live_rows) HIP_TRY(launch_scatter_add_rows(w.dX2p + H, H + E, w.prevp, n_live, E, grads->Wemb, E, st));
-        else HIP_TRY(launch_scatter_add_rows(w.dX2 + (size_t)Tv * N * (H + E) + H, H + E, w.prev, Tc * N, E, grads->Wemb, E, st));
-        HIP_TRY(tr(video, D, w.encidx, Re, D, bw.AT, ke));
-        HIP_TRY(tr(w.dX1, E, nullptr, Re, E, bw.BT, ke, grads->encode_image_b));
-        HIP_TRY(mm(bw.AT, ke, bw.BT, ke, grads->encode_image_W, E, D, E, ke, 1));
-        return S2VT_OK;
-    }
-    HIP_TRY(nn_bwd_slabs(w.dZ1, 4 * H, p->lstm1_W, 4 * H, w.dX1, E, Tv * B, E, 4 * H, w.dXs, st, w.dXs_floats));
-
-    // ---- remaining weight gradients: one contraction over all unrolled steps per weight block
-    {
-        TnArgs f{w.emb, w.encidx, E, w.dZ1, 4 * H, grads->lstm1_W, 4 * H, Tv * B, E, 4 * H, 1};
-        f.gather_rows = Tv * B;
-        HIP_TRY(launch_gemm_tn(f, st));
-        TnArgs g{w.H1, nullptr, H, w.dZ1, 4 * H, grads->lstm1_W + (size_t)E * 4 * H, 4 * H, T * B, H, 4 * H, 1};
-        g.colsum = grads->lstm1_b;
-        HIP_TRY(launch_gemm_tn(g, st));
-        // embedding rows (gradient of tf.nn.embedding_lookup): scatter-add of the embed slice of dX2
-        if (live_rows) HIP_TRY(launch_scatter_add_rows(w.dX2p + H, H + E, w.prevp, n_live, E, grads->Wemb, E, st));
-        else HIP_TRY(launch_scatter_add_rows(w.dX2 + (size_t)Tv * N * (H + E) + H, H + E, w.prev, Tc * N, E, grads->Wemb, E, st));
-        // frame embedding
-        TnArgs h{video, w.encidx, D, w.dX1, E, grads->encode_image_W, E, Tv * B, D, E, 1};
-        h.gather_rows = Tv * B;
-        h.colsum = grads->encode_image_b;
-        HIP_TRY(launch_gemm_tn(h, st));
+        if (l2_deferred) HIP_TRY(x.l2_grads());            // beside LSTM1's recurrence (they read dZ2: final since ev[1])
+        HIP_TRY(bf16 && !split ? x.lstm1_tail_bf16() : x.lstm1_tail_fp32());
     }
     if (sd != st) HIP_TRY(fork_to(sd, st, ss.ev[2]));        // join: the caller's stream waits for the side stream's gradients
     return S2VT_OK;

@@ -242,20 +242,33 @@ def _small(oracle, B=4, rep=3, seed=3):
     return d, p, video, cap, vid, sid, N
 
 
-def test_bf16_phases_give_the_bits_of_the_whole_pass(gpu, oracle):
+@pytest.mark.parametrize("with_live", [False, True])
+def test_bf16_phases_give_the_bits_of_the_whole_pass(gpu, oracle, with_live):
+    """with_live: the live-row list of the captions' masks -- the transposed products over the packed live rows, and a lone phase 4
+    that reads the packed dZ2 rows phase 3 left in the workspace."""
     import torch
+    from s2vt_amd import hostglue
     d, p, video, cap, vid, sid, N = _small(oracle)
     dims = gpu.make_dims(d.dim_image, d.n_words, d.word_dim, d.lstm_dim, d.n_video_lstm_step, d.n_caption_lstm_step)
     dp_ = {k: _dev(v) for k, v in p.items()}
     params = gpu.make_params(dp_)
-    coef = _dev(np.random.default_rng(2).standard_normal(N * d.n_caption_lstm_step).astype(np.float32))
+    steps, live, ix = d.n_caption_lstm_step, None, slice(None)
+    if with_live:
+        mask = hostglue.masks_from_ids(cap)
+        steps = int(np.flatnonzero(mask.any(0))[-1]) + 1
+        live = _dev(np.flatnonzero(mask[:, :steps].T.reshape(-1) != 0).astype(np.int32))      # (as model.live_rows lists them)
+        assert 0 < live.numel() < 0.9 * steps * N
+        ix = live.long()
+    coef = _dev(np.random.default_rng(2).standard_normal(N * d.n_caption_lstm_step).astype(np.float32))[:steps * N][ix].contiguous()
+    tgt = _dev(cap).t().contiguous().view(-1)[:steps * N][ix].contiguous()
 
     def run(phases):
-        logits, ws = gpu.teacher_forced_fwd(dims, params, _dev(video), _dev(cap), N, 0.9, 99, _dev(vid), _dev(sid))
-        gpu.softmax_nll_fwd_bwd(logits, _dev(cap).t().contiguous().view(-1), coef, 0.0)
+        logits, ws = gpu.teacher_forced_fwd(dims, params, _dev(video), _dev(cap), N, 0.9, 99, _dev(vid), _dev(sid), steps=steps, live=live)
+        gpu.softmax_nll_fwd_bwd(logits, tgt, coef, 0.0)
         g = {k: torch.zeros_like(v) for k, v in dp_.items()}
         for ph in phases:
-            gpu.bptt_bwd(dims, params, gpu.make_params(g), _dev(video), N, logits, ws, 0.9, 99, _dev(vid), _dev(sid), phase=ph, precision="bf16")
+            gpu.bptt_bwd(dims, params, gpu.make_params(g), _dev(video), N, logits, ws, 0.9, 99, _dev(vid), _dev(sid), phase=ph, steps=steps, live=live,
+                         precision="bf16")
         torch.cuda.synchronize()
         return g
     whole = run([0])
