@@ -559,6 +559,17 @@ int s2vt_attn_decode_greedy(const s2vt_dims* d, const s2vt_attn_params* p, const
 size_t s2vt_attn_sample_workspace_bytes(const s2vt_dims* d, int32_t B, int32_t K, int32_t with_greedy);
 int s2vt_attn_sample(const s2vt_dims* d, const s2vt_attn_params* p, const float* video, int32_t B, int32_t K, int32_t with_greedy, uint64_t seed,
                      int32_t video_base, int32_t* ids_out, int32_t* greedy_out, void* workspace, size_t workspace_bytes, s2vt_stream stream);
+/* s2vt_attn_sample with flags (bit 0 = S2VT_SAMPLE_STOP_AT_EOS; any other bit: S2VT_E_BADARG; flags == 0 is s2vt_attn_sample).  Same
+ * argument checks, same workspace (s2vt_attn_sample_workspace_bytes serves both), K = 0 with with_greedy allowed.
+ * S2VT_SAMPLE_STOP_AT_EOS (opt-in; NOT what the reference's samplers do, which run all Tc steps for every row): a row leaves the decode
+ * loop once it has picked <eos> = 0 -- every later step's launches (query projection, attention step, LSTM3, output layer, vocabulary
+ * pick) cover the rows still sampling only, through a compact row list and its length kept on the device; no host round trip.
+ * Contract: for every row of ids_out / greedy_out, the ids up to and including the row's first <eos> are bit-identical to
+ * s2vt_attn_sample's, and the ids behind it are 0.  Every element of both arrays is written.  Those leading ids are the only positions
+ * the objective's mask keeps, so the REINFORCE update is the same update. */
+int s2vt_attn_sample_ex(const s2vt_dims* d, const s2vt_attn_params* p, const float* video, int32_t B, int32_t K, int32_t with_greedy, uint64_t seed,
+                        int32_t video_base, int32_t flags, int32_t* ids_out, int32_t* greedy_out, void* workspace, size_t workspace_bytes,
+                        s2vt_stream stream);
 /* Workspace of the three calls below for N = n_video * samples rows over n_video image blocks (0 on bad arguments). */
 size_t s2vt_attn_rows_workspace_bytes(const s2vt_dims* d, int32_t n_video, int32_t samples);
 /* s2vt_attn_teacher_forced_fwd on N rows that share n_video image blocks: caption [N, Tc], video [n_video, Tv, D], video_id / sample_id

@@ -125,6 +125,7 @@ SIGNATURES = {
     "s2vt_attention_bwd_rows": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "s2vt_attn_sample_workspace_bytes": (_sz, [_DP, _i32, _i32, _i32]),
     "s2vt_attn_sample": (C.c_int, [_DP, _AP, _vp, _i32, _i32, _i32, _u64, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "s2vt_attn_sample_ex": (C.c_int, [_DP, _AP, _vp, _i32, _i32, _i32, _u64, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
     "s2vt_attn_rows_workspace_bytes": (_sz, [_DP, _i32, _i32]),
     "s2vt_attn_teacher_forced_fwd_rows": (C.c_int, [_DP, _AP, _vp, _i32, _i32, _vp, _i32, _f32, _u64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "s2vt_attn_step_scalars_rows": (C.c_int, [_vp, _vp, _i64, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _DP, _i32, _i32, _vp, _sz, _vp]),

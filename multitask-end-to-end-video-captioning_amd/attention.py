@@ -206,19 +206,22 @@ class Attention_Caption_Generator:
     def active_steps(self, mask):
         return self._active_steps(mask, self.n_caption_lstm_steps)
 
-    def sample(self, video, K=0, with_greedy=True, seed=None, video_base=0):
+    def sample(self, video, K=0, with_greedy=True, seed=None, video_base=0, stop_at_eos=False):
         """K multinomial captions per video (+ the greedy caption): (sampled [K*B, Tc], greedy [B, Tc]) int32 device tensors, sample-major
         rows (row s * B + j is sample s of video j) -- the contract of Video_Caption_Generator.sample.  One prologue for the B videos, the
         decode loop on (K + greedy) * B rows that share the B image blocks, Gumbel-max over Philox with counters (video_base + j, s, step):
         no host round trip per step, no dropout, no <bos> (the sampler graphs of original_attention.py:155-251 with tf.multinomial in
         place of the argmax, as reinforcement_multisampling_tf_s2vt.py:294-339 does for its model).
-        K = 0: (None, greedy ids [B, Tc]) -- the greedy sampler in the shape train_common.greedy_eval expects."""
+        K = 0: (None, greedy ids [B, Tc]) -- the greedy sampler in the shape train_common.greedy_eval expects.
+        stop_at_eos (opt-in): rows that have emitted <eos> leave the decode loop (ids behind it read 0; the reference keeps
+        sampling and masks afterwards) -- ids up to and including the first <eos> are bit-identical, so the update is the same."""
         video = self._dev(video, torch.float32)
-        if K == 0:
+        if K == 0 and not stop_at_eos:
             assert with_greedy
             ids, _ = ops.attn_decode_greedy(self.dims, self.store.params, video, video_base)
             return None, ids
-        return ops.attn_sample(self.dims, self.store.params, video, int(K), self.sample_seed if seed is None else seed, video_base, with_greedy)
+        return ops.attn_sample(self.dims, self.store.params, video, int(K), self.sample_seed if seed is None else seed, video_base, with_greedy,
+                               stop_at_eos)
 
     def _pg_forward(self, video, cap, keep, steps, video_base, share):
         """The teacher-forced unroll of the N = S * B sample rows: on the B shared image blocks, or (share False) through the plain entry

@@ -267,6 +267,13 @@ int s2vt_frame_embed_fwd(const s2vt_dims* d, const s2vt_params* p, const float* 
 
 namespace s2vt_api {
 
+hipError_t launch_live_rows(const unsigned long long* picked, int stride, const int32_t* prev, const int32_t* nprev, int32_t* next,
+                            int32_t* nnext, int R, hipStream_t st)
+{
+    hipLaunchKernelGGL(live_rows_kernel, dim3(1), dim3(256), 0, st, picked, stride, prev, nprev, next, nnext, R);
+    return hipGetLastError();
+}
+
 // Workspace of one sampler pass.  Everything up to `split` depends on B only (the encode half); the rest on
 // the number of decode rows R.
 size_t carve_sample(Carver& c, const s2vt_dims* d, int B, int R, SampleWs* w)
@@ -527,9 +534,8 @@ int sample_decode(const s2vt_dims* d, const s2vt_params* p, int B, int K, int wi
             static const int lk = [] { const char* e = getenv("S2VT_EOS_LSTM_CFG"); return e ? atoi(e) : 4; }();     // kLstm[4] = gw32x16u
             static const int pk = [] { const char* e = getenv("S2VT_EOS_PICK_CFG"); return e ? atoi(e) : -1; }();
             lcfg = R > 64 ? lk : -1; pcfg = pk;
-            hipLaunchKernelGGL(live_rows_kernel, dim3(1), dim3(256), 0, st, t == 0 ? nullptr : w.packed + (size_t)(t - 1) * R * kPickStride, kPickStride,
-                               w.live[(t + 1) & 1], w.nlive + (t > 0 ? t - 1 : 0), w.live[t & 1], w.nlive + t, R);
-            HIP_TRY(hipGetLastError());
+            HIP_TRY(launch_live_rows(t == 0 ? nullptr : w.packed + (size_t)(t - 1) * R * kPickStride, kPickStride, w.live[(t + 1) & 1],
+                                     w.nlive + (t > 0 ? t - 1 : 0), w.live[t & 1], w.nlive + t, R, st));
             omap = w.live[t & 1]; mdev = w.nlive + t;
         }
         ASeg s2[2] = {t == 0 ? make_seg(p->Wemb, E, E, H, 0, w.bos)

@@ -125,7 +125,8 @@ inline hipError_t pick_call(const float* A, int lda, const float* W, const float
 }
 
 inline hipError_t store_call(const ASeg* segs, int nseg, const float* W, int ldw, const float* bias, float* C, int ldc, int M,
-                      int N, int act, int cfg, hipStream_t st, const float* cinit = nullptr, int ldcinit = 0, bool w_transposed = false)
+                      int N, int act, int cfg, hipStream_t st, const float* cinit = nullptr, int ldcinit = 0, bool w_transposed = false,
+                      const int* omap = nullptr, const int* m_dev = nullptr)
 {
     GemmArgs a;
     std::memset(&a, 0, sizeof(a));
@@ -134,6 +135,7 @@ inline hipError_t store_call(const ASeg* segs, int nseg, const float* W, int ldw
     a.W = W; a.ldw = ldw; a.M = M; a.N = N; a.gstride = 0; a.bias = bias;
     a.cinit = cinit; a.ldcinit = ldcinit;
     a.C = C; a.ldc = ldc; a.act = act;
+    a.omap = omap; a.m_dev = m_dev;                                          // live-row launch: row omap[m] of every operand and of C
     return launch_gemm(a, w_transposed ? EPI_STORE_NT : (int)EPI_STORE, cfg, st);
 }
 
@@ -222,6 +224,10 @@ int sample_encode(const s2vt_dims* d, const s2vt_params* p, const float* video, 
 int sample_decode(const s2vt_dims* d, const s2vt_params* p, int B, int K, int with_greedy, uint64_t seed, int video_base,
                   int32_t* ids_out, const SampleWs& w, s2vt_stream stream, int stop_at_eos = 0);
 bool sampler_params_ok(const s2vt_params* p);
+// stop-at-<eos> mode of the samplers (api.hip): next / *nnext = the rows of prev[0 .. *nprev) whose packed pick (picked[row * stride]) is
+// not <eos>, order preserved; picked == NULL (step 0): every row of R.  One workgroup.
+hipError_t launch_live_rows(const unsigned long long* picked, int stride, const int32_t* prev, const int32_t* nprev, int32_t* next,
+                            int32_t* nnext, int R, hipStream_t st);
 
 inline bool dims_ok(const s2vt_dims* d)
 {

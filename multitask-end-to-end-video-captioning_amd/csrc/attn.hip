@@ -42,7 +42,10 @@ constexpr int kAttnChunkRows = 32;       // frames whose tanh rows are resident 
 // nothing is copied per hypothesis; the query row hWa[b], alpha[t][b] (row stride B) and ctx[b] stay per hypothesis.  The index
 // is device data: clamped into [0, n_video).  ROWMAP = false is the kernel as it always was (sv == b, stride B): the same
 // arithmetic in the same order -- the chains above are the contract.
-template <bool ROWMAP>
+// LIVE (the early-exit sampler; with ROWMAP): the grid is still B workgroups, but only the first n = *n_live of them have a row -- workgroup
+// i >= n returns before any barrier, workgroup i < n is row b = live[i] (clamped into [0, B)) and does for it exactly what the ROWMAP
+// form does for row b.  The count is device data the host never sees.
+template <bool ROWMAP, bool LIVE = false>
 __global__ __launch_bounds__(256) void attn_fwd_kernel(const AttnFwdArgs a)
 {
     extern __shared__ float sm[];
@@ -52,7 +55,13 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const AttnFwdArgs a)
     float* ev = wl + ldT;                            // [64] scores
     float* xv = ev + kAttnMaxTv;                     // [64] exp(e), then alpha
     float* sc = xv + kAttnMaxTv;                     // [4] scalars
-    const int b = blockIdx.x, tid = threadIdx.x;
+    const int tid = threadIdx.x;
+    int b = blockIdx.x;
+    if constexpr (LIVE) {
+        if (b >= *a.n_live) return;
+        b = a.live[b];
+        b = b < 0 ? 0 : (b >= B ? B - 1 : b);
+    }
     int sv = b, Bs = B;                              // image block of this row and the blocks per frame
     if constexpr (ROWMAP) {
         Bs = a.n_video;
@@ -428,17 +437,21 @@ hipError_t launch_attn_fwd(const AttnFwdArgs& a0, hipStream_t st)
     a.vec = (!(a.H & 3) && al16(a.P) && al16(a.Vt) && al16(a.ctx) && (!a.hWa || al16(a.hWa))) ? 1 : 0;
     const size_t lds = ((size_t)(a.RC + 1) * a.ldT + 2 * kAttnMaxTv + 4) * sizeof(float);
     if (a.row_video && a.n_video <= 0) return hipErrorInvalidValue;
+    if ((a.live != nullptr) != (a.n_live != nullptr) || (a.live && !a.row_video)) return hipErrorInvalidValue;    // live rows: the row -> video form only
     static std::once_flag once;
     static hipError_t attr_err = hipSuccess;
     std::call_once(once, [] {
         attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (attr_err == hipSuccess)
             attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (attr_err == hipSuccess)
+            attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_kernel<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     });
     if (attr_err != hipSuccess) return attr_err;
     if (lds > 160 * 1024) return hipErrorInvalidValue;
     const auto launch = [&] {
-        if (a.row_video) hipLaunchKernelGGL(attn_fwd_kernel<true>, dim3(a.B), dim3(256), lds, st, a);
+        if (a.live) hipLaunchKernelGGL((attn_fwd_kernel<true, true>), dim3(a.B), dim3(256), lds, st, a);
+        else if (a.row_video) hipLaunchKernelGGL(attn_fwd_kernel<true>, dim3(a.B), dim3(256), lds, st, a);
         else hipLaunchKernelGGL(attn_fwd_kernel<false>, dim3(a.B), dim3(256), lds, st, a);
     };
     // launch profiler class 7: attention forward (flops = the score and context chains, 2 x 2 Tv B H; HBM-bound by P and V)
@@ -452,7 +465,7 @@ hipError_t launch_attn_fwd(const AttnFwdArgs& a0, hipStream_t st)
     (void)hipEventRecord(e0, st);
     launch();
     (void)hipEventRecord(e1, st);
-    prof_record(7, 0, a.row_video ? "attn_fwd(row->video)" : "attn_fwd(score+softmax+ctx)", 4.0 * a.Tv * a.B * (double)a.H, e0, e1);
+    prof_record(7, 0, a.live ? "attn_fwd(row->video, live rows)" : a.row_video ? "attn_fwd(row->video)" : "attn_fwd(score+softmax+ctx)", 4.0 * a.Tv * a.B * (double)a.H, e0, e1);
     return hipGetLastError();
 }
 

@@ -328,6 +328,8 @@ struct AttnSampleWs {
     float *c[2], *h[2];                // LSTM3 state [R][H]: step t reads slot t & 1 and writes the other
     float *hWa, *alpha, *ctx, *Y;      // [R][H], [Tv][R], [R][H], [R][H]
     unsigned long long* packed;        // picks [Tc][R][kPickStride]
+    int32_t* live[2];                  // stop-at-<eos> mode: the rows still sampling at the current / previous step (ascending) [R] ...
+    int32_t* nlive;                    // ... and their count per step [Tc], device-resident
 };
 
 size_t carve_attn_sample(Carver& c, const s2vt_dims* d, int B, int R, AttnSampleWs* out)
@@ -339,6 +341,8 @@ size_t carve_attn_sample(Carver& c, const s2vt_dims* d, int B, int R, AttnSample
     for (int i = 0; i < 2; ++i) { w.c[i] = c.take<float>(r * H); w.h[i] = c.take<float>(r * H); }
     w.hWa = c.take<float>(r * H); w.alpha = c.take<float>(Tv * r); w.ctx = c.take<float>(r * H); w.Y = c.take<float>(r * H);
     w.packed = c.take<unsigned long long>(Tc * r * kPickStride);
+    for (int i = 0; i < 2; ++i) w.live[i] = c.take<int32_t>(r);        // (at the end: the regions above lie where they always did)
+    w.nlive = c.take<int32_t>(Tc);
     if (out) *out = w;
     return c.off;
 }
@@ -360,13 +364,15 @@ __global__ void attn_sample_rows_kernel(int32_t* vid, int32_t* sid, int32_t* row
     rowvid[i] = i % B;
 }
 
-// ids[m][t] for rows m0 .. m0 + n - 1 of the R packed rows
+// ids[m][t] for rows m0 .. m0 + n - 1 of the R packed rows.  A word that was never written (stop-at-<eos> mode: the row had left the
+// loop; a pick always leaves a non-zero word) reads as <eos> = 0.
 __global__ void attn_unpack_rows_kernel(const unsigned long long* packed, int32_t* ids, int R, int m0, int n, int T, int stride)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n * T) return;
     const int m = i / T, t = i % T;
-    ids[i] = (int32_t)(~(uint32_t)packed[((size_t)t * R + m0 + m) * stride]);
+    const unsigned long long w = packed[((size_t)t * R + m0 + m) * stride];
+    ids[i] = w ? (int32_t)(~(uint32_t)w) : 0;
 }
 
 bool attn_beam_shape_ok(const s2vt_dims* d, int B, int beam)
@@ -786,8 +792,12 @@ size_t s2vt_attn_sample_workspace_bytes(const s2vt_dims* d, int32_t B, int32_t K
 // draws Gumbel-max noise from the Philox counters (video_base + j, s, step) for sample s >= 0 and takes the argmax for the greedy
 // block (sample id -1); the packed pick of step t-1 is the embedding gather index of step t.  No dropout, no <bos>, no host round
 // trip.  Per-step launches: the persistent recurrences (attn_chain*.hip) hold one image block per row and at most 64 rows.
-int s2vt_attn_sample(const s2vt_dims* d, const s2vt_attn_params* p, const float* video, int32_t B, int32_t K, int32_t with_greedy, uint64_t seed,
-                     int32_t video_base, int32_t* ids_out, int32_t* greedy_out, void* workspace, size_t workspace_bytes, s2vt_stream stream)
+// stop_at_eos (s2vt_attn_sample_ex): every step's five launches cover the rows still sampling only -- a compact list of rows and its
+// length, both on the device (live_rows_kernel on the picks of step t - 1); state stays where it is, indexed by the original row, so a
+// row's chains are those of the full launch (the tile does not enter a chain) and its ids up to its first <eos> the same bits.
+static int attn_sample_impl(const s2vt_dims* d, const s2vt_attn_params* p, const float* video, int32_t B, int32_t K, int32_t with_greedy,
+                            uint64_t seed, int32_t video_base, int stop_at_eos, int32_t* ids_out, int32_t* greedy_out, void* workspace,
+                            size_t workspace_bytes, s2vt_stream stream)
 {
     const int g = with_greedy ? 1 : 0;
     if (K < 0 || (K == 0 && !g) || !attn_rows_shape_ok(d, B, K + g) || !attn_params_ok(p) || !video || !workspace) return S2VT_E_BADARG;
@@ -815,31 +825,54 @@ int s2vt_attn_sample(const s2vt_dims* d, const s2vt_attn_params* p, const float*
     }
     NoiseIds none{nullptr, nullptr, 0};
     NoiseIds ids{w.vid, w.sid, seed};
+    // stop-at-<eos> mode: tiles for launches whose row count only the device knows -- row tiles small enough that the launch shrinks
+    // with the count (the reasoning of the S2VT sampler, api.hip sample_decode).  Dev knobs: S2VT_ATTN_EOS_STORE_CFG (the query and
+    // output-layer products; -1 = the cost model's tile, 64 rows at these widths), S2VT_ATTN_EOS_LSTM_CFG, S2VT_ATTN_EOS_PICK_CFG.
+    // Measured at R = 384, Tv = 5, mean length 6.8 (tools/bench_attn_rl.py --stop-at-eos, table in profiles/NOTES.md), ms per sampler
+    // call, 5.30 for the loop that never stops: these defaults 4.06 (the cost model's store tile is 64x32 there); cell step on the
+    // tile the full row count would get (96 rows) 4.69, on 16 / 48 / 64 rows 6.36 / 4.83 / 4.68; store 64x64 / 64x96 / 64x128
+    // 4.78 / 5.45 / 6.23; pick 32x96 / 64x64 / 64x128 instead of choose_pick's 64x96 4.25 / 4.18 / 4.33.
+    int scfg = -1, lcfg = -1, pcfg = -1;
+    if (stop_at_eos) {
+        static const int sk = [] { const char* e = getenv("S2VT_ATTN_EOS_STORE_CFG"); return e ? atoi(e) : -1; }();
+        static const int lk = [] { const char* e = getenv("S2VT_ATTN_EOS_LSTM_CFG"); return e ? atoi(e) : 4; }();     // kLstm[4] = gw32x16u
+        static const int pk = [] { const char* e = getenv("S2VT_ATTN_EOS_PICK_CFG"); return e ? atoi(e) : -1; }();
+        scfg = sk; lcfg = R > 64 ? lk : -1; pcfg = pk;
+    }
     for (int t = 0; t < Tc; ++t) {
         const float *c_prev = w.c[t & 1], *h_prev = w.h[t & 1];
         float *c_new = w.c[(t & 1) ^ 1], *h_new = w.h[(t & 1) ^ 1];
+        const unsigned long long* tok = t > 0 ? w.packed + (size_t)(t - 1) * R * kPickStride : nullptr;    // the word picked at step t-1 (:196-197)
+        const int* omap = nullptr;
+        const int* mdev = nullptr;
+        if (stop_at_eos) {
+            // a finished row's state stays in whichever slot it was last written to and is never read again; its later pick words stay zero
+            HIP_TRY(launch_live_rows(tok, kPickStride, w.live[(t + 1) & 1], w.nlive + (t > 0 ? t - 1 : 0), w.live[t & 1], w.nlive + t, R, st));
+            omap = w.live[t & 1]; mdev = w.nlive + t;
+        }
         if (t > 0) {       // the query is the clean h (no dropout in the samplers, :188,:235); step 0: the zero state
             ASeg sq = make_seg(h_prev, H, H, 0);
-            HIP_TRY(store_call(&sq, 1, p->embed_att_Wa, H, nullptr, w.hWa, H, R, H, 0, -1, st));
+            HIP_TRY(store_call(&sq, 1, p->embed_att_Wa, H, nullptr, w.hWa, H, R, H, 0, scfg, st, nullptr, 0, false, omap, mdev));
         }
         AttnFwdArgs a;
         std::memset(&a, 0, sizeof(a));
         a.hWa = t > 0 ? w.hWa : nullptr; a.P = w.P; a.Vt = w.Vt; a.w = p->embed_att_w; a.alpha = w.alpha; a.ctx = w.ctx;
         a.Tv = Tv; a.B = R; a.H = H; a.row_video = w.rowvid; a.n_video = B;
+        a.live = omap; a.n_live = mdev;
         HIP_TRY(launch_attn_fwd(a, st));
-        const unsigned long long* tok = t > 0 ? w.packed + (size_t)(t - 1) * R * kPickStride : nullptr;    // the word picked at step t-1 (:196-197)
         if (t == 0) {
             ASeg s3 = make_seg(w.ctx, H, H, 0);
-            HIP_TRY(lstm_call(&s3, 1, p->lstm3_W, p->lstm3_b, c_prev, 0, c_new, h_new, nullptr, nullptr, R, H, 1.0f, none, 0, -1, st));
+            HIP_TRY(lstm_call(&s3, 1, p->lstm3_W, p->lstm3_b, c_prev, 0, c_new, h_new, nullptr, nullptr, R, H, 1.0f, none, 0, lcfg, st, nullptr, 0, 0, omap, mdev));
             ASeg sy[2] = {make_seg(w.ctx, H, H, H), make_seg(h_new, H, H, 0)};
-            HIP_TRY(store_call(sy, 2, p->embed_nn_Wp, H, p->embed_nn_bp, w.Y, H, R, H, 1, -1, st));
+            HIP_TRY(store_call(sy, 2, p->embed_nn_Wp, H, p->embed_nn_bp, w.Y, H, R, H, 1, scfg, st, nullptr, 0, false, omap, mdev));
         } else {
             ASeg s3[3] = {make_seg(p->Wemb, H, H, H, 0, nullptr, tok, kPickStride), make_seg(h_prev, H, H, 2 * H), make_seg(w.ctx, H, H, 0)};
-            HIP_TRY(lstm_call(s3, 3, p->lstm3_W, p->lstm3_b, c_prev, 0, c_new, h_new, nullptr, nullptr, R, H, 1.0f, none, 0, -1, st));
+            HIP_TRY(lstm_call(s3, 3, p->lstm3_W, p->lstm3_b, c_prev, 0, c_new, h_new, nullptr, nullptr, R, H, 1.0f, none, 0, lcfg, st, nullptr, 0, 0, omap, mdev));
             ASeg sy[3] = {make_seg(p->Wemb, H, H, 2 * H, 0, nullptr, tok, kPickStride), make_seg(w.ctx, H, H, H), make_seg(h_new, H, H, 0)};
-            HIP_TRY(store_call(sy, 3, p->embed_nn_Wp, H, p->embed_nn_bp, w.Y, H, R, H, 1, -1, st));
+            HIP_TRY(store_call(sy, 3, p->embed_nn_Wp, H, p->embed_nn_bp, w.Y, H, R, H, 1, scfg, st, nullptr, 0, false, omap, mdev));
         }
-        HIP_TRY(pick_call(w.Y, H, p->embed_word_W, p->embed_word_b, R, H, V, ids, t, w.packed + (size_t)t * R * kPickStride, nullptr, -1, st, kPickStride));
+        HIP_TRY(pick_call(w.Y, H, p->embed_word_W, p->embed_word_b, R, H, V, ids, t, w.packed + (size_t)t * R * kPickStride, nullptr, pcfg, st, kPickStride,
+                          omap, mdev));
     }
     if (K > 0) {
         hipLaunchKernelGGL(attn_unpack_rows_kernel, dim3((K * B * Tc + 255) / 256), dim3(256), 0, st, w.packed, ids_out, R, 0, (int)(K * B), Tc, kPickStride);
@@ -850,6 +883,21 @@ int s2vt_attn_sample(const s2vt_dims* d, const s2vt_attn_params* p, const float*
         HIP_TRY(hipGetLastError());
     }
     return S2VT_OK;
+}
+
+int s2vt_attn_sample(const s2vt_dims* d, const s2vt_attn_params* p, const float* video, int32_t B, int32_t K, int32_t with_greedy, uint64_t seed,
+                     int32_t video_base, int32_t* ids_out, int32_t* greedy_out, void* workspace, size_t workspace_bytes, s2vt_stream stream)
+{
+    return attn_sample_impl(d, p, video, B, K, with_greedy, seed, video_base, 0, ids_out, greedy_out, workspace, workspace_bytes, stream);
+}
+
+int s2vt_attn_sample_ex(const s2vt_dims* d, const s2vt_attn_params* p, const float* video, int32_t B, int32_t K, int32_t with_greedy, uint64_t seed,
+                        int32_t video_base, int32_t flags, int32_t* ids_out, int32_t* greedy_out, void* workspace, size_t workspace_bytes,
+                        s2vt_stream stream)
+{
+    if (flags & ~S2VT_SAMPLE_STOP_AT_EOS) return S2VT_E_BADARG;
+    return attn_sample_impl(d, p, video, B, K, with_greedy, seed, video_base, flags & S2VT_SAMPLE_STOP_AT_EOS, ids_out, greedy_out, workspace,
+                            workspace_bytes, stream);
 }
 
 size_t s2vt_attn_beam_workspace_bytes(const s2vt_dims* d, int32_t B, int32_t beam)

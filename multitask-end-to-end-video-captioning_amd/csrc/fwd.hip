@@ -18,7 +18,7 @@ struct CfgEntry {
     const char* name;
     KernelFn vec, scalar;   // 16-byte vector loads / scalar loads (unaligned or odd shapes)
     int BM, CG, NT, lds_bytes;
-    KernelFn vec_om, scalar_om;   // the live-row forms (GemmArgs::omap / m_dev): cell-step and pick tiles only
+    KernelFn vec_om, scalar_om;   // the live-row forms (GemmArgs::omap / m_dev): cell-step, pick and register-staged store tiles (not W^T, not LDS-DMA store)
     int fallback;                 // LDS-DMA entries (vector path only): the table index of the register-staged tile that takes the launch
                                   // when the operands are not 16-byte aligned (-1: this entry has a scalar form of its own)
 };
@@ -28,7 +28,7 @@ constexpr CfgEntry make_entry(const char* name)
 {
     using C = GemmCfg<WM, WN, TM, TN, NG, EPI, true, BKT, PW, BT>;
     KernelFn om = nullptr, om_s = nullptr;
-    if constexpr (EPI == EPI_LSTM || EPI == EPI_LSTM_GW || EPI == EPI_PICK) {
+    if constexpr (EPI == EPI_LSTM || EPI == EPI_LSTM_GW || EPI == EPI_PICK || (EPI == EPI_STORE && !BT)) {
         om = gemm_kernel<WM, WN, TM, TN, NG, EPI, true, BKT, PW, BT, true>;
         om_s = gemm_kernel<WM, WN, TM, TN, NG, EPI, false, BKT, PW, BT, true>;
     }
@@ -352,6 +352,7 @@ hipError_t launch_gemm(const GemmArgs& a, int epi, int cfg, hipStream_t st)
         (long)ceil_div(a.M, t[cfg].BM) * ceil_div(a.N, t[cfg].CG) >= 512)
         cfg = cfg == 2 ? 8 : 9;
     if (t[cfg].fallback >= 0 && !can_vec(a, epi == EPI_STORE_NT)) cfg = t[cfg].fallback;       // LDS-DMA tiles: aligned operands only
+    if ((a.omap || a.m_dev) && !t[cfg].vec_om && t[cfg].fallback >= 0) cfg = t[cfg].fallback;  // ... and (store) no live-row form: their register-staged twin
     const CfgEntry& e = t[cfg];
     if (a.M <= 0 || a.N <= 0) return hipSuccess;
     const int mt = ceil_div(a.M, e.BM), nt = ceil_div(a.N, e.CG);

@@ -85,8 +85,8 @@ struct GemmArgs {
                                 // 16 rows per line made ~4000 serialized atomics per line at M = 64 (15-18 us of a 48 us launch)
     float* logits_out;          // optional [M, ldc]
     // live-row launches (the OM instantiations: sampler steps that skip finished samples).  Row m of the launch is a COMPACT index;
-    // every per-row access -- A segments (before their own rowmod / rowidx / rowkey), cinit, c_prev, the state / pick outputs, the
-    // noise ids -- uses row omap[m] of the caller's arrays, and only the first *m_dev rows exist (tiles behind them return at once).
+    // every per-row access -- A segments (before their own rowmod / rowidx / rowkey), cinit, c_prev, the state / pick / STORE outputs,
+    // the noise ids -- uses row omap[m] of the caller's arrays, and only the first *m_dev rows exist (tiles behind them return at once).
     const int* omap;
     const int* m_dev;
 };
@@ -1052,7 +1052,7 @@ __global__ __launch_bounds__(64 * (WM * WN + PW)) void gemm_kernel(const GemmArg
                         float v = acc[i][j][r];
                         if (g.bias) v = v + bj;
                         if (g.act == 1) v = dm_tanhf(v);
-                        g.C[(size_t)blockIdx.y * g.slab_stride + (size_t)m * g.ldc + col] = v;
+                        g.C[(size_t)blockIdx.y * g.slab_stride + (size_t)orow(m) * g.ldc + col] = v;
                     }
                 }
         }

@@ -217,6 +217,10 @@ struct AttnFwdArgs {
     // reads block clamp(row_video[b], 0, n_video - 1) of P / Vt [Tv, n_video, H]; hWa, alpha, asum, ctx stay per row (stride B).
     const int32_t* row_video;    // [B] device, or NULL
     int n_video;
+    // live rows (the early-exit sampler; needs row_video): workgroup i < *n_live is row live[i], the others return at once.  Both
+    // device-resident, both NULL = every row.  Everything else is indexed by the row as above.
+    const int32_t* live;         // [<= B] rows, each in [0, B)
+    const int32_t* n_live;       // [1]
 };
 hipError_t launch_attn_fwd(const AttnFwdArgs& a, hipStream_t st);
 struct AttnBwdArgs {

@@ -795,8 +795,10 @@ def attention_bwd_rows(hWa, P, Vt, w, alpha, dctx, dw, dP=None, dVt=None):
     return dh, dP, dVt
 
 
-def attn_sample(dims: Dims, params: AttnParams, video, K: int, seed: int, video_base: int = 0, with_greedy: bool = True):
-    """K multinomial captions per video (+ greedy) from the attention captioner: (sampled [K*B,Tc] | None, greedy [B,Tc] | None) int32."""
+def attn_sample(dims: Dims, params: AttnParams, video, K: int, seed: int, video_base: int = 0, with_greedy: bool = True, stop_at_eos: bool = False):
+    """K multinomial captions per video (+ greedy) from the attention captioner: (sampled [K*B,Tc] | None, greedy [B,Tc] | None) int32.
+    stop_at_eos (opt-in, not the reference's behaviour; s2vt_attn_sample_ex): a row leaves the loop once it has picked <eos>; its later
+    ids are 0.  Ids up to and including the first <eos> -- the positions the objective's mask keeps -- are unchanged."""
     _chk_f32(video)
     assert video.is_contiguous()
     B = video.shape[0]
@@ -807,8 +809,12 @@ def attn_sample(dims: Dims, params: AttnParams, video, K: int, seed: int, video_
     Tc = dims.n_caption_lstm_step
     ids = torch.empty((K * B, Tc), dtype=torch.int32, device=video.device) if K > 0 else None
     gr = torch.empty((B, Tc), dtype=torch.int32, device=video.device) if g else None
-    check(lib().s2vt_attn_sample(C.byref(dims), C.byref(params), _ptr(video), B, K, g, seed, int(video_base), _ptr(ids), _ptr(gr), _ptr(ws),
-                                 ws.numel(), _stream()), "s2vt_attn_sample")
+    if stop_at_eos:
+        check(lib().s2vt_attn_sample_ex(C.byref(dims), C.byref(params), _ptr(video), B, K, g, seed, int(video_base), 1, _ptr(ids), _ptr(gr),
+                                        _ptr(ws), ws.numel(), _stream()), "s2vt_attn_sample_ex")
+    else:
+        check(lib().s2vt_attn_sample(C.byref(dims), C.byref(params), _ptr(video), B, K, g, seed, int(video_base), _ptr(ids), _ptr(gr), _ptr(ws),
+                                     ws.numel(), _stream()), "s2vt_attn_sample")
     return ids, gr
 
 

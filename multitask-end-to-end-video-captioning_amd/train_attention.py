@@ -47,8 +47,9 @@ def train(cfg: Config, train_corpus: Corpus, test_corpus: Corpus | None = None, 
     reinforce: the self-critical stage instead of cross entropy -- per step `samples` multinomial captions and the greedy one per video
     (model.sample, global video indices in the noise counters), CIDEr-D of both against the training references, and
     model.reinforce_update with reward = the samples' scores and baseline = the greedy caption's; logging, checkpoints and the
-    per-epoch evaluation are the same.  restore: variables (and Adam slots) of an XE checkpoint, the step counter starting at 0;
-    resume: a checkpoint of this driver, counters included."""
+    per-epoch evaluation are the same.  cfg.stop_at_eos: the sampler's early-exit mode (model.sample(stop_at_eos=True)) -- same update.
+    restore: variables (and Adam slots) of an XE checkpoint, the step counter starting at 0; resume: a checkpoint of this driver,
+    counters included."""
     from . import attention as A
     par = DataParallel(model.device if model is not None else None)
     if not par.chief:
@@ -100,7 +101,8 @@ def train(cfg: Config, train_corpus: Corpus, test_corpus: Corpus | None = None, 
             rb = {}
 
             def rl_step():
-                sampled, greedy = model.sample(b["feats"], K, True, seed=cfg.seed + 7919 * (model.global_step + 1), video_base=b["lo"])
+                sampled, greedy = model.sample(b["feats"], K, True, seed=cfg.seed + 7919 * (model.global_step + 1), video_base=b["lo"],
+                                               stop_at_eos=cfg.stop_at_eos)
                 s_host, g_host = sampled.cpu().numpy(), greedy.cpu().numpy()
 
                 def rewards():              # on the host while the GPU runs the teacher-forced forward
@@ -161,9 +163,10 @@ def main():
     ap.add_argument("--reinforce", action="store_true", help="the self-critical REINFORCE stage (CIDEr-D reward) instead of cross entropy")
     ap.add_argument("--samples", type=int, default=5, help="multinomial samples per video and step of --reinforce (K)")
     ap.add_argument("--restore", help="--reinforce: the XE checkpoint to start from (variables and Adam slots; the step counter starts at 0)")
+    ap.add_argument("--stop-at-eos", action="store_true", help="samples leave the decode loop at their first <eos> (same update, shorter sampler loop)")
     a = ap.parse_args()
     make = reinforce_config if a.reinforce else attention_config
-    cfg = make(n_epochs=a.epochs, batch_size=a.batch_size, model_path=a.model_path, n_video_lstm_step=a.frames,
+    cfg = make(n_epochs=a.epochs, batch_size=a.batch_size, model_path=a.model_path, n_video_lstm_step=a.frames, stop_at_eos=a.stop_at_eos,
                model_name=f"batch_size{a.batch_size}_beta10_m05_{a.frames}img_attention_{'reinforce_' if a.reinforce else ''}model")
     tr = Corpus(a.train_sents, a.train_feats, vocabulary_file=a.vocab)
     te = Corpus(a.test_sents, a.test_feats, vocabulary=tr.vocabulary) if a.test_sents and a.test_feats else None
