@@ -18,6 +18,14 @@
 // shared-block attention backward of attn.hip, the image-side gradient products on Tv * B rows.  Scope: these forms run the PER-STEP
 // launches; the persistent recurrences (attn_chain*.hip: one image block per row, B <= 64) are not used by them and are unchanged -- at
 // the working shape N = 320 they would not be eligible anyway.
+//
+// In this file: the decode step of the three samplers (greedy, multinomial, beam) is ONE function, decode_step on a DecodeStep (its
+// attention half, attn_attend, also serves the teacher-forced unroll), so the ascending-k chains of LSTM3 and of the output layer are
+// stated once.  The backward is a driver (attn_bptt_bwd_impl: validate and carve, decide `persistent` and `gated`) over the stages of
+// the per-call context AttnBwd, in this order: vocab, output_layer_grads (at once, or beside the persistent recurrence), dcat,
+// recurrence_persistent | recurrence_steps, lstm3_and_query_grads, image_side -- with one exit: once the gate has been armed or the
+// side stream forked, every path passes the join, a failed launch's included.  The image blocks (encidx, Vt, P) are an AttnImg in
+// each of the three workspaces.
 #include <hip/hip_runtime.h>
 
 #include <climits>
@@ -166,11 +174,18 @@ __global__ __launch_bounds__(256) void attn_loss_inputs_kernel(const int32_t* ca
     if (threadIdx.x == 0) *mask_sum = (float)sh[0];
 }
 
+// The image blocks of a call's videos: what attn_prologue makes and every attention launch reads.  Each workspace carves the three
+// regions where it always did (they are not adjacent).
+struct AttnImg {
+    int32_t* encidx;               // [Tv*B] the row of video[B*Tv, d] feeding time-major row (frame t, video b)
+    float *Vt, *P;                 // [Tv*B, H] frame embeddings (time-major) and the hoisted image part
+};
+
 // Saved activations + backward scratch, carved from the caller's buffer.  Everything is time-major ([step][row]), so a
 // truncated unroll (caption_steps < Tc) is the leading part of the full one's layout.
 struct AttnWs {
-    int32_t *encidx, *prev, *tgt, *vid, *sid;
-    float *Vt, *P;                 // [Tv*B, H] frame embeddings (time-major) and the hoisted image part
+    AttnImg img;
+    int32_t *prev, *tgt, *vid, *sid;
     float *hWa, *alpha, *asum, *ctx;   // [Tc][B][H], [Tc][Tv][B], [Tc][B], [Tc][B][H]
     float *G3, *C3, *H3, *O3;      // gates [Tc][B][4H] (first the hoisted partial); states / dropped outputs [(Tc+1)][B][H], slot t+1 = step t
     float* Y;                      // [Tc*B, H] output layer
@@ -190,9 +205,9 @@ size_t carve_attn(Carver& c, const s2vt_dims* d, int B, AttnWs* out, int n_video
 {
     const size_t H = d->lstm_dim, V = d->n_words, Tv = d->n_video_lstm_step, Tc = d->n_caption_lstm_step, b = B, nv = n_video > 0 ? n_video : B;
     AttnWs w;
-    w.encidx = c.take<int32_t>(Tv * nv); w.prev = c.take<int32_t>(Tc * b); w.tgt = c.take<int32_t>(Tc * b);
+    w.img.encidx = c.take<int32_t>(Tv * nv); w.prev = c.take<int32_t>(Tc * b); w.tgt = c.take<int32_t>(Tc * b);
     w.vid = c.take<int32_t>(b); w.sid = c.take<int32_t>(b);
-    w.Vt = c.take<float>(Tv * nv * H); w.P = c.take<float>(Tv * nv * H);
+    w.img.Vt = c.take<float>(Tv * nv * H); w.img.P = c.take<float>(Tv * nv * H);
     w.hWa = c.take<float>(Tc * b * H); w.alpha = c.take<float>(Tc * Tv * b); w.asum = c.take<float>(Tc * b); w.ctx = c.take<float>(Tc * b * H);
     w.G3 = c.take<float>(Tc * b * 4 * H); w.C3 = c.take<float>((Tc + 1) * b * H); w.H3 = c.take<float>((Tc + 1) * b * H);
     w.O3 = c.take<float>((Tc + 1) * b * H);
@@ -240,7 +255,7 @@ bool attn_params_ok(const s2vt_attn_params* p)
 }
 
 // frame embedding to H dims in time-major rows (frame t, video b) (:95-98) and the hoisted image part V @ Ua + ba (:107)
-int attn_prologue(const s2vt_dims* d, const s2vt_attn_params* p, const float* video, int B, const AttnWs& w, hipStream_t st)
+int attn_prologue(const s2vt_dims* d, const s2vt_attn_params* p, const float* video, int B, const AttnImg& w, hipStream_t st)
 {
     const int H = d->lstm_dim, D = d->dim_image, Tv = d->n_video_lstm_step;
     hipLaunchKernelGGL(attn_enc_index_kernel, dim3((B * Tv + 255) / 256), dim3(256), 0, st, w.encidx, B, Tv);
@@ -252,21 +267,65 @@ int attn_prologue(const s2vt_dims* d, const s2vt_attn_params* p, const float* vi
     return S2VT_OK;
 }
 
-hipError_t attn_step(const s2vt_attn_params* p, const AttnWs& w, int t, int Tv, int B, int H, const float* query, hipStream_t st, int n_video = 0)
+// (inside a step or a stage: hand a failed launch's error to the driver, whose HIP_TRY records it)
+#define HIP_CHECK(expr) do { const hipError_t _e = (expr); if (_e != hipSuccess) return _e; } while (0)
+
+// One decode step on M rows: what the greedy loop, the multinomial sampler and the beam step differ in is data, not code -- where a
+// row's state lives, how its word and its parent's h are gathered, which image block it reads, and the early-exit mode's row list and
+// tiles.  The teacher-forced unroll uses the first half (attn_attend) with its own query.
+struct DecodeStep {
+    const s2vt_attn_params* p; AttnImg img;
+    int t, M, H, Tv;
+    const float *c_prev, *h_prev; float *c_new, *h_new;     // LSTM3 state [M][H]: slots t / t + 1 of a history, or ping-pong
+    const int32_t* h_rows;                                  // h_prev is gathered through it (beam: the clamped parent), or NULL = row m
+    const unsigned long long* word_key; const int32_t* word_idx;   // the word fed at t > 0: the packed picks of step t-1 (stride kPickStride), or clamped words (beam)
+    float *hWa, *alpha, *asum, *ctx, *Y;                    // the step's [M][H], [Tv][M], [M] (or NULL), [M][H], [M][H]
+    const int32_t* row_video; int n_video;                  // the row -> video form: the M rows share n_video image blocks (NULL, 0: one per row)
+    const int32_t *live, *n_live; int store_cfg, lstm_cfg;  // early-exit mode: every launch covers rows live[0 .. *n_live) only (device-resident); its tile knobs (-1: the cost model's)
+};
+
+// query -> score / softmax / context (:113-128): hWa = query @ Wa, then ONE attention launch
+hipError_t attn_attend(const DecodeStep& s, const float* query, hipStream_t st)
 {
-    const size_t BH = (size_t)B * H;
-    if (t > 0) {       // (step 0: the query is the zero state, h_prev @ Wa = 0, :102)
-        ASeg sq = make_seg(query, H, H, 0);
-        hipError_t e = store_call(&sq, 1, p->embed_att_Wa, H, nullptr, w.hWa + t * BH, H, B, H, 0, -1, st);
-        if (e != hipSuccess) return e;
+    const int H = s.H;
+    if (s.t > 0) {     // (step 0: the query is the zero state, h_prev @ Wa = 0, :102)
+        ASeg sq = make_seg(query, H, H, 0, 0, s.h_rows);
+        HIP_CHECK(store_call(&sq, 1, s.p->embed_att_Wa, H, nullptr, s.hWa, H, s.M, H, 0, s.store_cfg, st, nullptr, 0, false, s.live, s.n_live));
     }
     AttnFwdArgs a;
     std::memset(&a, 0, sizeof(a));
-    a.hWa = t > 0 ? w.hWa + t * BH : nullptr; a.P = w.P; a.Vt = w.Vt; a.w = p->embed_att_w;
-    a.alpha = w.alpha + (size_t)t * Tv * B; a.asum = w.asum + (size_t)t * B; a.ctx = w.ctx + t * BH;
-    a.Tv = Tv; a.B = B; a.H = H;
-    if (n_video > 0) { a.row_video = w.rowvid; a.n_video = n_video; }       // the B rows share n_video image blocks (row -> video form)
+    a.hWa = s.t > 0 ? s.hWa : nullptr; a.P = s.img.P; a.Vt = s.img.Vt; a.w = s.p->embed_att_w;
+    a.alpha = s.alpha; a.asum = s.asum; a.ctx = s.ctx;
+    a.Tv = s.Tv; a.B = s.M; a.H = H;
+    a.row_video = s.row_video; a.n_video = s.n_video;
+    a.live = s.live; a.n_live = s.n_live;
     return launch_attn_fwd(a, st);
+}
+
+// The decode step of the samplers (build_generator / build_sampler, :155-251; no dropout -- self.lstm3, not lstm3_dropout, :188,:235 --
+// so the query is the clean h): attention, then LSTM3 as ONE ascending-k chain over the word's embedding rows, h_prev, the context
+// (blocks in order of availability), then the output layer tanh([embed ; atten ; h_new] @ Wp + bp) in the order
+// [2H:3H], [H:2H], [0:H].  Step 0 has no word (current_embed = 0, :169) and starts from the zero state, so both chains are shorter.
+hipError_t decode_step(const DecodeStep& s, hipStream_t st)
+{
+    const s2vt_attn_params* p = s.p;
+    const int H = s.H, ks = s.word_key ? kPickStride : 1;
+    const NoiseIds none{nullptr, nullptr, 0};
+    const int z = s.t == 0;      // step 0: LSTM3's chain is the context block alone, the output layer's has no word block
+    HIP_CHECK(attn_attend(s, s.h_prev, st));
+    ASeg s3[3] = {make_seg(p->Wemb, H, H, H, 0, s.word_idx, s.word_key, ks), make_seg(s.h_prev, H, H, 2 * H, 0, s.h_rows), make_seg(s.ctx, H, H, 0)};
+    HIP_CHECK(lstm_call(s3 + 2 * z, 3 - 2 * z, p->lstm3_W, p->lstm3_b, s.c_prev, 0, s.c_new, s.h_new, nullptr, nullptr, s.M, H, 1.0f, none, 0, s.lstm_cfg, st,
+                        nullptr, 0, 0, s.live, s.n_live));
+    ASeg sy[3] = {make_seg(p->Wemb, H, H, 2 * H, 0, s.word_idx, s.word_key, ks), make_seg(s.ctx, H, H, H), make_seg(s.h_new, H, H, 0)};
+    return store_call(sy + z, 3 - z, p->embed_nn_Wp, H, p->embed_nn_bp, s.Y, H, s.M, H, 1, s.store_cfg, st, nullptr, 0, false, s.live, s.n_live);
+}
+
+// alphas [steps][Tv][rows] out of the workspace
+hipError_t copy_alphas_out(float* dst, const float* src, size_t bytes, hipStream_t st)
+{
+    CopyList cl;
+    if (cl.add(dst, src, bytes)) return launch_copy_regions(cl, st);
+    return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, st);
 }
 
 
@@ -297,7 +356,7 @@ __global__ __launch_bounds__(256) void attn_beam_gather_kernel(const int32_t* pa
 constexpr int kBeamTopkMax = 16;
 
 struct AttnBeamWs {
-    AttnWs img;                        // encidx, Vt, P [Tv*B, H] of the B videos (attn_prologue); nothing else of it is carved
+    AttnImg img;                       // of the B videos (s2vt_attn_beam_encode)
     float *c[2], *h[2];                // LSTM3 state [Rmax][H]: step t writes slot t & 1 and reads the other (rows are permuted between steps)
     float* cg;                         // the parents' cell state, gathered [Rmax][H]
     int32_t *par, *word;               // clamped parent rows / words [Rmax]
@@ -309,7 +368,6 @@ size_t carve_attn_beam(Carver& c, const s2vt_dims* d, int B, int beam, AttnBeamW
 {
     const size_t H = d->lstm_dim, V = d->n_words, Tv = d->n_video_lstm_step, b = B, Rmax = (size_t)B * beam;
     AttnBeamWs w;
-    std::memset(&w, 0, sizeof(w));
     w.img.encidx = c.take<int32_t>(Tv * b);
     w.img.Vt = c.take<float>(Tv * b * H); w.img.P = c.take<float>(Tv * b * H);
     for (int i = 0; i < 2; ++i) { w.c[i] = c.take<float>(Rmax * H); w.h[i] = c.take<float>(Rmax * H); }
@@ -323,8 +381,8 @@ size_t carve_attn_beam(Carver& c, const s2vt_dims* d, int B, int beam, AttnBeamW
 
 // The multinomial sampler's workspace: the image blocks of the B videos and one step's worth of per-row state for R = (K + greedy) B rows.
 struct AttnSampleWs {
-    int32_t *encidx, *vid, *sid, *rowvid;
-    float *Vt, *P;                     // [Tv*B, H]
+    AttnImg img;                       // of the B videos
+    int32_t *vid, *sid, *rowvid;
     float *c[2], *h[2];                // LSTM3 state [R][H]: step t reads slot t & 1 and writes the other
     float *hWa, *alpha, *ctx, *Y;      // [R][H], [Tv][R], [R][H], [R][H]
     unsigned long long* packed;        // picks [Tc][R][kPickStride]
@@ -336,8 +394,8 @@ size_t carve_attn_sample(Carver& c, const s2vt_dims* d, int B, int R, AttnSample
 {
     const size_t H = d->lstm_dim, Tv = d->n_video_lstm_step, Tc = d->n_caption_lstm_step, b = B, r = R;
     AttnSampleWs w;
-    w.encidx = c.take<int32_t>(Tv * b); w.vid = c.take<int32_t>(r); w.sid = c.take<int32_t>(r); w.rowvid = c.take<int32_t>(r);
-    w.Vt = c.take<float>(Tv * b * H); w.P = c.take<float>(Tv * b * H);
+    w.img.encidx = c.take<int32_t>(Tv * b); w.vid = c.take<int32_t>(r); w.sid = c.take<int32_t>(r); w.rowvid = c.take<int32_t>(r);
+    w.img.Vt = c.take<float>(Tv * b * H); w.img.P = c.take<float>(Tv * b * H);
     for (int i = 0; i < 2; ++i) { w.c[i] = c.take<float>(r * H); w.h[i] = c.take<float>(r * H); }
     w.hWa = c.take<float>(r * H); w.alpha = c.take<float>(Tv * r); w.ctx = c.take<float>(r * H); w.Y = c.take<float>(r * H);
     w.packed = c.take<unsigned long long>(Tc * r * kPickStride);
@@ -380,6 +438,213 @@ bool attn_beam_shape_ok(const s2vt_dims* d, int B, int beam)
     return attn_dims_ok(d) && B > 0 && beam >= 1 && beam <= kBeamTopkMax && (int64_t)B * beam <= INT_MAX / 4;
 }
 
+// ---- the teacher-forced unroll and its backward: what both check alike, in the ABI's order (bad argument, alignment, workspace), and
+// the carve.  ptrs_ok: the call's own pointers; own_rc: the one check each makes of its own, which comes before the workspace's size
+int attn_unroll_open(const s2vt_dims* d, bool ptrs_ok, int B, int caption_steps, float keep, const int32_t* video_id, const int32_t* sample_id,
+                     void* workspace, size_t workspace_bytes, int n_video, int own_rc, AttnWs* w)
+{
+    if (!attn_dims_ok(d) || !ptrs_ok || !workspace || B <= 0) return S2VT_E_BADARG;
+    if (!(keep > 0.0f) || (keep < 1.0f && (!video_id || !sample_id))) return S2VT_E_BADARG;
+    if (reinterpret_cast<uintptr_t>(workspace) & 255u) return S2VT_E_ALIGN;
+    if (caption_steps < 1 || caption_steps > d->n_caption_lstm_step) return S2VT_E_BADARG;
+    if (own_rc != S2VT_OK) return own_rc;
+    Carver c(workspace, workspace_bytes);
+    carve_attn(c, d, B, w, n_video);
+    return c.ok() ? S2VT_OK : S2VT_E_WORKSPACE;
+}
+
+// the persistent recurrences (attn_chain*.hip) load W3 and Wa 16 bytes at a time
+bool attn_chain_weights_ok(const s2vt_attn_params* p)
+{
+    return !chain_fault() && !(reinterpret_cast<uintptr_t>(p->lstm3_W) & 15) && !(reinterpret_cast<uintptr_t>(p->embed_att_Wa) & 15);
+}
+
+// the whole forward recurrence -- query projection, score / softmax / context, LSTM3, all Tc steps -- as ONE persistent launch
+AttnChainLaunch attn_fwd_chain_args(const s2vt_attn_params* p, const AttnWs& w, int B, int H, int Tc, int Tv, float keep, const NoiseIds& ids)
+{
+    const size_t BH = (size_t)B * H;
+    AttnChainLaunch a;
+    std::memset(&a, 0, sizeof(a));
+    a.W3 = p->lstm3_W; a.ldw = 4 * H; a.b3 = p->lstm3_b;
+    a.cinit = w.G3; a.cinit_tstride = (size_t)4 * BH; a.ldcinit = 4 * H;
+    a.C = w.C3; a.Hh = w.H3; a.Out = w.O3; a.state_tstride = BH; a.gates = w.G3; a.gates_tstride = (size_t)4 * BH;
+    a.Wa = p->embed_att_Wa; a.ldwa = H; a.P = w.img.P; a.Vt = w.img.Vt; a.w = p->embed_att_w;
+    a.hWa = w.hWa; a.hwa_tstride = BH; a.alpha = w.alpha; a.asum = w.asum; a.ctx = w.ctx;
+    a.B = B; a.H = H; a.T = Tc; a.Tv = Tv;
+    a.keep = keep; a.seed_lo = (uint32_t)ids.seed; a.seed_hi = (uint32_t)(ids.seed >> 32); a.drop_code0 = kDropCode3;
+    a.video_id = ids.video_id; a.sample_id = ids.sample_id;
+    a.img = w.aimg; a.sync = w.async_;
+    return a;
+}
+
+// A weight gradient C[M, N] += A[rows, M]^T B[rows, N] (+ colsum += B's column sums); idx: A's rows gathered out of a table of gather_rows
+// rows (0 = not stated)
+TnArgs tn(const float* A, const int32_t* idx, int gather_rows, int lda, const float* B, int ldb, float* C, int ldc, int rows, int M, int N, float* colsum = nullptr)
+{
+    return TnArgs{A, idx, lda, B, ldb, C, ldc, rows, M, N, 1, colsum, gather_rows};
+}
+
+// One backward call of the attention captioner: what every stage reads (filled once by attn_bptt_bwd_impl, which is the driver) and the
+// stages themselves, each straight-line, in the driver's order.  n_video > 0 is the shared-block form: B sample-major rows over n_video
+// image blocks, per-step launches, the attention backward of launch_attn_bwd_rows (dP / dVt one block per video, summed over its rows),
+// the image-side products on Tv * n_video rows.
+struct AttnBwd {
+    SideStream& ss;
+    int H, V, D, Tv, Tc, B, n_video;     // (Tc: the steps the forward call unrolled)
+    int NV, R, R1; size_t BH;            // image blocks per frame; rows of the all-step products: every step | the steps that have a word
+    AttnWs w;
+    const s2vt_attn_params *p, *grads; const float *video, *dlogits, *reg_coef; float reg_m, keep; uint64_t seed; const int32_t *video_id, *sample_id;
+    hipStream_t st; bool persistent, gated;   // the recurrence as one launch; the weight gradients that feed nothing in it beside it (side stream)
+    bool side_used = false;              // the gate has been armed or the side stream forked: the driver owes the join
+
+    TnArgs dwout() const { return tn(w.Y, nullptr, 0, H, dlogits, V, grads->embed_word_W, V, R, H, V, grads->embed_word_b); }
+
+    // ---- vocabulary projection: dWout, dbout (at once, or deferred: on the side stream behind the gate) and d(output layer), back
+    // through its tanh
+    hipError_t vocab() const
+    {
+        if (!gated) HIP_CHECK(launch_gemm_tn(dwout(), st));
+        HIP_CHECK(nn_bwd_slabs(dlogits, V, p->embed_word_W, V, w.dY, H, R, H, V, w.bslab, st, w.bslab_floats));
+        hipLaunchKernelGGL(attn_tanh_bwd_kernel, dim3((unsigned)(((size_t)R * H / 4 + 255) / 256)), dim3(256), 0, st, w.dY, w.Y, (size_t)R * H / 4);
+        return hipGetLastError();
+    }
+    // ---- output layer: Wp rows [output1 ; atten ; current_embed] and its bias (either stream, as dWout) ...
+    hipError_t output_layer_grads(hipStream_t s) const
+    {
+        HIP_CHECK(launch_gemm_tn(tn(w.O3 + BH, nullptr, 0, H, w.dY, H, grads->embed_nn_Wp, H, R, H, H, grads->embed_nn_bp), s));
+        HIP_CHECK(launch_gemm_tn(tn(w.ctx, nullptr, 0, H, w.dY, H, grads->embed_nn_Wp + (size_t)H * H, H, R, H, H), s));
+        return Tc > 1 ? launch_gemm_tn(tn(p->Wemb, w.prev + B, V, H, w.dY + BH, H, grads->embed_nn_Wp + (size_t)2 * H * H, H, R1, H, H), s) : hipSuccess;
+    }
+    // ... and d[out | ctx | emb] for every step at once; the image-side accumulators of the recurrence start from zero
+    hipError_t dcat() const
+    {
+        HIP_CHECK(nn_bwd_slabs(w.dY, H, p->embed_nn_Wp, H, w.dcat, 3 * H, R, 3 * H, H, w.bslab, st, w.bslab_floats));
+        ZeroList z;
+        z.add(w.dPt, (size_t)Tv * NV * H * 4); z.add(w.dVtt, (size_t)Tv * NV * H * 4);
+        return launch_zero_regions(z, st);
+    }
+
+    // ---- the recurrence, back through time, as ONE persistent launch: cell backward, dz @ [W3 h rows ; W3 context rows]^T, attention
+    // backward, dhWa @ Wa^T, all Tc steps
+    hipError_t recurrence_persistent()
+    {
+        AttnBwdChainLaunch a;
+        std::memset(&a, 0, sizeof(a));
+        a.W3 = p->lstm3_W; a.ldw = 4 * H; a.Wa = p->embed_att_Wa; a.ldwa = H;
+        a.gates = w.G3; a.gates_tstride = (size_t)4 * BH; a.C = w.C3; a.state_tstride = BH;
+        a.dcat = w.dcat; a.dcat_tstride = (size_t)3 * BH; a.ld_cat = 3 * H; a.dZ = w.dZ3; a.dz_tstride = (size_t)4 * BH;
+        a.hWa = w.hWa; a.hwa_tstride = BH; a.P = w.img.P; a.Vt = w.img.Vt; a.w = p->embed_att_w; a.alpha = w.alpha;
+        a.reg_coef = reg_coef; a.asum = w.asum; a.reg_m = reg_m;
+        a.dhWa = w.dhWa; a.dhwa_tstride = BH; a.dP = w.dPt; a.dVt = w.dVtt; a.dw = grads->embed_att_w;
+        a.deh = w.deh;
+        a.B = B; a.H = H; a.T = Tc; a.Tv = Tv;
+        a.keep = keep; a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32); a.drop_code0 = kDropCode3;
+        a.video_id = video_id; a.sample_id = sample_id;
+        a.img = w.bimg; a.ex = w.bex; a.dctxs = w.brow_; a.sync = w.bsync;
+        ChainGate gate{ss.s, ss.ev[3], false};
+        if (gated) { chain_gate_arm(&gate); side_used = true; }
+        const hipError_t re = launch_attn_bwd_chain(a, st);
+        chain_gate_arm(nullptr);
+        HIP_CHECK(re);
+        if (gated) {
+            // (reads: dlogits, Y, dY, O3, ctx, Wemb -- final since before the launch; writes: the gradients of embed_word_W/b and embed_nn_Wp/bp,
+            //  which nothing else in this call touches.  A gate that did not fire -- a zero-step launch -- puts the side stream behind the caller's)
+            if (!gate.fired) HIP_CHECK(fork_to(st, ss.s, ss.ev[3]));
+            HIP_CHECK(launch_gemm_tn(dwout(), ss.s));
+            HIP_CHECK(output_layer_grads(ss.s));
+        }
+        // the embedding block of dz @ W3^T does not feed the recurrence: all steps >= 1 at once, on top of the output layer's block
+        if (Tc > 1) {
+            ASeg sz = make_seg(w.dZ3 + 4 * BH, 4 * H, 4 * H, 0);
+            HIP_CHECK(store_call(&sz, 1, p->lstm3_W + (size_t)H * 4 * H, 4 * H, nullptr, w.dEmb + BH, H, R1, H, 0, -1, st, w.dcat + 3 * BH + 2 * H, 3 * H, true));
+        }
+        return hipSuccess;
+    }
+
+    // ---- the recurrence in per-step launches.  Split-K plan of a per-step data-gradient product (order-free): what nn_bwd makes of
+    // the slabs asked of it over a reduction of K
+    static int slabs_made(int asked, int K)
+    {
+        const int kper = ((K + asked - 1) / asked + BK - 1) / BK * BK;
+        return (K + kper - 1) / kper;
+    }
+    hipError_t recurrence_steps() const
+    {
+        // enough slabs for >= ~512 workgroups
+        int sx = (512 + ((3 * H + 63) / 64) - 1) / ((3 * H + 63) / 64) / ((B + 63) / 64);
+        sx = sx < 1 ? 1 : (sx > kXSlabs ? kXSlabs : sx);
+        int sq = kQSlabs;
+        while (sq > 1 && H / sq < 128) --sq;
+        const int nx = slabs_made(sx, 4 * H), nq = slabs_made(sq, H);
+        for (int t = Tc - 1; t >= 0; --t) {
+            const bool last = t == Tc - 1;
+            AttnCellBwdArgs a;      // BasicLSTMCell backward of step t -> dz
+            std::memset(&a, 0, sizeof(a));
+            a.gates = w.G3 + (size_t)t * 4 * BH; a.c_new = w.C3 + (t + 1) * BH; a.c_prev = w.C3 + t * BH;
+            a.dcat = w.dcat + (size_t)t * 3 * BH; a.ld_cat = 3 * H;
+            a.dqs = last ? nullptr : w.dqs; a.nq = nq; a.q_stride = BH;
+            a.dxs = last ? nullptr : w.dxs; a.nx = nx; a.x_stride = 3 * BH; a.ld_x = 3 * H; a.x_col0 = 2 * H;
+            a.dc_in = last ? nullptr : w.dc; a.dc_out = w.dc; a.dz = w.dZ3 + (size_t)t * 4 * BH;
+            a.M = B; a.H = H; a.keep = keep; a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32); a.drop_code = kDropCode3 + (uint32_t)t;
+            a.video_id = video_id; a.sample_id = sample_id;
+            hipLaunchKernelGGL(attn_cell_bwd_kernel, dim3((B * H + 255) / 256), dim3(256), 0, st, a);
+            HIP_CHECK(hipGetLastError());
+            // d[ctx | emb | h_prev] = dz @ W3^T as split-K slabs: the attention backward sums the ctx and emb blocks, the next
+            // (earlier) step's cell backward the h block
+            HIP_CHECK(nn_bwd(w.dZ3 + (size_t)t * 4 * BH, 4 * H, p->lstm3_W, 4 * H, w.dxs, 3 * H, B, 3 * H, 4 * H, sx, 3 * BH, st, sx > 1 ? kSlabTileCfg : -1));
+            AttnBwdArgs g;
+            std::memset(&g, 0, sizeof(g));
+            g.hWa = t > 0 ? w.hWa + t * BH : nullptr; g.P = w.img.P; g.Vt = w.img.Vt; g.w = p->embed_att_w; g.alpha = w.alpha + (size_t)t * Tv * B;
+            g.dctx = w.dcat + (size_t)t * 3 * BH + H; g.ld_dctx = 3 * H;
+            g.slabs = w.dxs; g.nslab = nx; g.slab_stride = 3 * BH; g.ld_slab = 3 * H; g.ctx_col0 = 0; g.emb_col0 = H;
+            if (t > 0) { g.demb_dense = w.dcat + (size_t)t * 3 * BH + 2 * H; g.ld_demb = 3 * H; g.demb_out = w.dEmb + t * BH; }
+            if (reg_coef) { g.reg_coef = reg_coef + (size_t)t * B; g.asum = w.asum + (size_t)t * B; g.reg_m = reg_m; }
+            g.dhWa = t > 0 ? w.dhWa + t * BH : nullptr; g.dP = w.dPt; g.dVt = w.dVtt; g.acc = 1; g.dw = grads->embed_att_w;
+            g.Tv = Tv; g.B = B; g.H = H;
+            AttnBwdRowsArgs r;      // (the shared-block form: the rows of a video are summed into its one block)
+            std::memset(&r, 0, sizeof(r));
+            r.a = g; r.n_video = n_video; r.samples = n_video > 0 ? B / n_video : 0; r.de_rows = w.deh; r.dctx_rows = w.dctxr;
+            HIP_CHECK(n_video > 0 ? launch_attn_bwd_rows(r, st) : launch_attn_bwd(g, st));
+            // gradient w.r.t. the previous step's dropped output through this step's query: dhWa @ Wa^T (slabs, summed by the cell backward)
+            if (t > 0) HIP_CHECK(nn_bwd(w.dhWa + t * BH, H, p->embed_att_Wa, H, w.dqs, H, B, H, H, sq, BH, st, sq > 1 ? kSlabTileCfg : -1));
+        }
+        return hipSuccess;
+    }
+
+    // ---- weight gradients of the recurrence, one contraction over all unrolled steps per block: W3 rows [0, H) atten (+ b3), [2H, 3H)
+    // h_prev, [H, 2H) current_embed; Wa (the query of step t = the out of step t-1); the embedding rows (tf.nn.embedding_lookup, :141-142)
+    hipError_t lstm3_and_query_grads() const
+    {
+        HIP_CHECK(launch_gemm_tn(tn(w.ctx, nullptr, 0, H, w.dZ3, 4 * H, grads->lstm3_W, 4 * H, R, H, 4 * H, grads->lstm3_b), st));
+        HIP_CHECK(launch_gemm_tn(tn(w.H3, nullptr, 0, H, w.dZ3, 4 * H, grads->lstm3_W + (size_t)2 * H * 4 * H, 4 * H, R, H, 4 * H), st));
+        if (Tc > 1) {
+            HIP_CHECK(launch_gemm_tn(tn(p->Wemb, w.prev + B, V, H, w.dZ3 + 4 * BH, 4 * H, grads->lstm3_W + (size_t)H * 4 * H, 4 * H, R1, H, 4 * H), st));
+            HIP_CHECK(launch_gemm_tn(tn(w.O3 + BH, nullptr, 0, H, w.dhWa + BH, H, grads->embed_att_Wa, H, R1, H, H), st));
+            HIP_CHECK(launch_scatter_add_rows(w.dEmb + BH, H, w.prev + B, R1, H, grads->Wemb, H, st));
+        }
+        return hipSuccess;
+    }
+    // ---- image part P = V @ Ua + ba and the frame embedding V = video @ encode_image_W + b
+    hipError_t image_side() const
+    {
+        HIP_CHECK(launch_gemm_tn(tn(w.img.Vt, nullptr, 0, H, w.dPt, H, grads->embed_att_Ua, H, Tv * NV, H, H, grads->embed_att_ba), st));
+        ASeg sp = make_seg(w.dPt, H, H, 0);
+        HIP_CHECK(store_call(&sp, 1, p->embed_att_Ua, H, nullptr, w.dEv, H, Tv * NV, H, 0, -1, st, w.dVtt, H, true));     // dV = dV(ctx path) + dP @ Ua^T
+        return launch_gemm_tn(tn(video, w.img.encidx, Tv * NV, D, w.dEv, H, grads->encode_image_W, H, Tv * NV, D, H, grads->encode_image_b), st);
+    }
+
+    // every stage, in order, up to the first that fails
+    hipError_t stages()
+    {
+        HIP_CHECK(vocab());
+        if (!gated) HIP_CHECK(output_layer_grads(st));
+        HIP_CHECK(dcat());
+        HIP_CHECK(persistent ? recurrence_persistent() : recurrence_steps());
+        HIP_CHECK(lstm3_and_query_grads());
+        return image_side();
+    }
+};
+
 }  // namespace
 
 extern "C" {
@@ -397,18 +662,14 @@ static int attn_tf_fwd_impl(const s2vt_dims* d, const s2vt_attn_params* p, const
                             int32_t caption_steps, float keep, uint64_t seed, const int32_t* video_id, const int32_t* sample_id,
                             float* logits, float* alphas_out, void* workspace, size_t workspace_bytes, s2vt_stream stream, int n_video)
 {
-    if (!attn_dims_ok(d) || !attn_params_ok(p) || !video || !caption || !logits || !workspace || B <= 0) return S2VT_E_BADARG;
-    if (!(keep > 0.0f) || (keep < 1.0f && (!video_id || !sample_id))) return S2VT_E_BADARG;
-    if (reinterpret_cast<uintptr_t>(workspace) & 255u) return S2VT_E_ALIGN;
-    if (caption_steps < 1 || caption_steps > d->n_caption_lstm_step) return S2VT_E_BADARG;
-    if (chain_fault()) return S2VT_E_CHAIN_TIMEOUT;
-    const int H = d->lstm_dim, V = d->n_words, Tv = d->n_video_lstm_step, Tc = caption_steps;
-    Carver c(workspace, workspace_bytes);
     AttnWs w;
-    carve_attn(c, d, B, &w, n_video);
-    if (!c.ok()) return S2VT_E_WORKSPACE;
+    int rc = attn_unroll_open(d, attn_params_ok(p) && video && caption && logits, B, caption_steps, keep, video_id, sample_id, workspace, workspace_bytes,
+                              n_video, chain_fault() ? S2VT_E_CHAIN_TIMEOUT : S2VT_OK, &w);
+    if (rc != S2VT_OK) return rc;
+    const int H = d->lstm_dim, V = d->n_words, Tv = d->n_video_lstm_step, Tc = caption_steps;
     hipStream_t st = S(stream);
     const size_t BH = (size_t)B * H;
+    const NoiseIds ids{video_id, sample_id, seed};
 
     if (n_video > 0) HIP_TRY(launch_attn_row_video(w.rowvid, B, n_video, st));
     HIP_TRY(launch_prep_caption(caption, w.prev, w.tgt, B, d->n_caption_lstm_step, st));      // prev[t*B + b] = caption[b][t-1] for t >= 1
@@ -417,7 +678,7 @@ static int attn_tf_fwd_impl(const s2vt_dims* d, const s2vt_attn_params* p, const
         z.add(w.C3, BH * 4); z.add(w.H3, BH * 4); z.add(w.O3, BH * 4); z.add(w.G3, BH * 4 * 4);
         HIP_TRY(launch_zero_regions(z, st));
     }
-    int rc = attn_prologue(d, p, video, n_video > 0 ? n_video : B, w, st);
+    rc = attn_prologue(d, p, video, n_video > 0 ? n_video : B, w.img, st);
     if (rc != S2VT_OK) return rc;
     // the embedding rows of W3 for every step >= 1 in one product, written where the step's gates will go: the first block of
     // each pre-activation chain (the word fed at step t is caption[:, t-1], :141-142)
@@ -425,24 +686,15 @@ static int attn_tf_fwd_impl(const s2vt_dims* d, const s2vt_attn_params* p, const
         ASeg se = make_seg(p->Wemb, H, H, H, 0, w.prev + B);
         HIP_TRY(store_call(&se, 1, p->lstm3_W, 4 * H, nullptr, w.G3 + 4 * BH, 4 * H, (Tc - 1) * B, 4 * H, 0, -1, st));
     }
-    NoiseIds ids{video_id, sample_id, seed};
-    if (n_video == 0 && attn_chain_eligible(B, H, Tv) && !chain_fault() && !(reinterpret_cast<uintptr_t>(p->lstm3_W) & 15) && !(reinterpret_cast<uintptr_t>(p->embed_att_Wa) & 15)) {
-        // the whole recurrence -- query projection, score / softmax / context, LSTM3, all Tc steps -- in ONE persistent launch
-        AttnChainLaunch a;
-        std::memset(&a, 0, sizeof(a));
-        a.W3 = p->lstm3_W; a.ldw = 4 * H; a.b3 = p->lstm3_b;
-        a.cinit = w.G3; a.cinit_tstride = (size_t)4 * BH; a.ldcinit = 4 * H;
-        a.C = w.C3; a.Hh = w.H3; a.Out = w.O3; a.state_tstride = BH; a.gates = w.G3; a.gates_tstride = (size_t)4 * BH;
-        a.Wa = p->embed_att_Wa; a.ldwa = H; a.P = w.P; a.Vt = w.Vt; a.w = p->embed_att_w;
-        a.hWa = w.hWa; a.hwa_tstride = BH; a.alpha = w.alpha; a.asum = w.asum; a.ctx = w.ctx;
-        a.B = B; a.H = H; a.T = Tc; a.Tv = Tv;
-        a.keep = keep; a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32); a.drop_code0 = kDropCode3;
-        a.video_id = video_id; a.sample_id = sample_id;
-        a.img = w.aimg; a.sync = w.async_;
-        HIP_TRY(launch_attn_chain(a, st));
+    if (n_video == 0 && attn_chain_eligible(B, H, Tv) && attn_chain_weights_ok(p)) {
+        HIP_TRY(launch_attn_chain(attn_fwd_chain_args(p, w, B, H, Tc, Tv, keep, ids), st));
     } else {
+        DecodeStep s{};     // (its attention half: the query is the DROPPED output, `h_prev = output1`, :135)
+        s.p = p; s.img = w.img; s.M = B; s.H = H; s.Tv = Tv; s.store_cfg = -1;
+        s.row_video = w.rowvid; s.n_video = n_video;       // (n_video > 0: the B rows share n_video image blocks; else NULL, 0)
         for (int t = 0; t < Tc; ++t) {
-            HIP_TRY(attn_step(p, w, t, Tv, B, H, w.O3 + t * BH, st, n_video));                            // (:113-128)
+            s.t = t; s.hWa = w.hWa + t * BH; s.alpha = w.alpha + (size_t)t * Tv * B; s.asum = w.asum + (size_t)t * B; s.ctx = w.ctx + t * BH;
+            HIP_TRY(attn_attend(s, w.O3 + t * BH, st));                                                     // (:113-128)
             // LSTM3 (:131): the chain continues from the hoisted partial with the recurrent rows, then the context rows
             ASeg s3[2] = {make_seg(w.H3 + t * BH, H, H, 2 * H), make_seg(w.ctx + t * BH, H, H, 0)};
             HIP_TRY(lstm_call(s3, 2, p->lstm3_W, p->lstm3_b, w.C3 + t * BH, 0, w.C3 + (t + 1) * BH, w.H3 + (t + 1) * BH, w.O3 + (t + 1) * BH,
@@ -461,11 +713,7 @@ static int attn_tf_fwd_impl(const s2vt_dims* d, const s2vt_attn_params* p, const
     // vocabulary logits (:143), rows t*B + b
     ASeg so = make_seg(w.Y, H, H, 0);
     HIP_TRY(store_call(&so, 1, p->embed_word_W, V, p->embed_word_b, logits, V, Tc * B, V, 0, -1, st));
-    if (alphas_out) {
-        CopyList cl;
-        if (cl.add(alphas_out, w.alpha, (size_t)Tc * Tv * B * 4)) HIP_TRY(launch_copy_regions(cl, st));
-        else HIP_TRY(hipMemcpyAsync(alphas_out, w.alpha, (size_t)Tc * Tv * B * 4, hipMemcpyDeviceToDevice, st));
-    }
+    if (alphas_out) HIP_TRY(copy_alphas_out(alphas_out, w.alpha, (size_t)Tc * Tv * B * 4, st));
     return S2VT_OK;
 }
 
@@ -496,15 +744,16 @@ int s2vt_attn_loss_inputs(const int32_t* caption, const float* mask, int32_t B, 
     return S2VT_OK;
 }
 
-int s2vt_attn_step_scalars(const float* coef, const float* nll, int64_t R, const float* reg_coef, float reg_m, const float* mask_sum_local,
-                           const float* mask_sum_global, float* loss, float* gscale, float* sumsq, const s2vt_dims* d, int32_t B,
-                           void* workspace, size_t workspace_bytes, s2vt_stream stream)
+// rows: the unroll's B, or n_video * samples of the shared-block form (n_video > 0); shape_ok: what the entry point checks of them
+static int attn_step_scalars_impl(const float* coef, const float* nll, int64_t R, const float* reg_coef, float reg_m, const float* mask_sum_local,
+                                  const float* mask_sum_global, float* loss, float* gscale, float* sumsq, const s2vt_dims* d, bool shape_ok,
+                                  int rows, int n_video, void* workspace, size_t workspace_bytes, s2vt_stream stream)
 {
-    if (!coef || !nll || R < 0 || !mask_sum_local || !mask_sum_global || !attn_dims_ok(d) || B <= 0 || !workspace) return S2VT_E_BADARG;
-    if (R > (int64_t)d->n_caption_lstm_step * B) return S2VT_E_BADARG;
+    if (!coef || !nll || R < 0 || !mask_sum_local || !mask_sum_global || !shape_ok || !workspace) return S2VT_E_BADARG;
+    if (R > (int64_t)d->n_caption_lstm_step * rows) return S2VT_E_BADARG;
     Carver c(workspace, workspace_bytes);
     AttnWs w;
-    carve_attn(c, d, B, &w);
+    carve_attn(c, d, rows, &w, n_video);
     if (!c.ok()) return S2VT_E_WORKSPACE;
     hipLaunchKernelGGL(attn_step_scalars_kernel, dim3(1), dim3(256), 0, S(stream), coef, nll, reg_coef, w.asum, reg_m, (int)R, mask_sum_local,
                        mask_sum_global, loss, gscale, sumsq);
@@ -512,177 +761,50 @@ int s2vt_attn_step_scalars(const float* coef, const float* nll, int64_t R, const
     return S2VT_OK;
 }
 
-// n_video as attn_tf_fwd_impl: > 0 is the shared-block form -- per-step launches, the attention backward of launch_attn_bwd_rows (dP / dVt
-// one block per video, summed over its rows), the image-side products on Tv * n_video rows.
+int s2vt_attn_step_scalars(const float* coef, const float* nll, int64_t R, const float* reg_coef, float reg_m, const float* mask_sum_local,
+                           const float* mask_sum_global, float* loss, float* gscale, float* sumsq, const s2vt_dims* d, int32_t B,
+                           void* workspace, size_t workspace_bytes, s2vt_stream stream)
+{
+    return attn_step_scalars_impl(coef, nll, R, reg_coef, reg_m, mask_sum_local, mask_sum_global, loss, gscale, sumsq, d, attn_dims_ok(d) && B > 0, B, 0,
+                                  workspace, workspace_bytes, stream);
+}
+
+// The driver only: validate and carve, decide `persistent` and `gated`, then the stages of AttnBwd in order -- vocab, output_layer_grads
+// (now, or beside the persistent recurrence), dcat, recurrence_persistent | recurrence_steps, lstm3_and_query_grads, image_side -- and ONE
+// exit: once the gate has been armed or the side stream forked, a call that fails passes the join like one that succeeds.
 static int attn_bptt_bwd_impl(const s2vt_dims* d, const s2vt_attn_params* p, const s2vt_attn_params* grads, const float* video, int32_t B,
                               const float* dlogits, int32_t caption_steps, const float* reg_coef, float reg_m, float keep, uint64_t seed,
                               const int32_t* video_id, const int32_t* sample_id, void* workspace, size_t workspace_bytes, s2vt_stream stream,
                               int n_video)
 {
-    if (!attn_dims_ok(d) || !attn_params_ok(p) || !attn_params_ok(grads) || !video || !dlogits || !workspace || B <= 0) return S2VT_E_BADARG;
-    if (!(keep > 0.0f) || (keep < 1.0f && (!video_id || !sample_id))) return S2VT_E_BADARG;
-    if (reinterpret_cast<uintptr_t>(workspace) & 255u) return S2VT_E_ALIGN;
-    if (caption_steps < 1 || caption_steps > d->n_caption_lstm_step) return S2VT_E_BADARG;
-    if (d->lstm_dim & 3) return S2VT_E_BADARG;
-    const int H = d->lstm_dim, V = d->n_words, D = d->dim_image, Tv = d->n_video_lstm_step, Tc = caption_steps;
-    Carver c(workspace, workspace_bytes);
     AttnWs w;
-    carve_attn(c, d, B, &w, n_video);
-    if (!c.ok()) return S2VT_E_WORKSPACE;
-    hipStream_t st = S(stream);
-    const size_t BH = (size_t)B * H;
-    const int R = Tc * B, R1 = (Tc - 1) * B;
-    const int NV = n_video > 0 ? n_video : B;                 // image blocks per frame
-
-    const bool persistent = n_video == 0 && attn_bwd_chain_eligible(B, H, Tv) && !chain_fault() && !(reinterpret_cast<uintptr_t>(p->lstm3_W) & 15) &&
-                            !(reinterpret_cast<uintptr_t>(p->embed_att_Wa) & 15);
+    const int rc = attn_unroll_open(d, attn_params_ok(p) && attn_params_ok(grads) && video && dlogits, B, caption_steps, keep, video_id, sample_id, workspace,
+                                    workspace_bytes, n_video, d && (d->lstm_dim & 3) ? S2VT_E_BADARG : S2VT_OK, &w);
+    if (rc != S2VT_OK) return rc;
+    AttnBwd x{side_stream()};
+    const SideStream& ss = x.ss;
+    const int H = d->lstm_dim, Tv = d->n_video_lstm_step, Tc = caption_steps;
+    x.H = H; x.V = d->n_words; x.D = d->dim_image; x.Tv = Tv; x.Tc = Tc; x.B = B; x.n_video = n_video;
+    x.NV = n_video > 0 ? n_video : B; x.R = Tc * B; x.R1 = (Tc - 1) * B; x.BH = (size_t)B * H;
+    x.p = p; x.grads = grads; x.video = video; x.dlogits = dlogits; x.reg_coef = reg_coef; x.reg_m = reg_m;
+    x.keep = keep; x.seed = seed; x.video_id = video_id; x.sample_id = sample_id; x.st = S(stream); x.w = w;
+    x.persistent = n_video == 0 && attn_bwd_chain_eligible(B, H, Tv) && attn_chain_weights_ok(p);
     // Gated overlap (S2VT_OVERLAP=0 switches it off): the weight gradients of the vocabulary projection and of the output layer feed
     // nothing in the recurrence -- with the persistent backward recurrence they are launched on the side stream once its grid is resident and
     // run BESIDE it (a one-wave-per-SIMD grid that waits in hand-offs more than half of its time), joined at the end of the call.
     // Measured (bench.py --workload attention / attention32, S2VT_OVERLAP=0 against 2, twice each): Tv = 5: 2.63 -> 2.57 ms per step; Tv = 32: 3.25 -> 3.27.
     // This recurrence holds 150 KB of LDS per CU, so the LDS-staged contractions cannot share a CU with it (as they do with the LSTM recurrences'
     // 64 KB): they fill the CUs its workgroups leave at the end and run beside the launches that follow it.  On for the register-frames form only.
-    SideStream& ss = side_stream();
-    const bool gated = ss.ok && ss.mode == 2 && persistent && Tv <= 5;
+    x.gated = ss.ok && ss.mode == 2 && x.persistent && Tv <= 5;
     std::unique_lock<std::mutex> side_lk(side_stream_mutex(), std::defer_lock);
-    if (gated) side_lk.lock();
-    ChainGate gate{ss.s, ss.ev[3], false};
-    // ---- vocabulary projection: dWout, dbout, d(output layer)
-    TnArgs dwout{w.Y, nullptr, H, dlogits, V, grads->embed_word_W, V, R, H, V, 1};
-    dwout.colsum = grads->embed_word_b;
-    if (!gated) HIP_TRY(launch_gemm_tn(dwout, st));
-    HIP_TRY(nn_bwd_slabs(dlogits, V, p->embed_word_W, V, w.dY, H, R, H, V, w.bslab, st, w.bslab_floats));
-    hipLaunchKernelGGL(attn_tanh_bwd_kernel, dim3((unsigned)(((size_t)R * H / 4 + 255) / 256)), dim3(256), 0, st, w.dY, w.Y, (size_t)R * H / 4);
-    HIP_TRY(hipGetLastError());
-    // ---- output layer: Wp rows [output1 ; atten ; current_embed], its bias, and d[out | ctx | emb] for every step at once
-    auto output_layer_grads = [&](hipStream_t s) -> int {
-        TnArgs a{w.O3 + BH, nullptr, H, w.dY, H, grads->embed_nn_Wp, H, R, H, H, 1};
-        a.colsum = grads->embed_nn_bp;
-        HIP_TRY(launch_gemm_tn(a, s));
-        TnArgs b{w.ctx, nullptr, H, w.dY, H, grads->embed_nn_Wp + (size_t)H * H, H, R, H, H, 1};
-        HIP_TRY(launch_gemm_tn(b, s));
-        if (Tc > 1) {
-            TnArgs e{p->Wemb, w.prev + B, H, w.dY + BH, H, grads->embed_nn_Wp + (size_t)2 * H * H, H, R1, H, H, 1};
-            e.gather_rows = V;
-            HIP_TRY(launch_gemm_tn(e, s));
-        }
-        return S2VT_OK;
-    };
-    if (!gated) { const int rc = output_layer_grads(st); if (rc != S2VT_OK) return rc; }
-    HIP_TRY(nn_bwd_slabs(w.dY, H, p->embed_nn_Wp, H, w.dcat, 3 * H, R, 3 * H, H, w.bslab, st, w.bslab_floats));
-    {
-        ZeroList z;
-        z.add(w.dPt, (size_t)Tv * NV * H * 4); z.add(w.dVtt, (size_t)Tv * NV * H * 4);
-        HIP_TRY(launch_zero_regions(z, st));
-    }
-    // ---- the recurrence, back through time
-    if (persistent) {
-        // ONE persistent launch: cell backward, dz @ [W3 h rows ; W3 context rows]^T, attention backward, dhWa @ Wa^T, all Tc steps
-        AttnBwdChainLaunch a;
-        std::memset(&a, 0, sizeof(a));
-        a.W3 = p->lstm3_W; a.ldw = 4 * H; a.Wa = p->embed_att_Wa; a.ldwa = H;
-        a.gates = w.G3; a.gates_tstride = (size_t)4 * BH; a.C = w.C3; a.state_tstride = BH;
-        a.dcat = w.dcat; a.dcat_tstride = (size_t)3 * BH; a.ld_cat = 3 * H; a.dZ = w.dZ3; a.dz_tstride = (size_t)4 * BH;
-        a.hWa = w.hWa; a.hwa_tstride = BH; a.P = w.P; a.Vt = w.Vt; a.w = p->embed_att_w; a.alpha = w.alpha;
-        a.reg_coef = reg_coef; a.asum = w.asum; a.reg_m = reg_m;
-        a.dhWa = w.dhWa; a.dhwa_tstride = BH; a.dP = w.dPt; a.dVt = w.dVtt; a.dw = grads->embed_att_w;
-        a.deh = w.deh;
-        a.B = B; a.H = H; a.T = Tc; a.Tv = Tv;
-        a.keep = keep; a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32); a.drop_code0 = kDropCode3;
-        a.video_id = video_id; a.sample_id = sample_id;
-        a.img = w.bimg; a.ex = w.bex; a.dctxs = w.brow_; a.sync = w.bsync;
-        if (gated) chain_gate_arm(&gate);
-        const hipError_t re = launch_attn_bwd_chain(a, st);
-        chain_gate_arm(nullptr);
-        HIP_TRY(re);
-        if (gated) {
-            // (reads: dlogits, Y, dY, O3, ctx, Wemb -- final since before the launch; writes: the gradients of embed_word_W/b and embed_nn_Wp/bp,
-            //  which nothing else in this call touches.  A gate that did not fire -- a zero-step launch -- puts the side stream behind the caller's)
-            if (!gate.fired) HIP_TRY(fork_to(st, ss.s, ss.ev[3]));
-            HIP_TRY(launch_gemm_tn(dwout, ss.s));
-            const int rc = output_layer_grads(ss.s);
-            if (rc != S2VT_OK) return rc;
-        }
-        // the embedding block of dz @ W3^T does not feed the recurrence: all steps >= 1 at once, on top of the output layer's block
-        if (Tc > 1) {
-            ASeg sz = make_seg(w.dZ3 + 4 * BH, 4 * H, 4 * H, 0);
-            HIP_TRY(store_call(&sz, 1, p->lstm3_W + (size_t)H * 4 * H, 4 * H, nullptr, w.dEmb + BH, H, R1, H, 0, -1, st, w.dcat + 3 * BH + 2 * H, 3 * H, true));
-        }
-    } else {
-        // split-K plans of the two per-step data-gradient products (order-free): enough slabs for >= ~512 workgroups
-        int sx = (512 + ((3 * H + 63) / 64) - 1) / ((3 * H + 63) / 64) / ((B + 63) / 64);
-        if (sx < 1) sx = 1;
-        if (sx > kXSlabs) sx = kXSlabs;
-        const int kperx = ((4 * H + sx - 1) / sx + BK - 1) / BK * BK, nx = (4 * H + kperx - 1) / kperx;
-        int sq = kQSlabs;
-        while (sq > 1 && H / sq < 128) --sq;
-        const int kperq = ((H + sq - 1) / sq + BK - 1) / BK * BK, nq = (H + kperq - 1) / kperq;
-        for (int t = Tc - 1; t >= 0; --t) {
-            const bool last = t == Tc - 1;
-            AttnCellBwdArgs a;
-            std::memset(&a, 0, sizeof(a));
-            a.gates = w.G3 + (size_t)t * 4 * BH; a.c_new = w.C3 + (t + 1) * BH; a.c_prev = w.C3 + t * BH;
-            a.dcat = w.dcat + (size_t)t * 3 * BH; a.ld_cat = 3 * H;
-            a.dqs = last ? nullptr : w.dqs; a.nq = nq; a.q_stride = BH;
-            a.dxs = last ? nullptr : w.dxs; a.nx = nx; a.x_stride = 3 * BH; a.ld_x = 3 * H; a.x_col0 = 2 * H;
-            a.dc_in = last ? nullptr : w.dc; a.dc_out = w.dc; a.dz = w.dZ3 + (size_t)t * 4 * BH;
-            a.M = B; a.H = H; a.keep = keep; a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32); a.drop_code = kDropCode3 + (uint32_t)t;
-            a.video_id = video_id; a.sample_id = sample_id;
-            hipLaunchKernelGGL(attn_cell_bwd_kernel, dim3((B * H + 255) / 256), dim3(256), 0, st, a);
-            HIP_TRY(hipGetLastError());
-            // d[ctx | emb | h_prev] = dz @ W3^T as split-K slabs: the attention backward sums the ctx and emb blocks, the next
-            // (earlier) step's cell backward the h block
-            HIP_TRY(nn_bwd(w.dZ3 + (size_t)t * 4 * BH, 4 * H, p->lstm3_W, 4 * H, w.dxs, 3 * H, B, 3 * H, 4 * H, sx, 3 * BH, st, sx > 1 ? kSlabTileCfg : -1));
-            AttnBwdArgs g;
-            std::memset(&g, 0, sizeof(g));
-            g.hWa = t > 0 ? w.hWa + t * BH : nullptr; g.P = w.P; g.Vt = w.Vt; g.w = p->embed_att_w; g.alpha = w.alpha + (size_t)t * Tv * B;
-            g.dctx = w.dcat + (size_t)t * 3 * BH + H; g.ld_dctx = 3 * H;
-            g.slabs = w.dxs; g.nslab = nx; g.slab_stride = 3 * BH; g.ld_slab = 3 * H; g.ctx_col0 = 0; g.emb_col0 = H;
-            if (t > 0) { g.demb_dense = w.dcat + (size_t)t * 3 * BH + 2 * H; g.ld_demb = 3 * H; g.demb_out = w.dEmb + t * BH; }
-            if (reg_coef) { g.reg_coef = reg_coef + (size_t)t * B; g.asum = w.asum + (size_t)t * B; g.reg_m = reg_m; }
-            g.dhWa = t > 0 ? w.dhWa + t * BH : nullptr; g.dP = w.dPt; g.dVt = w.dVtt; g.acc = 1; g.dw = grads->embed_att_w;
-            g.Tv = Tv; g.B = B; g.H = H;
-            if (n_video > 0) {
-                AttnBwdRowsArgs r;
-                std::memset(&r, 0, sizeof(r));
-                r.a = g; r.n_video = n_video; r.samples = B / n_video; r.de_rows = w.deh; r.dctx_rows = w.dctxr;
-                HIP_TRY(launch_attn_bwd_rows(r, st));
-            } else {
-                HIP_TRY(launch_attn_bwd(g, st));
-            }
-            // gradient w.r.t. the previous step's dropped output through this step's query: dhWa @ Wa^T (slabs, summed by the cell backward)
-            if (t > 0) HIP_TRY(nn_bwd(w.dhWa + t * BH, H, p->embed_att_Wa, H, w.dqs, H, B, H, H, sq, BH, st, sq > 1 ? kSlabTileCfg : -1));
-        }
-    }
-    // ---- weight gradients of the recurrence, one contraction over all unrolled steps per block
-    {
-        TnArgs a{w.ctx, nullptr, H, w.dZ3, 4 * H, grads->lstm3_W, 4 * H, R, H, 4 * H, 1};                               // rows [0, H): atten
-        a.colsum = grads->lstm3_b;
-        HIP_TRY(launch_gemm_tn(a, st));
-        TnArgs h{w.H3, nullptr, H, w.dZ3, 4 * H, grads->lstm3_W + (size_t)2 * H * 4 * H, 4 * H, R, H, 4 * H, 1};        // rows [2H, 3H): h_prev
-        HIP_TRY(launch_gemm_tn(h, st));
-        if (Tc > 1) {
-            TnArgs e{p->Wemb, w.prev + B, H, w.dZ3 + 4 * BH, 4 * H, grads->lstm3_W + (size_t)H * 4 * H, 4 * H, R1, H, 4 * H, 1};   // rows [H, 2H): current_embed
-            e.gather_rows = V;
-            HIP_TRY(launch_gemm_tn(e, st));
-            TnArgs q{w.O3 + BH, nullptr, H, w.dhWa + BH, H, grads->embed_att_Wa, H, R1, H, H, 1};                       // query of step t = out of step t-1
-            HIP_TRY(launch_gemm_tn(q, st));
-            HIP_TRY(launch_scatter_add_rows(w.dEmb + BH, H, w.prev + B, R1, H, grads->Wemb, H, st));                    // tf.nn.embedding_lookup (:141-142)
-        }
-    }
-    // ---- image part P = V @ Ua + ba and the frame embedding V = video @ encode_image_W + b
-    {
-        TnArgs u{w.Vt, nullptr, H, w.dPt, H, grads->embed_att_Ua, H, Tv * NV, H, H, 1};
-        u.colsum = grads->embed_att_ba;
-        HIP_TRY(launch_gemm_tn(u, st));
-        ASeg sp = make_seg(w.dPt, H, H, 0);
-        HIP_TRY(store_call(&sp, 1, p->embed_att_Ua, H, nullptr, w.dEv, H, Tv * NV, H, 0, -1, st, w.dVtt, H, true));     // dV = dV(ctx path) + dP @ Ua^T
-        TnArgs v{video, w.encidx, D, w.dEv, H, grads->encode_image_W, H, Tv * NV, D, H, 1};
-        v.gather_rows = Tv * NV;
-        v.colsum = grads->encode_image_b;
-        HIP_TRY(launch_gemm_tn(v, st));
-    }
-    if (gated) HIP_TRY(fork_to(ss.s, st, ss.ev[2]));        // join: the caller's stream waits for the side stream's gradients
+    if (x.gated) side_lk.lock();
+
+    const hipError_t e = x.stages();
+    // join: the caller's stream waits for the side stream's gradients (after a failed launch too: nothing stays behind on the side stream
+    // that the caller's stream does not wait for)
+    const hipError_t j = x.side_used ? fork_to(ss.s, x.st, ss.ev[2]) : hipSuccess;
+    HIP_TRY(e);
+    HIP_TRY(j);
     return S2VT_OK;
 }
 
@@ -698,16 +820,9 @@ int s2vt_attn_step_scalars_rows(const float* coef, const float* nll, int64_t R, 
                                 const float* mask_sum_global, float* loss, float* gscale, float* sumsq, const s2vt_dims* d, int32_t n_video,
                                 int32_t samples, void* workspace, size_t workspace_bytes, s2vt_stream stream)
 {
-    if (!coef || !nll || R < 0 || !mask_sum_local || !mask_sum_global || !attn_rows_shape_ok(d, n_video, samples) || !workspace) return S2VT_E_BADARG;
-    if (R > (int64_t)d->n_caption_lstm_step * n_video * samples) return S2VT_E_BADARG;
-    Carver c(workspace, workspace_bytes);
-    AttnWs w;
-    carve_attn(c, d, n_video * samples, &w, n_video);
-    if (!c.ok()) return S2VT_E_WORKSPACE;
-    hipLaunchKernelGGL(attn_step_scalars_kernel, dim3(1), dim3(256), 0, S(stream), coef, nll, reg_coef, w.asum, reg_m, (int)R, mask_sum_local,
-                       mask_sum_global, loss, gscale, sumsq);
-    HIP_TRY(hipGetLastError());
-    return S2VT_OK;
+    const bool ok = attn_rows_shape_ok(d, n_video, samples);
+    return attn_step_scalars_impl(coef, nll, R, reg_coef, reg_m, mask_sum_local, mask_sum_global, loss, gscale, sumsq, d, ok, ok ? n_video * samples : 0,
+                                  n_video, workspace, workspace_bytes, stream);
 }
 
 int s2vt_attn_bptt_bwd_rows(const s2vt_dims* d, const s2vt_attn_params* p, const s2vt_attn_params* grads, const float* video, int32_t n_video,
@@ -739,37 +854,22 @@ int s2vt_attn_decode_greedy(const s2vt_dims* d, const s2vt_attn_params* p, const
     }
     hipLaunchKernelGGL(attn_rows_kernel, dim3((B + 255) / 256), dim3(256), 0, st, w.vid, w.sid, B, video_base);
     HIP_TRY(hipGetLastError());
-    int rc = attn_prologue(d, p, video, B, w, st);
+    const int rc = attn_prologue(d, p, video, B, w.img, st);
     if (rc != S2VT_OK) return rc;
-    NoiseIds none{nullptr, nullptr, 0};
-    NoiseIds ids{w.vid, w.sid, 0};
+    const NoiseIds ids{w.vid, w.sid, 0};
+    DecodeStep s{};     // state in the history slots t / t + 1, one image block per row, the regulariser's sum kept
+    s.p = p; s.img = w.img; s.M = B; s.H = H; s.Tv = Tv; s.store_cfg = s.lstm_cfg = -1;
     for (int t = 0; t < Tc; ++t) {
-        // no dropout in the samplers (self.lstm3, not lstm3_dropout, :188,:235): the query is the clean h
-        HIP_TRY(attn_step(p, w, t, Tv, B, H, w.H3 + t * BH, st));
-        const unsigned long long* tok = t > 0 ? w.packed + (size_t)(t - 1) * B * kPickStride : nullptr;    // the word picked at step t-1 (:196-197)
-        if (t == 0) {
-            ASeg s3 = make_seg(w.ctx, H, H, 0);
-            HIP_TRY(lstm_call(&s3, 1, p->lstm3_W, p->lstm3_b, w.C3, 0, w.C3 + BH, w.H3 + BH, nullptr, nullptr, B, H, 1.0f, none, 0, -1, st));
-            ASeg sy[2] = {make_seg(w.ctx, H, H, H), make_seg(w.H3 + BH, H, H, 0)};
-            HIP_TRY(store_call(sy, 2, p->embed_nn_Wp, H, p->embed_nn_bp, w.Y, H, B, H, 1, -1, st));
-        } else {
-            ASeg s3[3] = {make_seg(p->Wemb, H, H, H, 0, nullptr, tok, kPickStride), make_seg(w.H3 + t * BH, H, H, 2 * H), make_seg(w.ctx + t * BH, H, H, 0)};
-            HIP_TRY(lstm_call(s3, 3, p->lstm3_W, p->lstm3_b, w.C3 + t * BH, 0, w.C3 + (t + 1) * BH, w.H3 + (t + 1) * BH, nullptr, nullptr, B, H, 1.0f,
-                              none, 0, -1, st));
-            ASeg sy[3] = {make_seg(p->Wemb, H, H, 2 * H, 0, nullptr, tok, kPickStride), make_seg(w.ctx + t * BH, H, H, H),
-                          make_seg(w.H3 + (t + 1) * BH, H, H, 0)};
-            HIP_TRY(store_call(sy, 3, p->embed_nn_Wp, H, p->embed_nn_bp, w.Y + t * BH, H, B, H, 1, -1, st));
-        }
-        HIP_TRY(pick_call(w.Y + t * BH, H, p->embed_word_W, p->embed_word_b, B, H, V, ids, t, w.packed + (size_t)t * B * kPickStride, nullptr, -1, st,
-                          kPickStride));
+        s.t = t;
+        s.c_prev = w.C3 + t * BH; s.h_prev = w.H3 + t * BH; s.c_new = w.C3 + (t + 1) * BH; s.h_new = w.H3 + (t + 1) * BH;
+        s.word_key = t > 0 ? w.packed + (size_t)(t - 1) * B * kPickStride : nullptr;                      // the word picked at step t-1 (:196-197)
+        s.hWa = w.hWa + t * BH; s.alpha = w.alpha + (size_t)t * Tv * B; s.asum = w.asum + (size_t)t * B; s.ctx = w.ctx + t * BH; s.Y = w.Y + t * BH;
+        HIP_TRY(decode_step(s, st));
+        HIP_TRY(pick_call(s.Y, H, p->embed_word_W, p->embed_word_b, B, H, V, ids, t, w.packed + (size_t)t * B * kPickStride, nullptr, -1, st, kPickStride));
     }
     hipLaunchKernelGGL(attn_unpack_ids_kernel, dim3((B * Tc + 255) / 256), dim3(256), 0, st, w.packed, ids_out, B, Tc, kPickStride);
     HIP_TRY(hipGetLastError());
-    if (alphas_out) {
-        CopyList cl;
-        if (cl.add(alphas_out, w.alpha, (size_t)Tc * Tv * B * 4)) HIP_TRY(launch_copy_regions(cl, st));
-        else HIP_TRY(hipMemcpyAsync(alphas_out, w.alpha, (size_t)Tc * Tv * B * 4, hipMemcpyDeviceToDevice, st));
-    }
+    if (alphas_out) HIP_TRY(copy_alphas_out(alphas_out, w.alpha, (size_t)Tc * Tv * B * 4, st));
     return S2VT_OK;
 }
 
@@ -816,15 +916,9 @@ static int attn_sample_impl(const s2vt_dims* d, const s2vt_attn_params* p, const
     }
     hipLaunchKernelGGL(attn_sample_rows_kernel, dim3((R + 255) / 256), dim3(256), 0, st, w.vid, w.sid, w.rowvid, R, (int)B, (int)K, (int)video_base);
     HIP_TRY(hipGetLastError());
-    {
-        AttnWs img;
-        std::memset(&img, 0, sizeof(img));
-        img.encidx = w.encidx; img.Vt = w.Vt; img.P = w.P;
-        const int rc = attn_prologue(d, p, video, B, img, st);
-        if (rc != S2VT_OK) return rc;
-    }
-    NoiseIds none{nullptr, nullptr, 0};
-    NoiseIds ids{w.vid, w.sid, seed};
+    const int rc = attn_prologue(d, p, video, B, w.img, st);
+    if (rc != S2VT_OK) return rc;
+    const NoiseIds ids{w.vid, w.sid, seed};
     // stop-at-<eos> mode: tiles for launches whose row count only the device knows -- row tiles small enough that the launch shrinks
     // with the count (the reasoning of the S2VT sampler, api.hip sample_decode).  Dev knobs: S2VT_ATTN_EOS_STORE_CFG (the query and
     // output-layer products; -1 = the cost model's tile, 64 rows at these widths), S2VT_ATTN_EOS_LSTM_CFG, S2VT_ATTN_EOS_PICK_CFG.
@@ -839,40 +933,21 @@ static int attn_sample_impl(const s2vt_dims* d, const s2vt_attn_params* p, const
         static const int pk = [] { const char* e = getenv("S2VT_ATTN_EOS_PICK_CFG"); return e ? atoi(e) : -1; }();
         scfg = sk; lcfg = R > 64 ? lk : -1; pcfg = pk;
     }
+    DecodeStep s{};     // state ping-pong (step t reads slot t & 1), the R rows over the B image blocks, one step's worth of everything else
+    s.p = p; s.img = w.img; s.M = R; s.H = H; s.Tv = Tv; s.store_cfg = scfg; s.lstm_cfg = lcfg;
+    s.hWa = w.hWa; s.alpha = w.alpha; s.ctx = w.ctx; s.Y = w.Y; s.row_video = w.rowvid; s.n_video = B;
     for (int t = 0; t < Tc; ++t) {
-        const float *c_prev = w.c[t & 1], *h_prev = w.h[t & 1];
-        float *c_new = w.c[(t & 1) ^ 1], *h_new = w.h[(t & 1) ^ 1];
-        const unsigned long long* tok = t > 0 ? w.packed + (size_t)(t - 1) * R * kPickStride : nullptr;    // the word picked at step t-1 (:196-197)
-        const int* omap = nullptr;
-        const int* mdev = nullptr;
+        s.t = t;
+        s.c_prev = w.c[t & 1]; s.h_prev = w.h[t & 1]; s.c_new = w.c[(t & 1) ^ 1]; s.h_new = w.h[(t & 1) ^ 1];
+        s.word_key = t > 0 ? w.packed + (size_t)(t - 1) * R * kPickStride : nullptr;                      // the word picked at step t-1 (:196-197)
         if (stop_at_eos) {
             // a finished row's state stays in whichever slot it was last written to and is never read again; its later pick words stay zero
-            HIP_TRY(launch_live_rows(tok, kPickStride, w.live[(t + 1) & 1], w.nlive + (t > 0 ? t - 1 : 0), w.live[t & 1], w.nlive + t, R, st));
-            omap = w.live[t & 1]; mdev = w.nlive + t;
+            HIP_TRY(launch_live_rows(s.word_key, kPickStride, w.live[(t + 1) & 1], w.nlive + (t > 0 ? t - 1 : 0), w.live[t & 1], w.nlive + t, R, st));
+            s.live = w.live[t & 1]; s.n_live = w.nlive + t;
         }
-        if (t > 0) {       // the query is the clean h (no dropout in the samplers, :188,:235); step 0: the zero state
-            ASeg sq = make_seg(h_prev, H, H, 0);
-            HIP_TRY(store_call(&sq, 1, p->embed_att_Wa, H, nullptr, w.hWa, H, R, H, 0, scfg, st, nullptr, 0, false, omap, mdev));
-        }
-        AttnFwdArgs a;
-        std::memset(&a, 0, sizeof(a));
-        a.hWa = t > 0 ? w.hWa : nullptr; a.P = w.P; a.Vt = w.Vt; a.w = p->embed_att_w; a.alpha = w.alpha; a.ctx = w.ctx;
-        a.Tv = Tv; a.B = R; a.H = H; a.row_video = w.rowvid; a.n_video = B;
-        a.live = omap; a.n_live = mdev;
-        HIP_TRY(launch_attn_fwd(a, st));
-        if (t == 0) {
-            ASeg s3 = make_seg(w.ctx, H, H, 0);
-            HIP_TRY(lstm_call(&s3, 1, p->lstm3_W, p->lstm3_b, c_prev, 0, c_new, h_new, nullptr, nullptr, R, H, 1.0f, none, 0, lcfg, st, nullptr, 0, 0, omap, mdev));
-            ASeg sy[2] = {make_seg(w.ctx, H, H, H), make_seg(h_new, H, H, 0)};
-            HIP_TRY(store_call(sy, 2, p->embed_nn_Wp, H, p->embed_nn_bp, w.Y, H, R, H, 1, scfg, st, nullptr, 0, false, omap, mdev));
-        } else {
-            ASeg s3[3] = {make_seg(p->Wemb, H, H, H, 0, nullptr, tok, kPickStride), make_seg(h_prev, H, H, 2 * H), make_seg(w.ctx, H, H, 0)};
-            HIP_TRY(lstm_call(s3, 3, p->lstm3_W, p->lstm3_b, c_prev, 0, c_new, h_new, nullptr, nullptr, R, H, 1.0f, none, 0, lcfg, st, nullptr, 0, 0, omap, mdev));
-            ASeg sy[3] = {make_seg(p->Wemb, H, H, 2 * H, 0, nullptr, tok, kPickStride), make_seg(w.ctx, H, H, H), make_seg(h_new, H, H, 0)};
-            HIP_TRY(store_call(sy, 3, p->embed_nn_Wp, H, p->embed_nn_bp, w.Y, H, R, H, 1, scfg, st, nullptr, 0, false, omap, mdev));
-        }
+        HIP_TRY(decode_step(s, st));
         HIP_TRY(pick_call(w.Y, H, p->embed_word_W, p->embed_word_b, R, H, V, ids, t, w.packed + (size_t)t * R * kPickStride, nullptr, pcfg, st, kPickStride,
-                          omap, mdev));
+                          s.live, s.n_live));
     }
     if (K > 0) {
         hipLaunchKernelGGL(attn_unpack_rows_kernel, dim3((K * B * Tc + 255) / 256), dim3(256), 0, st, w.packed, ids_out, R, 0, (int)(K * B), Tc, kPickStride);
@@ -934,41 +1009,17 @@ int s2vt_attn_beam_step(const s2vt_dims* d, const s2vt_attn_params* p, int32_t B
     if (R == 0) return S2VT_OK;
     const int H = d->lstm_dim, V = d->n_words, Tv = d->n_video_lstm_step;
     hipStream_t st = S(stream);
-    const float *c_prev = w.c[(t & 1) ^ 1], *h_prev = w.h[(t & 1) ^ 1];
-    float *c_new = w.c[t & 1], *h_new = w.h[t & 1];
     // 1. gather: the parents' cell state (zeros at step 0), the clamped parent rows and words
-    hipLaunchKernelGGL(attn_beam_gather_kernel, dim3(R), dim3(256), 0, st, parent, word, (int)t, (int)(B * beam), H, V, c_prev, w.cg, w.par, w.word);
+    hipLaunchKernelGGL(attn_beam_gather_kernel, dim3(R), dim3(256), 0, st, parent, word, (int)t, (int)(B * beam), H, V, w.c[(t & 1) ^ 1], w.cg, w.par, w.word);
     HIP_TRY(hipGetLastError());
-    // 2. query projection of the parent's clean h (no dropout in the samplers, :188), gathered through the parent index
-    //    (step 0: the query is the zero state, h_prev @ Wa = 0)
-    if (t > 0) {
-        ASeg sq = make_seg(h_prev, H, H, 0, 0, w.par);
-        HIP_TRY(store_call(&sq, 1, p->embed_att_Wa, H, nullptr, w.hWa, H, R, H, 0, -1, st));
-    }
-    // 3. score -> softmax -> context, row -> video: hypothesis m reads its video's one [Tv, H] block of P and Vt
-    {
-        AttnFwdArgs a;
-        std::memset(&a, 0, sizeof(a));
-        a.hWa = t > 0 ? w.hWa : nullptr; a.P = w.img.P; a.Vt = w.img.Vt; a.w = p->embed_att_w;
-        a.alpha = alphas_out ? alphas_out : w.alpha; a.ctx = w.ctx;
-        a.Tv = Tv; a.B = R; a.H = H;
-        a.row_video = video_of_row; a.n_video = B;
-        HIP_TRY(launch_attn_fwd(a, st));
-    }
-    // 4. LSTM3: one chain over the word's embedding rows (none at step 0: current_embed = 0, :169), the parent's h, the context;
-    // 5. output layer tanh([embed ; atten ; output1] @ Wp + bp) in the order [2H:3H], [H:2H], [0:H]
-    NoiseIds none{nullptr, nullptr, 0};
-    if (t == 0) {
-        ASeg s3 = make_seg(w.ctx, H, H, 0);
-        HIP_TRY(lstm_call(&s3, 1, p->lstm3_W, p->lstm3_b, w.cg, 0, c_new, h_new, nullptr, nullptr, R, H, 1.0f, none, 0, -1, st));
-        ASeg sy[2] = {make_seg(w.ctx, H, H, H), make_seg(h_new, H, H, 0)};
-        HIP_TRY(store_call(sy, 2, p->embed_nn_Wp, H, p->embed_nn_bp, w.Y, H, R, H, 1, -1, st));
-    } else {
-        ASeg s3[3] = {make_seg(p->Wemb, H, H, H, 0, w.word), make_seg(h_prev, H, H, 2 * H, 0, w.par), make_seg(w.ctx, H, H, 0)};
-        HIP_TRY(lstm_call(s3, 3, p->lstm3_W, p->lstm3_b, w.cg, 0, c_new, h_new, nullptr, nullptr, R, H, 1.0f, none, 0, -1, st));
-        ASeg sy[3] = {make_seg(p->Wemb, H, H, 2 * H, 0, w.word), make_seg(w.ctx, H, H, H), make_seg(h_new, H, H, 0)};
-        HIP_TRY(store_call(sy, 3, p->embed_nn_Wp, H, p->embed_nn_bp, w.Y, H, R, H, 1, -1, st));
-    }
+    // 2. - 5. the decode step on the R hypotheses: state ping-pong (step t writes slot t & 1; rows are permuted between steps), the
+    // parent's clean h gathered through the parent index and its cell state from the dense copy, the word's embedding rows through
+    // the clamped word, row -> video: hypothesis m reads its video's one [Tv, H] block of P and Vt
+    DecodeStep s{};
+    s.p = p; s.img = w.img; s.t = t; s.M = R; s.H = H; s.Tv = Tv; s.store_cfg = s.lstm_cfg = -1;
+    s.c_prev = w.cg; s.h_prev = w.h[(t & 1) ^ 1]; s.h_rows = w.par; s.c_new = w.c[t & 1]; s.h_new = w.h[t & 1]; s.word_idx = w.word;
+    s.hWa = w.hWa; s.alpha = alphas_out ? alphas_out : w.alpha; s.ctx = w.ctx; s.Y = w.Y; s.row_video = video_of_row; s.n_video = B;
+    HIP_TRY(decode_step(s, st));
     // 6. vocabulary logits on the store tile, 7. top-k words and their log-probabilities
     float* logits = logits_out ? logits_out : w.logits;
     ASeg so = make_seg(w.Y, H, H, 0);
