@@ -1,6 +1,8 @@
 // api.hip -- extern "C" boundary of libs2vt_hip.so (declared in include/s2vt.h) and the on-device
-// drivers of the sampler loops.  Everything here is host code + a few trivial helper kernels; the
-// contraction kernels live in gemm_mfma.h / fwd.hip.
+// drivers of the S2VT sampler: the workspace carve (carve_sample_enc, carve_sample), the encode half (sample_encode), the
+// LSTM2 decode step shared with the beam search (lstm2_step) and the decode driver over the stages of SampleDecode
+// (sample_decode).  Everything here is host code + a few trivial helper kernels; the contraction kernels live in
+// gemm_mfma.h / fwd.hip.
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
@@ -162,11 +164,12 @@ int s2vt_math_eval(int fn, const float* x, float* y, int64_t n, s2vt_stream stre
     return S2VT_OK;
 }
 
-int s2vt_gemm_nt(const s2vt_operand* segs, int32_t nseg, const float* Wt, int32_t ldw, const float* bias, const float* Cinit,
-                 int32_t ldcinit, float* C, int32_t ldc, int32_t M, int32_t N, int32_t act_tanh, int32_t tile_cfg,
-                 s2vt_stream stream)
+// C = act([segs] @ W + bias) continuing Cinit; W as [k][n] rows (ldw >= N) or, w_transposed, as [n][k] rows (ldw >= the segments' K)
+static int gemm_impl(const s2vt_operand* segs, int32_t nseg, const float* W, int32_t ldw, const float* bias, const float* Cinit,
+                     int32_t ldcinit, float* C, int32_t ldc, int32_t M, int32_t N, int32_t act_tanh, int32_t tile_cfg,
+                     s2vt_stream stream, bool w_transposed)
 {
-    if (!segs || nseg < 1 || nseg > 3 || !Wt || !C || M < 0 || N <= 0 || ldc < N) return S2VT_E_BADARG;
+    if (!segs || nseg < 1 || nseg > 3 || !W || !C || M < 0 || N <= 0 || ldc < N || (!w_transposed && ldw < N)) return S2VT_E_BADARG;
     if (Cinit && ldcinit < N) return S2VT_E_BADARG;
     ASeg a[3];
     int kw = 0;
@@ -175,10 +178,17 @@ int s2vt_gemm_nt(const s2vt_operand* segs, int32_t nseg, const float* Wt, int32_
         seg_from_operand(a[i], &segs[i], kw);
         kw += segs[i].k;
     }
-    if (ldw < kw) return S2VT_E_BADARG;
+    if (w_transposed && ldw < kw) return S2VT_E_BADARG;
     if (M == 0) return S2VT_OK;
-    HIP_TRY(store_call(a, nseg, Wt, ldw, bias, C, ldc, M, N, act_tanh ? 1 : 0, tile_cfg, S(stream), Cinit, ldcinit, true));
+    HIP_TRY(store_call(a, nseg, W, ldw, bias, C, ldc, M, N, act_tanh ? 1 : 0, tile_cfg, S(stream), Cinit, ldcinit, w_transposed));
     return S2VT_OK;
+}
+
+int s2vt_gemm_nt(const s2vt_operand* segs, int32_t nseg, const float* Wt, int32_t ldw, const float* bias, const float* Cinit,
+                 int32_t ldcinit, float* C, int32_t ldc, int32_t M, int32_t N, int32_t act_tanh, int32_t tile_cfg,
+                 s2vt_stream stream)
+{
+    return gemm_impl(segs, nseg, Wt, ldw, bias, Cinit, ldcinit, C, ldc, M, N, act_tanh, tile_cfg, stream, true);
 }
 
 int s2vt_gumbel_eval(uint64_t seed, int32_t video, int32_t sample, int32_t step, float* out, int32_t V, s2vt_stream stream)
@@ -194,18 +204,7 @@ int s2vt_gemm(const s2vt_operand* segs, int32_t nseg, const float* W, int32_t ld
               int32_t ldcinit, float* C, int32_t ldc, int32_t M, int32_t N, int32_t act_tanh, int32_t tile_cfg,
               s2vt_stream stream)
 {
-    if (!segs || nseg < 1 || nseg > 3 || !W || !C || M < 0 || N <= 0 || ldw < N || ldc < N) return S2VT_E_BADARG;
-    if (Cinit && ldcinit < N) return S2VT_E_BADARG;
-    ASeg a[3];
-    int kw = 0;
-    for (int i = 0; i < nseg; ++i) {
-        if (segs[i].k < 0 || (segs[i].ptr && segs[i].ld < segs[i].k)) return S2VT_E_BADARG;
-        seg_from_operand(a[i], &segs[i], kw);
-        kw += segs[i].k;
-    }
-    if (M == 0) return S2VT_OK;
-    HIP_TRY(store_call(a, nseg, W, ldw, bias, C, ldc, M, N, act_tanh ? 1 : 0, tile_cfg, S(stream), Cinit, ldcinit));
-    return S2VT_OK;
+    return gemm_impl(segs, nseg, W, ldw, bias, Cinit, ldcinit, C, ldc, M, N, act_tanh, tile_cfg, stream, false);
 }
 
 int s2vt_lstm_cell_fwd(const s2vt_operand* x0, const s2vt_operand* x1, const float* h_prev, const float* c_prev,
@@ -274,33 +273,51 @@ hipError_t launch_live_rows(const unsigned long long* picked, int stride, const 
     return hipGetLastError();
 }
 
-// Workspace of one sampler pass.  Everything up to `split` depends on B only (the encode half); the rest on
-// the number of decode rows R.
+// The sampler's environment switches, read once per process.  (decode_loop.hip and decode4.hip read the two forms' own switches.)
+struct SamplerKnobs {
+    bool frag_small;              // S2VT_DECLOOP unset or >= 1: the fragment-order operands are carved at <= 64 rows
+    bool frag_big;                // S2VT_DECLOOP >= 2 or S2VT_DEC4=1: also at 257-384 rows
+    int eos_lstm_cfg, eos_pick_cfg;   // dev knobs: tiles of the early-exit mode's launches (S2VT_EOS_LSTM_CFG, default kLstm[4] = gw32x16u; S2VT_EOS_PICK_CFG)
+};
+const SamplerKnobs& sampler_knobs()
+{
+    static const SamplerKnobs k = [] {
+        const char* loop = getenv("S2VT_DECLOOP"); const char* dec4 = getenv("S2VT_DEC4");
+        const char* lc = getenv("S2VT_EOS_LSTM_CFG"); const char* pc = getenv("S2VT_EOS_PICK_CFG");
+        return SamplerKnobs{!loop || atoi(loop) >= 1, (loop && atoi(loop) >= 2) || (dec4 && dec4[0] == '1'), lc ? atoi(lc) : 4, pc ? atoi(pc) : -1};
+    }();
+    return k;
+}
+
+// The eight regions of the encode half: they depend on B only and lead the sampler's and the beam search's workspaces.
+void carve_sample_enc(Carver& c, const s2vt_dims* d, int B, SampleEnc& e)
+{
+    const size_t H = d->lstm_dim, E = d->word_dim, Tv = d->n_video_lstm_step, T = Tv + d->n_caption_lstm_step;
+    e.emb = c.take<float>((size_t)B * Tv * E);
+    e.Xp1 = c.take<float>((size_t)B * Tv * 4 * H);
+    e.c1 = c.take<float>((T + 1) * B * H); e.h1 = c.take<float>((T + 1) * B * H);     // LSTM1 state history, slot 0 = zeros
+    e.G1 = c.take<float>(T * B * 4 * H);                                                // LSTM1 activated gates (reused by the update pass)
+    e.P2 = c.take<float>(T * B * 4 * H);                                                // h1[t+1] @ W2[0:H] for every step
+    e.c2e = c.take<float>((Tv + 1) * (size_t)B * H); e.h2e = c.take<float>((Tv + 1) * (size_t)B * H);
+}
+
+// Workspace of one sampler pass: the encode half, then what depends on the number of decode rows R.
 size_t carve_sample(Carver& c, const s2vt_dims* d, int B, int R, SampleWs* w)
 {
-    const size_t H = d->lstm_dim, E = d->word_dim, Tv = d->n_video_lstm_step, Tc = d->n_caption_lstm_step, T = Tv + Tc;
+    const size_t H = d->lstm_dim, E = d->word_dim, Tc = d->n_caption_lstm_step;
     SampleWs t;
-    t.emb = c.take<float>((size_t)B * Tv * E);
-    t.Xp1 = c.take<float>((size_t)B * Tv * 4 * H);
-    t.c1 = c.take<float>((T + 1) * B * H); t.h1 = c.take<float>((T + 1) * B * H);     // LSTM1 state history, slot 0 = zeros
-    t.G1 = c.take<float>(T * B * 4 * H);                                                // LSTM1 activated gates (reused by the update pass)
-    t.P2 = c.take<float>(T * B * 4 * H);                                                // h1[t+1] @ W2[0:H] for every step
-    t.c2e = c.take<float>((Tv + 1) * (size_t)B * H); t.h2e = c.take<float>((Tv + 1) * (size_t)B * H);
+    carve_sample_enc(c, d, B, t);
     for (int i = 0; i < 2; ++i) { t.c2[i] = c.take<float>((size_t)R * H); t.h2[i] = c.take<float>((size_t)R * H); }
     t.packed = c.take<unsigned long long>((size_t)Tc * R * kPickStride);
     t.vid = c.take<int32_t>(R); t.sid = c.take<int32_t>(R); t.bos = c.take<int32_t>(R);
     t.chain_sync = c.take<unsigned>(kChainSyncBytes / 4);
     t.chain_abuf = c.take<float>(chain_scratch_floats((int)H));
     t.wemb_p = t.w2_p = t.himg[0] = t.himg[1] = nullptr;
-    // fragment-order operands of the persistent decode loop (decode_loop.hip: default at <= 64 rows since round 6; S2VT_DECLOOP=2 / S2VT_DEC4=1 also at
+    // fragment-order operands of the persistent decode loop (decode_loop.hip: default at <= 64 rows; S2VT_DECLOOP=2 / S2VT_DEC4=1 also at
     // 257-384 rows, where both forms measured no gain) -- sized by the shape and the two opt-in switches, never by the device: every caller of the
     // size query sees the same carve.  (24.6 + 40 MB of packed operands at the bench dimensions: not taken at 384 rows unless asked for.)
-    static const bool big_rows = [] {
-        const char* a = getenv("S2VT_DECLOOP"); const char* b = getenv("S2VT_DEC4");
-        return (a && atoi(a) >= 2) || (b && b[0] == '1');
-    }();
-    static const bool small_rows = [] { const char* a = getenv("S2VT_DECLOOP"); return !a || atoi(a) >= 1; }();
-    if (((R <= 64 && small_rows) || (R > 256 && R <= 384 && big_rows)) && (H & 3) == 0 && H >= 132 &&
+    const SamplerKnobs& k = sampler_knobs();
+    if (((R <= 64 && k.frag_small) || (R > 256 && R <= 384 && k.frag_big)) && (H & 3) == 0 && H >= 132 &&
         (size_t)d->n_words * ((E + 15) / 16 * 16) * 4 < (1ull << 31)) {
         Dec4Geom q;
         decode4_geometry(R, (int)H, (int)E, &q);
@@ -346,7 +363,7 @@ hipError_t lstm_recurrence(const float* W, int kw0, const float* bias, const flo
 // Encoding stage (tf_s2vt.py:97-122) plus everything of the decoding stage that does not depend on a
 // sampled word: frame embedding, the whole LSTM1 trajectory, its products with the out1 rows of W2, LSTM2 over
 // the Tv frames.  Leaves the encoder state in slot Tv of w.c2e / w.h2e.
-int sample_encode(const s2vt_dims* d, const s2vt_params* p, const float* video, int B, const SampleWs& w, s2vt_stream stream)
+int sample_encode(const s2vt_dims* d, const s2vt_params* p, const float* video, int B, const SampleEnc& w, s2vt_stream stream)
 {
     const int H = d->lstm_dim, E = d->word_dim, Tv = d->n_video_lstm_step, Tc = d->n_caption_lstm_step;
     hipStream_t st = S(stream);
@@ -385,65 +402,58 @@ int sample_encode(const s2vt_dims* d, const s2vt_params* p, const float* video, 
     return S2VT_OK;
 }
 
-// side streams of the row-group decode loop (S2VT_SAMPLE_GROUPS), created once per process
-struct GroupStreams {
-    hipStream_t s[2] = {nullptr, nullptr};
-    hipEvent_t fork = nullptr, join[2] = {nullptr, nullptr};
-    bool ok = false;
-};
-GroupStreams& group_streams()
+// The chain of the cell on [out1 ; word ; h2] continues the hoisted out1 partial (W2 rows 0:H) with the word's rows
+// of Wemb at kw = H, then h2 at kw = H + E.
+hipError_t lstm2_step(const Lstm2Step& s, hipStream_t st)
 {
-    static GroupStreams gs = [] {
-        GroupStreams t;
-        for (auto& x : t.s)
-            if (hipStreamCreateWithFlags(&x, hipStreamNonBlocking) != hipSuccess) return t;
-        if (hipEventCreateWithFlags(&t.fork, hipEventDisableTiming) != hipSuccess) return t;
-        for (auto& e : t.join)
-            if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return t;
-        t.ok = true;
-        return t;
-    }();
-    return gs;
+    const NoiseIds none{nullptr, nullptr, 0};
+    ASeg s2[2] = {make_seg(s.p->Wemb, s.E, s.E, s.H, 0, s.word_idx, s.word_key, s.word_key ? kPickStride : 1),
+                  make_seg(s.h_prev, s.H, s.H, s.H + s.E, s.state_rowmod)};
+    return lstm_call(s2, 2, s.p->lstm2_W, s.p->lstm2_b, s.c_prev, s.state_rowmod, s.c_new, s.h_new, nullptr, nullptr, s.M, s.H, 1.0f, none, 0,
+                     s.lstm_cfg, st, s.partial, 4 * s.H, s.partial_rowmod, s.live, s.n_live);
 }
 
-// Decoding stage (tf_s2vt.py:126-153 as specialised by the samplers): LSTM2 + vocab at M = R rows, K
-// multinomial row blocks then (with_greedy) one argmax block; the R rows of a video share its out1
-// partial (row % B).  Needs sample_encode's results in the same workspace.
-int sample_decode(const s2vt_dims* d, const s2vt_params* p, int B, int K, int with_greedy, uint64_t seed, int video_base,
-                  int32_t* ids_out, const SampleWs& w, s2vt_stream stream, int stop_at_eos)
-{
-    const int H = d->lstm_dim, E = d->word_dim, V = d->n_words, Tv = d->n_video_lstm_step, Tc = d->n_caption_lstm_step;
-    const int R = (K + (with_greedy ? 1 : 0)) * B;
-    hipStream_t st = S(stream);
-    const size_t BH = (size_t)B * H;
+// (inside a stage: hand a failed launch's error to the driver, whose HIP_TRY records it)
+#define HIP_CHECK(expr) do { const hipError_t _e = (expr); if (_e != hipSuccess) return _e; } while (0)
+
+// One decode call of the sampler: R rows = K multinomial row blocks then (with_greedy) one argmax block, row r of video r % B.  The
+// workspace may be carved for more rows than the call decodes (session API): whether the fragment-order operands exist follows the
+// carve, every stride, grid and eligibility test the R of the call.  The stages are straight-line.
+struct SampleDecode {
+    const s2vt_params* p; const SampleWs& w;
+    int B, K, R; uint64_t seed; int video_base; bool stop_at_eos; hipStream_t st;
+    int H, E, V, Tv, Tc;
+    size_t BH, enc;          // enc: where sample_encode left the encoder state, slot Tv of the c2e / h2e history
+    Dec4Geom q4;
+
+    unsigned long long* picks(int t) const { return w.packed + (size_t)t * R * kPickStride; }     // the packed picks of step t [R]
+    const float* partial(int t) const { return w.P2 + (size_t)(Tv + t) * 4 * BH; }                // the out1 partial of step t [B][4H]
+    NoiseIds ids() const { return NoiseIds{w.vid, w.sid, seed}; }
+
+    hipError_t open()
     {
         ZeroList z;
         z.add(w.packed, (size_t)Tc * R * kPickStride * 8);
-        HIP_TRY(launch_zero_regions(z, st));
+        HIP_CHECK(launch_zero_regions(z, st));
+        hipLaunchKernelGGL(sampler_rows_kernel, dim3((R + 255) / 256), dim3(256), 0, st, w.vid, w.sid, B, K, R, video_base);
+        hipLaunchKernelGGL(fill_i32_kernel, dim3((R + 255) / 256), dim3(256), 0, st, w.bos, 1, R);   // <bos> = 1
+        return hipGetLastError();
     }
-    hipLaunchKernelGGL(sampler_rows_kernel, dim3((R + 255) / 256), dim3(256), 0, st, w.vid, w.sid, B, K, R, video_base);
-    hipLaunchKernelGGL(fill_i32_kernel, dim3((R + 255) / 256), dim3(256), 0, st, w.bos, 1, R);   // <bos> = 1
-    HIP_TRY(hipGetLastError());
-    NoiseIds none{nullptr, nullptr, 0};
-    NoiseIds ids{w.vid, w.sid, seed};
-    const size_t enc = (size_t)Tv * B * H;   // where sample_encode left the encoder state: slot Tv of the history
-    int cur2 = 0;
-    // 257-384 rows: the LSTM2 step runs on fragment-order operands packed once per call (decode4.hip); same chain, same bits
-    const bool loop1 = !stop_at_eos && w.wemb_p && (B & 15) == 0 && decode_loop_eligible(R, H, E, V) && chain_operands_ok(p->embed_word_W, V, w.himg[0]);
-    const bool dec4 = !stop_at_eos && (loop1 || (w.wemb_p && decode4_eligible(R, H, E)));
-    Dec4Geom q4;
-    if (dec4) {
+    // the fragment-order operands (decode4.hip), packed once per call: same chain, same bits
+    hipError_t pack_fragments()
+    {
         decode4_geometry(R, H, E, &q4);
-        HIP_TRY(decode4_pack(p->Wemb, p->lstm2_W, V, H, E, q4, w.wemb_p, w.w2_p, st));
-        HIP_TRY(decode4_state_to_image(w.h2e + enc, B, R, H, q4, w.himg[0], st));
-        HIP_TRY(hipMemsetAsync(w.himg[1], 0, (size_t)q4.img_tiles * q4.hgp * 1024, st));
+        HIP_CHECK(decode4_pack(p->Wemb, p->lstm2_W, V, H, E, q4, w.wemb_p, w.w2_p, st));
+        HIP_CHECK(decode4_state_to_image(w.h2e + enc, B, R, H, q4, w.himg[0], st));
+        return hipMemsetAsync(w.himg[1], 0, (size_t)q4.img_tiles * q4.hgp * 1024, st);
     }
-    if (loop1) {
-        // all Tc steps -- LSTM2, vocabulary logits, pick -- in one persistent launch (decode_loop.hip)
+    // all Tc steps -- LSTM2, vocabulary logits, pick -- in one persistent launch (decode_loop.hip)
+    hipError_t persistent_loop()
+    {
         DecLoopLaunch a;
         std::memset(&a, 0, sizeof(a));
         a.wemb_p = w.wemb_p; a.w2_p = w.w2_p; a.bias2 = p->lstm2_b;
-        a.P2 = w.P2 + (size_t)Tv * 4 * BH; a.p2_tstride = (size_t)4 * BH; a.ldp2 = 4 * H; a.B = B;
+        a.P2 = partial(0); a.p2_tstride = (size_t)4 * BH; a.ldp2 = 4 * H; a.B = B;
         a.c0 = w.c2e + enc;
         a.himg0 = w.himg[0]; a.himg1 = w.himg[1];
         a.packed = w.packed; a.pick_stride = kPickStride;
@@ -451,101 +461,72 @@ int sample_decode(const s2vt_dims* d, const s2vt_params* p, int B, int K, int wi
         a.seed = seed; a.video_base = video_base; a.noise_rows = K * B;
         a.R = R; a.H = H; a.E = E; a.V = V; a.Tc = Tc;
         a.sync = w.chain_sync;
-        HIP_TRY(launch_decode_loop(a, q4, st));
-        hipLaunchKernelGGL(unpack_ids_kernel, dim3((R * Tc + 255) / 256), dim3(256), 0, st, w.packed, ids_out, R, Tc, kPickStride);
-        HIP_TRY(hipGetLastError());
-        return S2VT_OK;
+        return launch_decode_loop(a, q4, st);
     }
-    // Row groups (opt-in, S2VT_SAMPLE_GROUPS=2|3; round-4 verdict item 2): rows never interact, so the R rows can be cut into groups of whole
-    // sample blocks, each group running its own chain of {LSTM2 step, pick} launches on a stream of its own -- pick(t) of one group
-    // beside LSTM2(t+1) of another.  Same chains, same noise ids per row: token ids bit-identical.  Measured: see there.
-    static const int n_groups = [] { const char* e = getenv("S2VT_SAMPLE_GROUPS"); const int g = e ? atoi(e) : 1; return g < 1 ? 1 : (g > 3 ? 3 : g); }();
-    static const int g_lcfg = [] { const char* e = getenv("S2VT_GROUP_LSTM_CFG"); return e ? atoi(e) : -1; }();     // dev knobs: tiles of the group launches
-    static const int g_pcfg = [] { const char* e = getenv("S2VT_GROUP_PICK_CFG"); return e ? atoi(e) : -1; }();
-    const int blocks = R / B;
-    if (n_groups > 1 && !dec4 && !stop_at_eos && blocks >= n_groups) {
-        GroupStreams& gs = group_streams();
-        if (gs.ok) {
-            HIP_TRY(hipEventRecord(gs.fork, st));
-            int b0 = 0;
-            for (int g = 0; g < n_groups; ++g) {
-                const int nb = blocks / n_groups + (g < blocks % n_groups ? 1 : 0);
-                const int r0 = b0 * B, Rg = nb * B;
-                b0 += nb;
-                hipStream_t sg = g == 0 ? st : gs.s[g - 1];
-                if (g > 0) HIP_TRY(hipStreamWaitEvent(sg, gs.fork, 0));
-                NoiseIds idg{w.vid + r0, w.sid + r0, seed};
-                int cur = 0;
-                for (int t = 0; t < Tc; ++t) {
-                    const int nxt = cur ^ 1;
-                    const float* h2p = t == 0 ? w.h2e + enc : w.h2[cur] + (size_t)r0 * H;
-                    const float* c2p = t == 0 ? w.c2e + enc : w.c2[cur] + (size_t)r0 * H;
-                    const int smod = t == 0 ? B : 0;
-                    ASeg s2[2] = {t == 0 ? make_seg(p->Wemb, E, E, H, 0, w.bos)
-                                         : make_seg(p->Wemb, E, E, H, 0, nullptr, w.packed + ((size_t)(t - 1) * R + r0) * kPickStride, kPickStride),
-                                  make_seg(h2p, H, H, H + E, smod)};
-                    HIP_TRY(lstm_call(s2, 2, p->lstm2_W, p->lstm2_b, c2p, smod, w.c2[nxt] + (size_t)r0 * H, w.h2[nxt] + (size_t)r0 * H, nullptr, nullptr,
-                                      Rg, H, 1.0f, none, 0, g_lcfg, sg, w.P2 + (size_t)(Tv + t) * 4 * BH, 4 * H, B));
-                    HIP_TRY(pick_call(w.h2[nxt] + (size_t)r0 * H, H, p->embed_word_W, p->embed_word_b, Rg, H, V, idg, t,
-                                      w.packed + ((size_t)t * R + r0) * kPickStride, nullptr, g_pcfg, sg, kPickStride));
-                    cur = nxt;
-                }
-                if (g > 0) {
-                    HIP_TRY(hipEventRecord(gs.join[g - 1], sg));
-                    HIP_TRY(hipStreamWaitEvent(st, gs.join[g - 1], 0));
-                }
-            }
-            hipLaunchKernelGGL(unpack_ids_kernel, dim3((R * Tc + 255) / 256), dim3(256), 0, st, w.packed, ids_out, R, Tc, kPickStride);
-            HIP_TRY(hipGetLastError());
-            return S2VT_OK;
-        }
+    // step t with the LSTM2 cell on the fragment-order operands (decode4.hip), then the pick
+    hipError_t step_fragment(int t)
+    {
+        const int nxt = (t + 1) & 1;
+        Dec4Launch a;
+        std::memset(&a, 0, sizeof(a));
+        a.wemb_p = w.wemb_p; a.w2_p = w.w2_p; a.bias = p->lstm2_b;
+        a.cinit = partial(t); a.ldcinit = 4 * H; a.cinit_rowmod = B;
+        a.tok = t == 0 ? nullptr : picks(t - 1); a.tok_stride = kPickStride; a.tok_const = 1;     // <bos> = 1
+        a.himg_in = w.himg[t & 1]; a.himg_out = w.himg[nxt];
+        a.c_prev = t == 0 ? w.c2e + enc : w.c2[t & 1]; a.cprev_rowmod = t == 0 ? B : 0;
+        a.c_new = w.c2[nxt]; a.h_new = w.h2[nxt];
+        a.R = R; a.H = H; a.E = E; a.V = V;
+        HIP_CHECK(launch_decode_lstm4(a, q4, st));
+        return pick_call(w.h2[nxt], H, p->embed_word_W, p->embed_word_b, R, H, V, ids(), t, picks(t), nullptr, -1, st, kPickStride);
     }
-    for (int t = 0; t < Tc; ++t) {
-        const int nxt2 = cur2 ^ 1;
-        if (dec4) {
-            Dec4Launch a;
-            std::memset(&a, 0, sizeof(a));
-            a.wemb_p = w.wemb_p; a.w2_p = w.w2_p; a.bias = p->lstm2_b;
-            a.cinit = w.P2 + (size_t)(Tv + t) * 4 * BH; a.ldcinit = 4 * H; a.cinit_rowmod = B;
-            a.tok = t == 0 ? nullptr : w.packed + (size_t)(t - 1) * R * kPickStride; a.tok_stride = kPickStride; a.tok_const = 1;     // <bos> = 1
-            a.himg_in = w.himg[t & 1]; a.himg_out = w.himg[(t + 1) & 1];
-            a.c_prev = t == 0 ? w.c2e + enc : w.c2[cur2]; a.cprev_rowmod = t == 0 ? B : 0;
-            a.c_new = w.c2[nxt2]; a.h_new = w.h2[nxt2];
-            a.R = R; a.H = H; a.E = E; a.V = V;
-            HIP_TRY(launch_decode_lstm4(a, q4, st));
-            HIP_TRY(pick_call(w.h2[nxt2], H, p->embed_word_W, p->embed_word_b, R, H, V, ids, t, w.packed + (size_t)t * R * kPickStride,
-                              nullptr, -1, st, kPickStride));
-            cur2 = nxt2;
-            continue;
-        }
-        const float* h2p = t == 0 ? w.h2e + enc : w.h2[cur2];
-        const float* c2p = t == 0 ? w.c2e + enc : w.c2[cur2];
-        const int smod = t == 0 ? B : 0;
-        // stop-at-<eos> mode: the launch covers the rows still sampling (compact index -> row through the live list, their number on
-        // the device); a finished row's state stays where it is, nothing reads it again, its later words are never written (= <eos>)
-        const int* omap = nullptr;
-        const int* mdev = nullptr;
-        int lcfg = -1, pcfg = -1;
+    // step t as two launches of the contraction kernel: the LSTM2 cell, then the pick.  Stop-at-<eos> mode: both cover the rows still
+    // sampling (compact index -> row through the live list, their number on the device); a finished row's state stays where it is,
+    // nothing reads it again, its later words are never written (= <eos>)
+    hipError_t step_launches(int t)
+    {
+        const int nxt = (t + 1) & 1;
+        Lstm2Step s{};
+        s.p = p; s.M = R; s.H = H; s.E = E;
+        s.partial = partial(t); s.partial_rowmod = B;
+        if (t == 0) { s.word_idx = w.bos; s.c_prev = w.c2e + enc; s.h_prev = w.h2e + enc; s.state_rowmod = B; }
+        else { s.word_key = picks(t - 1); s.c_prev = w.c2[t & 1]; s.h_prev = w.h2[t & 1]; }
+        s.c_new = w.c2[nxt]; s.h_new = w.h2[nxt];
+        s.lstm_cfg = -1;
+        int pick_cfg = -1;
         if (stop_at_eos) {
             // tiles for a launch whose live-row count only the device knows: small row tiles cost a few % while every row is live
-            // and follow the count down afterwards (dev knobs: S2VT_EOS_LSTM_CFG / S2VT_EOS_PICK_CFG)
+            // and follow the count down afterwards
             // -- measured at R = 384, mean length 7 (tools/eos_sweep.sh): cell step on 32-row tiles 2.40 ms per sampler call against 2.79
             // with the tile the full row count would get (96 rows) and 3.32 for the loop that never stops; the pick's 64 x 96 tile stays
-            static const int lk = [] { const char* e = getenv("S2VT_EOS_LSTM_CFG"); return e ? atoi(e) : 4; }();     // kLstm[4] = gw32x16u
-            static const int pk = [] { const char* e = getenv("S2VT_EOS_PICK_CFG"); return e ? atoi(e) : -1; }();
-            lcfg = R > 64 ? lk : -1; pcfg = pk;
-            HIP_TRY(launch_live_rows(t == 0 ? nullptr : w.packed + (size_t)(t - 1) * R * kPickStride, kPickStride, w.live[(t + 1) & 1],
-                                     w.nlive + (t > 0 ? t - 1 : 0), w.live[t & 1], w.nlive + t, R, st));
-            omap = w.live[t & 1]; mdev = w.nlive + t;
+            if (R > 64) s.lstm_cfg = sampler_knobs().eos_lstm_cfg;
+            pick_cfg = sampler_knobs().eos_pick_cfg;
+            HIP_CHECK(launch_live_rows(t == 0 ? nullptr : picks(t - 1), kPickStride, w.live[nxt], w.nlive + (t > 0 ? t - 1 : 0), w.live[t & 1], w.nlive + t, R, st));
+            s.live = w.live[t & 1]; s.n_live = w.nlive + t;
         }
-        ASeg s2[2] = {t == 0 ? make_seg(p->Wemb, E, E, H, 0, w.bos)
-                             : make_seg(p->Wemb, E, E, H, 0, nullptr, w.packed + (size_t)(t - 1) * R * kPickStride, kPickStride),
-                      make_seg(h2p, H, H, H + E, smod)};
-        HIP_TRY(lstm_call(s2, 2, p->lstm2_W, p->lstm2_b, c2p, smod, w.c2[nxt2], w.h2[nxt2], nullptr, nullptr, R, H, 1.0f,
-                          none, 0, lcfg, st, w.P2 + (size_t)(Tv + t) * 4 * BH, 4 * H, B, omap, mdev));
-        HIP_TRY(pick_call(w.h2[nxt2], H, p->embed_word_W, p->embed_word_b, R, H, V, ids, t, w.packed + (size_t)t * R * kPickStride,
-                          nullptr, pcfg, st, kPickStride, omap, mdev));
-        cur2 = nxt2;
+        HIP_CHECK(lstm2_step(s, st));
+        return pick_call(w.h2[nxt], H, p->embed_word_W, p->embed_word_b, R, H, V, ids(), t, picks(t), nullptr, pick_cfg, st, kPickStride, s.live, s.n_live);
+    }
+};
+
+// Decoding stage (tf_s2vt.py:126-153 as specialised by the samplers): LSTM2 + vocab at M = R rows; the R rows of a video share its
+// out1 partial (row % B).  Needs sample_encode's results in the same workspace.  The driver picks one of three forms -- the persistent
+// launch (<= 64 rows), per-step launches on the fragment-order operands (257-384 rows, opt-in), per-step launches of the contraction
+// kernel -- and leaves through the one unpack.  The early-exit mode takes the last form only: the other two cannot skip rows.
+int sample_decode(const s2vt_dims* d, const s2vt_params* p, int B, int K, int with_greedy, uint64_t seed, int video_base,
+                  int32_t* ids_out, const SampleWs& w, s2vt_stream stream, int stop_at_eos)
+{
+    const int H = d->lstm_dim, E = d->word_dim, V = d->n_words, Tv = d->n_video_lstm_step, Tc = d->n_caption_lstm_step;
+    const int R = (K + (with_greedy ? 1 : 0)) * B;
+    hipStream_t st = S(stream);
+    SampleDecode s{p, w, B, K, R, seed, video_base, stop_at_eos != 0, st, H, E, V, Tv, Tc, (size_t)B * H, (size_t)Tv * B * H, {}};
+    HIP_TRY(s.open());
+    const bool loop1 = !stop_at_eos && w.wemb_p && (B & 15) == 0 && decode_loop_eligible(R, H, E, V) && chain_operands_ok(p->embed_word_W, V, w.himg[0]);
+    const bool dec4 = !stop_at_eos && (loop1 || (w.wemb_p && decode4_eligible(R, H, E)));
+    if (dec4) HIP_TRY(s.pack_fragments());
+    if (loop1) {
+        HIP_TRY(s.persistent_loop());
+    } else {
+        for (int t = 0; t < Tc; ++t) HIP_TRY(dec4 ? s.step_fragment(t) : s.step_launches(t));
     }
     hipLaunchKernelGGL(unpack_ids_kernel, dim3((R * Tc + 255) / 256), dim3(256), 0, st, w.packed, ids_out, R, Tc, kPickStride);
     HIP_TRY(hipGetLastError());
@@ -574,24 +555,6 @@ size_t s2vt_sample_workspace_bytes(const s2vt_dims* d, int32_t B, int32_t K, int
     return carve_sample(c, d, B, (K + (with_greedy ? 1 : 0)) * B, nullptr);
 }
 
-int s2vt_sample(const s2vt_dims* d, const s2vt_params* p, const float* video, int32_t B, int32_t K, int32_t with_greedy,
-                uint64_t seed, int32_t video_base, int32_t* ids_out, void* workspace, size_t workspace_bytes,
-                s2vt_stream stream)
-{
-    if (!dims_ok(d) || !sampler_params_ok(p) || !video || !ids_out || !workspace || B <= 0 || K < 0 || (K == 0 && !with_greedy))
-        return S2VT_E_BADARG;
-    if (reinterpret_cast<uintptr_t>(workspace) & 255u) return S2VT_E_ALIGN;
-    if (chain_fault()) return S2VT_E_CHAIN_TIMEOUT;
-    const int R = (K + (with_greedy ? 1 : 0)) * B;
-    Carver c(workspace, workspace_bytes);
-    SampleWs w;
-    carve_sample(c, d, B, R, &w);
-    if (!c.ok()) return S2VT_E_WORKSPACE;
-    int rc = sample_encode(d, p, video, B, w, stream);
-    if (rc != S2VT_OK) return rc;
-    return sample_decode(d, p, B, K, with_greedy, seed, video_base, ids_out, w, stream);
-}
-
 int s2vt_sample_ex(const s2vt_dims* d, const s2vt_params* p, const float* video, int32_t B, int32_t K, int32_t with_greedy,
                    uint64_t seed, int32_t video_base, int32_t flags, int32_t* ids_out, void* workspace, size_t workspace_bytes,
                    s2vt_stream stream)
@@ -608,6 +571,13 @@ int s2vt_sample_ex(const s2vt_dims* d, const s2vt_params* p, const float* video,
     int rc = sample_encode(d, p, video, B, w, stream);
     if (rc != S2VT_OK) return rc;
     return sample_decode(d, p, B, K, with_greedy, seed, video_base, ids_out, w, stream, flags & S2VT_SAMPLE_STOP_AT_EOS);
+}
+
+int s2vt_sample(const s2vt_dims* d, const s2vt_params* p, const float* video, int32_t B, int32_t K, int32_t with_greedy,
+                uint64_t seed, int32_t video_base, int32_t* ids_out, void* workspace, size_t workspace_bytes,
+                s2vt_stream stream)
+{
+    return s2vt_sample_ex(d, p, video, B, K, with_greedy, seed, video_base, 0, ids_out, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

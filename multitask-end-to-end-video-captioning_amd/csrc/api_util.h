@@ -1,4 +1,4 @@
-// api_util.h -- host-side helpers shared by the extern "C" translation units (api.hip, train.hip)
+// api_util.h -- host-side helpers shared by the extern "C" translation units (api.hip, attn.hip, attn_model.hip, beam.hip, session.hip, train.hip)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -200,13 +200,18 @@ inline hipError_t nn_bwd_slabs(const float* A, int lda, const float* Wt, int ldw
 }
 
 
-// ---- sampler halves (api.hip), shared with the session API (session.hip)
-struct SampleWs {
-    float *emb, *Xp1, *c1, *h1, *G1, *P2, *c2e, *h2e, *c2[2], *h2[2];   // c2e / h2e: LSTM2 state history of the encoding stage [Tv+1][B][H]
-    unsigned long long* packed;
-    int32_t *vid, *sid, *bos;
+// ---- sampler halves (api.hip), shared with the session API (session.hip) and the beam search (beam.hip)
+// The encode half: what sample_encode fills for B videos.  The eight regions lead every workspace that holds one, in this order
+// (carve_sample_enc); the persistent recurrences' scratch is carved by the owner, wherever its layout has it.
+struct SampleEnc {
+    float *emb, *Xp1, *c1, *h1, *G1, *P2, *c2e, *h2e;   // c2e / h2e: LSTM2 state history of the encoding stage [Tv+1][B][H]
     float* chain_abuf;       // persistent-recurrence scratch (chain.hip): fragment images of h + arrival counters
     unsigned* chain_sync;
+};
+struct SampleWs : SampleEnc {
+    float *c2[2], *h2[2];    // LSTM2 state of the R decode rows, ping-pong: step t reads slot t & 1 (step 0: the encoder state) and writes the other
+    unsigned long long* packed;
+    int32_t *vid, *sid, *bos;
     float *wemb_p, *w2_p, *himg[2];   // fragment-order operands of the decode loop's LSTM2 step (decode4.hip); NULL when R is outside its range
     int32_t* live[2];        // stop-at-<eos> mode: the rows still sampling at the current / next step (ascending), ...
     int32_t* nlive;          // ... and their count per step [Tc + 1], device-resident
@@ -219,10 +224,25 @@ hipError_t lstm_recurrence(const float* W, int kw0, const float* bias, const flo
                            float* out, size_t out_tstride, int M, int H, int T, float keep, const NoiseIds& ids,
                            uint32_t drop_code0, float* chain_abuf, unsigned* chain_sync, hipStream_t st, const int32_t* perm = nullptr,
                            const int32_t* nlive = nullptr);
+void carve_sample_enc(Carver& c, const s2vt_dims* d, int B, SampleEnc& e);
 size_t carve_sample(Carver& c, const s2vt_dims* d, int B, int R, SampleWs* w);
-int sample_encode(const s2vt_dims* d, const s2vt_params* p, const float* video, int B, const SampleWs& w, s2vt_stream stream);
+int sample_encode(const s2vt_dims* d, const s2vt_params* p, const float* video, int B, const SampleEnc& w, s2vt_stream stream);
 int sample_decode(const s2vt_dims* d, const s2vt_params* p, int B, int K, int with_greedy, uint64_t seed, int video_base,
                   int32_t* ids_out, const SampleWs& w, s2vt_stream stream, int stop_at_eos = 0);
+
+// One LSTM2 step of the decoding stage on M rows (sampler loop, beam step).  What the callers differ in is data: where the hoisted
+// out1 partial of a row lies, how its word is gathered, where its state lives, and the early-exit mode's row list and tile.
+struct Lstm2Step {
+    const s2vt_params* p;
+    int M, H, E;
+    const float* partial; int partial_rowmod;     // h1 @ W2[0:H] of this step [.][4H]: P2 + (Tv + t) 4BH with row % B, or rows gathered beforehand (0)
+    const int32_t* word_idx;                      // the word fed: a list of ids (<bos> at step 0; the beam's clamped words), or ...
+    const unsigned long long* word_key;           // ... the packed picks of step t - 1 (kPickStride apart)
+    const float *c_prev, *h_prev; int state_rowmod;   // step 0 of the sampler: the encoder state with row % B; else one row each (0)
+    float *c_new, *h_new;
+    const int32_t *live, *n_live; int lstm_cfg;   // early-exit mode: the launch covers rows live[0 .. *n_live) only (device-resident); its tile knob (-1: the cost model's)
+};
+hipError_t lstm2_step(const Lstm2Step& s, hipStream_t st);
 bool sampler_params_ok(const s2vt_params* p);
 // stop-at-<eos> mode of the samplers (api.hip): next / *nnext = the rows of prev[0 .. *nprev) whose packed pick (picked[row * stride]) is
 // not <eos>, order preserved; picked == NULL (step 0): every row of R.  One workgroup.

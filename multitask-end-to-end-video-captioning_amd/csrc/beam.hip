@@ -175,7 +175,7 @@ namespace {
 constexpr int kTopkMax = 16;
 
 struct BeamWs {
-    SampleWs enc;                       // the sampler's encode half for B rows (sample_encode)
+    SampleEnc enc;                      // the sampler's encode half for B rows (sample_encode)
     float *c2, *h2;                     // LSTM2 state after the last step [Rmax][H] (row = hypothesis of that step)
     float *c2g, *h2g, *p2g;             // the cell's gathered inputs [Rmax][H], [Rmax][H], [Rmax][4H]
     int32_t* word;                      // clamped words [Rmax]
@@ -184,19 +184,12 @@ struct BeamWs {
 
 size_t carve_beam(Carver& c, const s2vt_dims* d, int B, int beam, BeamWs* w)
 {
-    const size_t H = d->lstm_dim, E = d->word_dim, V = d->n_words, Tv = d->n_video_lstm_step, Tc = d->n_caption_lstm_step, T = Tv + Tc;
+    const size_t H = d->lstm_dim, V = d->n_words;
     const size_t Rmax = (size_t)B * beam;
     BeamWs t;
-    std::memset(&t, 0, sizeof(t));
-    SampleWs& e = t.enc;
-    e.emb = c.take<float>((size_t)B * Tv * E);
-    e.Xp1 = c.take<float>((size_t)B * Tv * 4 * H);
-    e.c1 = c.take<float>((T + 1) * B * H); e.h1 = c.take<float>((T + 1) * B * H);
-    e.G1 = c.take<float>(T * B * 4 * H);
-    e.P2 = c.take<float>(T * B * 4 * H);
-    e.c2e = c.take<float>((Tv + 1) * (size_t)B * H); e.h2e = c.take<float>((Tv + 1) * (size_t)B * H);
-    e.chain_sync = c.take<unsigned>(kChainSyncBytes / 4);
-    e.chain_abuf = c.take<float>(chain_scratch_floats((int)H));
+    carve_sample_enc(c, d, B, t.enc);
+    t.enc.chain_sync = c.take<unsigned>(kChainSyncBytes / 4);
+    t.enc.chain_abuf = c.take<float>(chain_scratch_floats((int)H));
     t.c2 = c.take<float>(Rmax * H); t.h2 = c.take<float>(Rmax * H);
     t.c2g = c.take<float>(Rmax * H); t.h2g = c.take<float>(Rmax * H);
     t.p2g = c.take<float>(Rmax * 4 * H);
@@ -264,10 +257,12 @@ int s2vt_beam_step(const s2vt_dims* d, const s2vt_params* p, int32_t B, int32_t 
                        w.enc.c2e + (size_t)Tv * BH, w.enc.h2e + (size_t)Tv * BH, w.c2, w.h2, w.enc.P2 + (size_t)(Tv + t) * 4 * BH, w.c2g,
                        w.h2g, w.p2g, w.word);
     HIP_TRY(hipGetLastError());
-    // 2. LSTM2 at R rows: the chain continues from the gathered out1 partial with the word rows of Wemb, then the parent's h
-    NoiseIds none{nullptr, nullptr, 0};
-    ASeg s2[2] = {make_seg(p->Wemb, E, E, H, 0, w.word), make_seg(w.h2g, H, H, H + E)};
-    HIP_TRY(lstm_call(s2, 2, p->lstm2_W, p->lstm2_b, w.c2g, 0, w.c2, w.h2, nullptr, nullptr, R, H, 1.0f, none, 0, -1, st, w.p2g, 4 * H, 0));
+    // 2. LSTM2 at R rows on the gathered partial, words and parent state
+    Lstm2Step s2{};
+    s2.p = p; s2.M = R; s2.H = H; s2.E = E;
+    s2.partial = w.p2g; s2.word_idx = w.word; s2.c_prev = w.c2g; s2.h_prev = w.h2g;
+    s2.c_new = w.c2; s2.h_new = w.h2; s2.lstm_cfg = -1;
+    HIP_TRY(lstm2_step(s2, st));
     // 3. vocabulary logits on the store tile
     float* logits = logits_out ? logits_out : w.logits;
     ASeg so = make_seg(w.h2, H, H, 0);

@@ -14,20 +14,26 @@ def _dev(a):
     return torch.as_tensor(np.ascontiguousarray(a)).cuda()
 
 
-def test_session_encode_decode_matches_oracle(gpu, oracle):
+# the second case: 16 videos at H = 992, the smallest shape test_gpu_decode_loop.py runs through the persistent decode loop; the session
+# carves for (max_K + 1) * 16 = 48 rows and decodes 16 (greedy) and 32 (multinomial)
+@pytest.mark.parametrize("dims,n_video,max_B,max_K,K", [
+    (DIMS, 6, 8, 4, 3),
+    (dict(dim_image=256, n_words=2000, word_dim=300, lstm_dim=992, n_video_lstm_step=5, n_caption_lstm_step=8), 16, 16, 2, 2),
+], ids=["H64_B6", "H992_B16"])
+def test_session_encode_decode_matches_oracle(gpu, oracle, dims, n_video, max_B, max_K, K):
     import torch
-    d = oracle.Dims(label_dim=0, **DIMS)
+    d = oracle.Dims(label_dim=0, **dims)
     p = oracle.init_params(d, seed=3)
     rng = np.random.default_rng(0)
-    video = np.abs(rng.standard_normal((6, 5, 128)) * 0.5).astype(np.float32)
-    ref_s, ref_g = oracle.sample_captions(p, d, video, K=3, seed=11)
-    dims = gpu.make_dims(128, 260, 32, 64, 5, 8)
+    video = np.abs(rng.standard_normal((n_video, dims["n_video_lstm_step"], dims["dim_image"])) * 0.5).astype(np.float32)
+    ref_s, ref_g = oracle.sample_captions(p, d, video, K=K, seed=11)
+    gdims = gpu.make_dims(*(dims[k] for k in ("dim_image", "n_words", "word_dim", "lstm_dim", "n_video_lstm_step", "n_caption_lstm_step")))
     dp = {k: _dev(v) for k, v in p.items()}
     params = gpu.make_params(dp)
-    ses = gpu.Session(dims, max_B=8, max_K=4)
+    ses = gpu.Session(gdims, max_B=max_B, max_K=max_K)
     ses.encode(params, _dev(video))
     g = ses.decode_greedy(params)
-    s = ses.decode_multinomial(params, 3, seed=11)
+    s = ses.decode_multinomial(params, K, seed=11)
     g2 = ses.decode_greedy(params)                       # a second decode on the same encode
     torch.cuda.synchronize()
     assert np.array_equal(g.cpu().numpy(), ref_g) and np.array_equal(g2.cpu().numpy(), ref_g)

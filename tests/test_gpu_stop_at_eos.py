@@ -13,6 +13,9 @@ pytestmark = pytest.mark.gpu
     (dict(dim_image=128, n_words=260, word_dim=32, lstm_dim=64, n_video_lstm_step=5, n_caption_lstm_step=12), 16, 2, 4.0),
     (dict(dim_image=1536, n_words=12000, word_dim=500, lstm_dim=1000, n_video_lstm_step=5, n_caption_lstm_step=20), 64, 5, 7.5),
     (dict(dim_image=96, n_words=300, word_dim=20, lstm_dim=48, n_video_lstm_step=2, n_caption_lstm_step=7), 100, 3, 4.5),   # R = 400: several scan chunks
+    # R = 48, B % 16 == 0, H >= 132: the plain sampler runs the persistent decode loop, the early-exit one the live-row launches
+    # beside the fragment-order operands the workspace holds for the former
+    (dict(dim_image=256, n_words=2000, word_dim=300, lstm_dim=992, n_video_lstm_step=5, n_caption_lstm_step=8), 16, 2, 5.5),
 ])
 def test_stop_at_eos_ids_equal_up_to_first_eos(gpu, dims, B, K, eos_bias):
     import torch
