@@ -191,6 +191,24 @@ int s2vt_sample_ex(const s2vt_dims* d, const s2vt_params* p, const float* video,
                    uint64_t seed, int32_t video_base, int32_t flags, int32_t* ids_out, void* workspace, size_t workspace_bytes,
                    s2vt_stream stream);
 
+/* ---- mixed sampler: build_mix_sample of reinforce_multitask_e2e_attribute_by_groudtruth_greedy_s2vt.py:512-599 (built at :828, run
+ * beside build_sampler on the same batch at :957-960), whose reward is that script's baseline.  A greedy decode in which the word fed
+ * back at step t >= 1 is the ground-truth word caption[b][t - 1] with probability p_gt and the row's own argmax of step t - 1 otherwise
+ * (:576-587: tf.multinomial over log([p, 1.00001 - p]), so p_gt = p / 1.00001); step 0 feeds <bos> = 1; the emitted id is always the
+ * argmax (:595), whatever was fed.  ids_out: int32 [(1 + with_greedy) * B, Tc] -- block 0 the B mixed rows, block 1 (with_greedy) the
+ * plain greedy rows of build_sampler, bit-identical to s2vt_sample's greedy block; both decode from ONE encode.
+ * The coin is a pure function of (seed, global video id, step): u = u01(philox4x32_10(counter (0, video_base + b, 0, t), key (seed_lo,
+ * seed_hi ^ 0x4D495853)).x) with u01(x) = ((x >> 9) + 0.5) * 2^-23, ground truth iff u < p_gt -- p_gt = 1 always feeds it, p_gt = 0
+ * never; a batch split over ranks draws the same coins (as the Gumbel stream of s2vt_sample).
+ * caption: DEVICE int32 [B][n_caption_lstm_step] row-major; an id outside [0, n_words) is clamped into that range where it is read, so
+ * no caption can make the embedding gather leave Wemb.  Errors: S2VT_E_BADARG (a NULL pointer, B <= 0, p_gt outside [0, 1] or NaN),
+ * S2VT_E_ALIGN, S2VT_E_WORKSPACE, S2VT_E_CHAIN_TIMEOUT as s2vt_sample_ex.  The workspace is s2vt_sample's for the same row count
+ * followed by the fed words; ..._workspace_bytes: 0 on bad arguments. */
+size_t s2vt_sample_mix_workspace_bytes(const s2vt_dims* d, int32_t B, int32_t with_greedy);
+int s2vt_sample_mix(const s2vt_dims* d, const s2vt_params* p, const float* video, int32_t B, const int32_t* caption, float p_gt,
+                    int32_t with_greedy, uint64_t seed, int32_t video_base, int32_t* ids_out, void* workspace, size_t workspace_bytes,
+                    s2vt_stream stream);
+
 /* ---- batched beam search: build_generator(beam_size, length_normalization_factor) of final_beam_search.py:201-294 for B videos
  * at once.  The reference runs one B = 1 graph per live beam per step (beam_probability, :203-224) and keeps the captions in TopN
  * heaps (beam_search.py:44-80); here one call per decode step advances every live hypothesis of every video, and only the

@@ -57,6 +57,24 @@ __global__ void unpack_ids_kernel(const unsigned long long* packed, int32_t* ids
     ids[i] = w ? (int32_t)(~(uint32_t)w) : 0;
 }
 
+// mixed mode: the word every row is fed at step t >= 1 -- its own pick of step t - 1 (decoded as unpack_ids_kernel does), or, for the
+// rows [mix_lo, mix_lo + B) whose coin says so, the ground-truth word caption[b][t - 1] clamped into [0, V)
+__global__ __launch_bounds__(256) void mix_words_kernel(const unsigned long long* picked, int stride, const int32_t* caption, int Tc, int t,
+                                                        int mix_lo, int B, int R, int V, int video_base, uint32_t seed_lo, uint32_t seed_hi,
+                                                        float p_gt, int32_t* word)
+{
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= R) return;
+    const unsigned long long w = picked[(size_t)r * stride];
+    int32_t id = w ? (int32_t)(~(uint32_t)w) : 0;
+    const int b = r - mix_lo;
+    if (b >= 0 && b < B && mix_feeds_truth(seed_lo, seed_hi, (uint32_t)(video_base + b), (uint32_t)t, p_gt)) {
+        const int32_t c = caption[(size_t)b * Tc + t - 1];
+        id = c < 0 ? 0 : c >= V ? V - 1 : c;
+    }
+    word[r] = id;
+}
+
 // stop-at-<eos> mode: the rows still sampling at step t from those of step t - 1 and the words they just picked (a row leaves
 // once it has picked <eos> = 0; order preserved).  One workgroup; step 0: every row.
 __global__ __launch_bounds__(256) void live_rows_kernel(const unsigned long long* picked, int stride, const int32_t* prev, const int32_t* nprev,
@@ -416,7 +434,8 @@ hipError_t lstm2_step(const Lstm2Step& s, hipStream_t st)
 // (inside a stage: hand a failed launch's error to the driver, whose HIP_TRY records it)
 #define HIP_CHECK(expr) do { const hipError_t _e = (expr); if (_e != hipSuccess) return _e; } while (0)
 
-// One decode call of the sampler: R rows = K multinomial row blocks then (with_greedy) one argmax block, row r of video r % B.  The
+// One decode call of the sampler: R rows = K multinomial row blocks, then (mixed mode) one argmax block fed ground-truth words by coin, then
+// (with_greedy) one argmax block, row r of video r % B.  The
 // workspace may be carved for more rows than the call decodes (session API): whether the fragment-order operands exist follows the
 // carve, every stride, grid and eligibility test the R of the call.  The stages are straight-line.
 struct SampleDecode {
@@ -425,6 +444,7 @@ struct SampleDecode {
     int H, E, V, Tv, Tc;
     size_t BH, enc;          // enc: where sample_encode left the encoder state, slot Tv of the c2e / h2e history
     Dec4Geom q4;
+    const SampleMix* mix = nullptr;   // mixed mode: the argmax block at rows [K B, K B + B) is fed ground-truth words by coin
 
     unsigned long long* picks(int t) const { return w.packed + (size_t)t * R * kPickStride; }     // the packed picks of step t [R]
     const float* partial(int t) const { return w.P2 + (size_t)(Tv + t) * 4 * BH; }                // the out1 partial of step t [B][4H]
@@ -479,6 +499,13 @@ struct SampleDecode {
         HIP_CHECK(launch_decode_lstm4(a, q4, st));
         return pick_call(w.h2[nxt], H, p->embed_word_W, p->embed_word_b, R, H, V, ids(), t, picks(t), nullptr, -1, st, kPickStride);
     }
+    // mixed mode, t >= 1: the words step t is fed, chosen per row between its pick of step t - 1 and the ground-truth caption
+    hipError_t mix_words(int t)
+    {
+        hipLaunchKernelGGL(mix_words_kernel, dim3((R + 255) / 256), dim3(256), 0, st, picks(t - 1), kPickStride, mix->caption, Tc, t, K * B, B, R, V,
+                           video_base, (uint32_t)seed, (uint32_t)(seed >> 32), mix->p_gt, mix->word);
+        return hipGetLastError();
+    }
     // step t as two launches of the contraction kernel: the LSTM2 cell, then the pick.  Stop-at-<eos> mode: both cover the rows still
     // sampling (compact index -> row through the live list, their number on the device); a finished row's state stays where it is,
     // nothing reads it again, its later words are never written (= <eos>)
@@ -489,7 +516,11 @@ struct SampleDecode {
         s.p = p; s.M = R; s.H = H; s.E = E;
         s.partial = partial(t); s.partial_rowmod = B;
         if (t == 0) { s.word_idx = w.bos; s.c_prev = w.c2e + enc; s.h_prev = w.h2e + enc; s.state_rowmod = B; }
-        else { s.word_key = picks(t - 1); s.c_prev = w.c2[t & 1]; s.h_prev = w.h2[t & 1]; }
+        else {
+            if (mix) { HIP_CHECK(mix_words(t)); s.word_idx = mix->word; }
+            else s.word_key = picks(t - 1);
+            s.c_prev = w.c2[t & 1]; s.h_prev = w.h2[t & 1];
+        }
         s.c_new = w.c2[nxt]; s.h_new = w.h2[nxt];
         s.lstm_cfg = -1;
         int pick_cfg = -1;
@@ -511,17 +542,18 @@ struct SampleDecode {
 // Decoding stage (tf_s2vt.py:126-153 as specialised by the samplers): LSTM2 + vocab at M = R rows; the R rows of a video share its
 // out1 partial (row % B).  Needs sample_encode's results in the same workspace.  The driver picks one of three forms -- the persistent
 // launch (<= 64 rows), per-step launches on the fragment-order operands (257-384 rows, opt-in), per-step launches of the contraction
-// kernel -- and leaves through the one unpack.  The early-exit mode takes the last form only: the other two cannot skip rows.
+// kernel -- and leaves through the one unpack.  The early-exit mode takes the last form only: the other two cannot skip rows.  So does the
+// mixed mode (one more argmax block in front of the greedy one): the other two read the fed word from the packed picks.
 int sample_decode(const s2vt_dims* d, const s2vt_params* p, int B, int K, int with_greedy, uint64_t seed, int video_base,
-                  int32_t* ids_out, const SampleWs& w, s2vt_stream stream, int stop_at_eos)
+                  int32_t* ids_out, const SampleWs& w, s2vt_stream stream, int stop_at_eos, const SampleMix* mix)
 {
     const int H = d->lstm_dim, E = d->word_dim, V = d->n_words, Tv = d->n_video_lstm_step, Tc = d->n_caption_lstm_step;
-    const int R = (K + (with_greedy ? 1 : 0)) * B;
+    const int R = (K + (mix ? 1 : 0) + (with_greedy ? 1 : 0)) * B;
     hipStream_t st = S(stream);
-    SampleDecode s{p, w, B, K, R, seed, video_base, stop_at_eos != 0, st, H, E, V, Tv, Tc, (size_t)B * H, (size_t)Tv * B * H, {}};
+    SampleDecode s{p, w, B, K, R, seed, video_base, stop_at_eos != 0, st, H, E, V, Tv, Tc, (size_t)B * H, (size_t)Tv * B * H, {}, mix};
     HIP_TRY(s.open());
-    const bool loop1 = !stop_at_eos && w.wemb_p && (B & 15) == 0 && decode_loop_eligible(R, H, E, V) && chain_operands_ok(p->embed_word_W, V, w.himg[0]);
-    const bool dec4 = !stop_at_eos && (loop1 || (w.wemb_p && decode4_eligible(R, H, E)));
+    const bool loop1 = !stop_at_eos && !mix && w.wemb_p && (B & 15) == 0 && decode_loop_eligible(R, H, E, V) && chain_operands_ok(p->embed_word_W, V, w.himg[0]);
+    const bool dec4 = !stop_at_eos && !mix && (loop1 || (w.wemb_p && decode4_eligible(R, H, E)));
     if (dec4) HIP_TRY(s.pack_fragments());
     if (loop1) {
         HIP_TRY(s.persistent_loop());
@@ -578,6 +610,40 @@ int s2vt_sample(const s2vt_dims* d, const s2vt_params* p, const float* video, in
                 s2vt_stream stream)
 {
     return s2vt_sample_ex(d, p, video, B, K, with_greedy, seed, video_base, 0, ids_out, workspace, workspace_bytes, stream);
+}
+
+// mixed sampler: carve_sample for R = (1 + with_greedy) * B rows, then the fed words [R]
+static size_t carve_sample_mix(Carver& c, const s2vt_dims* d, int B, int R, SampleWs* w, SampleMix* m)
+{
+    carve_sample(c, d, B, R, w);
+    int32_t* word = c.take<int32_t>(R);
+    if (m) m->word = word;
+    return c.off;
+}
+
+size_t s2vt_sample_mix_workspace_bytes(const s2vt_dims* d, int32_t B, int32_t with_greedy)
+{
+    if (!dims_ok(d) || B <= 0) return 0;
+    Carver c(nullptr, 0);
+    return carve_sample_mix(c, d, B, (1 + (with_greedy ? 1 : 0)) * B, nullptr, nullptr);
+}
+
+int s2vt_sample_mix(const s2vt_dims* d, const s2vt_params* p, const float* video, int32_t B, const int32_t* caption, float p_gt,
+                    int32_t with_greedy, uint64_t seed, int32_t video_base, int32_t* ids_out, void* workspace, size_t workspace_bytes,
+                    s2vt_stream stream)
+{
+    if (!dims_ok(d) || !sampler_params_ok(p) || !video || !caption || !ids_out || !workspace || B <= 0 || !(p_gt >= 0.0f && p_gt <= 1.0f))
+        return S2VT_E_BADARG;                                                     // (a NaN p_gt fails both comparisons)
+    if (reinterpret_cast<uintptr_t>(workspace) & 255u) return S2VT_E_ALIGN;
+    if (chain_fault()) return S2VT_E_CHAIN_TIMEOUT;
+    Carver c(workspace, workspace_bytes);
+    SampleWs w;
+    SampleMix m{caption, p_gt, nullptr};
+    carve_sample_mix(c, d, B, (1 + (with_greedy ? 1 : 0)) * B, &w, &m);
+    if (!c.ok()) return S2VT_E_WORKSPACE;
+    int rc = sample_encode(d, p, video, B, w, stream);
+    if (rc != S2VT_OK) return rc;
+    return sample_decode(d, p, B, 0, with_greedy, seed, video_base, ids_out, w, stream, 0, &m);
 }
 
 }  // extern "C"

@@ -227,8 +227,15 @@ hipError_t lstm_recurrence(const float* W, int kw0, const float* bias, const flo
 void carve_sample_enc(Carver& c, const s2vt_dims* d, int B, SampleEnc& e);
 size_t carve_sample(Carver& c, const s2vt_dims* d, int B, int R, SampleWs* w);
 int sample_encode(const s2vt_dims* d, const s2vt_params* p, const float* video, int B, const SampleEnc& w, s2vt_stream stream);
+// The mixed mode of the decode (s2vt_sample_mix): one more block of B argmax rows between the multinomial blocks and the greedy one,
+// whose fed word at step t >= 1 is caption[b][t - 1] when the row's coin says so (detmath.h mix_feeds_truth) and its own pick otherwise.
+struct SampleMix {
+    const int32_t* caption;  // device, [B][Tc] row-major; ids are clamped into [0, n_words) where they are read
+    float p_gt;
+    int32_t* word;           // [R]: the words fed at the current step, behind carve_sample's regions
+};
 int sample_decode(const s2vt_dims* d, const s2vt_params* p, int B, int K, int with_greedy, uint64_t seed, int video_base,
-                  int32_t* ids_out, const SampleWs& w, s2vt_stream stream, int stop_at_eos = 0);
+                  int32_t* ids_out, const SampleWs& w, s2vt_stream stream, int stop_at_eos = 0, const SampleMix* mix = nullptr);
 
 // One LSTM2 step of the decoding stage on M rows (sampler loop, beam step).  What the callers differ in is data: where the hoisted
 // out1 partial of a row lies, how its word is gathered, where its state lives, and the early-exit mode's row list and tile.

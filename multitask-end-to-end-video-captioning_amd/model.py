@@ -483,6 +483,47 @@ class Video_Caption_Generator:
             return {"sampled_captions": g.cpu().numpy().astype(np.int64)}
         return Output("sampled_captions", fn, [video]), video
 
+    def mix_sample(self, video, caption, true_word_prob=0.9, with_greedy=True, seed=None, video_base=0):
+        """The mixed decode of build_mix_sample (reinforce_multitask_e2e_attribute_by_groudtruth_greedy_s2vt.py:512-599): a greedy decode
+        in which the word fed back at step t >= 1 is the ground-truth word caption[:, t-1] with probability true_word_prob / 1.00001
+        (tf.multinomial over log([p, 1.00001 - p]), :547-557, drawn per row per step) and the row's own argmax otherwise; the emitted id
+        is always the argmax.  Returns (mix [B,Tc], greedy [B,Tc] | None) int32 device tensors, both from ONE encode; greedy is
+        build_sampler's caption.  video: features, or frames once a CNN is attached (inference mode, no feature dropout, :520-526).
+        caption [B, Tc]: a numpy array or list is checked on the host (shape, 0 <= id < n_words: ValueError); a device tensor is passed
+        through and the kernel clamps its ids.  The coins are a function of (seed, video_base + row, step): ranks draw what one process
+        would.  No state is kept for reuse_sampler_state: a sample() call's saved trajectory stays valid across this call."""
+        p_gt = np.float32(np.float64(true_word_prob) / np.float64(1.00001))
+        if not 0.0 <= float(p_gt) <= 1.0:                          # (NaN fails too)
+            raise ValueError(f"true_word_prob must lie in [0, 1.00001], got {true_word_prob!r}")
+        video = self._features(video, video_base=video_base)
+        if isinstance(caption, torch.Tensor) and caption.is_cuda:
+            cap = caption.to(device=self.device, dtype=torch.int32).contiguous()
+        else:
+            host = caption.numpy() if isinstance(caption, torch.Tensor) else np.asarray(caption)
+            want = (video.shape[0], self.n_caption_lstm_step)
+            if host.shape != want or not np.issubdtype(host.dtype, np.integer):
+                raise ValueError(f"mix_sample: caption must be integer ids of shape {want}, got {host.dtype} {host.shape}")
+            if host.size and (host.min() < 0 or host.max() >= self.n_words):
+                raise ValueError(f"mix_sample: caption ids must lie in [0, {self.n_words}), got [{host.min()}, {host.max()}]")
+            cap = self._dev(host, torch.int32)
+        return ops.sample_mix(self.dims, self.store.params, video, cap, float(p_gt), self.sample_seed if seed is None else seed,
+                              video_base, with_greedy)
+
+    def build_mix_sample(self, true_word_prob=0.9):
+        """The mixed sampler graph (reinforce_multitask_e2e_attribute_by_groudtruth_greedy_s2vt.py:512-599, built at :828): returns
+        (sampled_captions, video, caption) in the reference's order, fetched alone or beside build_sampler's output as at :957-960.
+        true_word_prob: the constant the reference writes into the graph (:553).  Every run draws fresh coins, as the stateful TF op
+        does: run number n (from 1) uses seed sample_seed + 7919 * n."""
+        video = self._video_placeholder(None)
+        caption = Placeholder("caption", (self.batch_size, self.n_caption_lstm_step), np.int32)
+        state = {"calls": 0}
+
+        def fn(v, c):
+            state["calls"] += 1
+            m, _ = self.mix_sample(v, c, true_word_prob, False, seed=self.sample_seed + 7919 * state["calls"])
+            return {"sampled_captions": m.cpu().numpy().astype(np.int64)}
+        return Output("sampled_captions", fn, [video, caption]), video, caption
+
     def build_multinomial_sampler(self):
         """One multinomial caption per video (reinforcement_multisampling_tf_s2vt.py:294-339).
         Every run draws from a fresh Philox stream (the TF op is stateful too)."""

@@ -253,6 +253,27 @@ sample.last_state = None
 sample.serial = 0
 
 
+def sample_mix(dims: Dims, params: Params, video, caption, p_gt: float, seed: int, video_base: int = 0, with_greedy: bool = True):
+    """The mixed decode of build_mix_sample (s2vt_sample_mix): a greedy decode whose fed word at step t >= 1 is caption[:, t-1] with
+    probability p_gt (the coin: a pure function of seed, global video id and step) and the row's own argmax otherwise; with_greedy adds the
+    plain greedy rows from the same encode.  caption: int32 device tensor [B, Tc] (ids outside [0, n_words) are clamped by the kernel).
+    Returns (mix [B,Tc], greedy [B,Tc] | None) int32.  A workspace of its own: sample.last_state is left alone, so
+    teacher_forced_fwd(sampler_state=...) never sees a mixed call's buffers."""
+    _chk_f32(video)
+    assert video.is_contiguous()
+    B = video.shape[0]
+    assert caption.is_cuda and caption.dtype == torch.int32 and caption.is_contiguous()
+    assert tuple(caption.shape) == (B, dims.n_caption_lstm_step)
+    g = 1 if with_greedy else 0
+    L = lib()
+    nbytes = L.s2vt_sample_mix_workspace_bytes(C.byref(dims), B, g)
+    ws = workspace(nbytes, video.device, "sample_mix")
+    ids = torch.empty(((1 + g) * B, dims.n_caption_lstm_step), dtype=torch.int32, device=video.device)
+    check(L.s2vt_sample_mix(C.byref(dims), C.byref(params), _ptr(video), B, _ptr(caption), float(p_gt), g, seed, video_base, _ptr(ids),
+                            _ptr(ws), ws.numel(), _stream()), "s2vt_sample_mix")
+    return ids[:B], (ids[B:] if with_greedy else None)
+
+
 def train_workspace(dims: Dims, B: int, N: int, device):
     nbytes = lib().s2vt_train_workspace_bytes(C.byref(dims), B, N)
     assert nbytes > 0, "bad dims / B / N (N must be a multiple of B)"

@@ -60,7 +60,12 @@ def train(cfg: Config, train_corpus: Corpus, test_corpus: Corpus | None = None, 
     cfg.batch_size is the GLOBAL batch (the reference's batch_size).  Under torch.distributed.run every rank walks the
     same shuffled epoch, takes its shard of each batch (videos [lo, hi) of the global batch, global indices in the noise
     counters), scores its own captions, and the gradient bucket is all-reduced inside reinforce_update; rank 0 logs and
-    writes checkpoints.  restore: variables of an earlier model (optimistic, :667 -- the step counter of an XE checkpoint
+    writes checkpoints.
+    cfg.mix_baseline = P (None: off): the step of reinforce_multitask_e2e_attribute_by_groudtruth_greedy_s2vt.py:957-979 -- the GREEDY caption is the
+    policy's sample and the baseline is the reward of a mixed decode, a greedy decode fed the batch's own ground-truth sentence word by word with
+    probability P / 1.00001 (model.mix_sample; one call decodes both from one encode, coins keyed by the global video index).  The update runs on
+    the greedy ids with their own mask: model.mixed_update when cfg.lambda_loss > 0 (that script's objective, :850), reinforce_update otherwise.
+    One caption per video: cfg.multisample must be 1.  restore: variables of an earlier model (optimistic, :667 -- the step counter of an XE checkpoint
     does not match this script's 'g_step', Adam's slots do); resume: a checkpoint of THIS driver, counters included."""
     import torch
     from . import model as M
@@ -69,6 +74,15 @@ def train(cfg: Config, train_corpus: Corpus, test_corpus: Corpus | None = None, 
         log = lambda *_: None
     wordtoix, ixtoword = hostglue.preProBuildWordVocab(train_corpus.vocabulary)
     K = cfg.multisample
+    mix_p = cfg.mix_baseline
+    if mix_p is not None:
+        if K != 1:
+            raise ValueError(f"mix_baseline: the greedy caption is the one sample per video (reinforce_multitask_e2e_attribute_by_groudtruth_greedy_s2vt.py"
+                             f":957-979), so multisample / --samples must be 1, got {K}")
+        if not 0.0 <= float(mix_p) <= 1.0:
+            raise ValueError(f"mix_baseline is a probability in [0, 1], got {mix_p!r}")
+        if cfg.stop_at_eos:
+            raise ValueError("mix_baseline: the mixed decode has no early-exit form; drop stop_at_eos")
     B = par.per_rank(cfg.batch_size)
     multitask = attr_vocabulary is not None
     if model is None:
@@ -107,9 +121,10 @@ def train(cfg: Config, train_corpus: Corpus, test_corpus: Corpus | None = None, 
         out = dict(lo=lo, video=model._dev(train_corpus.features.batch(vid), torch.float32), rows=rows)
         if multitask:
             out["labels"] = model._dev(labels[rows], torch.float32)
-            if cfg.lambda_loss > 0:             # the batch's own sentences are the ground truth of the XE term (..._s2vt.py:977-983)
-                gt, gm = hostglue.sentence_padding_toix(caps[idx, 1].tolist(), wordtoix, cfg.n_caption_lstm_step)
-                out["gt"], out["gmask"] = np.asarray(gt, np.int32), np.asarray(gm, np.float32)
+        if (multitask and cfg.lambda_loss > 0) or mix_p is not None:
+            # the batch's own sentences are the ground truth of the XE term (..._s2vt.py:977-983) and the words the mixed decode is fed
+            gt, gm = hostglue.sentence_padding_toix(caps[idx, 1].tolist(), wordtoix, cfg.n_caption_lstm_step)
+            out["gt"], out["gmask"] = np.asarray(gt, np.int32), np.asarray(gm, np.float32)
         return out
 
     for epoch in range(cfg.n_epochs):
@@ -148,12 +163,25 @@ def train(cfg: Config, train_corpus: Corpus, test_corpus: Corpus | None = None, 
                                               clip_norm=cfg.clip_norm, video_base=lo, reuse_sampler_state=True, reward_fn=rewards,
                                               active_steps=steps, live_mask=hostglue.masks_from_ids(s_host))
 
+            def step_mix():         # ..._by_groudtruth_greedy_s2vt.py:957-979: r = reward(greedy), b = reward(mixed decode), the update on the greedy ids
+                mix, greedy_words = model.mix_sample(video, cur["gt"], mix_p, True, seed=cfg.seed + 7919 * (model.global_step + 1), video_base=lo)
+                m_host, g_host = mix.cpu().numpy(), greedy_words.cpu().numpy()
+                model.check_health()
+                rb["r"], rb["b"] = scorer.score_ids(g_host, rows), scorer.score_ids(m_host, rows)
+                g_mask = hostglue.masks_from_ids(g_host)
+                labels_ = cur["labels"] if multitask else None
+                if cfg.lambda_loss > 0:
+                    return model.mixed_update(video, greedy_words, g_mask, rb["r"], rb["b"], cur["gt"], cur["gmask"], lr=learning_rate(cfg, model.global_step),
+                                              lambda_loss=cfg.lambda_loss, clip_norm=cfg.clip_norm, video_base=lo, true_labels=labels_, decay_all=multitask)
+                return model.reinforce_update(video, greedy_words, g_mask, rb["r"], rb["b"], lr=learning_rate(cfg, model.global_step), clip_norm=cfg.clip_norm,
+                                              video_base=lo, true_labels=labels_)
+
             def overlap():          # while the GPU runs the update: the next batch, and the previous step's log lines
                 if gnext is not None:
                     nxt.update(prepare(gnext))
                 if pending is not None:
                     pending()
-            st, loss = run_step(model, step, log, overlap=overlap)
+            st, loss = run_step(model, step if mix_p is None else step_mix, log, overlap=overlap)
             r, b = rb["r"], rb["b"]
             losses.append(loss); adv.append(float(r.mean() - b.mean()))
             t1 = time.time()
@@ -189,11 +217,14 @@ def main():
     ap.add_argument("--stop-at-eos", action="store_true", help="samples leave the decode loop at their first <eos> (same update, shorter sampler loop)")
     ap.add_argument("--attr-vocab", help="multitask scripts: file with one attribute word per line (label_dim = its length)")
     ap.add_argument("--alpha", type=float, default=0.05); ap.add_argument("--lambda-loss", type=float, default=0.0)
+    ap.add_argument("--mix-baseline", type=float, metavar="P", help="the greedy caption is the policy's sample and the baseline is the reward of a greedy "
+                    "decode fed ground-truth words with probability P / 1.00001 (reinforce_multitask_e2e_attribute_by_groudtruth_greedy_s2vt.py:957-979; "
+                    "0.9 there); needs --samples 1; with --lambda-loss > 0 the update is that script's mixed objective")
     ap.add_argument("--grad-precision", choices=("fp32", "bf16"), help="the backward's gradient contractions on bf16 operands (non-parity "
                     "fast mode, DESIGN.md §3); default: S2VT_GRAD_PRECISION, else fp32")
     a = ap.parse_args()
     cfg = rl_config(n_epochs=a.epochs, batch_size=a.batch_size, multisample=a.samples, model_path=a.model_path, stop_at_eos=a.stop_at_eos,
-                    alpha=a.alpha, lambda_loss=a.lambda_loss)
+                    alpha=a.alpha, lambda_loss=a.lambda_loss, mix_baseline=a.mix_baseline)
     tr = Corpus(a.train_sents, a.train_feats, vocabulary_file=a.vocab)
     te = Corpus(a.test_sents, a.test_feats, vocabulary=tr.vocabulary) if a.test_sents and a.test_feats else None
     attr = [l.strip() for l in open(a.attr_vocab)] if a.attr_vocab else None
