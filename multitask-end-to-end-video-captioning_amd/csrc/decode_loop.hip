@@ -22,7 +22,8 @@
 //
 // Same arithmetic as the launches it replaces: each z and each logit is the same ascending-k fmaf chain (carried partial,
 // embedding rows, recurrent rows; then + bias), the keys are the same expressions, ties go to the lowest column -- ids are
-// bit-identical (tests/test_gpu_decode_loop.py runs the sampler both ways in child processes: four shapes, two seeds each).
+// bit-identical (tests/test_gpu_decode_loop.py runs the sampler both ways in child processes: four shapes, two seeds each;
+// tests/test_gpu_decode_loop_edges.py holds it to the CPU oracle at the edges of the window decode_loop_eligible admits).
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>

@@ -2,7 +2,9 @@
 Since round 6 it is the product path at <= 64 decode rows (S2VT_DECLOOP unset / 1; its phase B runs on loader waves) and opt-in at 257-384 rows
 (S2VT_DECLOOP=2, measured slower than the launches there).  Same chains, same keys: the token ids are those of the per-step launches
 (S2VT_DECLOOP=0), bit for bit, at the bench dimensions (B = 64, K = 5: R = 384), at 320 rows (five row tiles per part), with a vocabulary that
-leaves workgroups idle in the pick phase, with a batch that is not a power of two, and at 16 / 32 / 48 / 64 rows incl. a greedy-only batch."""
+leaves workgroups idle in the pick phase, with a batch that is not a power of two, and at 16 / 32 / 48 / 64 rows incl. a greedy-only batch.
+All of it at H >= 992 on default-scale weights; tests/test_gpu_decode_loop_edges.py runs the edges of the admitted window (H 132 .. 1008, E 1 .. 129,
+V 8 .. 12288, one step, no greedy rows) against the CPU oracle on inputs whose ids react to the decode state, and the exact ties between workgroups."""
 import os
 import subprocess
 import sys
