@@ -250,6 +250,36 @@ int s2vt_teacher_forced_fwd(const s2vt_dims* d, const s2vt_params* p, const floa
                             const int32_t* sample_id, float* logits_out, void* workspace, size_t workspace_bytes,
                             s2vt_stream stream);
 
+/* ---- scheduled-sampling unroll: build_model of generate_words_tf_s2vt.py:101-211 (forward) -------------------------------------------
+ * The training unroll decodes: at step t >= 1 row n of LSTM2 is fed the ground-truth word caption[n][t - 1] when its coin says so and
+ * its own argmax of step t - 1 otherwise (:159-168); step 0 feeds <bos> = 1 (:161-163).  The argmax is behind tf.stop_gradient (:166),
+ * so the gradient of the step is that of a teacher-forced step on the words that were fed: after the call the training workspace
+ * (s2vt_train_workspace_bytes, unchanged) is what s2vt_teacher_forced_fwd leaves for a caption whose previous words are `fed` -- prev
+ * holds the fed words, tgt the ground truth, G1 .. O2 the activations -- and s2vt_bptt_bwd* / s2vt_bptt_dvideo run on it as they are.
+ * Coin (:136-139,159: tf.multinomial over log([p, 1.00001 - p]), so p_gt = p / 1.00001; p = 0.5 is written into the reference's graph):
+ * s2vt_sample_mix's, extended by the sample id -- u = u01(philox4x32_10(counter (0, video_id[n], sample_id[n], t), key (coin_seed_lo,
+ * coin_seed_hi ^ 0x4D495853)).x), ground truth iff u < p_gt.  With sample_id = 0 these are s2vt_sample_mix's coins for video_base + b =
+ * video_id.  video_id / sample_id are required whatever keep says; they also key the dropout streams (keep, seed: as s2vt_teacher_forced_fwd).
+ * Per step: the dropout-wrapped cells (:151-154,181-184), logits = xw_plus_b(dropped out2) (:189), generated = argmax (lowest index on ties,
+ * :193).  Quirk SQ1 (:194-199): the running mask one_mask[n] *= (generated[n] != 0) is updated BEFORE it weighs the step's cross entropy,
+ * so it follows the model's own picks, not the caption, and the position at which the model emits <eos> is already masked (s2vt_caption_mask
+ * keeps that position).  All outputs are device memory:
+ *   logits_out [Tc*N, V] time-major, bit-identical to s2vt_teacher_forced_fwd's for the same fed words (:200 `probs`);
+ *   generated, fed [N, Tc] int32 (fed[:, 0] = 1);  mask [N, Tc] (:201 `caption_mask`, transposed);
+ *   coef_tm [Tc*N] = loss_weight * mask and target_tm [Tc*N] = caption, both time-major: what s2vt_softmax_nll_fwd_bwd takes (smoothing 0;
+ *   the loss of :198-210 is sum(coef * nll) / sum(mask) + the weight decay term);
+ *   *mask_sum, *mask_sum_copy = sum(mask), each may be NULL (the copy: the gradient bucket's tail slot), summed in a fixed order.
+ * sum(mask) = 0 -- every row emits <eos> at step 0 -- is the reference's 0/0 and is not repaired here.
+ * caption: device int32 [N, Tc]; an id outside [0, n_words) is clamped into that range where it is read.  One fused cell launch, one pick
+ * launch and one small launch per step, no host round trip.  scratch: s2vt_scheduled_scratch_bytes(d, N) bytes (0 on bad arguments), 256-byte
+ * aligned like the workspace.  Errors: S2VT_E_BADARG (a NULL pointer other than the two sums, N % B != 0, keep <= 0, p_gt outside [0, 1] or
+ * NaN), S2VT_E_ALIGN, S2VT_E_WORKSPACE, S2VT_E_CHAIN_TIMEOUT. */
+size_t s2vt_scheduled_scratch_bytes(const s2vt_dims* d, int32_t N);
+int s2vt_scheduled_fwd(const s2vt_dims* d, const s2vt_params* p, const float* video, int32_t B, int32_t N, const int32_t* caption, float p_gt,
+                       uint64_t coin_seed, float loss_weight, float keep, uint64_t seed, const int32_t* video_id, const int32_t* sample_id,
+                       float* logits_out, int32_t* generated, int32_t* fed, float* mask, float* coef_tm, int32_t* target_tm, float* mask_sum,
+                       float* mask_sum_copy, void* workspace, size_t workspace_bytes, void* scratch, size_t scratch_bytes, s2vt_stream stream);
+
 /* Same, inside a REINFORCE step: LSTM1's state trajectory depends only on the frames and the weights, and the
  * sampler pass of the step (s2vt_sample / s2vt_encode_fwd on the SAME video block, SAME weights) has just
  * computed it.  Pass that call's workspace (and its row count R = (K + with_greedy) * B) and the trajectory and
@@ -483,6 +513,13 @@ int s2vt_adam_tf(float* theta, const float* g, float* m, float* v, int64_t n, co
  * *applied_step tells the host which update was the last one applied. */
 int s2vt_adam_tf_guarded(float* theta, const float* g, float* m, float* v, int64_t n, const float* sumsq, float clip_norm,
                          float lr, int64_t step, float beta1, float beta2, float eps, int32_t* applied_step, s2vt_stream stream);
+
+/* tf.train.GradientDescentOptimizer behind tf.clip_by_global_norm (generate_words_tf_s2vt.py:412-418): theta -= lr * g * clip_norm /
+ * max(sqrt(*sumsq), clip_norm) over one flat range (clip_norm <= 0 or sumsq NULL: no clipping, as s2vt_adam_tf), step >= 1.  The same
+ * receipt (*applied_step = step, may be NULL) and the same on-device no-op while a persistent-recurrence fault is pending as
+ * s2vt_adam_tf_guarded. */
+int s2vt_sgd_guarded(float* theta, const float* g, int64_t n, const float* sumsq, float clip_norm, float lr, int64_t step, int32_t* applied_step,
+                     s2vt_stream stream);
 
 /* ---- temporal attention, one decode step (original_attention.py:106-128) ----------------------
  * Inputs: hWa [B,H] = h_prev @ embed_att_Wa (s2vt_gemm); P [Tv,B,H] = Vt @ embed_att_Ua + ba (hoisted,

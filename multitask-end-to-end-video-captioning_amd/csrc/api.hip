@@ -68,7 +68,7 @@ __global__ __launch_bounds__(256) void mix_words_kernel(const unsigned long long
     const unsigned long long w = picked[(size_t)r * stride];
     int32_t id = w ? (int32_t)(~(uint32_t)w) : 0;
     const int b = r - mix_lo;
-    if (b >= 0 && b < B && mix_feeds_truth(seed_lo, seed_hi, (uint32_t)(video_base + b), (uint32_t)t, p_gt)) {
+    if (b >= 0 && b < B && mix_feeds_truth(seed_lo, seed_hi, (uint32_t)(video_base + b), 0u, (uint32_t)t, p_gt)) {
         const int32_t c = caption[(size_t)b * Tc + t - 1];
         id = c < 0 ? 0 : c >= V ? V - 1 : c;
     }

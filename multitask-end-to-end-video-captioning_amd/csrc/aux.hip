@@ -946,6 +946,40 @@ hipError_t launch_adam_tf(float* theta, const float* g, float* m, float* v, int6
     return hipGetLastError();
 }
 
+// tf.train.GradientDescentOptimizer behind tf.clip_by_global_norm (generate_words_tf_s2vt.py:412-418): theta -= lr * (g * s), s as in
+// adam_tf_kernel; the same fault guard and receipt.  16-byte pieces where both pointers allow, per element the same expression.
+__global__ __launch_bounds__(256) void sgd_kernel(float* theta, const float* g, int64_t n, const float* sumsq, float clip, float lr,
+                                                  const unsigned* fault, int32_t* applied_step, int32_t step)
+{
+    if (fault && *fault != 0u) return;             // a persistent recurrence upstream timed out: leave the variables alone
+    if (applied_step && blockIdx.x == 0 && threadIdx.x == 0) *applied_step = step;
+    float s = 1.0f;
+    if (sumsq && clip > 0.f) {
+        const float nrm = sqrtf(*sumsq);
+        s = clip / fmaxf(nrm, clip);
+    }
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    const bool vec = ((reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(theta)) & 15u) == 0;
+    const int64_t n4 = vec ? n >> 2 : 0;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
+        const float4 gv = reinterpret_cast<const float4*>(g)[i];
+        float4 th = reinterpret_cast<float4*>(theta)[i];
+        th.x -= lr * (gv.x * s); th.y -= lr * (gv.y * s); th.z -= lr * (gv.z * s); th.w -= lr * (gv.w * s);
+        reinterpret_cast<float4*>(theta)[i] = th;
+    }
+    for (int64_t i = 4 * n4 + (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) theta[i] -= lr * (g[i] * s);
+}
+
+hipError_t launch_sgd(float* theta, const float* g, int64_t n, const float* sumsq, float clip, float lr, hipStream_t st, const unsigned* fault,
+                      int32_t* applied_step, int32_t step)
+{
+    if (n <= 0) return hipSuccess;
+    int blocks = (int)((n + 1023) / 1024);
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(sgd_kernel, dim3(blocks), dim3(256), 0, st, theta, g, n, sumsq, clip, lr, fault, applied_step, step);
+    return hipGetLastError();
+}
+
 // ---------------------------------------------------------------------------------------------
 // TN GEMM launcher
 // ---------------------------------------------------------------------------------------------

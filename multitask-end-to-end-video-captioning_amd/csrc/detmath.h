@@ -188,11 +188,13 @@ __device__ __forceinline__ float dropout_keep01(uint32_t seed_lo, uint32_t seed_
 }
 
 // The coin of the mixed sampler (build_mix_sample, reinforce_multitask_e2e_attribute_by_groudtruth_greedy_s2vt.py:547-557,576-587:
-// tf.multinomial over log([p, 1.00001 - p]) per row per step): key (seed_lo, seed_hi ^ 'MIXS'), counter (0, video, 0, step), word x.
+// tf.multinomial over log([p, 1.00001 - p]) per row per step): key (seed_lo, seed_hi ^ 'MIXS'), counter (0, video, sample, step), word x.
 // true = the row is fed the ground-truth word.  u lies strictly inside (0, 1): p_gt = 1 always feeds it, p_gt = 0 never.
-__device__ __forceinline__ bool mix_feeds_truth(uint32_t seed_lo, uint32_t seed_hi, uint32_t video, uint32_t step, float p_gt)
+// sample: 0 in the mixed sampler (one row per video); the scheduled-sampling unroll (generate_words_tf_s2vt.py:136-139,159) passes the row's
+// sample id, so the rows of one video draw their own coins and sample 0 draws the mixed sampler's.
+__device__ __forceinline__ bool mix_feeds_truth(uint32_t seed_lo, uint32_t seed_hi, uint32_t video, uint32_t sample, uint32_t step, float p_gt)
 {
-    const u32x4 v = philox4x32_10(0u, video, 0u, step, seed_lo, seed_hi ^ 0x4D495853u);
+    const u32x4 v = philox4x32_10(0u, video, sample, step, seed_lo, seed_hi ^ 0x4D495853u);
     return u01(v.x) < p_gt;
 }
 

@@ -102,6 +102,9 @@ hipError_t launch_grad_finalize(float* g, const float* theta, int64_t n, const f
 hipError_t launch_adam_tf(float* theta, const float* g, float* m, float* v, int64_t n, const float* sumsq, float clip,
                           float lr_t, float b1, float b2, float eps, hipStream_t st, const unsigned* fault = nullptr,
                           int32_t* applied_step = nullptr, int32_t step = 0);
+// theta -= lr * g * clip / max(sqrt(*sumsq), clip) (plain gradient descent behind the global-norm clip); fault / applied_step as above
+hipError_t launch_sgd(float* theta, const float* g, int64_t n, const float* sumsq, float clip, float lr, hipStream_t st,
+                      const unsigned* fault = nullptr, int32_t* applied_step = nullptr, int32_t step = 0);
 
 // ---- a whole LSTM recurrence (T steps, M <= 64 rows) in one persistent launch (chain.hip)
 struct ChainArgs {

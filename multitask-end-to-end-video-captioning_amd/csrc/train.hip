@@ -305,6 +305,201 @@ hipError_t lstm_recurrence_bwd(const float* W, int kw0, const float* gates, cons
     return hipSuccess;
 }
 
+
+// The stages of a training unroll that do not depend on a word, shared by the teacher-forced and the scheduled-sampling forward: the
+// frame-gather index, zero initial states, frame embedding, LSTM1's whole trajectory of T steps on B rows (or its copy out of the sampler
+// pass's workspace), its dropped output O1 for the N sample rows, and the out1 partials of LSTM2's Tv encode steps in G2.
+int unroll_front(const s2vt_dims* d, const s2vt_params* p, const float* video, int B, int N, int T, float keep, uint64_t seed,
+                 const int32_t* video_id, const int32_t* sample_id, const TrainWs& w, const void* sampler_workspace,
+                 size_t sampler_workspace_bytes, int sampler_rows, s2vt_stream stream)
+{
+    const int H = d->lstm_dim, E = d->word_dim, Tv = d->n_video_lstm_step;
+    const size_t NH = (size_t)N * H, BH = (size_t)B * H;
+    hipStream_t st = S(stream);
+    hipLaunchKernelGGL(enc_index_kernel, dim3((B * Tv + 255) / 256), dim3(256), 0, st, w.encidx, B, Tv);
+    HIP_TRY(hipGetLastError());
+    // zero initial states (tf_s2vt.py:105-107): slot 0 of the state histories
+    {
+        ZeroList z;
+        if (!sampler_workspace) { z.add(w.C1, BH * 4); z.add(w.H1, BH * 4); }      // (taken whole from the sampler pass otherwise)
+        z.add(w.C2, NH * 4); z.add(w.H2, NH * 4);
+        HIP_TRY(launch_zero_regions(z, st));
+    }
+    if (!sampler_workspace) {                     // (with the sampler's workspace the frame embedding is taken from there too, below)
+        int rc = s2vt_frame_embed_fwd(d, p, video, B, w.emb, stream);
+        if (rc != S2VT_OK) return rc;
+    }
+
+    NoiseIds none{nullptr, nullptr, 0};
+    // Every contraction below is the SAME ascending-k chain as concat([x, h]) @ W (tf_s2vt.py:119-143):
+    // the rows of W that multiply non-recurrent inputs are consumed first, for all time steps in one
+    // batched launch; the per-step launch then continues each chain from that partial with the
+    // recurrent rows.
+    // ---- LSTM1: input rows of W1 for the Tv frames (row j*Tv + t of emb), then the recurrence on B rows
+    if (sampler_workspace) {
+        // The sampler pass of this step already ran LSTM1 on these videos with these weights (its state never
+        // sees a word or a dropout mask): take its state history and activated gates instead of recomputing.
+        Carver sc(const_cast<void*>(sampler_workspace), sampler_workspace_bytes);
+        SampleWs sw;
+        carve_sample(sc, d, B, sampler_rows, &sw);
+        if (!sc.ok() || sampler_rows <= 0) return S2VT_E_WORKSPACE;
+        CopyList cl;
+        // (the frame embedding the backward's dW1 product reads: the same product of the same operands in the sampler pass)
+        if (cl.add(w.C1, sw.c1, (size_t)(T + 1) * BH * 4) && cl.add(w.H1, sw.h1, (size_t)(T + 1) * BH * 4) && cl.add(w.G1, sw.G1, (size_t)T * 4 * BH * 4) &&
+            cl.add(w.emb, sw.emb, (size_t)B * Tv * E * 4)) {
+            HIP_TRY(launch_copy_regions(cl, st));                                  // one library launch
+        } else {                                                                   // (B * H not a multiple of 4: the runtime's copies)
+            HIP_TRY(hipMemcpyAsync(w.emb, sw.emb, (size_t)B * Tv * E * 4, hipMemcpyDeviceToDevice, st));
+            HIP_TRY(hipMemcpyAsync(w.C1, sw.c1, (size_t)(T + 1) * BH * 4, hipMemcpyDeviceToDevice, st));
+            HIP_TRY(hipMemcpyAsync(w.H1, sw.h1, (size_t)(T + 1) * BH * 4, hipMemcpyDeviceToDevice, st));
+            HIP_TRY(hipMemcpyAsync(w.G1, sw.G1, (size_t)T * 4 * BH * 4, hipMemcpyDeviceToDevice, st));
+        }
+    } else {
+        {
+            ASeg sx = make_seg(w.emb, E, E, 0);
+            HIP_TRY(store_call(&sx, 1, p->lstm1_W, 4 * H, nullptr, w.Xp1, 4 * H, B * Tv, 4 * H, 0, -1, st));
+        }
+        // tf_s2vt.py:119 (encode) / :140 (decode, zero padding input: only the recurrent rows remain)
+        HIP_TRY(lstm_recurrence(p->lstm1_W, E, p->lstm1_b, w.Xp1, (size_t)4 * H, Tv * 4 * H, Tv, w.C1, w.H1, BH, w.G1, (size_t)4 * BH,
+                                nullptr, 0, B, H, T, 1.0f, none, 0, w.chain_abuf, w.chain_sync, st));
+    }
+    // DropoutWrapper(LSTM1) output for the N sample rows (tf_s2vt.py:75; code = 256 + t)
+    HIP_TRY(launch_expand_dropout(w.H1 + BH, w.O1, T, B, N, H, keep, seed, 256u, video_id, sample_id, st));
+    // ---- LSTM2, encode steps: the out1 rows of W2, written where the step's activated gates will go (the step kernel reads its
+    // partial, then overwrites it)
+    {
+        ASeg se = make_seg(w.O1, H, H, 0);                                       // encode: the word slot is the zero padding (:122)
+        HIP_TRY(store_call(&se, 1, p->lstm2_W, 4 * H, nullptr, w.G2, 4 * H, Tv * N, 4 * H, 0, -1, st));
+    }
+    return S2VT_OK;
+}
+
+// ---- scheduled sampling (generate_words_tf_s2vt.py:101-211): the kernels around the per-step decode launches
+__device__ __forceinline__ int32_t clamp_word(int32_t c, int V) { return c < 0 ? 0 : c >= V ? V - 1 : c; }
+
+// before step 0: <bos> = 1 as every row's first fed word (:161-163), the ground truth as the workspace's time-major targets, and the
+// all-argmax sample ids of the pick launches
+__global__ __launch_bounds__(256) void sched_open_kernel(const int32_t* caption, int N, int Tc, int V, int32_t* prev, int32_t* tgt, int32_t* fed,
+                                                         int32_t* argmax_sid)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= N * Tc) return;
+    const int t = i / N, n = i - t * N;
+    tgt[i] = clamp_word(caption[(size_t)n * Tc + t], V);
+    if (t == 0) { prev[n] = 1; fed[(size_t)n * Tc] = 1; argmax_sid[n] = -1; }
+}
+
+// behind the pick of step t, one thread per row: the row's argmax out of its packed pick (decoded as unpack_ids_kernel does), the running
+// mask one_mask *= (generated != 0) updated BEFORE it weighs the step (:194-199), the step's loss coefficient and target, and the word
+// step t + 1 is fed -- caption[n][t] when the coin of step t + 1 says so, the pick otherwise (:159-168)
+__global__ __launch_bounds__(256) void sched_step_kernel(const unsigned long long* picked, int stride, const int32_t* caption, int N, int Tc, int t,
+                                                         int V, const int32_t* video_id, const int32_t* sample_id, uint32_t seed_lo,
+                                                         uint32_t seed_hi, float p_gt, float loss_weight, float* running, int32_t* generated,
+                                                         int32_t* fed, float* mask, float* coef_tm, int32_t* target_tm, int32_t* prev)
+{
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    if (n >= N) return;
+    const unsigned long long w = picked[(size_t)n * stride];
+    const int32_t g = w ? (int32_t)(~(uint32_t)w) : 0;
+    const float m = (t == 0 ? 1.0f : running[n]) * (g != 0 ? 1.0f : 0.0f);
+    running[n] = m;
+    const int32_t truth = clamp_word(caption[(size_t)n * Tc + t], V);
+    generated[(size_t)n * Tc + t] = g;
+    mask[(size_t)n * Tc + t] = m;
+    coef_tm[(size_t)t * N + n] = loss_weight * m;
+    target_tm[(size_t)t * N + n] = truth;
+    if (t + 1 < Tc) {
+        const int32_t word = mix_feeds_truth(seed_lo, seed_hi, (uint32_t)video_id[n], (uint32_t)sample_id[n], (uint32_t)(t + 1), p_gt) ? truth : g;
+        fed[(size_t)n * Tc + t + 1] = word;
+        prev[(size_t)(t + 1) * N + n] = word;
+    }
+}
+
+// sum(mask) in a fixed order: one workgroup, thread i adds entries i, i + 256, ..., then the tree of caption_mask_kernel
+__global__ __launch_bounds__(256) void sched_mask_sum_kernel(const float* mask, int n, float* mask_sum, float* mask_sum_copy)
+{
+    __shared__ float sh[4];
+    float local = 0.f;
+    for (int i = threadIdx.x; i < n; i += 256) local += mask[i];
+    for (int off = 32; off > 0; off >>= 1) local += __shfl_down(local, off, 64);
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = local;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const float total = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+        if (mask_sum) *mask_sum = total;
+        if (mask_sum_copy) *mask_sum_copy = total;
+    }
+}
+
+// The scratch of the scheduled unroll beside the training workspace: every step's packed picks (zeroed up front: the pick packs by atomic
+// maximum), the running mask, the pick launches' sample ids
+struct SchedScratch { unsigned long long* packed; float* running; int32_t* argmax_sid; };
+size_t carve_sched(Carver& c, const s2vt_dims* d, int N, SchedScratch* out)
+{
+    SchedScratch s;
+    s.packed = c.take<unsigned long long>((size_t)d->n_caption_lstm_step * N * kPickStride);
+    s.running = c.take<float>(N);
+    s.argmax_sid = c.take<int32_t>(N);
+    if (out) *out = s;
+    return c.off;
+}
+
+// (inside a stage: hand a failed launch's error to the driver, whose HIP_TRY records it)
+#define HIP_CHECK(expr) do { const hipError_t _e = (expr); if (_e != hipSuccess) return _e; } while (0)
+
+// The decoding stage of the scheduled unroll, in straight-line stages.  Step t continues DESIGN section 3's chain of the cell on
+// [out1 ; word ; h2] from the out1 partial in G2[Tv + t] with the fed word's rows of Wemb at kw = H, then H2[Tv + t] at kw = H + E -- the
+// blocks the teacher-forced pass multiplies in the same order, so the activations are the ones it leaves for the same fed words.
+struct SchedDecode {
+    const s2vt_params* p; const TrainWs& w; const SchedScratch& x;
+    int N, H, E, V, Tv, Tc; float keep; NoiseIds ids; hipStream_t st;
+    const int32_t* caption; float p_gt, loss_weight; uint64_t coin_seed;
+    float* logits; int32_t *generated, *fed; float *mask, *coef_tm; int32_t* target_tm;
+    size_t NH;
+
+    unsigned long long* picks(int t) const { return x.packed + (size_t)t * N * kPickStride; }
+
+    hipError_t open()
+    {
+        ZeroList z;
+        z.add(x.packed, (size_t)Tc * N * kPickStride * 8);
+        HIP_CHECK(launch_zero_regions(z, st));
+        hipLaunchKernelGGL(sched_open_kernel, dim3((N * Tc + 255) / 256), dim3(256), 0, st, caption, N, Tc, V, w.prev, w.tgt, fed, x.argmax_sid);
+        return hipGetLastError();
+    }
+    // out1 @ W2[0:H] of the Tc decode steps, where the steps' activated gates will go
+    hipError_t decode_partials()
+    {
+        ASeg so = make_seg(w.O1 + (size_t)Tv * NH, H, H, 0);
+        return store_call(&so, 1, p->lstm2_W, 4 * H, nullptr, w.G2 + (size_t)Tv * 4 * NH, 4 * H, Tc * N, 4 * H, 0, -1, st);
+    }
+    // LSTM2 over the Tv frames (:151-154; the word slot is the zero padding): leaves the encoder state in slot Tv of C2 / H2
+    hipError_t encode()
+    {
+        return lstm_recurrence(p->lstm2_W, H + E, p->lstm2_b, w.G2, (size_t)4 * NH, 4 * H, Tv, w.C2, w.H2, NH, w.G2, (size_t)4 * NH, w.O2, NH, N, H,
+                               Tv, keep, ids, 512u, w.chain_abuf, w.chain_sync, st);
+    }
+    hipError_t step(int t)
+    {
+        const int u = Tv + t;
+        float* const g2 = w.G2 + (size_t)u * 4 * NH;
+        ASeg s2[2] = {make_seg(p->Wemb, E, E, H, 0, w.prev + (size_t)t * N), make_seg(w.H2 + (size_t)u * NH, H, H, H + E)};
+        HIP_CHECK(lstm_call(s2, 2, p->lstm2_W, p->lstm2_b, w.C2 + (size_t)u * NH, 0, w.C2 + (size_t)(u + 1) * NH, w.H2 + (size_t)(u + 1) * NH,
+                            w.O2 + (size_t)u * NH, g2, N, H, keep, ids, 512u + (uint32_t)u, -1, st, g2, 4 * H, 0));
+        const NoiseIds argmax{ids.video_id, x.argmax_sid, 0};                 // (sample id -1: no noise is drawn, the seed is not read)
+        HIP_CHECK(pick_call(w.O2 + (size_t)u * NH, H, p->embed_word_W, p->embed_word_b, N, H, V, argmax, t, picks(t), logits + (size_t)t * N * V, -1,
+                            st, kPickStride));
+        hipLaunchKernelGGL(sched_step_kernel, dim3((N + 255) / 256), dim3(256), 0, st, picks(t), kPickStride, caption, N, Tc, t, V, ids.video_id,
+                           ids.sample_id, (uint32_t)coin_seed, (uint32_t)(coin_seed >> 32), p_gt, loss_weight, x.running, generated, fed, mask,
+                           coef_tm, target_tm, w.prev);
+        return hipGetLastError();
+    }
+    hipError_t close(float* mask_sum, float* mask_sum_copy)
+    {
+        hipLaunchKernelGGL(sched_mask_sum_kernel, dim3(1), dim3(256), 0, st, mask, N * Tc, mask_sum, mask_sum_copy);
+        return hipGetLastError();
+    }
+};
 }  // namespace
 
 extern "C" {
@@ -405,62 +600,15 @@ int s2vt_teacher_forced_fwd_live(const s2vt_dims* d, const s2vt_params* p, const
     hipStream_t st = S(stream);
 
     HIP_TRY(launch_prep_caption(caption, w.prev, w.tgt, N, d->n_caption_lstm_step, st));
-    hipLaunchKernelGGL(enc_index_kernel, dim3((B * Tv + 255) / 256), dim3(256), 0, st, w.encidx, B, Tv);
-    HIP_TRY(hipGetLastError());
-    const size_t NH = (size_t)N * H, BH = (size_t)B * H;
-    // zero initial states (tf_s2vt.py:105-107): slot 0 of the state histories
     {
-        ZeroList z;
-        if (!sampler_workspace) { z.add(w.C1, BH * 4); z.add(w.H1, BH * 4); }      // (taken whole from the sampler pass otherwise)
-        z.add(w.C2, NH * 4); z.add(w.H2, NH * 4);
-        HIP_TRY(launch_zero_regions(z, st));
-    }
-    if (!sampler_workspace) {                     // (with the sampler's workspace the frame embedding is taken from there too, below)
-        int rc = s2vt_frame_embed_fwd(d, p, video, B, w.emb, stream);
+        const int rc = unroll_front(d, p, video, B, N, T, keep, seed, video_id, sample_id, w, sampler_workspace, sampler_workspace_bytes,
+                                    sampler_rows, stream);
         if (rc != S2VT_OK) return rc;
     }
-
-    NoiseIds none{nullptr, nullptr, 0};
+    const size_t NH = (size_t)N * H;
     NoiseIds ids{video_id, sample_id, seed};
-    // Every contraction below is the SAME ascending-k chain as concat([x, h]) @ W (tf_s2vt.py:119-143):
-    // the rows of W that multiply non-recurrent inputs are consumed first, for all time steps in one
-    // batched launch; the per-step launch then continues each chain from that partial with the
-    // recurrent rows.
-    // ---- LSTM1: input rows of W1 for the Tv frames (row j*Tv + t of emb), then the recurrence on B rows
-    if (sampler_workspace) {
-        // The sampler pass of this step already ran LSTM1 on these videos with these weights (its state never
-        // sees a word or a dropout mask): take its state history and activated gates instead of recomputing.
-        Carver sc(const_cast<void*>(sampler_workspace), sampler_workspace_bytes);
-        SampleWs sw;
-        carve_sample(sc, d, B, sampler_rows, &sw);
-        if (!sc.ok() || sampler_rows <= 0) return S2VT_E_WORKSPACE;
-        CopyList cl;
-        // (the frame embedding the backward's dW1 product reads: the same product of the same operands in the sampler pass)
-        if (cl.add(w.C1, sw.c1, (size_t)(T + 1) * BH * 4) && cl.add(w.H1, sw.h1, (size_t)(T + 1) * BH * 4) && cl.add(w.G1, sw.G1, (size_t)T * 4 * BH * 4) &&
-            cl.add(w.emb, sw.emb, (size_t)B * Tv * E * 4)) {
-            HIP_TRY(launch_copy_regions(cl, st));                                  // one library launch
-        } else {                                                                   // (B * H not a multiple of 4: the runtime's copies)
-            HIP_TRY(hipMemcpyAsync(w.emb, sw.emb, (size_t)B * Tv * E * 4, hipMemcpyDeviceToDevice, st));
-            HIP_TRY(hipMemcpyAsync(w.C1, sw.c1, (size_t)(T + 1) * BH * 4, hipMemcpyDeviceToDevice, st));
-            HIP_TRY(hipMemcpyAsync(w.H1, sw.h1, (size_t)(T + 1) * BH * 4, hipMemcpyDeviceToDevice, st));
-            HIP_TRY(hipMemcpyAsync(w.G1, sw.G1, (size_t)T * 4 * BH * 4, hipMemcpyDeviceToDevice, st));
-        }
-    } else {
-        {
-            ASeg sx = make_seg(w.emb, E, E, 0);
-            HIP_TRY(store_call(&sx, 1, p->lstm1_W, 4 * H, nullptr, w.Xp1, 4 * H, B * Tv, 4 * H, 0, -1, st));
-        }
-        // tf_s2vt.py:119 (encode) / :140 (decode, zero padding input: only the recurrent rows remain)
-        HIP_TRY(lstm_recurrence(p->lstm1_W, E, p->lstm1_b, w.Xp1, (size_t)4 * H, Tv * 4 * H, Tv, w.C1, w.H1, BH, w.G1, (size_t)4 * BH,
-                                nullptr, 0, B, H, T, 1.0f, none, 0, w.chain_abuf, w.chain_sync, st));
-    }
-    // DropoutWrapper(LSTM1) output for the N sample rows (tf_s2vt.py:75; code = 256 + t)
-    HIP_TRY(launch_expand_dropout(w.H1 + BH, w.O1, T, B, N, H, keep, seed, 256u, video_id, sample_id, st));
-    // ---- LSTM2: rows of W2 for [out1 ; embed(prev word)] for all steps at once, written where the
-    // step's activated gates will go (the step kernel reads its partial, then overwrites it)
+    // ---- LSTM2, decode steps: rows of W2 for [out1 ; embed(prev word)] for all steps at once
     {
-        ASeg se = make_seg(w.O1, H, H, 0);                                       // encode: the word slot is the zero padding (:122)
-        HIP_TRY(store_call(&se, 1, p->lstm2_W, 4 * H, nullptr, w.G2, 4 * H, Tv * N, 4 * H, 0, -1, st));
         if (!live_rows) {
             ASeg sd[2] = {make_seg(w.O1 + (size_t)Tv * NH, H, H, 0), make_seg(p->Wemb, E, E, H, 0, w.prev)};   // decode (:143)
             HIP_TRY(store_call(sd, 2, p->lstm2_W, 4 * H, nullptr, w.G2 + (size_t)Tv * 4 * NH, 4 * H, Tc * N, 4 * H, 0, -1, st));
@@ -496,6 +644,47 @@ int s2vt_teacher_forced_fwd_live(const s2vt_dims* d, const s2vt_params* p, const
     // row live_rows[r] of the unroll: a masked position's logits feed nothing, its loss term and gradient are exact zeros)
     ASeg so = make_seg(w.O2 + (size_t)Tv * NH, H, H, 0, 0, live_rows);
     HIP_TRY(store_call(&so, 1, p->embed_word_W, V, p->embed_word_b, logits, V, live_rows ? n_live : Tc * N, V, 0, -1, st));
+    return S2VT_OK;
+}
+
+size_t s2vt_scheduled_scratch_bytes(const s2vt_dims* d, int32_t N)
+{
+    if (!dims_ok(d) || N <= 0) return 0;
+    Carver c(nullptr, 0);
+    return carve_sched(c, d, N, nullptr);
+}
+
+int s2vt_scheduled_fwd(const s2vt_dims* d, const s2vt_params* p, const float* video, int32_t B, int32_t N, const int32_t* caption, float p_gt,
+                       uint64_t coin_seed, float loss_weight, float keep, uint64_t seed, const int32_t* video_id, const int32_t* sample_id,
+                       float* logits_out, int32_t* generated, int32_t* fed, float* mask, float* coef_tm, int32_t* target_tm, float* mask_sum,
+                       float* mask_sum_copy, void* workspace, size_t workspace_bytes, void* scratch, size_t scratch_bytes, s2vt_stream stream)
+{
+    if (!dims_ok(d) || !params_ok(p) || !video || !caption || !video_id || !sample_id || !logits_out || !generated || !fed || !mask || !coef_tm ||
+        !target_tm || !workspace || !scratch || B <= 0 || N <= 0 || N % B)
+        return S2VT_E_BADARG;
+    if (!(p_gt >= 0.0f && p_gt <= 1.0f) || !(keep > 0.0f)) return S2VT_E_BADARG;              // (a NaN fails the comparisons)
+    if ((reinterpret_cast<uintptr_t>(workspace) | reinterpret_cast<uintptr_t>(scratch)) & 255u) return S2VT_E_ALIGN;
+    if (chain_fault()) return S2VT_E_CHAIN_TIMEOUT;
+    const int H = d->lstm_dim, E = d->word_dim, V = d->n_words, Tv = d->n_video_lstm_step, Tc = d->n_caption_lstm_step;
+    Carver c(workspace, workspace_bytes);
+    TrainWs w;
+    carve_train(c, d, B, N, &w);
+    Carver cs(scratch, scratch_bytes);
+    SchedScratch x;
+    carve_sched(cs, d, N, &x);
+    if (!c.ok() || !cs.ok()) return S2VT_E_WORKSPACE;
+    hipStream_t st = S(stream);
+    SchedDecode s{p, w, x, N, H, E, V, Tv, Tc, keep, NoiseIds{video_id, sample_id, seed}, st, caption, p_gt, loss_weight, coin_seed,
+                  logits_out, generated, fed, mask, coef_tm, target_tm, (size_t)N * H};
+    HIP_TRY(s.open());
+    {
+        const int rc = unroll_front(d, p, video, B, N, Tv + Tc, keep, seed, video_id, sample_id, w, nullptr, 0, 0, stream);
+        if (rc != S2VT_OK) return rc;
+    }
+    HIP_TRY(s.decode_partials());
+    HIP_TRY(s.encode());
+    for (int t = 0; t < Tc; ++t) HIP_TRY(s.step(t));
+    HIP_TRY(s.close(mask_sum, mask_sum_copy));
     return S2VT_OK;
 }
 
@@ -631,9 +820,6 @@ static int split_grad_mode(int N)
 // are final:  kVocab = the vocab projection (embed_word_W / _b final);  kLstm2 = LSTM2's recurrence + its weight gradients (lstm2_W / _b
 // final);  kRest = everything after (dX2, LSTM1, Wemb, frame embedding);  kLstm2AndRest = kLstm2 + kRest;  kAll = all.
 enum BwdPhase { kAll = 0, kVocab = 1, kLstm2AndRest = 2, kLstm2 = 3, kRest = 4 };
-
-// (inside a stage: hand a failed launch's error to the driver, whose HIP_TRY records it)
-#define HIP_CHECK(expr) do { const hipError_t _e = (expr); if (_e != hipSuccess) return _e; } while (0)
 
 // A weight gradient C[M, N] += A[rows, M]^T B[rows, N] (+ colsum += B's column sums); idx: A's rows gathered out of a table of gather_rows
 // rows (0 = not stated)
@@ -1205,6 +1391,15 @@ int s2vt_adam_tf_guarded(float* theta, const float* g, float* m, float* v, int64
     const double lr_t = (double)lr * sqrt(1.0 - pow((double)beta2, (double)step)) / (1.0 - pow((double)beta1, (double)step));
     HIP_TRY(launch_adam_tf(theta, g, m, v, n, sumsq, clip_norm, (float)lr_t, beta1, beta2, eps, S(stream), chain_fault_word(), applied_step,
                            (int32_t)step));
+    return S2VT_OK;
+}
+
+int s2vt_sgd_guarded(float* theta, const float* g, int64_t n, const float* sumsq, float clip_norm, float lr, int64_t step, int32_t* applied_step,
+                     s2vt_stream stream)
+{
+    if (!theta || !g || n < 0 || step < 1) return S2VT_E_BADARG;
+    if (chain_fault()) return S2VT_E_CHAIN_TIMEOUT;        // (a fault raised after this check is caught by the kernel itself)
+    HIP_TRY(launch_sgd(theta, g, n, sumsq, clip_norm, lr, S(stream), chain_fault_word(), applied_step, (int32_t)step));
     return S2VT_OK;
 }
 

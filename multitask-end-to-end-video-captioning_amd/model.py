@@ -732,7 +732,8 @@ class Video_Caption_Generator:
         video, N, _, ws, *_ = self._ctx
         return ops.bptt_dvideo(self.dims, self.store.params, video.shape[0], N, ws)
 
-    def apply_gradients(self, mask_sum, lr, clip_norm, weight_decay=0.0, attr_scale=None, extra_sumsq=None, decay_all=False, loss_terms=None):
+    def apply_gradients(self, mask_sum, lr, clip_norm, weight_decay=0.0, attr_scale=None, extra_sumsq=None, decay_all=False, loss_terms=None,
+                        optimizer="adam"):
         """All-reduce (RCCL, one flat bucket + sum(mask) in its tail), 1/sum(mask), weight decay,
         tf.clip_by_global_norm, TF-form Adam (reinforcement_multisampling_tf_s2vt.py:643-652).
         attr_scale: constant normaliser of the attribute-head gradients (their range of the bucket is
@@ -740,7 +741,11 @@ class Video_Caption_Generator:
         extra_sumsq: callable(gscale) -> device scalar, the squared norm of gradients held OUTSIDE the bucket (the CNN of
         the end-to-end scripts) that tf.clip_by_global_norm sees in the same list; it is called once 1/sum(mask) is
         known.  decay_all: the e2e scripts' always-true weight-decay predicate (e2e_tf_s2vt.py:199) -- the LSTM biases
-        are decayed as well."""
+        are decayed as well.
+        optimizer: "adam", or "sgd" = tf.train.GradientDescentOptimizer (generate_words_tf_s2vt.py:414), which leaves Adam's moments
+        and its count of applied updates alone."""
+        if optimizer not in ("adam", "sgd"):
+            raise ValueError(f"optimizer must be 'adam' or 'sgd', got {optimizer!r}")
         st = self.store
         early = getattr(self, "_early", None)
         if early is not None and dp.active():
@@ -773,6 +778,12 @@ class Video_Caption_Generator:
         ops.grad_finalize(st.grad[nd:st.numel], st.theta[nd:], self._gscale, weight_decay if decay_all else 0.0, self._sumsq)
         if extra_sumsq is not None:
             self._sumsq += extra_sumsq(self._gscale)
+        if optimizer == "sgd":
+            self.global_step += 1
+            self._sampler_state = None
+            # (the receipt recover() reads counts applied updates as adam_t does: an SGD step reports the count unchanged)
+            ops.sgd(st.theta, st.grad[:st.numel], self._sumsq, clip_norm, lr, max(1, self.adam_t), applied_step=self._applied)
+            return
         self.global_step += 1
         self.adam_t += 1
         self._sampler_state = None                 # the variables change: a saved sampler trajectory is stale from here on
@@ -943,6 +954,112 @@ class Video_Caption_Generator:
         st = StepStats(self._loss[0], self._sumsq, msum[0])
         st.attr_loss = attr_loss
         return st
+
+    def scheduled_update(self, video, caption, lr, true_word_prob=0.5, clip_norm=10.0, optimizer="adam", video_base=0, keep=None,
+                         coin_seed=None):
+        """build_model + train_op of generate_words_tf_s2vt.py:101-211,412-418: scheduled sampling.  The unroll decodes; at step t >= 1 a
+        per-row coin feeds LSTM2 the ground-truth word caption[:, t-1] with probability true_word_prob / 1.00001 (:136-139) and the row's
+        own argmax otherwise.  The argmax is behind tf.stop_gradient (:166), so the backward is the teacher-forced one on the words that
+        were fed (ops.scheduled_fwd leaves the workspace so).  Loss (:198-210): per-row softmax cross entropy against caption[:, t], no label
+        smoothing, no batch mean, weighed by the running mask one_mask *= (generated != 0) -- made from the model's own picks and updated
+        BEFORE it weighs the step, so the position where the model emits <eos> is already masked (quirk SQ1) -- divided by sum(mask), plus
+        weight decay on the non-'bias' variables.  Every row emitting <eos> at step 0 makes sum(mask) = 0 and the loss 0/0, as in the
+        reference: the update is then NaN; callers that read the loss (train_xe does) stop there.
+        caption [N, Tc], N = rep * B sample-major rows over the B videos.  optimizer: "adam", or "sgd" as the reference's train() has it.
+        coin_seed None: sample_seed + 7919 * (global_step + 1), fresh coins every step.  Data parallel: sum(mask) rides in the gradient
+        bucket's tail slot, as in reinforce_update with a device-made mask.
+        Returns StepStats (.loss without the weight-decay term) plus .mask [N, Tc], .generated, .fed [N, Tc] int32 device tensors."""
+        p_gt = np.float32(np.float64(true_word_prob) / np.float64(1.00001))
+        if not 0.0 <= float(p_gt) <= 1.0:                          # (NaN fails too)
+            raise ValueError(f"true_word_prob must lie in [0, 1.00001], got {true_word_prob!r}")
+        video = self._dev(video, torch.float32)
+        cap = self._dev(caption, torch.int32)
+        B, N = video.shape[0], cap.shape[0]
+        if N % B or cap.dim() != 2 or cap.shape[1] != self.n_caption_lstm_step:
+            raise ValueError(f"scheduled_update: caption must be [rep * {B}, {self.n_caption_lstm_step}], got {tuple(cap.shape)}")
+        keep = self.dropout_rate if keep is None else keep
+        vid, sid = self._row_ids(B, N // B, video_base)
+        seed = self.dropout_seed + 104729 * self.global_step
+        if coin_seed is None:
+            coin_seed = self.sample_seed + 7919 * (self.global_step + 1)
+        st_ = self.store
+        f = ops.scheduled_fwd(self.dims, st_.params, video, cap, N, float(p_gt), coin_seed, self.loss_weight, keep, seed, vid, sid,
+                              mask_sum_copy=st_.grad[st_.numel:st_.numel + 1])
+        logits, coef, target, msum = f["logits"], f["coef_tm"], f["target_tm"], f["mask_sum"]
+        self.last_scheduled = f                                  # (build_scheduled_model's fetches read the logits before the softmax overwrites them)
+        keep_logits = getattr(self, "_keep_scheduled_logits", False)
+        if keep_logits:
+            f["probs"] = logits.clone()
+        dlogits = logits
+        if self.grad_precision == "fp32" and ops.split_grad_active(N):
+            nll, _, in_planes = ops.softmax_nll_fwd_bwd_split(logits, target, coef, 0.0, self.dims, B, N)
+            if in_planes:
+                dlogits = _PlanesDlogits(logits, target, coef, 0.0)
+        else:
+            nll, _ = ops.softmax_nll_fwd_bwd(logits, target, coef, 0.0)
+        self._coef_used = coef
+        self._ctx = (video, N, dlogits, f["ws"], keep, seed, vid, sid, self.n_caption_lstm_step, None)
+        self.backward(keep_tail=True)
+        self.apply_gradients(None, lr, clip_norm, weight_decay=self.decay_value, loss_terms=(coef, nll, msum), optimizer=optimizer)
+        st = StepStats(self._loss[0], self._sumsq, msum[0])
+        st.mask, st.generated, st.fed = f["mask"], f["generated"], f["fed"]
+        return st
+
+    @staticmethod
+    def inverse_sigmoid_prob(k_value, steps):
+        """The commented schedule of generate_words_tf_s2vt.py:134: p = k / (k + exp(steps / k)), in float64."""
+        k = float(k_value)
+        x = float(steps) / k
+        return k / (k + math.exp(x)) if x < 700.0 else 0.0      # (exp overflows a double past ~709: the limit)
+
+    def build_scheduled_model(self, true_word_prob=0.5, k_value=None):
+        """The scheduled-sampling graph: (loss, video, caption, caption_mask, probs, steps) as generate_words_tf_s2vt.py:101-211.  Here
+        caption_mask is an OUTPUT, fetched as [Tc, B, 1] (:201, the stacked running masks), and probs a list of Tc fetches [B, V] (the
+        logits of :200).  steps is a placeholder that may be fed; it is ignored, as in the reference (:134 is commented out, p = 0.5 is
+        written into the graph), unless k_value is given: then p = k / (k + exp(steps / k)) is evaluated on the host in float64.
+        Fetching loss / caption_mask / probs evaluates the forward only; minimize() builds the train_op.  Every run draws fresh coins, as
+        the stateful TF op does."""
+        B, Tc = self.batch_size, self.n_caption_lstm_step
+        video = self._video_placeholder(B)
+        caption = Placeholder("caption", (B, Tc), np.int32)
+        steps = Placeholder("steps", (), np.int32)
+        state = {"calls": 0}
+
+        def prob(s):
+            return true_word_prob if k_value is None else self.inverse_sigmoid_prob(k_value, 0 if s is None else s)
+
+        def coin_seed():
+            state["calls"] += 1
+            return self.sample_seed + 7919 * (self.global_step + 1) + 104723 * state["calls"]
+
+        def fetches(f, loss):
+            out = {"loss": loss, "caption_mask": f["mask"].t().contiguous().cpu().numpy()[:, :, None]}
+            pr = f["probs"].view(Tc, -1, self.n_words).cpu().numpy()
+            out.update({f"probs_{t}": pr[t] for t in range(Tc)})
+            return out
+
+        def fn(v, c, s=None):
+            v = self._features(v, dropout=True, draw=0)
+            c = self._dev(c, torch.int32)
+            n = c.shape[0]
+            p_gt = np.float32(np.float64(prob(s)) / np.float64(1.00001))
+            vid, sid = self._row_ids(v.shape[0], n // v.shape[0], 0)
+            seed = self.dropout_seed + 104729 * self.global_step
+            f = ops.scheduled_fwd(self.dims, self.store.params, v, c, n, float(p_gt), coin_seed(), self.loss_weight, self.dropout_rate, seed, vid, sid)
+            f["probs"] = f["logits"].clone()
+            nll, _ = ops.softmax_nll_fwd_bwd(f["logits"], f["target_tm"], f["coef_tm"], 0.0)
+            return fetches(f, float(torch.dot(f["coef_tm"], nll) / f["mask_sum"][0]) + self.l2_term())
+        inputs = [video, caption]
+        loss = Output("loss", fn, inputs)
+        loss.graph = {"kind": "build_scheduled_model", "inputs": inputs, "steps": steps, "prob": prob, "coin_seed": coin_seed, "fetches": fetches}
+        mask_out = Output("caption_mask", fn, inputs)
+        probs = [Output(f"probs_{t}", fn, inputs) for t in range(Tc)]
+        loss.graph["outputs"] = [mask_out] + probs
+        if k_value is not None:                                  # the schedule reads the step count: the placeholder must be fed
+            for o in [loss, mask_out] + probs:
+                o.inputs = inputs + [steps]
+            loss.graph["inputs"] = inputs + [steps]
+        return loss, video, caption, mask_out, probs, steps
 
     def _attr_terms(self, video, true_labels, normalised=True):
         """The attribute head's half of a multitask update: its gradients into the bucket's attr range (unscaled), the scale
@@ -1150,13 +1267,20 @@ class Video_Caption_Generator:
         out.value = value
         return out
 
-    def minimize(self, build_model_outputs, learning_rate, clip_norm=10.0):
+    def minimize(self, build_model_outputs, learning_rate, clip_norm=10.0, optimizer="adam"):
         """train_op of tf_s2vt.py:442-445: AdamOptimizer(learning_rate).compute_gradients(tf_loss) ->
         clip_by_global_norm(10) -> apply_gradients(global_step) -- and of multitask_e2e_attribute_s2vt.py:715-717 /
         e2e_tf_s2vt.py:533-536, the same statement over the multitask loss and over CNN + captioner.  `build_model_outputs` =
         the tuple build_model() returned (5, 6 or 7 long); sess.run([train_op, tf_loss(, tf_multilabel_loss)], feed_dict) is ONE
-        update, and the losses fetched beside it are the ones the update differentiated (same dropout masks, pre-update weights)."""
+        update, and the losses fetched beside it are the ones the update differentiated (same dropout masks, pre-update weights).
+        The 6-tuple of build_scheduled_model() gives the train_op of generate_words_tf_s2vt.py:412-418 (optimizer="sgd" is that script's
+        GradientDescentOptimizer); caption_mask and probs fetched beside it are the update's own.  optimizer="sgd" with a build_model
+        tuple is not wired (no script of the reference trains build_model that way)."""
         loss = build_model_outputs[0]
+        if getattr(loss, "graph", None) and loss.graph.get("kind") == "build_scheduled_model":
+            return self._minimize_scheduled(loss, learning_rate, clip_norm, optimizer)
+        if optimizer != "adam":
+            raise ValueError("minimize(optimizer=...) other than 'adam' needs build_scheduled_model()'s outputs")
         graph = getattr(loss, "graph", None) or {"inputs": list(build_model_outputs[1:4]), "normalised": True, "multilabel_loss": None}
         lr = learning_rate.value if hasattr(learning_rate, "value") else (lambda: float(learning_rate))
 
@@ -1175,6 +1299,25 @@ class Video_Caption_Generator:
         provides = {loss: "loss"}
         if graph["multilabel_loss"] is not None:
             provides[graph["multilabel_loss"]] = "multilabel_loss"
+        return Output("train_op", fn, graph["inputs"], provides=provides)
+
+    def _minimize_scheduled(self, loss, learning_rate, clip_norm, optimizer):
+        graph = loss.graph
+        lr = learning_rate.value if hasattr(learning_rate, "value") else (lambda: float(learning_rate))
+
+        def fn(v, c, s=None):
+            wd = self.l2_term()                                                # the l2 term of :203-210, pre-update
+            self._keep_scheduled_logits = True
+            try:
+                st = self.scheduled_update(self._features(v, dropout=True, draw=0), c, lr(), true_word_prob=graph["prob"](s),
+                                           clip_norm=clip_norm, optimizer=optimizer, coin_seed=graph["coin_seed"]())
+            finally:
+                self._keep_scheduled_logits = False
+            out = graph["fetches"](self.last_scheduled, float(st.loss) + wd)
+            out["train_op"] = None
+            return out
+        provides = {loss: "loss"}
+        provides.update({o: o.name for o in graph["outputs"]})
         return Output("train_op", fn, graph["inputs"], provides=provides)
 
     def reinforce_train_op(self, build_loss_outputs, rewards, base_line, learning_rate, clip_norm=5.0):

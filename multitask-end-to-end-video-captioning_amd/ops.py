@@ -312,6 +312,41 @@ def teacher_forced_fwd(dims: Dims, params: Params, video, caption, N: int, keep=
     return logits, ws
 
 
+def scheduled_fwd(dims: Dims, params: Params, video, caption, N: int, p_gt: float, coin_seed: int, loss_weight=1.0, keep=1.0, seed=0,
+                  video_id=None, sample_id=None, ws=None, mask_sum=None, mask_sum_copy=None):
+    """The scheduled-sampling unroll of generate_words_tf_s2vt.py:101-211 (s2vt_scheduled_fwd): the training forward decodes, and at step
+    t >= 1 each row is fed caption[:, t-1] with probability p_gt (the coin: a pure function of coin_seed, video id, sample id and step) and its
+    own argmax otherwise.  caption: int32 device tensor [N, Tc] (ids outside [0, n_words) are clamped by the kernel); video_id / sample_id
+    [N] int32 are required.  Returns a dict: logits [Tc*N, V] time-major, generated / fed [N, Tc] int32, mask [N, Tc], coef_tm [Tc*N]
+    (= loss_weight * mask), target_tm [Tc*N] int32, mask_sum [1], ws -- the training workspace, left as teacher_forced_fwd leaves it for
+    the fed words, so bptt_bwd runs on it."""
+    _chk_f32(video, mask_sum, mask_sum_copy)
+    assert video.is_contiguous()
+    assert caption.is_cuda and caption.dtype == torch.int32 and caption.is_contiguous()
+    Tc = dims.n_caption_lstm_step
+    assert tuple(caption.shape) == (N, Tc)
+    for t in (video_id, sample_id):
+        assert t is not None and t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.numel() == N, "video_id / sample_id: int32 [N]"
+    B = video.shape[0]
+    dev = video.device
+    L = lib()
+    if ws is None:
+        ws = train_workspace(dims, B, N, dev)
+    nb = L.s2vt_scheduled_scratch_bytes(C.byref(dims), N)
+    assert nb > 0, "bad dims / N"
+    scratch = workspace(nb, dev, "scheduled")
+    out = dict(logits=torch.empty((Tc * N, dims.n_words), dtype=torch.float32, device=dev),
+               generated=torch.empty((N, Tc), dtype=torch.int32, device=dev), fed=torch.empty((N, Tc), dtype=torch.int32, device=dev),
+               mask=torch.empty((N, Tc), dtype=torch.float32, device=dev), coef_tm=torch.empty(Tc * N, dtype=torch.float32, device=dev),
+               target_tm=torch.empty(Tc * N, dtype=torch.int32, device=dev),
+               mask_sum=torch.empty(1, dtype=torch.float32, device=dev) if mask_sum is None else mask_sum, ws=ws)
+    check(L.s2vt_scheduled_fwd(C.byref(dims), C.byref(params), _ptr(video), B, N, _ptr(caption), float(p_gt), int(coin_seed) & (2 ** 64 - 1),
+                               float(loss_weight), float(keep), seed, _ptr(video_id), _ptr(sample_id), _ptr(out["logits"]), _ptr(out["generated"]),
+                               _ptr(out["fed"]), _ptr(out["mask"]), _ptr(out["coef_tm"]), _ptr(out["target_tm"]), _ptr(out["mask_sum"]),
+                               _ptr(mask_sum_copy), _ptr(ws), ws.numel(), _ptr(scratch), scratch.numel(), _stream()), "s2vt_scheduled_fwd")
+    return out
+
+
 def softmax_nll_fwd_bwd(logits, target, coef, smoothing=0.0):
     """In place: logits <- coef * (softmax - q).  Returns (nll [R], lp_target [R]).  smoothing: a float, or a CUDA fp32
     tensor [R] with one label-smoothing value per row."""
@@ -630,6 +665,16 @@ def adam_tf(theta, g, m, v, sumsq, clip_norm, lr, step, beta1=0.9, beta2=0.999, 
         assert applied_step.is_cuda and applied_step.dtype == torch.int32
     check(lib().s2vt_adam_tf_guarded(_ptr(theta), _ptr(g), _ptr(m), _ptr(v), theta.numel(), _ptr(sumsq), float(clip_norm), float(lr),
                                      int(step), beta1, beta2, eps, _ptr(applied_step), _stream()), "s2vt_adam_tf")
+
+
+def sgd(theta, g, sumsq, clip_norm, lr, step, applied_step=None):
+    """theta -= lr * g * clip_norm / max(sqrt(sumsq), clip_norm) (s2vt_sgd_guarded): tf.train.GradientDescentOptimizer behind
+    tf.clip_by_global_norm.  applied_step: as adam_tf."""
+    _chk_f32(theta, g, sumsq)
+    if applied_step is not None:
+        assert applied_step.is_cuda and applied_step.dtype == torch.int32
+    check(lib().s2vt_sgd_guarded(_ptr(theta), _ptr(g), theta.numel(), _ptr(sumsq), float(clip_norm), float(lr), int(step), _ptr(applied_step),
+                                 _stream()), "s2vt_sgd")
 
 
 def chain_fault() -> bool:

@@ -4,7 +4,11 @@
 
 Per step the reference runs sess.run([train_op, tf_loss]) on build_model (label-smoothed XE with the Q1
 batch-mean rule, weight decay, clip 10, Adam, lr 1e-3 halved every 5000 steps); here that is
-Video_Caption_Generator.xe_update.  One process per GPU under torch.distributed.run for data parallel."""
+Video_Caption_Generator.xe_update.  One process per GPU under torch.distributed.run for data parallel.
+
+--scheduled-sampling P trains as generate_words_tf_s2vt.py does instead (Video_Caption_Generator.scheduled_update): the unroll decodes and
+a per-row coin feeds the ground-truth word with probability P / 1.00001 (the script writes P = 0.5), or, with --ss-k K, with the inverse
+sigmoid schedule K / (K + exp(step / K)) of its commented line :134; --optimizer sgd is that script's GradientDescentOptimizer."""
 from __future__ import annotations
 
 import argparse
@@ -20,8 +24,11 @@ from .train_common import (Config, Corpus, DataParallel, StepLog, epoch_batches,
 
 
 def train(cfg: Config, train_corpus: Corpus, test_corpus: Corpus | None = None, model=None, log=print, resume=None,
-          grad_precision=None):
-    """cfg.batch_size is the GLOBAL batch; data parallel as in train_rl.train (shards of each shuffled batch, Q1's per-step
+          grad_precision=None, scheduled_sampling=None, ss_k=None, optimizer="adam"):
+    """scheduled_sampling: None = cross entropy; a probability = scheduled sampling with that true-word probability (ss_k: the inverse
+    sigmoid schedule on the step counter instead).  Its mask comes from the model's own picks, so a batch in which every row emits <eos>
+    at step 0 has sum(mask) = 0 and a 0/0 loss, as in the reference: the run stops there, before another checkpoint is written.
+    cfg.batch_size is the GLOBAL batch; data parallel as in train_rl.train (shards of each shuffled batch, Q1's per-step
     mask sums and the gradient bucket all-reduced inside xe_update, rank 0 logs and saves)."""
     from . import model as M
     par = DataParallel(model.device if model is not None else None)
@@ -69,9 +76,18 @@ def train(cfg: Config, train_corpus: Corpus, test_corpus: Corpus | None = None, 
                 if pending is not None:
                     pending()
             b = cur
-            st, loss = run_step(model, lambda: model.xe_update(b["feats"], b["ind"], b["mask"], lr=learning_rate(cfg, model.global_step),
-                                                               clip_norm=cfg.clip_norm, video_base=b["lo"], active_steps=b["steps"]),
-                                log, overlap=overlap)
+            if scheduled_sampling is None:
+                update = lambda: model.xe_update(b["feats"], b["ind"], b["mask"], lr=learning_rate(cfg, model.global_step),
+                                                 clip_norm=cfg.clip_norm, video_base=b["lo"], active_steps=b["steps"])
+            else:
+                prob = scheduled_sampling if ss_k is None else model.inverse_sigmoid_prob(ss_k, model.global_step)
+                update = lambda: model.scheduled_update(b["feats"], b["ind"], lr=learning_rate(cfg, model.global_step), true_word_prob=prob,
+                                                        clip_norm=cfg.clip_norm, optimizer=optimizer, video_base=b["lo"])
+            st, loss = run_step(model, update, log, overlap=overlap)
+            if scheduled_sampling is not None and not np.isfinite(loss):
+                raise FloatingPointError(f"scheduled sampling, step {model.global_step}: the loss is {loss} -- the mask is empty (every row "
+                                         "emitted <eos> at step 0, sum(mask) = 0) or the update diverged; the variables are not usable "
+                                         "from here on and no further checkpoint is written")
             losses.append(loss)
             t1 = time.time()
 
@@ -103,11 +119,20 @@ def main():
     ap.add_argument("--model-path", default="./new_s2vt_models")
     ap.add_argument("--grad-precision", choices=("fp32", "bf16"), help="the backward's gradient contractions on bf16 operands (non-parity "
                     "fast mode, DESIGN.md §3); default: S2VT_GRAD_PRECISION, else fp32")
+    ap.add_argument("--scheduled-sampling", type=float, metavar="P", help="scheduled-sampling training (generate_words_tf_s2vt.py): feed the "
+                    "ground-truth word with probability P / 1.00001, the model's own argmax otherwise (the script writes 0.5)")
+    ap.add_argument("--ss-k", type=float, metavar="K", help="with scheduled sampling: P = K / (K + exp(step / K)) (the script's k_value = 5000)")
+    ap.add_argument("--optimizer", choices=("adam", "sgd"), default="adam", help="sgd: the scheduled-sampling script's GradientDescentOptimizer")
     a = ap.parse_args()
+    if a.ss_k is not None and a.scheduled_sampling is None:
+        a.scheduled_sampling = 0.5
+    if a.optimizer != "adam" and a.scheduled_sampling is None:
+        ap.error("--optimizer sgd is wired for --scheduled-sampling only")
     cfg = Config(n_epochs=a.epochs, batch_size=a.batch_size, model_path=a.model_path, model_name=f"batch_size{a.batch_size}_s2vt_model")
     tr = Corpus(a.train_sents, a.train_feats, vocabulary_file=a.vocab)
     te = Corpus(a.test_sents, a.test_feats, vocabulary=tr.vocabulary) if a.test_sents and a.test_feats else None
-    train(cfg, tr, te, resume=a.resume, grad_precision=a.grad_precision)
+    train(cfg, tr, te, resume=a.resume, grad_precision=a.grad_precision, scheduled_sampling=a.scheduled_sampling, ss_k=a.ss_k,
+          optimizer=a.optimizer)
 
 
 if __name__ == "__main__":

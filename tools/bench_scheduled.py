@@ -1,0 +1,93 @@
+#!/usr/bin/env python
+"""Step time of scheduled-sampling training (Video_Caption_Generator.scheduled_update) against the teacher-forced cross-entropy step
+(xe_update(q1=False)) at bench.py's dimensions: B = 64, Tc = 20, |V| = 12000, bench.py's synthetic inputs (the statements of its make_step),
+its warm-up / timed counts.
+
+    python tools/bench_scheduled.py [--steps 150] [--warmup 10] [--pairs 3] [--only scheduled|xe] [--optimizer adam|sgd]
+
+Both steps run in ONE process in alternating pairs (scheduled, xe, scheduled, xe, ...), each block of --steps steps bracketed by
+device synchronisation, so clock and thermal drift hit both alike; one JSON line with every block's ms per step and the medians.
+The xe step unrolls all Tc steps here (active_steps=None), as the scheduled step must: its mask is only known on the device.
+--only: one kind alone, no pairing -- the body of a `rocprofv3 --kernel-trace --stats` run (the per-launch cost of sched_step_kernel
+and of the per-step cell / pick launches is read off that table)."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=150)
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--pairs", type=int, default=3)
+    ap.add_argument("--only", choices=("scheduled", "xe"))
+    ap.add_argument("--optimizer", choices=("adam", "sgd"), default="adam")
+    ap.add_argument("--true-word-prob", type=float, default=0.5)
+    a = ap.parse_args()
+
+    import numpy as np
+    import torch
+    import bench
+    import s2vt_amd
+    from s2vt_amd import model as M
+    from s2vt_amd import ops
+    s2vt_amd.lib()
+    dev = torch.device("cuda")
+    B = 64
+    TC, TV, D, E, H, V = bench.TC, bench.TV, bench.D, bench.E, bench.H, bench.V
+
+    def make():
+        return M.Video_Caption_Generator(D, V, E, H, B, 0, TV, TC, device=dev, seed=1234, multisample=1)
+    # bench.py's synthetic inputs of the xe workload: the same generator seeds, drawn by the same statements
+    g = torch.Generator().manual_seed(1234)
+    video = (torch.randn(B, TV, D, generator=g) * 0.5).abs().to(dev)
+    rng = np.random.default_rng(1234)
+    ln = 1 + np.minimum(rng.poisson(6, B), TC - 2)
+    cap = rng.integers(2, V, (B, TC)).astype(np.int32)
+    for j in range(B):
+        cap[j, ln[j]:] = 0
+    gt = torch.as_tensor(cap).to(dev)
+    is_eos = (gt == 0)
+    gt_mask = ((torch.cumsum(is_eos.int(), 1) - is_eos.int()) == 0).float()
+
+    models = {"scheduled": make(), "xe": make()}
+    steps = {
+        "scheduled": lambda m: m.scheduled_update(video, gt, lr=1e-3, true_word_prob=a.true_word_prob, clip_norm=10.0, optimizer=a.optimizer),
+        "xe": lambda m: m.xe_update(video, gt, gt_mask, lr=1e-3, clip_norm=10.0, q1=False, smoothing=0.0, active_steps=None, live_mask=None),
+    }
+    kinds = [a.only] if a.only else ["scheduled", "xe"]
+
+    def block(kind, n):
+        m = models[kind]
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(n):
+            st = steps[kind](m)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / n * 1e3, st
+
+    for k in kinds:
+        block(k, a.warmup)
+    out = {k: [] for k in kinds}
+    last = {}
+    for _ in range(a.pairs if not a.only else 1):
+        for k in kinds:
+            ms, last[k] = block(k, a.steps)
+            out[k].append(round(ms, 4))
+    line = {"tool": "bench_scheduled", "B": B, "Tc": TC, "V": V, "steps": a.steps, "warmup": a.warmup, "optimizer": a.optimizer,
+            "ms_per_step": out, "median_ms": {k: round(statistics.median(v), 4) for k, v in out.items()},
+            "last_loss": {k: float(last[k].loss) for k in kinds}, "last_mask_sum": {k: float(last[k].mask_sum) for k in kinds},
+            "chain_timeouts": int(ops.chain_timeouts())}
+    if not a.only:
+        line["scheduled_over_xe"] = round(line["median_ms"]["scheduled"] / line["median_ms"]["xe"], 3)
+    print(json.dumps(line))
+
+
+if __name__ == "__main__":
+    main()
