@@ -53,8 +53,25 @@ typedef struct s2vt_dims {
     int32_t n_video_lstm_step;    /* Tv  = 5    */
     int32_t n_caption_lstm_step;  /* Tc  = 20 (35 in the reference files) */
     int32_t label_dim;            /* A   = 400 attributes (multitask head), 0 if absent */
-    int32_t reserved;
+    int32_t reserved;             /* model bits: 0 = tf_s2vt.py, or S2VT_MODEL_RESIDUAL (the field keeps its name: the struct is unchanged) */
 } s2vt_dims;
+
+/* Model bit in s2vt_dims.reserved: the residual captioner of residual_tf_s2vt.py.  At every decode step (build_model :149-151,
+ * build_generator :206-208, build_sampler :263-265) output2 = output1 + output2 before logit_words = xw_plus_b(output2, embed_word_W,
+ * embed_word_b); nothing else differs from tf_s2vt.py -- same variables, same checkpoint layout.  Contract:
+ * s = fl32(o1 + o2), one fp32 addition per element; o1 = LSTM1's DropoutWrapper output of that decode step (dropped, code 256 + step, in the
+ * training unroll; undropped in samplers, generator and beam search), o2 = LSTM2's; LSTM2's recurrent state stays the un-summed h'; the
+ * logits are the same ascending-k chain on s.  Backward: dWout = s^T dlogits, and ds = dlogits Wout^T reaches LSTM2 as before AND is added to
+ * the gradient w.r.t. LSTM1's dropped output of the decode steps.
+ *   Honoured by: s2vt_sample / _ex, s2vt_beam_encode / _step, s2vt_teacher_forced_fwd (+ _reuse / _steps / _live), s2vt_bptt_bwd (+ _phase /
+ *     _steps / _live / _bf16 / _split) and their workspace-size functions.  The sampler workspace grows by one [R, H] float block, the beam
+ *     workspace by [B beam, H] floats + [B beam] int32, each rounded up to 256 bytes, behind the plain regions; the training workspace and the
+ *     bf16 / split scratch do not change.  A residual model's sampler always takes per-step launches (no persistent decode loop).
+ *   Accepted, same behaviour (no logits there, or they only read what the calls above leave): s2vt_frame_embed_fwd / _bwd, s2vt_bptt_dvideo,
+ *     s2vt_split_grad_dlogits_planes, s2vt_softmax_nll_fwd_bwd_split, s2vt_bf16_grad_workspace_bytes, s2vt_split_grad_workspace_bytes.
+ *   Every other entry point that takes s2vt_dims (s2vt_sample_mix, s2vt_scheduled_fwd, s2vt_create and the handle calls, every s2vt_attn_*)
+ *     returns S2VT_E_BADARG (size functions: 0) when the bit is set.  Any other bit: S2VT_E_BADARG / 0 everywhere. */
+#define S2VT_MODEL_RESIDUAL 1
 
 /* Trainable variables (tf_s2vt.py:68-88; LSTM kernels are created lazily by BasicLSTMCell under
  * s2vt/LSTM{1,2}/basic_lstm_cell/{weights,biases}).  The same struct carries gradients. */
@@ -155,6 +172,14 @@ int s2vt_lstm_cell_fwd(const s2vt_operand* x0, const s2vt_operand* x1, const flo
                        int32_t state_rowmod, const float* W, const float* b, float* c_new, float* h_new, float* out,
                        float* gates, int32_t M, int32_t H, float keep, uint64_t seed, const int32_t* video_id,
                        const int32_t* sample_id, uint32_t drop_code, int32_t tile_cfg, s2vt_stream stream);
+/* The same with a residual operand, the decode step of residual_tf_s2vt.py:149-151,206-208,263-265: out[m] = dropout(h'[m]) + res[row(m)],
+ * one fp32 addition in the cell kernel's epilogue (no launch of its own).  res: k == H, ld >= H, rowmod / rowidx honoured as in s2vt_gemm
+ * (row(m) = m % rowmod, then rowidx[.]); res->ptr and `out` are required.  c_new, h_new (the un-summed h') and gates are exactly those of
+ * s2vt_lstm_cell_fwd. */
+int s2vt_lstm_cell_fwd_res(const s2vt_operand* x0, const s2vt_operand* x1, const float* h_prev, const float* c_prev,
+                           int32_t state_rowmod, const float* W, const float* b, const s2vt_operand* res, float* c_new, float* h_new,
+                           float* out, float* gates, int32_t M, int32_t H, float keep, uint64_t seed, const int32_t* video_id,
+                           const int32_t* sample_id, uint32_t drop_code, int32_t tile_cfg, s2vt_stream stream);
 
 /* ---- vocab logits + token pick, one decode step ---------------------------------------------
  * logits = out2 @ embed_word_W + embed_word_b (tf_s2vt.py:153); token = tf.argmax(logits,1) for

@@ -19,6 +19,9 @@ class S2VTChainTimeout(S2VTLibraryError):
     Video_Caption_Generator.recover() (synchronise, acknowledge, fall back to per-step launches) and repeat the step."""
 
 
+MODEL_RESIDUAL = 1      # S2VT_MODEL_RESIDUAL: the model bit carried in Dims.reserved (residual_tf_s2vt.py)
+
+
 class Dims(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("dim_image", "n_words", "word_dim", "lstm_dim", "n_video_lstm_step",
                                          "n_caption_lstm_step", "label_dim", "reserved")]
@@ -75,6 +78,8 @@ SIGNATURES = {
     "s2vt_gemm_nt": (C.c_int, [_OP, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "s2vt_lstm_cell_fwd": (C.c_int, [_OP, _OP, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _f32, _u64, _vp,
                                      _vp, _u32, _i32, _vp]),
+    "s2vt_lstm_cell_fwd_res": (C.c_int, [_OP, _OP, _vp, _vp, _i32, _vp, _vp, _OP, _vp, _vp, _vp, _vp, _i32, _i32, _f32, _u64, _vp,
+                                         _vp, _u32, _i32, _vp]),
     "s2vt_vocab_pick": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _i32, _u64, _vp, _vp, _vp, _i32, _vp]),
     "s2vt_frame_embed_fwd": (C.c_int, [_DP, _PP, _vp, _i32, _vp, _vp]),
     "s2vt_sample_workspace_bytes": (_sz, [_DP, _i32, _i32, _i32]),

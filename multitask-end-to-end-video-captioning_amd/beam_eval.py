@@ -63,6 +63,8 @@ def main(argv=None):
     ap.add_argument("--n-caption-lstm-step", type=int, default=35)
     ap.add_argument("--out", default="beam_captions.txt")
     ap.add_argument("--model", choices=("auto", "s2vt", "attention"), default="auto")
+    ap.add_argument("--residual", action="store_true", help="decode as the residual captioner of residual_tf_s2vt.py (an S2VT checkpoint "
+                    "does not say which script trained it)")
     a = ap.parse_args(argv)
 
     from . import hostglue, reward, tfckpt
@@ -80,9 +82,11 @@ def main(argv=None):
     Tc = a.n_caption_lstm_step
     if model_kind(raw, a.model) == "attention":
         from . import attention as A
+        if a.residual:
+            raise SystemExit("--residual is an S2VT variant; this checkpoint is an attention model")
         model = A.Attention_Caption_Generator(D, V, E, a.batch_size, Tv, Tc, 1.0, bias_init_vector=None)    # dim_hidden = Wemb.shape[1] (:65)
     else:
-        model = M.Video_Caption_Generator(D, V, E, H, a.batch_size, Tv + Tc, Tv, Tc, bias_init_vector=None)
+        model = M.Video_Caption_Generator(D, V, E, H, a.batch_size, Tv + Tc, Tv, Tc, bias_init_vector=None, residual=a.residual)
     optimistic_restore(model, a.checkpoint)
     scorer = reward.CiderD(corpus.index.refs_by_video(), wordtoix)
     decoded, cider = beam_eval(model, corpus, ixtoword, scorer, a.batch_size, a.beam, a.lnf)

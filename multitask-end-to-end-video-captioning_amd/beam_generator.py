@@ -78,6 +78,16 @@ class BeamSearchGenerator:
             c2, h2, _, _ = ops.lstm_cell_fwd(ops.operand(h1), ops.operand(None, k=E), h2, c2, p["lstm2_W"], p["lstm2_b"], 1)
         return c1, h1, c2, h2
 
+    def _lstm2_decode(self, h1, word_idx, h2, c2, n):
+        """LSTM2 of one decode step on n rows sharing LSTM1's row h1; returns (c2, h2, what the vocabulary projection reads): h2, or on
+        a residual model out1 + out2 (residual_tf_s2vt.py:206-208), summed in the cell launch."""
+        m = self.m
+        p = m.store.p
+        res = ops.operand(h1, rowmod=1) if getattr(m, "residual", False) else None
+        c2, h2, out, _ = ops.lstm_cell_fwd(ops.operand(h1, rowmod=1), ops.operand(p["Wemb"], rowidx=word_idx), h2, c2, p["lstm2_W"], p["lstm2_b"], n,
+                                           res=res)
+        return c2, h2, (out if getattr(m, "residual", False) else h2)
+
     def _step(self, c1, h1, c2, h2, words):
         """One decode step (beam_probability, :203-224) for len(words) beams: LSTM1 on its shared state (1 row),
         LSTM2 per beam; returns new states and (top-k word ids, their log-probs) per beam."""
@@ -86,8 +96,8 @@ class BeamSearchGenerator:
         n = len(words)
         c1, h1, _, _ = ops.lstm_cell_fwd(ops.operand(None, k=E), None, h1, c1, p["lstm1_W"], p["lstm1_b"], 1)
         idx = torch.as_tensor(words, dtype=torch.int32, device=m.device)
-        c2, h2, _, _ = ops.lstm_cell_fwd(ops.operand(h1, rowmod=1), ops.operand(p["Wemb"], rowidx=idx), h2, c2, p["lstm2_W"], p["lstm2_b"], n)
-        logits = ops.gemm([ops.operand(h2)], p["embed_word_W"], p["embed_word_b"], M=n)
+        c2, h2, o2 = self._lstm2_decode(h1, idx, h2, c2, n)
+        logits = ops.gemm([ops.operand(o2)], p["embed_word_W"], p["embed_word_b"], M=n)
         top_l, top_i = torch.topk(logits, self.beam_size, dim=1)                       # selection only
         zero_t = torch.zeros(n, dtype=torch.int32, device=m.device)
         _, lp0 = ops.softmax_nll_fwd_bwd(logits.clone(), zero_t, torch.zeros(n, device=m.device), 0.0)   # lp0 = l[0] - lse
@@ -107,8 +117,8 @@ class BeamSearchGenerator:
         ids = []
         for _ in range(m.n_caption_lstm_step):
             c1, h1, _, _ = ops.lstm_cell_fwd(ops.operand(None, k=E), None, h1, c1, p["lstm1_W"], p["lstm1_b"], 1)
-            c2, h2, _, _ = ops.lstm_cell_fwd(ops.operand(h1), ops.operand(p["Wemb"], rowidx=word), h2, c2, p["lstm2_W"], p["lstm2_b"], 1)
-            logits = ops.gemm([ops.operand(h2)], p["embed_word_W"], p["embed_word_b"], M=1)
+            c2, h2, o2 = self._lstm2_decode(h1, word, h2, c2, 1)
+            logits = ops.gemm([ops.operand(o2)], p["embed_word_W"], p["embed_word_b"], M=1)
             word, _ = ops.softmax_unshifted_argmax(logits)
             ids.append(word)
         return torch.cat(ids).cpu().numpy().astype(np.int64)

@@ -225,10 +225,11 @@ int s2vt_gemm(const s2vt_operand* segs, int32_t nseg, const float* W, int32_t ld
     return gemm_impl(segs, nseg, W, ldw, bias, Cinit, ldcinit, C, ldc, M, N, act_tanh, tile_cfg, stream, false);
 }
 
-int s2vt_lstm_cell_fwd(const s2vt_operand* x0, const s2vt_operand* x1, const float* h_prev, const float* c_prev,
-                       int32_t state_rowmod, const float* W, const float* b, float* c_new, float* h_new, float* out,
-                       float* gates, int32_t M, int32_t H, float keep, uint64_t seed, const int32_t* video_id,
-                       const int32_t* sample_id, uint32_t drop_code, int32_t tile_cfg, s2vt_stream stream)
+// res != NULL: the residual form, out[m] = dropout(h'[m]) + res[row(m)]
+static int lstm_cell_impl(const s2vt_operand* x0, const s2vt_operand* x1, const float* h_prev, const float* c_prev,
+                          int32_t state_rowmod, const float* W, const float* b, float* c_new, float* h_new, float* out,
+                          float* gates, int32_t M, int32_t H, float keep, uint64_t seed, const int32_t* video_id,
+                          const int32_t* sample_id, uint32_t drop_code, int32_t tile_cfg, s2vt_stream stream, const s2vt_operand* res)
 {
     if (!h_prev || !c_prev || !W || !b || !c_new || !h_new || M < 0 || H <= 0) return S2VT_E_BADARG;
     if (keep < 1.0f && (!video_id || !sample_id || !out || !(keep > 0.0f))) return S2VT_E_BADARG;
@@ -244,9 +245,30 @@ int s2vt_lstm_cell_fwd(const s2vt_operand* x0, const s2vt_operand* x1, const flo
     a[n++] = make_seg(h_prev, H, H, kw, state_rowmod);
     if (M == 0) return S2VT_OK;
     NoiseIds ids{video_id, sample_id, seed};
+    ASeg r;
+    if (res) seg_from_operand(r, res, 0);
     HIP_TRY(lstm_call(a, n, W, b, c_prev, state_rowmod, c_new, h_new, out, gates, M, H, keep, ids, drop_code, tile_cfg,
-                      S(stream)));
+                      S(stream), nullptr, 0, 0, nullptr, nullptr, res ? &r : nullptr));
     return S2VT_OK;
+}
+
+int s2vt_lstm_cell_fwd(const s2vt_operand* x0, const s2vt_operand* x1, const float* h_prev, const float* c_prev,
+                       int32_t state_rowmod, const float* W, const float* b, float* c_new, float* h_new, float* out,
+                       float* gates, int32_t M, int32_t H, float keep, uint64_t seed, const int32_t* video_id,
+                       const int32_t* sample_id, uint32_t drop_code, int32_t tile_cfg, s2vt_stream stream)
+{
+    return lstm_cell_impl(x0, x1, h_prev, c_prev, state_rowmod, W, b, c_new, h_new, out, gates, M, H, keep, seed, video_id, sample_id, drop_code,
+                          tile_cfg, stream, nullptr);
+}
+
+int s2vt_lstm_cell_fwd_res(const s2vt_operand* x0, const s2vt_operand* x1, const float* h_prev, const float* c_prev,
+                           int32_t state_rowmod, const float* W, const float* b, const s2vt_operand* res, float* c_new, float* h_new,
+                           float* out, float* gates, int32_t M, int32_t H, float keep, uint64_t seed, const int32_t* video_id,
+                           const int32_t* sample_id, uint32_t drop_code, int32_t tile_cfg, s2vt_stream stream)
+{
+    if (!res || !res->ptr || !out || res->k != H || res->ld < H || res->rowmod < 0) return S2VT_E_BADARG;
+    return lstm_cell_impl(x0, x1, h_prev, c_prev, state_rowmod, W, b, c_new, h_new, out, gates, M, H, keep, seed, video_id, sample_id, drop_code,
+                          tile_cfg, stream, res);
 }
 
 int s2vt_vocab_pick(const float* out2, int32_t ld, const float* W, const float* b, int32_t M, int32_t H, int32_t V,
@@ -269,7 +291,7 @@ int s2vt_vocab_pick(const float* out2, int32_t ld, const float* W, const float* 
 int s2vt_frame_embed_fwd(const s2vt_dims* d, const s2vt_params* p, const float* video, int32_t B, float* emb,
                          s2vt_stream stream)
 {
-    if (!dims_ok(d) || !p || !p->encode_image_W || !p->encode_image_b || !video || !emb || B < 0) return S2VT_E_BADARG;
+    if (!dims_ok_res(d) || !p || !p->encode_image_W || !p->encode_image_b || !video || !emb || B < 0) return S2VT_E_BADARG;   // (no logits here: the variants agree)
     if (B == 0) return S2VT_OK;
     ASeg a = make_seg(video, d->dim_image, d->dim_image, 0);
     HIP_TRY(store_call(&a, 1, p->encode_image_W, d->word_dim, p->encode_image_b, emb, d->word_dim,
@@ -344,6 +366,9 @@ size_t carve_sample(Carver& c, const s2vt_dims* d, int B, int R, SampleWs* w)
         for (int i = 0; i < 2; ++i) t.himg[i] = c.take<float>((size_t)q.img_tiles * q.hgp * 256);
     }
     t.live[0] = c.take<int32_t>(R); t.live[1] = c.take<int32_t>(R); t.nlive = c.take<int32_t>(Tc + 1);
+    // residual model: the one block it adds, behind every region of the plain carve (callers that re-carve to find LSTM1's history see
+    // the same offsets either way)
+    t.out2 = is_residual(d) ? c.take<float>((size_t)R * H) : nullptr;
     if (w) *w = t;
     return c.off;
 }
@@ -427,8 +452,9 @@ hipError_t lstm2_step(const Lstm2Step& s, hipStream_t st)
     const NoiseIds none{nullptr, nullptr, 0};
     ASeg s2[2] = {make_seg(s.p->Wemb, s.E, s.E, s.H, 0, s.word_idx, s.word_key, s.word_key ? kPickStride : 1),
                   make_seg(s.h_prev, s.H, s.H, s.H + s.E, s.state_rowmod)};
-    return lstm_call(s2, 2, s.p->lstm2_W, s.p->lstm2_b, s.c_prev, s.state_rowmod, s.c_new, s.h_new, nullptr, nullptr, s.M, s.H, 1.0f, none, 0,
-                     s.lstm_cfg, st, s.partial, 4 * s.H, s.partial_rowmod, s.live, s.n_live);
+    const ASeg res = make_seg(s.out1, s.H, s.H, 0, s.out1_rowmod, s.out1_rowidx);
+    return lstm_call(s2, 2, s.p->lstm2_W, s.p->lstm2_b, s.c_prev, s.state_rowmod, s.c_new, s.h_new, s.out, nullptr, s.M, s.H, 1.0f, none, 0,
+                     s.lstm_cfg, st, s.partial, 4 * s.H, s.partial_rowmod, s.live, s.n_live, s.out ? &res : nullptr);
 }
 
 // (inside a stage: hand a failed launch's error to the driver, whose HIP_TRY records it)
@@ -534,8 +560,10 @@ struct SampleDecode {
             HIP_CHECK(launch_live_rows(t == 0 ? nullptr : picks(t - 1), kPickStride, w.live[nxt], w.nlive + (t > 0 ? t - 1 : 0), w.live[t & 1], w.nlive + t, R, st));
             s.live = w.live[t & 1]; s.n_live = w.nlive + t;
         }
+        // residual model: the cell launch also writes out1 + h' (out1 = slot Tv + t + 1 of LSTM1's history, row % B), and the pick reads that
+        if (w.out2) { s.out = w.out2; s.out1 = w.h1 + (size_t)(Tv + t + 1) * BH; s.out1_rowmod = B; }
         HIP_CHECK(lstm2_step(s, st));
-        return pick_call(w.h2[nxt], H, p->embed_word_W, p->embed_word_b, R, H, V, ids(), t, picks(t), nullptr, pick_cfg, st, kPickStride, s.live, s.n_live);
+        return pick_call(w.out2 ? w.out2 : w.h2[nxt], H, p->embed_word_W, p->embed_word_b, R, H, V, ids(), t, picks(t), nullptr, pick_cfg, st, kPickStride, s.live, s.n_live);
     }
 };
 
@@ -543,7 +571,8 @@ struct SampleDecode {
 // out1 partial (row % B).  Needs sample_encode's results in the same workspace.  The driver picks one of three forms -- the persistent
 // launch (<= 64 rows), per-step launches on the fragment-order operands (257-384 rows, opt-in), per-step launches of the contraction
 // kernel -- and leaves through the one unpack.  The early-exit mode takes the last form only: the other two cannot skip rows.  So does the
-// mixed mode (one more argmax block in front of the greedy one): the other two read the fed word from the packed picks.
+// mixed mode (one more argmax block in front of the greedy one): the other two read the fed word from the packed picks.  The residual
+// model (w.out2) takes the last form too: the other two project h2, not out1 + h2 (extending them is open).
 int sample_decode(const s2vt_dims* d, const s2vt_params* p, int B, int K, int with_greedy, uint64_t seed, int video_base,
                   int32_t* ids_out, const SampleWs& w, s2vt_stream stream, int stop_at_eos, const SampleMix* mix)
 {
@@ -552,8 +581,8 @@ int sample_decode(const s2vt_dims* d, const s2vt_params* p, int B, int K, int wi
     hipStream_t st = S(stream);
     SampleDecode s{p, w, B, K, R, seed, video_base, stop_at_eos != 0, st, H, E, V, Tv, Tc, (size_t)B * H, (size_t)Tv * B * H, {}, mix};
     HIP_TRY(s.open());
-    const bool loop1 = !stop_at_eos && !mix && w.wemb_p && (B & 15) == 0 && decode_loop_eligible(R, H, E, V) && chain_operands_ok(p->embed_word_W, V, w.himg[0]);
-    const bool dec4 = !stop_at_eos && !mix && (loop1 || (w.wemb_p && decode4_eligible(R, H, E)));
+    const bool loop1 = !stop_at_eos && !mix && !w.out2 && w.wemb_p && (B & 15) == 0 && decode_loop_eligible(R, H, E, V) && chain_operands_ok(p->embed_word_W, V, w.himg[0]);
+    const bool dec4 = !stop_at_eos && !mix && !w.out2 && (loop1 || (w.wemb_p && decode4_eligible(R, H, E)));
     if (dec4) HIP_TRY(s.pack_fragments());
     if (loop1) {
         HIP_TRY(s.persistent_loop());
@@ -582,7 +611,7 @@ int s2vt_build_flags(void)
 
 size_t s2vt_sample_workspace_bytes(const s2vt_dims* d, int32_t B, int32_t K, int32_t with_greedy)
 {
-    if (!dims_ok(d) || B <= 0 || K < 0) return 0;
+    if (!dims_ok_res(d) || B <= 0 || K < 0) return 0;
     Carver c(nullptr, 0);
     return carve_sample(c, d, B, (K + (with_greedy ? 1 : 0)) * B, nullptr);
 }
@@ -591,7 +620,7 @@ int s2vt_sample_ex(const s2vt_dims* d, const s2vt_params* p, const float* video,
                    uint64_t seed, int32_t video_base, int32_t flags, int32_t* ids_out, void* workspace, size_t workspace_bytes,
                    s2vt_stream stream)
 {
-    if (!dims_ok(d) || !sampler_params_ok(p) || !video || !ids_out || !workspace || B <= 0 || K < 0 || (K == 0 && !with_greedy) || (flags & ~1))
+    if (!dims_ok_res(d) || !sampler_params_ok(p) || !video || !ids_out || !workspace || B <= 0 || K < 0 || (K == 0 && !with_greedy) || (flags & ~1))
         return S2VT_E_BADARG;
     if (reinterpret_cast<uintptr_t>(workspace) & 255u) return S2VT_E_ALIGN;
     if (chain_fault()) return S2VT_E_CHAIN_TIMEOUT;

@@ -92,7 +92,7 @@ struct NoiseIds {
 inline hipError_t lstm_call(const ASeg* segs, int nseg, const float* W, const float* b, const float* c_prev, int cprev_rowmod,
                      float* c_new, float* h_new, float* out, float* gates, int M, int H, float keep, const NoiseIds& ids,
                      uint32_t drop_code, int cfg, hipStream_t st, const float* cinit = nullptr, int ldcinit = 0,
-                     int cinit_rowmod = 0, const int* omap = nullptr, const int* m_dev = nullptr)
+                     int cinit_rowmod = 0, const int* omap = nullptr, const int* m_dev = nullptr, const ASeg* res = nullptr)
 {
     GemmArgs a;
     std::memset(&a, 0, sizeof(a));
@@ -105,6 +105,7 @@ inline hipError_t lstm_call(const ASeg* segs, int nseg, const float* W, const fl
     a.seed_lo = (uint32_t)ids.seed; a.seed_hi = (uint32_t)(ids.seed >> 32);
     a.cinit = cinit; a.ldcinit = ldcinit; a.cinit_rowmod = cinit_rowmod;   // a carried partial chain (hoisted input products)
     a.omap = omap; a.m_dev = m_dev;                                          // live-row launch (gemm_mfma.h)
+    if (res) { a.res = res->ptr; a.res_rowidx = res->rowidx; a.res_ld = res->ld; a.res_rowmod = res->rowmod; }   // residual form: out += res[row(m)]
     return launch_gemm(a, EPI_LSTM, cfg, st);
 }
 
@@ -215,6 +216,7 @@ struct SampleWs : SampleEnc {
     float *wemb_p, *w2_p, *himg[2];   // fragment-order operands of the decode loop's LSTM2 step (decode4.hip); NULL when R is outside its range
     int32_t* live[2];        // stop-at-<eos> mode: the rows still sampling at the current / next step (ascending), ...
     int32_t* nlive;          // ... and their count per step [Tc + 1], device-resident
+    float* out2;             // residual model only (else NULL): out1 + out2 of the current step [R][H], what the pick reads; carved last
 };
 
 // One LSTM recurrence of T steps on M rows: ONE persistent launch when the shape fits (chain_eligible), else T
@@ -248,6 +250,9 @@ struct Lstm2Step {
     const float *c_prev, *h_prev; int state_rowmod;   // step 0 of the sampler: the encoder state with row % B; else one row each (0)
     float *c_new, *h_new;
     const int32_t *live, *n_live; int lstm_cfg;   // early-exit mode: the launch covers rows live[0 .. *n_live) only (device-resident); its tile knob (-1: the cost model's)
+    // residual model (residual_tf_s2vt.py:263-265): out[m] = h_new[m] + out1[row(m)], out1 = LSTM1's output of this decode step read in place
+    // ([B][H]; row % out1_rowmod, then out1_rowidx) -- one fp32 addition in the cell launch's epilogue.  out == NULL: the plain model
+    float* out; const float* out1; int out1_rowmod; const int32_t* out1_rowidx;
 };
 hipError_t lstm2_step(const Lstm2Step& s, hipStream_t st);
 bool sampler_params_ok(const s2vt_params* p);
@@ -256,11 +261,16 @@ bool sampler_params_ok(const s2vt_params* p);
 hipError_t launch_live_rows(const unsigned long long* picked, int stride, const int32_t* prev, const int32_t* nprev, int32_t* next,
                             int32_t* nnext, int R, hipStream_t st);
 
-inline bool dims_ok(const s2vt_dims* d)
+// The model bits ride in s2vt_dims::reserved.  dims_ok: a PLAIN model -- what every entry point that does not implement a variant asks
+// for, so that none ignores a bit silently; dims_ok_res: a plain or a residual model (S2VT_MODEL_RESIDUAL), for the entry points that
+// implement the residual sum (residual_tf_s2vt.py:149-151) or only read what those leave.
+inline bool dims_ok_res(const s2vt_dims* d)
 {
     return d && d->dim_image > 0 && d->n_words > 0 && d->word_dim > 0 && d->lstm_dim > 0 && d->n_video_lstm_step > 0 &&
-           d->n_caption_lstm_step > 0;
+           d->n_caption_lstm_step > 0 && (d->reserved & ~S2VT_MODEL_RESIDUAL) == 0;
 }
+inline bool dims_ok(const s2vt_dims* d) { return dims_ok_res(d) && d->reserved == 0; }
+inline bool is_residual(const s2vt_dims* d) { return (d->reserved & S2VT_MODEL_RESIDUAL) != 0; }
 
 
 }  // namespace s2vt_api

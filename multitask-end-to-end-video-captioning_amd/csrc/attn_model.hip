@@ -245,7 +245,7 @@ size_t carve_attn(Carver& c, const s2vt_dims* d, int B, AttnWs* out, int n_video
 bool attn_dims_ok(const s2vt_dims* d)
 {
     return d && d->dim_image > 0 && d->n_words > 0 && d->lstm_dim > 0 && d->n_video_lstm_step > 0 && d->n_video_lstm_step <= 64 &&
-           d->n_caption_lstm_step > 0;
+           d->n_caption_lstm_step > 0 && d->reserved == 0;      // (no model bit is implemented here: refused, never ignored)
 }
 
 bool attn_params_ok(const s2vt_attn_params* p)

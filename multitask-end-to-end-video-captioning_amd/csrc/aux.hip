@@ -582,10 +582,13 @@ hipError_t launch_expand_dropout(const float* h, float* out, int T, int B, int N
     return hipGetLastError();
 }
 
+// ADD: a second addend `add` [T - add_t0][N][H] (rows H apart) joins dout at steps t >= add_t0 -- one fp32 addition in front of the
+// mask, d = dout + add -- in the same pass and the same fixed order (the residual model: ds reaches LSTM1's dropped output too)
+template <bool ADD>
 __global__ __launch_bounds__(256) void reduce_dropout_kernel(const float* dout, int ld_out, float* dh, int T, int B, int N,
                                                              int H, float keep, uint32_t seed_lo, uint32_t seed_hi,
                                                              uint32_t code_base, const int32_t* video_id,
-                                                             const int32_t* sample_id)
+                                                             const int32_t* sample_id, const float* add, int add_t0)
 {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= (size_t)T * B * H) return;
@@ -595,6 +598,9 @@ __global__ __launch_bounds__(256) void reduce_dropout_kernel(const float* dout, 
     float acc = 0.f;
     for (int n = j; n < N; n += B) {
         float d = dout[((size_t)t * N + n) * ld_out + u];
+        if constexpr (ADD) {
+            if (t >= add_t0) d = d + add[((size_t)(t - add_t0) * N + n) * H + u];
+        }
         if (keep < 1.0f)
             d = (d / keep) * dropout_keep01(seed_lo, seed_hi, (uint32_t)video_id[n], (uint32_t)sample_id[n],
                                             code_base + (uint32_t)t, (uint32_t)u, keep);
@@ -605,12 +611,30 @@ __global__ __launch_bounds__(256) void reduce_dropout_kernel(const float* dout, 
 
 hipError_t launch_reduce_dropout(const float* dout, int ld_out, float* dh, int T, int B, int N, int H, float keep,
                                  uint64_t seed, uint32_t code_base, const int32_t* video_id, const int32_t* sample_id,
-                                 hipStream_t st)
+                                 hipStream_t st, const float* add, int add_t0)
 {
     const size_t n = (size_t)T * B * H;
     if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(reduce_dropout_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dout, ld_out, dh, T, B, N, H,
-                       keep, (uint32_t)seed, (uint32_t)(seed >> 32), code_base, video_id, sample_id);
+    if (add)
+        hipLaunchKernelGGL(reduce_dropout_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dout, ld_out, dh, T, B, N, H,
+                           keep, (uint32_t)seed, (uint32_t)(seed >> 32), code_base, video_id, sample_id, add, add_t0);
+    else
+        hipLaunchKernelGGL(reduce_dropout_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dout, ld_out, dh, T, B, N, H,
+                           keep, (uint32_t)seed, (uint32_t)(seed >> 32), code_base, video_id, sample_id, add, add_t0);
+    return hipGetLastError();
+}
+
+// a[i] += b[i], i < n (the residual model's training unroll: O2[Tv:] <- O1[Tv:] + O2[Tv:], one fp32 addition per element)
+__global__ __launch_bounds__(256) void add_inplace_kernel(float* a, const float* b, size_t n)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) a[i] = b[i] + a[i];
+}
+
+hipError_t launch_add_inplace(float* a, const float* b, size_t n, hipStream_t st)
+{
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(add_inplace_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a, b, n);
     return hipGetLastError();
 }
 

@@ -143,7 +143,7 @@ hipError_t launch_vocab_topk(const float* logits, int ld, int R, int V, int k, i
 __global__ __launch_bounds__(256) void beam_gather_kernel(const int32_t* video_of_row, const int32_t* parent, const int32_t* word, int t,
                                                           int B, int Rmax, int H, int V, const float* c_enc, const float* h_enc,
                                                           const float* c_prev, const float* h_prev, const float* P2t, float* c_out,
-                                                          float* h_out, float* p2_out, int32_t* word_out)
+                                                          float* h_out, float* p2_out, int32_t* word_out, int32_t* vid_out)
 {
     const int m = blockIdx.x;
     int vid = video_of_row[m];
@@ -163,6 +163,7 @@ __global__ __launch_bounds__(256) void beam_gather_kernel(const int32_t* video_o
     }
     for (int i = threadIdx.x; i < 4 * H; i += 256) p2_out[(size_t)m * 4 * H + i] = ps[i];
     if (threadIdx.x == 0) {
+        if (vid_out) vid_out[m] = vid;                       // residual model: the clamped row -> video map of the cell launch's out1 operand
         const int wd = word[m];
         word_out[m] = wd < 0 ? 0 : (wd >= V ? V - 1 : wd);
     }
@@ -180,6 +181,7 @@ struct BeamWs {
     float *c2g, *h2g, *p2g;             // the cell's gathered inputs [Rmax][H], [Rmax][H], [Rmax][4H]
     int32_t* word;                      // clamped words [Rmax]
     float* logits;                      // [Rmax][V] (when the caller does not ask for them)
+    float* out2; int32_t* vid;          // residual model only (else NULL), carved last: out1 + out2 of the step [Rmax][H], the clamped videos [Rmax]
 };
 
 size_t carve_beam(Carver& c, const s2vt_dims* d, int B, int beam, BeamWs* w)
@@ -195,13 +197,15 @@ size_t carve_beam(Carver& c, const s2vt_dims* d, int B, int beam, BeamWs* w)
     t.p2g = c.take<float>(Rmax * 4 * H);
     t.word = c.take<int32_t>(Rmax);
     t.logits = c.take<float>(Rmax * V);
+    t.out2 = nullptr; t.vid = nullptr;
+    if (is_residual(d)) { t.out2 = c.take<float>(Rmax * H); t.vid = c.take<int32_t>(Rmax); }
     if (w) *w = t;
     return c.off;
 }
 
 bool beam_shape_ok(const s2vt_dims* d, int B, int beam)
 {
-    return dims_ok(d) && B > 0 && beam >= 1 && beam <= kTopkMax && (int64_t)B * beam <= INT_MAX / 4;
+    return dims_ok_res(d) && B > 0 && beam >= 1 && beam <= kTopkMax && (int64_t)B * beam <= INT_MAX / 4;
 }
 
 }  // namespace
@@ -255,17 +259,19 @@ int s2vt_beam_step(const s2vt_dims* d, const s2vt_params* p, int32_t B, int32_t 
     // 1. gather: parents' LSTM2 state, the video's LSTM1 partial of this step, the words
     hipLaunchKernelGGL(beam_gather_kernel, dim3(R), dim3(256), 0, st, video_of_row, parent, word, (int)t, (int)B, (int)(B * beam), H, V,
                        w.enc.c2e + (size_t)Tv * BH, w.enc.h2e + (size_t)Tv * BH, w.c2, w.h2, w.enc.P2 + (size_t)(Tv + t) * 4 * BH, w.c2g,
-                       w.h2g, w.p2g, w.word);
+                       w.h2g, w.p2g, w.word, w.vid);
     HIP_TRY(hipGetLastError());
     // 2. LSTM2 at R rows on the gathered partial, words and parent state
     Lstm2Step s2{};
     s2.p = p; s2.M = R; s2.H = H; s2.E = E;
     s2.partial = w.p2g; s2.word_idx = w.word; s2.c_prev = w.c2g; s2.h_prev = w.h2g;
     s2.c_new = w.c2; s2.h_new = w.h2; s2.lstm_cfg = -1;
+    // residual model (residual_tf_s2vt.py:206-208): the cell launch also writes out1 + h', out1 = slot Tv + t + 1 of the video's LSTM1 history
+    if (w.out2) { s2.out = w.out2; s2.out1 = w.enc.h1 + (size_t)(Tv + t + 1) * BH; s2.out1_rowidx = w.vid; }
     HIP_TRY(lstm2_step(s2, st));
     // 3. vocabulary logits on the store tile
     float* logits = logits_out ? logits_out : w.logits;
-    ASeg so = make_seg(w.h2, H, H, 0);
+    ASeg so = make_seg(w.out2 ? w.out2 : w.h2, H, H, 0);
     HIP_TRY(store_call(&so, 1, p->embed_word_W, V, p->embed_word_b, logits, V, R, V, 0, -1, st));
     // 4. top-k words and their log-probabilities
     HIP_TRY(launch_vocab_topk(logits, V, R, V, k, top_ids, top_logp, st));

@@ -21,6 +21,7 @@ struct CfgEntry {
     KernelFn vec_om, scalar_om;   // the live-row forms (GemmArgs::omap / m_dev): cell-step, pick and register-staged store tiles (not W^T, not LDS-DMA store)
     int fallback;                 // LDS-DMA entries (vector path only): the table index of the register-staged tile that takes the launch
                                   // when the operands are not 16-byte aligned (-1: this entry has a scalar form of its own)
+    KernelFn res[4];              // cell-step tiles: the residual forms (GemmArgs::res) of vec, scalar, vec_om, scalar_om
 };
 
 template <int WM, int WN, int TM, int TN, int NG, int EPI, int BKT = 32, int PW = 0, bool BT = false>
@@ -32,8 +33,15 @@ constexpr CfgEntry make_entry(const char* name)
         om = gemm_kernel<WM, WN, TM, TN, NG, EPI, true, BKT, PW, BT, true>;
         om_s = gemm_kernel<WM, WN, TM, TN, NG, EPI, false, BKT, PW, BT, true>;
     }
-    return CfgEntry{name, gemm_kernel<WM, WN, TM, TN, NG, EPI, true, BKT, PW, BT>,
-                    gemm_kernel<WM, WN, TM, TN, NG, EPI, false, BKT, PW, BT>, C::BM, C::CG, C::NT, C::LDS_FLOATS * 4, om, om_s, -1};
+    CfgEntry e{name, gemm_kernel<WM, WN, TM, TN, NG, EPI, true, BKT, PW, BT>,
+               gemm_kernel<WM, WN, TM, TN, NG, EPI, false, BKT, PW, BT>, C::BM, C::CG, C::NT, C::LDS_FLOATS * 4, om, om_s, -1, {nullptr, nullptr, nullptr, nullptr}};
+    if constexpr (EPI == EPI_LSTM || EPI == EPI_LSTM_GW) {
+        e.res[0] = gemm_kernel<WM, WN, TM, TN, NG, EPI, true, BKT, PW, BT, false, 0, true>;
+        e.res[1] = gemm_kernel<WM, WN, TM, TN, NG, EPI, false, BKT, PW, BT, false, 0, true>;
+        e.res[2] = gemm_kernel<WM, WN, TM, TN, NG, EPI, true, BKT, PW, BT, true, 0, true>;
+        e.res[3] = gemm_kernel<WM, WN, TM, TN, NG, EPI, false, BKT, PW, BT, true, 0, true>;
+    }
+    return e;
 }
 // LDS-DMA ring tiles (gemm_mfma.h, DM > 0): PW loader waves issue buffer_load ... lds pieces DM stages deep, the MFMA waves only read
 // fragments and multiply.  Vector path only; `fallback` names the register-staged tile for unaligned operands.
@@ -43,8 +51,13 @@ constexpr CfgEntry make_dma_entry(const char* name, int fallback)
     using C = GemmCfg<WM, WN, TM, TN, NG, EPI, true, BKT, PW, BT, DM>;
     KernelFn om = nullptr;
     if constexpr (EPI == EPI_LSTM || EPI == EPI_LSTM_GW || EPI == EPI_PICK) om = gemm_kernel<WM, WN, TM, TN, NG, EPI, true, BKT, PW, BT, true, DM>;
-    return CfgEntry{name, gemm_kernel<WM, WN, TM, TN, NG, EPI, true, BKT, PW, BT, false, DM>, nullptr, C::BM, C::CG, C::NT, C::LDS_FLOATS * 4, om,
-                    nullptr, fallback};
+    CfgEntry e{name, gemm_kernel<WM, WN, TM, TN, NG, EPI, true, BKT, PW, BT, false, DM>, nullptr, C::BM, C::CG, C::NT, C::LDS_FLOATS * 4, om,
+               nullptr, fallback, {nullptr, nullptr, nullptr, nullptr}};
+    if constexpr (EPI == EPI_LSTM || EPI == EPI_LSTM_GW) {
+        e.res[0] = gemm_kernel<WM, WN, TM, TN, NG, EPI, true, BKT, PW, BT, false, DM, true>;
+        e.res[2] = gemm_kernel<WM, WN, TM, TN, NG, EPI, true, BKT, PW, BT, true, DM, true>;
+    }
+    return e;
 }
 
 // name = BMxBN(wavesMxwavesN)
@@ -243,7 +256,7 @@ void set_lds_attrs()
         int n;
         const CfgEntry* t = table(epi, &n);
         for (int i = 0; i < n; ++i) {
-            for (KernelFn fn : {t[i].vec, t[i].scalar, t[i].vec_om, t[i].scalar_om}) {
+            for (KernelFn fn : {t[i].vec, t[i].scalar, t[i].vec_om, t[i].scalar_om, t[i].res[0], t[i].res[1], t[i].res[2], t[i].res[3]}) {
                 if (!fn) continue;
                 const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
                                                          t[i].lds_bytes);
@@ -390,6 +403,11 @@ hipError_t launch_gemm(const GemmArgs& a, int epi, int cfg, hipStream_t st)
     if (a.omap || a.m_dev) {                                           // live-row launch: its own instantiations
         if (!e.vec_om) return hipErrorInvalidValue;
         fn = fn == e.vec ? e.vec_om : e.scalar_om;
+    }
+    if (a.res) {                                                       // residual cell step: the RES twin of whichever form was chosen
+        if (epi != EPI_LSTM || !a.out) return hipErrorInvalidValue;
+        fn = e.res[(fn == e.vec || fn == e.vec_om ? 0 : 1) + ((a.omap || a.m_dev) ? 2 : 0)];
+        if (!fn) return hipErrorInvalidValue;
     }
     const int pcls = epi;                                              // profiler class (0 store, 1 LSTM, 2 pick, 3 = TN kernel, 4 store with W^T)
     if (!prof_wants(pcls, cfg)) {

@@ -89,6 +89,12 @@ struct GemmArgs {
     // the noise ids -- uses row omap[m] of the caller's arrays, and only the first *m_dev rows exist (tiles behind them return at once).
     const int* omap;
     const int* m_dev;
+    // residual form of the cell epilogues (the RES instantiations; residual_tf_s2vt.py:149-151): out[m] = dropout(h'[m]) + res[row(m)],
+    // one fp32 addition; row(m) = m % res_rowmod (when > 0), then res_rowidx[.] (when given) -- of the live-row launch's row omap[m]
+    const float* res;
+    const int* res_rowidx;
+    int res_ld;
+    int res_rowmod;
 };
 
 // ---- loads the compiler does not schedule (cdna_hip_programming.md §5.7): hipcc sinks ordinary prefetch loads next
@@ -215,9 +221,10 @@ struct GemmCfg {
     static_assert(DM == 0 || (PW > 0 && VEC), "LDS-DMA ring: loader waves, aligned operands");
 };
 
-template <int WM, int WN, int TM, int TN, int NG, int EPI, bool VEC, int BKT = 32, int PW = 0, bool BT = false, bool OM = false, int DM = 0>
+template <int WM, int WN, int TM, int TN, int NG, int EPI, bool VEC, int BKT = 32, int PW = 0, bool BT = false, bool OM = false, int DM = 0, bool RES = false>
 __global__ __launch_bounds__(64 * (WM * WN + PW)) void gemm_kernel(const GemmArgs g)
 {
+    static_assert(!RES || EPI == EPI_LSTM || EPI == EPI_LSTM_GW, "residual operand: cell epilogues only");
     using Cfg = GemmCfg<WM, WN, TM, TN, NG, EPI, VEC, BKT, PW, BT, DM>;
     constexpr int BK = Cfg::BK, KQ = Cfg::KQ, RS = Cfg::RS, PL = Cfg::PL, ABUF = Cfg::ABUF;   // (BK shadows the namespace-scope default)
     constexpr int NG4 = Cfg::NG4, SWZ_SHIFT = Cfg::SWZ_SHIFT;
@@ -297,6 +304,12 @@ __global__ __launch_bounds__(64 * (WM * WN + PW)) void gemm_kernel(const GemmArg
     }
     const bool omapped = OM && g.omap != nullptr;
     auto orow = [&](int m) __attribute__((always_inline)) { if constexpr (OM) return g.omap ? g.omap[m] : m; else return m; };
+    // RES: the residual operand's element for output row mo (already through orow), unit u
+    auto res_at = [&](int mo, int u) __attribute__((always_inline)) {
+        int rr = g.res_rowmod > 0 ? mo % g.res_rowmod : mo;
+        if (g.res_rowidx) rr = g.res_rowidx[rr];
+        return g.res[(size_t)rr * g.res_ld + u];
+    };
 
     f32x4 acc[TM][TN];
     // initial accumulator: +0 or a carried partial chain
@@ -1087,13 +1100,14 @@ __global__ __launch_bounds__(64 * (WM * WN + PW)) void gemm_kernel(const GemmArg
                     const float h = dm_tanhf(c) * so;
                     g.c_new[o] = c;
                     g.h_new[o] = h;
-                    if (g.out) {
+                    if (RES || g.out) {                  // (RES: out is required)
                         float ov = h;
                         if (g.keep < 1.0f) {
                             const float k01 = dropout_keep01(g.seed_lo, g.seed_hi, (uint32_t)g.video_id[mo],
                                                              (uint32_t)g.sample_id[mo], g.drop_code, (uint32_t)u, g.keep);
                             ov = (h / g.keep) * k01;
                         }
+                        if constexpr (RES) ov = ov + res_at(mo, u);
                         g.out[o] = ov;
                     }
                     if (g.gates) {
@@ -1139,13 +1153,14 @@ __global__ __launch_bounds__(64 * (WM * WN + PW)) void gemm_kernel(const GemmArg
             const float h = dm_tanhf(c) * so;
             g.c_new[o] = c;
             g.h_new[o] = h;
-            if (g.out) {
+            if (RES || g.out) {
                 float ov = h;
                 if (g.keep < 1.0f) {
                     const float k01 = dropout_keep01(g.seed_lo, g.seed_hi, (uint32_t)g.video_id[mo], (uint32_t)g.sample_id[mo],
                                                      g.drop_code, (uint32_t)u, g.keep);
                     ov = (h / g.keep) * k01;
                 }
+                if constexpr (RES) ov = ov + res_at(mo, u);
                 g.out[o] = ov;
             }
             if (g.gates) {

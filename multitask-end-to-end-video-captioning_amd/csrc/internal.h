@@ -64,9 +64,11 @@ hipError_t launch_lstm_bwd_pointwise(const float* gates, const float* c_new, con
 hipError_t launch_expand_dropout(const float* h, float* out, int T, int B, int N, int H, float keep, uint64_t seed,
                                  uint32_t code_base, const int32_t* video_id, const int32_t* sample_id, hipStream_t st);
 // dh[t][j][u] = sum_k (dout[t][k*B + j][u] / keep) * mask(k*B + j, t, u)   (adjoint of the above; dout rows ld_out apart)
+// add != NULL: dout[t] + add[t - add_t0] for t >= add_t0 (add: [T - add_t0][N][H], rows H apart), same pass, same order
 hipError_t launch_reduce_dropout(const float* dout, int ld_out, float* dh, int T, int B, int N, int H, float keep,
                                  uint64_t seed, uint32_t code_base, const int32_t* video_id, const int32_t* sample_id,
-                                 hipStream_t st);
+                                 hipStream_t st, const float* add = nullptr, int add_t0 = 0);
+hipError_t launch_add_inplace(float* a, const float* b, size_t n, hipStream_t st);      // a[i] = b[i] + a[i]
 hipError_t launch_colsum(const float* X, int ld, int M, int N, float* out, hipStream_t st);
 hipError_t launch_sum_slabs(float* dst, const float* slabs, int nslab, size_t stride, size_t n, hipStream_t st);
 // up to 8 buffers zeroed by one launch (sizes in 4-byte words)

@@ -149,7 +149,7 @@ int s2vt_unpack_weights(const float* Wx_packed, const float* Wh_packed, int32_t 
 int s2vt_frame_embed_bwd(const s2vt_dims* d, const float* video, const float* d_emb, int32_t B, float* d_encode_image_W,
                          float* d_encode_image_b, s2vt_stream stream)
 {
-    if (!dims_ok(d) || !video || !d_emb || !d_encode_image_W || !d_encode_image_b || B < 0) return S2VT_E_BADARG;
+    if (!dims_ok_res(d) || !video || !d_emb || !d_encode_image_W || !d_encode_image_b || B < 0) return S2VT_E_BADARG;
     if (B == 0) return S2VT_OK;
     const int R = B * d->n_video_lstm_step, D = d->dim_image, E = d->word_dim;
     TnArgs a{video, nullptr, D, d_emb, E, d_encode_image_W, E, R, D, E, 1};

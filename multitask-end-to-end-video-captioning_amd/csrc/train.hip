@@ -540,7 +540,7 @@ int s2vt_lstm_recurrence_bwd(const float* W, int32_t kw0, const float* gates, co
 
 size_t s2vt_train_workspace_bytes(const s2vt_dims* d, int32_t B, int32_t N)
 {
-    if (!dims_ok(d) || B <= 0 || N <= 0 || N % B) return 0;
+    if (!dims_ok_res(d) || B <= 0 || N <= 0 || N % B) return 0;      // (the residual model's unroll needs no region of its own)
     Carver c(nullptr, 0);
     return carve_train(c, d, B, N, nullptr);
 }
@@ -582,7 +582,7 @@ int s2vt_teacher_forced_fwd_live(const s2vt_dims* d, const s2vt_params* p, const
                                  int32_t sampler_rows, s2vt_stream stream)
 {
     if ((live_rows == nullptr) != (n_live == 0) || n_live < 0) return S2VT_E_BADARG;
-    if (!dims_ok(d) || !params_ok(p) || !video || !caption || !logits || !workspace || B <= 0 || N <= 0 || N % B)
+    if (!dims_ok_res(d) || !params_ok(p) || !video || !caption || !logits || !workspace || B <= 0 || N <= 0 || N % B)
         return S2VT_E_BADARG;
     if (!(keep > 0.0f) || (keep < 1.0f && (!video_id || !sample_id))) return S2VT_E_BADARG;
     if (reinterpret_cast<uintptr_t>(workspace) & 255u) return S2VT_E_ALIGN;
@@ -640,6 +640,13 @@ int s2vt_teacher_forced_fwd_live(const s2vt_dims* d, const s2vt_params* p, const
     HIP_TRY(lstm_recurrence(p->lstm2_W, H + E, p->lstm2_b, w.G2, (size_t)4 * NH, 4 * H, T, w.C2, w.H2, NH, w.G2, (size_t)4 * NH,
                             w.O2, NH, N, H, T, keep, ids, 512u, w.chain_abuf, w.chain_sync, st, rec_live ? w.perm : nullptr,
                             rec_live ? w.nlive : nullptr));
+    // Residual model (residual_tf_s2vt.py:149-151): output2 = output1 + output2 ahead of the vocabulary projection -- O2[Tv:] becomes
+    // s = O1[Tv:] + O2[Tv:] in place, whichever form the recurrence took (a row the live recurrence did not write holds nothing anyone
+    // reads, before or after).  Every later reader of the decode part of w.O2 wants s: the logits product below, dWout = s^T dlogits in all
+    // three precision modes (vocab_fp32's tn, vocab_tr's tr, vocab_fused's rows1).  The dropout backward of LSTM2 regenerates its mask
+    // from Philox and never reads O2; LSTM2's own weight gradients read O1 and H2 (the un-summed h'), the encode part of O2 is untouched.
+    // (The scheduled forward writes and reads O2 per step; it refuses the residual bit.)
+    if (is_residual(d)) HIP_TRY(launch_add_inplace(w.O2 + (size_t)Tv * NH, w.O1 + (size_t)Tv * NH, (size_t)Tc * NH, st));
     // vocab logits for all Tc steps at once (tf_s2vt.py:153): rows t*N + n -- or only the LIVE ones (row r of the output is
     // row live_rows[r] of the unroll: a masked position's logits feed nothing, its loss term and gradient are exact zeros)
     ASeg so = make_seg(w.O2 + (size_t)Tv * NH, H, H, 0, 0, live_rows);
@@ -1073,7 +1080,7 @@ static int bptt_bwd_body(const s2vt_dims* d, const s2vt_params* p, const s2vt_pa
     // (fused split mode: dlogits == NULL = its planes are in bf16_ws already, s2vt_softmax_nll_fwd_bwd_split -- read by the vocabulary
     //  phase only; phases 2 to 4 never look at dlogits and take the same NULL from a caller that runs the phases one by one)
     if (!dlogits && !fused) return S2VT_E_BADARG;
-    if (!dims_ok(d) || !params_ok(p) || !params_ok(grads) || !video || !workspace || B <= 0 || N <= 0 || N % B)
+    if (!dims_ok_res(d) || !params_ok(p) || !params_ok(grads) || !video || !workspace || B <= 0 || N <= 0 || N % B)
         return S2VT_E_BADARG;
     if (reinterpret_cast<uintptr_t>(workspace) & 255u) return S2VT_E_ALIGN;
     if (bf16 && (reinterpret_cast<uintptr_t>(bf16_ws) & 255u)) return S2VT_E_ALIGN;
@@ -1170,7 +1177,9 @@ static int bptt_bwd_body(const s2vt_dims* d, const s2vt_params* p, const s2vt_pa
         HIP_TRY(bf16 ? x.dx2_bf16(!do_l2) : x.dx2_fp32());
         // ---- LSTM1 back through time, on the B per-video rows: the gradient w.r.t. its dropped output is
         // first reduced over the rep sample rows of each video (with their dropout masks)
-        HIP_TRY(launch_reduce_dropout(w.dX2, H + E, w.dH1, T, B, N, H, keep, seed, 256u, video_id, sample_id, st));
+        // (residual model: ds = dlogits Wout^T -- w.dO2, which the vocab stage wrote and nothing since has touched, zeros at the rows a
+        //  live-row call does not unroll -- is also the gradient w.r.t. LSTM1's dropped output of the decode steps: d o1 = dX2[:, 0:H] + ds)
+        HIP_TRY(launch_reduce_dropout(w.dX2, H + E, w.dH1, T, B, N, H, keep, seed, 256u, video_id, sample_id, st, is_residual(d) ? w.dO2 : nullptr, Tv));
         if (l2_deferred) chain_gate_arm(&gate);
         const hipError_t re = lstm_recurrence_bwd(p->lstm1_W, E, w.G1, w.C1, w.dH1, (size_t)B * H, H, 0, w.dZ1, B, H, T, 1.0f, seed, 0u, nullptr, nullptr, sc, -1, st);
         chain_gate_arm(nullptr);
@@ -1193,7 +1202,7 @@ int s2vt_bptt_bwd_live(const s2vt_dims* d, const s2vt_params* p, const s2vt_para
 
 size_t s2vt_bf16_grad_workspace_bytes(const s2vt_dims* d, int32_t B, int32_t N)
 {
-    if (!dims_ok(d) || B <= 0 || N <= 0 || N % B) return 0;
+    if (!dims_ok_res(d) || B <= 0 || N <= 0 || N % B) return 0;
     Carver c(nullptr, 0);
     return carve_bf16(c, d, B, N, nullptr);
 }
@@ -1209,7 +1218,7 @@ int s2vt_bptt_bwd_bf16(const s2vt_dims* d, const s2vt_params* p, const s2vt_para
 
 size_t s2vt_split_grad_workspace_bytes(const s2vt_dims* d, int32_t B, int32_t N)
 {
-    if (!dims_ok(d) || B <= 0 || N <= 0 || N % B) return 0;
+    if (!dims_ok_res(d) || B <= 0 || N <= 0 || N % B) return 0;
     Carver c(nullptr, 0);
     return carve_bf16(c, d, B, N, nullptr, true);
 }
@@ -1233,7 +1242,7 @@ int s2vt_softmax_nll_fwd_bwd_split(float* logits, int32_t ld, int32_t R, int32_t
                                    const float* smoothing_rows, float* nll, float* lp_target, const s2vt_dims* d, int32_t B, int32_t N,
                                    void* split_ws, size_t split_ws_bytes, s2vt_stream stream)
 {
-    if (!logits || !target || !coef || R < 0 || V <= 0 || ld < V || !dims_ok(d) || B <= 0 || N <= 0 || N % B || !split_ws) return S2VT_E_BADARG;
+    if (!logits || !target || !coef || R < 0 || V <= 0 || ld < V || !dims_ok_res(d) || B <= 0 || N <= 0 || N % B || !split_ws) return S2VT_E_BADARG;
     if (V != d->n_words || (size_t)R > (size_t)d->n_caption_lstm_step * N || !s2vt_split_grad_active(N)) return S2VT_E_BADARG;
     if (reinterpret_cast<uintptr_t>(split_ws) & 255u) return S2VT_E_ALIGN;
     Carver cb(split_ws, split_ws_bytes);
@@ -1253,7 +1262,7 @@ int s2vt_softmax_nll_fwd_bwd_split(float* logits, int32_t ld, int32_t R, int32_t
 
 int s2vt_split_grad_dlogits_planes(const s2vt_dims* d, int32_t B, int32_t N, size_t* hi_offset, size_t* lo_offset, int32_t* ld)
 {
-    if (!dims_ok(d) || B <= 0 || N <= 0 || N % B || !hi_offset || !lo_offset || !ld) return S2VT_E_BADARG;
+    if (!dims_ok_res(d) || B <= 0 || N <= 0 || N % B || !hi_offset || !lo_offset || !ld) return S2VT_E_BADARG;
     Carver cb(nullptr, 0);
     Bf16Ws bw{};
     carve_bf16(cb, d, B, N, &bw, true);
@@ -1341,7 +1350,7 @@ int s2vt_gemm_bf16_nt(const uint16_t* A, int32_t lda, const uint16_t* Bm, int32_
 int s2vt_bptt_dvideo(const s2vt_dims* d, const s2vt_params* p, int32_t B, int32_t N, float* d_video, void* workspace,
                       size_t workspace_bytes, s2vt_stream stream)
 {
-    if (!dims_ok(d) || !p || !p->encode_image_W || !d_video || !workspace || B <= 0 || N <= 0 || N % B) return S2VT_E_BADARG;
+    if (!dims_ok_res(d) || !p || !p->encode_image_W || !d_video || !workspace || B <= 0 || N <= 0 || N % B) return S2VT_E_BADARG;
     Carver c(workspace, workspace_bytes);
     TrainWs w;
     carve_train(c, d, B, N, &w);

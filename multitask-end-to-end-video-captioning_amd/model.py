@@ -312,12 +312,15 @@ class Video_Caption_Generator:
     `device`, `seed`, `multisample` (the K the reference hard-codes into build_loss, batch_size*8 at
     reinforcement_multisampling_tf_s2vt.py:228) are additions.  width / height / channels describe the frame placeholder the
     build_* graphs expose once a CNN is attached (attach_cnn); feature_dim is the attribute head's input width and must equal
-    dim_image (it reads mean_t(video), :375)."""
+    dim_image (it reads mean_t(video), :375).
+    `residual=True` is the architecture of residual_tf_s2vt.py: at every decode step output2 = output1 + output2 ahead of the
+    vocabulary projection (:149-151, :206-208, :263-265); same variables and checkpoint layout.  The flag rides in the dims of every
+    library call; mix_sample / scheduled_update and their graphs are not implemented for it and raise ValueError."""
 
     def __init__(self, dim_image, n_words, word_dim, lstm_dim, batch_size, n_lstm_steps, n_video_lstm_step,
                  n_caption_lstm_step, bias_init_vector=None, loss_weight=1, decay_value=0.00005, dropout_rate=0.9,
                  width=299, height=299, channels=3, feature_dim=None, label_dim=0, alpha=0.0, device="cuda", seed=1234,
-                 multisample=8):
+                 multisample=8, residual=False):
         self.dim_image, self.n_words, self.word_dim, self.lstm_dim = dim_image, n_words, word_dim, lstm_dim
         self.batch_size, self.n_lstm_steps = batch_size, n_lstm_steps
         self.n_video_lstm_step, self.n_caption_lstm_step = n_video_lstm_step, n_caption_lstm_step
@@ -330,7 +333,8 @@ class Video_Caption_Generator:
         self.e2e = None                          # e2e.EndToEnd once a CNN is attached: the video placeholders then take frames
         self.multisample = multisample          # the reference hard-codes batch_size*8 in build_loss (:228)
         self.device = torch.device(device)
-        self.dims = ops.make_dims(dim_image, n_words, word_dim, lstm_dim, n_video_lstm_step, n_caption_lstm_step, label_dim)
+        self.residual = bool(residual)
+        self.dims = ops.make_dims(dim_image, n_words, word_dim, lstm_dim, n_video_lstm_step, n_caption_lstm_step, label_dim, self.residual)
         self.store = ParamStore(param_shapes(dim_image, n_words, word_dim, lstm_dim, label_dim), self.device)
         init_reference(self.store, seed)
         if bias_init_vector is not None:
@@ -353,6 +357,10 @@ class Video_Caption_Generator:
         self._sumsq = torch.zeros(1, dtype=torch.float32, device=self.device)
         self._gscale = torch.ones(1, dtype=torch.float32, device=self.device)
         self._ascale = torch.ones(1, dtype=torch.float32, device=self.device)
+
+    def _refuse_residual(self, what):
+        if self.residual:
+            raise ValueError(f"{what} is not implemented for a residual=True model (residual_tf_s2vt.py has no such graph)")
 
     @property
     def grad_precision(self) -> str:
@@ -492,6 +500,7 @@ class Video_Caption_Generator:
         caption [B, Tc]: a numpy array or list is checked on the host (shape, 0 <= id < n_words: ValueError); a device tensor is passed
         through and the kernel clamps its ids.  The coins are a function of (seed, video_base + row, step): ranks draw what one process
         would.  No state is kept for reuse_sampler_state: a sample() call's saved trajectory stays valid across this call."""
+        self._refuse_residual("mix_sample")
         p_gt = np.float32(np.float64(true_word_prob) / np.float64(1.00001))
         if not 0.0 <= float(p_gt) <= 1.0:                          # (NaN fails too)
             raise ValueError(f"true_word_prob must lie in [0, 1.00001], got {true_word_prob!r}")
@@ -514,6 +523,7 @@ class Video_Caption_Generator:
         (sampled_captions, video, caption) in the reference's order, fetched alone or beside build_sampler's output as at :957-960.
         true_word_prob: the constant the reference writes into the graph (:553).  Every run draws fresh coins, as the stateful TF op
         does: run number n (from 1) uses seed sample_seed + 7919 * n."""
+        self._refuse_residual("build_mix_sample")
         video = self._video_placeholder(None)
         caption = Placeholder("caption", (self.batch_size, self.n_caption_lstm_step), np.int32)
         state = {"calls": 0}
@@ -969,6 +979,7 @@ class Video_Caption_Generator:
         coin_seed None: sample_seed + 7919 * (global_step + 1), fresh coins every step.  Data parallel: sum(mask) rides in the gradient
         bucket's tail slot, as in reinforce_update with a device-made mask.
         Returns StepStats (.loss without the weight-decay term) plus .mask [N, Tc], .generated, .fed [N, Tc] int32 device tensors."""
+        self._refuse_residual("scheduled_update")
         p_gt = np.float32(np.float64(true_word_prob) / np.float64(1.00001))
         if not 0.0 <= float(p_gt) <= 1.0:                          # (NaN fails too)
             raise ValueError(f"true_word_prob must lie in [0, 1.00001], got {true_word_prob!r}")
@@ -1019,6 +1030,7 @@ class Video_Caption_Generator:
         written into the graph), unless k_value is given: then p = k / (k + exp(steps / k)) is evaluated on the host in float64.
         Fetching loss / caption_mask / probs evaluates the forward only; minimize() builds the train_op.  Every run draws fresh coins, as
         the stateful TF op does."""
+        self._refuse_residual("build_scheduled_model")
         B, Tc = self.batch_size, self.n_caption_lstm_step
         video = self._video_placeholder(B)
         caption = Placeholder("caption", (B, Tc), np.int32)

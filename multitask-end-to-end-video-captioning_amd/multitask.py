@@ -20,10 +20,10 @@ class Video_Caption_Generator(_model.Video_Caption_Generator):
     def __init__(self, dim_image, n_words, word_dim, lstm_dim, batch_size, n_lstm_steps, n_video_lstm_step,
                  n_caption_lstm_step, bias_init_vector=None, loss_weight=1, decay_value=0.00005, dropout_rate=0.9,
                  width=299, height=299, channels=3, feature_dim=1536, label_dim=400, alpha=0.2, device="cuda", seed=1234,
-                 multisample=1):
+                 multisample=1, residual=False):
         super().__init__(dim_image, n_words, word_dim, lstm_dim, batch_size, n_lstm_steps, n_video_lstm_step,
                          n_caption_lstm_step, bias_init_vector=bias_init_vector, loss_weight=loss_weight, decay_value=decay_value,
                          dropout_rate=dropout_rate, width=width, height=height, channels=channels,
                          feature_dim=feature_dim if label_dim else None, label_dim=label_dim, alpha=alpha, device=device, seed=seed,
-                         multisample=multisample)
+                         multisample=multisample, residual=residual)
         self.decay_all_variables = True          # `if 'bias' or 'BatchNorm' not in v.name` (:222): every trainable variable

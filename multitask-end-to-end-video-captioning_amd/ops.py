@@ -24,8 +24,11 @@ def _chk_f32(*ts):
             assert t.is_cuda and t.dtype == torch.float32, "expected a CUDA float32 tensor"
 
 
-def make_dims(dim_image, n_words, word_dim, lstm_dim, n_video_lstm_step, n_caption_lstm_step, label_dim=0) -> Dims:
-    return Dims(dim_image, n_words, word_dim, lstm_dim, n_video_lstm_step, n_caption_lstm_step, label_dim, 0)
+def make_dims(dim_image, n_words, word_dim, lstm_dim, n_video_lstm_step, n_caption_lstm_step, label_dim=0, residual=False) -> Dims:
+    """residual: the model bit S2VT_MODEL_RESIDUAL (residual_tf_s2vt.py: out1 + out2 into the vocabulary projection), carried in the
+    struct's spare word into every call that takes the dims."""
+    return Dims(dim_image, n_words, word_dim, lstm_dim, n_video_lstm_step, n_caption_lstm_step, label_dim,
+                _lib.MODEL_RESIDUAL if residual else 0)
 
 
 def make_params(tensors: dict) -> Params:
@@ -113,7 +116,8 @@ def gemm_nt_splitk(A, Wt, splits=0, tile_cfg=-1, out=None, slabs=None):
 
 
 def lstm_cell_fwd(x0, x1, h_prev, c_prev, W, b, M, state_rowmod=0, keep=1.0, seed=0, video_id=None, sample_id=None,
-                  drop_code=0, want_gates=False, tile_cfg=-1):
+                  drop_code=0, want_gates=False, tile_cfg=-1, res=None):
+    """res (an Operand of width H): the residual form, out = dropout(h') + res[row(m)] (s2vt_lstm_cell_fwd_res)."""
     _chk_f32(h_prev, c_prev, W, b)
     H = W.shape[1] // 4
     dev = W.device
@@ -121,6 +125,12 @@ def lstm_cell_fwd(x0, x1, h_prev, c_prev, W, b, M, state_rowmod=0, keep=1.0, see
     h = torch.empty_like(c)
     out = torch.empty_like(c)
     gates = torch.empty((M, 4 * H), dtype=torch.float32, device=dev) if want_gates else None
+    if res is not None:
+        check(lib().s2vt_lstm_cell_fwd_res(None if x0 is None else C.byref(x0), None if x1 is None else C.byref(x1), _ptr(h_prev),
+                                           _ptr(c_prev), state_rowmod, _ptr(W), _ptr(b), C.byref(res), _ptr(c), _ptr(h), _ptr(out),
+                                           _ptr(gates), M, H, float(keep), seed, _ptr(video_id), _ptr(sample_id), drop_code, tile_cfg,
+                                           _stream()), "s2vt_lstm_cell_fwd_res")
+        return c, h, out, gates
     check(lib().s2vt_lstm_cell_fwd(None if x0 is None else C.byref(x0), None if x1 is None else C.byref(x1), _ptr(h_prev),
                                    _ptr(c_prev), state_rowmod, _ptr(W), _ptr(b), _ptr(c), _ptr(h), _ptr(out), _ptr(gates),
                                    M, H, float(keep), seed, _ptr(video_id), _ptr(sample_id), drop_code, tile_cfg, _stream()),

@@ -44,6 +44,8 @@ class Config:
     alpha: float = 0.05                # multitask scripts: weight of the attribute head's multilabel loss (reinforce_multitask_e2e_attribute_loss.py:697)
     lambda_loss: float = 0.0           # multitask scripts: weight of the ground-truth XE term mixed into the REINFORCE objective
                                        # (reinforce_multitask_e2e_attribute_s2vt.py:670,850: 0.5 there); 0 = the pure self-critical objective
+    residual: bool = False             # the architecture of residual_tf_s2vt.py (out1 + out2 into the vocabulary projection): Video_Caption_Generator(residual=True);
+                                       # the epoch records of the step log carry it
     mix_baseline: float | None = None  # RL: P = the baseline is the reward of a greedy decode fed ground-truth words with probability P / 1.00001 and the
                                        # greedy caption is the sample (reinforce_multitask_e2e_attribute_by_groudtruth_greedy_s2vt.py:957-979: 0.9); None = off
 

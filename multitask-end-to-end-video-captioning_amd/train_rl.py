@@ -89,7 +89,10 @@ def train(cfg: Config, train_corpus: Corpus, test_corpus: Corpus | None = None, 
         model = M.Video_Caption_Generator(cfg.dim_image, len(wordtoix), cfg.word_dim, cfg.lstm_dim, B,
                                           cfg.n_video_lstm_step + cfg.n_caption_lstm_step, cfg.n_video_lstm_step,
                                           cfg.n_caption_lstm_step, bias_init_vector=None, seed=cfg.seed, multisample=K, device=par.device,
-                                          label_dim=len(attr_vocabulary) if multitask else 0, alpha=cfg.alpha if multitask else 0.0)
+                                          label_dim=len(attr_vocabulary) if multitask else 0, alpha=cfg.alpha if multitask else 0.0,
+                                          residual=cfg.residual)
+    if mix_p is not None and getattr(model, "residual", False):
+        raise ValueError("mix_baseline is not implemented for a residual model (residual=True / --residual)")
     if grad_precision is not None:
         model.grad_precision = grad_precision          # (None: the model's default, S2VT_GRAD_PRECISION)
     par.attach(model)
@@ -201,13 +204,13 @@ def train(cfg: Config, train_corpus: Corpus, test_corpus: Corpus | None = None, 
         if par.chief:
             entry["checkpoint"] = ck
         history.append(entry)
-        steplog.write(kind="epoch", **entry)
+        steplog.write(kind="epoch", residual=bool(cfg.residual), **entry)
         log(f"Epoch {epoch} is done: {entry}")
     steplog.close()
     return model, history
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--train-sents", required=True); ap.add_argument("--train-feats", required=True)
     ap.add_argument("--test-sents"); ap.add_argument("--test-feats")
@@ -220,11 +223,12 @@ def main():
     ap.add_argument("--mix-baseline", type=float, metavar="P", help="the greedy caption is the policy's sample and the baseline is the reward of a greedy "
                     "decode fed ground-truth words with probability P / 1.00001 (reinforce_multitask_e2e_attribute_by_groudtruth_greedy_s2vt.py:957-979; "
                     "0.9 there); needs --samples 1; with --lambda-loss > 0 the update is that script's mixed objective")
+    ap.add_argument("--residual", action="store_true", help="the residual captioner of residual_tf_s2vt.py: out1 + out2 into the vocabulary projection")
     ap.add_argument("--grad-precision", choices=("fp32", "bf16"), help="the backward's gradient contractions on bf16 operands (non-parity "
                     "fast mode, DESIGN.md §3); default: S2VT_GRAD_PRECISION, else fp32")
-    a = ap.parse_args()
+    a = ap.parse_args(argv)
     cfg = rl_config(n_epochs=a.epochs, batch_size=a.batch_size, multisample=a.samples, model_path=a.model_path, stop_at_eos=a.stop_at_eos,
-                    alpha=a.alpha, lambda_loss=a.lambda_loss, mix_baseline=a.mix_baseline)
+                    alpha=a.alpha, lambda_loss=a.lambda_loss, mix_baseline=a.mix_baseline, residual=a.residual)
     tr = Corpus(a.train_sents, a.train_feats, vocabulary_file=a.vocab)
     te = Corpus(a.test_sents, a.test_feats, vocabulary=tr.vocabulary) if a.test_sents and a.test_feats else None
     attr = [l.strip() for l in open(a.attr_vocab)] if a.attr_vocab else None

@@ -39,7 +39,10 @@ def train(cfg: Config, train_corpus: Corpus, test_corpus: Corpus | None = None, 
     if model is None:
         model = M.Video_Caption_Generator(cfg.dim_image, len(wordtoix), cfg.word_dim, cfg.lstm_dim, B,
                                           cfg.n_video_lstm_step + cfg.n_caption_lstm_step, cfg.n_video_lstm_step,
-                                          cfg.n_caption_lstm_step, bias_init_vector=None, seed=cfg.seed, device=par.device)
+                                          cfg.n_caption_lstm_step, bias_init_vector=None, seed=cfg.seed, device=par.device,
+                                          residual=cfg.residual)
+    if scheduled_sampling is not None and getattr(model, "residual", False):
+        raise ValueError("scheduled sampling is not implemented for a residual model (residual=True / --residual)")
     if grad_precision is not None:
         model.grad_precision = grad_precision          # (None: the model's default, S2VT_GRAD_PRECISION)
     par.attach(model)
@@ -104,13 +107,13 @@ def train(cfg: Config, train_corpus: Corpus, test_corpus: Corpus | None = None, 
         if par.chief:
             entry["checkpoint"] = ck
         history.append(entry)
-        steplog.write(kind="epoch", **entry)
+        steplog.write(kind="epoch", residual=bool(cfg.residual), **entry)
         log(f"Epoch {epoch} is done: {entry}")
     steplog.close()
     return model, history
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--train-sents", required=True); ap.add_argument("--train-feats", required=True)
     ap.add_argument("--test-sents"); ap.add_argument("--test-feats")
@@ -122,13 +125,15 @@ def main():
     ap.add_argument("--scheduled-sampling", type=float, metavar="P", help="scheduled-sampling training (generate_words_tf_s2vt.py): feed the "
                     "ground-truth word with probability P / 1.00001, the model's own argmax otherwise (the script writes 0.5)")
     ap.add_argument("--ss-k", type=float, metavar="K", help="with scheduled sampling: P = K / (K + exp(step / K)) (the script's k_value = 5000)")
+    ap.add_argument("--residual", action="store_true", help="the residual captioner of residual_tf_s2vt.py: out1 + out2 into the vocabulary projection")
     ap.add_argument("--optimizer", choices=("adam", "sgd"), default="adam", help="sgd: the scheduled-sampling script's GradientDescentOptimizer")
-    a = ap.parse_args()
+    a = ap.parse_args(argv)
     if a.ss_k is not None and a.scheduled_sampling is None:
         a.scheduled_sampling = 0.5
     if a.optimizer != "adam" and a.scheduled_sampling is None:
         ap.error("--optimizer sgd is wired for --scheduled-sampling only")
-    cfg = Config(n_epochs=a.epochs, batch_size=a.batch_size, model_path=a.model_path, model_name=f"batch_size{a.batch_size}_s2vt_model")
+    cfg = Config(n_epochs=a.epochs, batch_size=a.batch_size, model_path=a.model_path, model_name=f"batch_size{a.batch_size}_s2vt_model",
+                 residual=a.residual)
     tr = Corpus(a.train_sents, a.train_feats, vocabulary_file=a.vocab)
     te = Corpus(a.test_sents, a.test_feats, vocabulary=tr.vocabulary) if a.test_sents and a.test_feats else None
     train(cfg, tr, te, resume=a.resume, grad_precision=a.grad_precision, scheduled_sampling=a.scheduled_sampling, ss_k=a.ss_k,
