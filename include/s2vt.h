@@ -815,6 +815,20 @@ int s2vt_lstm_recurrence_bwd(const float* W, int32_t kw0, const float* gates, co
                              int32_t ld_ext, int32_t dext_t0, float* dZ, int32_t M, int32_t H, int32_t T, float keep, uint64_t seed,
                              const int32_t* video_id, const int32_t* sample_id, uint32_t drop_code0, int32_t persistent, void* scratch,
                              size_t scratch_bytes, s2vt_stream stream);
+/* Where in the training workspace of (d, B, N) LSTM2's pre-activation gradients lie after LSTM2's phase of the backward (phase 0, 2
+ * or 3): byte offset and length in floats of dZ2 [T][N][4H], T = n_video_lstm_step + n_caption_lstm_step, of which the steps the
+ * forward call unrolled are written.  They come out of the backward recurrence alone (no atomics behind them): what a test of its
+ * dispatch compares bit for bit. */
+int s2vt_train_workspace_dz2(const s2vt_dims* d, int32_t B, int32_t N, size_t* offset, size_t* floats);
+/* The same with dZ[t+1] @ W[kw0 : kw0 + H, :]^T on split-bf16 operands (x = hi + lo, hi = bf16(x), lo = bf16(x - hi); three bf16 MFMA
+ * products per fp32 one, fp32 accumulators: 16 significant bits per operand) -- the recurrence s2vt_bptt_bwd_split runs for LSTM2
+ * where its gradient products run split.  Same arguments and scratch.  Served by the register-weights form of the one-launch
+ * recurrence only: persistent = 1, 256 < M <= 384, more than 8 column tiles of 16 units, W 16-byte aligned; S2VT_E_BADARG elsewhere.
+ * The pointwise part, the dropout stream and the dZ history are fp32 as above. */
+int s2vt_lstm_recurrence_bwd_split(const float* W, int32_t kw0, const float* gates, const float* C_hist, const float* dext, int64_t dext_tstride,
+                                   int32_t ld_ext, int32_t dext_t0, float* dZ, int32_t M, int32_t H, int32_t T, float keep, uint64_t seed,
+                                   const int32_t* video_id, const int32_t* sample_id, uint32_t drop_code0, int32_t persistent, void* scratch,
+                                   size_t scratch_bytes, s2vt_stream stream);
 /* Grid-wide waits of the persistent recurrence that gave up (bounded spins), over all launches of this process; 0 =
  * healthy.  Read after synchronising the stream. */
 int s2vt_chain_timeouts(void);

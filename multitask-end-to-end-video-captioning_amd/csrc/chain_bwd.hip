@@ -12,6 +12,8 @@ namespace s2vt {
 
 namespace {
 
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+
 // ---------------------------------------------------------------------------------------------------------------------
 // The BACKWARD recurrence of a BasicLSTMCell (back-propagation through the unroll of tf_s2vt.py:113-153; tf.gradients,
 // reinforcement_multisampling_tf_s2vt.py:650) in one launch.  Step t (T-1 down to 0), per row m and unit u:
@@ -757,9 +759,320 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     }
 }
 
+// The register-weights recurrence on SPLIT-bf16 operands (the arithmetic of gemm_bf16x3_kernel: x = hi + lo, hi = bf16(x), lo = bf16(x - hi), 16
+// significant bits; three bf16 products per fp32 one, fp32 accumulators): where the backward's gradient products run split (train.hip), never on
+// anything that decides a token.  Grid, (unit group, gate, row part), LDS ring and its DMA, exchange, pointwise part, dropout stream, hand-offs and the
+// fp32 dZ history are those of the two kernels above; only the two operand formats and the main loop differ:
+//   * weights: lane l of wave w keeps column l & 15 of its column tile, k = 32 s + 8 (l >> 4) .. + 7 of every 32-deep k-step s, as the hi and lo B
+//     fragments of v_mfma_f32_16x16x32_bf16 -- 2 x 4 registers per k-step, 4 NG in all, what breg[4 NG] takes above;
+//   * dz image: a (row tile, 32-deep k-step) is a hi plane then a lo plane of 64 lanes x 16 bytes in A-fragment order (lane l: row l & 15,
+//     k = 32 s + 8 (l >> 4) .. + 7) -- the 2 KB of two fp32 k-groups, so the image, the ring and the DMA pieces keep their sizes and addresses.  A
+//     finished 16-unit column tile fills lane quarters 2 (kg & 1), + 1 of both planes of k-step kg / 2: one 16-byte slot per thread and gate;
+//   * main loop, per k-step and row tile: acc += Alo Bhi, acc += Ahi Blo, acc += Ahi Bhi, in this order (the small terms first), each product over
+//     a group of GS row tiles before the next (GS independent accumulators between dependent MFMAs; GS = all 5 tiles at TPP = 5, 3 at TPP = 6, where
+//     the registers allow no more).  The fragments are single-buffered: Alo of the next (k-step, group) is read under the two Ahi products, Ahi under
+//     the next Alo product.
+// LIVE = the live-row form (virtual rows, interleaved tiles, per-count instantiations of the product) -- one source for both here: the split form
+// needs no fragment double buffer and leaves the allocator the room that the fp32 dense form does not have.
+template <int NG, int TPP, bool LIVE>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void lstm_bwd_chain4_split_kernel(const BwdChainArgs g)
+{
+    constexpr int NC = 4;                                      // column tiles per workgroup
+    constexpr int CG = 8, NCH = NG / CG, NBUF = 3;             // 16-deep k-groups (= plane pairs / 2) per chunk, chunks per step, LDS chunk buffers
+    constexpr int CHF = TPP * CG * 256;                        // floats per chunk buffer
+    constexpr int NS = NG / 2, CS = CG / 2;                    // 32-deep k-steps; k-steps per chunk
+    constexpr int GS = TPP <= 5 ? TPP : 3;                     // row tiles whose fragments are in registers at a time
+    static_assert(NG % CG == 0 && NCH >= NBUF && CG % 4 == 0, "chunking");
+    constexpr int ZS = 20;
+    constexpr int PS = TPP;                                    // (row tile, column tile) slots one workgroup finishes per step: tpp * 4 / 4 gates
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float* Ab = smem;                                          // [NBUF][CG][TPP][64 lanes][16 bytes]: the A ring (group 2 s = hi plane of k-step s, 2 s + 1 = lo)
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int pwave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    float* zb = smem + NBUF * CHF + pwave * (16 * ZS);         // per-wave transpose tile
+    float* dzl = smem + NBUF * CHF + 4 * 16 * ZS;              // [4 gates][16 rows][17]: dz of one finished tile, regrouped for the image stores
+    const int l15 = lane & 15, lq = lane >> 4;
+    const int H = g.H, M = g.M, T = g.T;
+    // workgroup id -> (unit group, gate, row part): the four gates of a (unit group, part) share blockIdx % 8
+    const int wg = (int)blockIdx.x;
+    const int gate = (wg >> 3) & 3;
+    const int part = (wg >> 5) & 3;
+    const int jj = (wg >> 7) * 8 + (wg & 7);
+    if (jj >= g.ncg) return;                                   // (grid padded to whole groups of 8: these never take part)
+    const int u0 = jj * 16 * NC;
+    const int tpp = g.tpp;                                     // row tiles of a part
+    const int NT = g.img_tiles;                                // row tiles of an image (= parts * tpp)
+    const size_t img_floats = (size_t)NT * NG * 256;           // one gate image
+    constexpr int TS = LIVE ? 4 : 1;                           // image tiles between consecutive row tiles of this workgroup
+    const int tile0 = LIVE ? part : part * tpp;                // image tile of this workgroup's row tile 0
+
+    // ---- this wave's column tile of the slice -> registers, once, split: B[k = 32 s + 8 lq + e][n = l15] = Whh[u0 + 16 w + l15][gate H + k]
+    // (H % 4 == 0 and the launcher's alignment checks make every 4 floats one aligned load, wholly below H or wholly at zero)
+    u32x4v bhi[NS], blo[NS];
+    {
+        const int un = u0 + 16 * pwave + l15;
+        const float* wrow = g.W + (size_t)(g.kw0 + (un < H ? un : 0)) * g.ldw + (size_t)gate * H;
+#pragma unroll
+        for (int s_ = 0; s_ < NS; ++s_) {
+            const int kk = 32 * s_ + 8 * lq;
+            f32x4 v0 = {0.f, 0.f, 0.f, 0.f}, v1 = {0.f, 0.f, 0.f, 0.f};
+            if (un < H && kk < H) v0 = *reinterpret_cast<const f32x4*>(wrow + kk);
+            if (un < H && kk + 4 < H) v1 = *reinterpret_cast<const f32x4*>(wrow + kk + 4);
+            uint32_t h[4], l[4];
+            split2(v0[0], v0[1], h[0], l[0]); split2(v0[2], v0[3], h[1], l[1]);
+            split2(v1[0], v1[1], h[2], l[2]); split2(v1[2], v1[3], h[3], l[3]);
+            bhi[s_] = u32x4v{h[0], h[1], h[2], h[3]}; blo[s_] = u32x4v{l[0], l[1], l[2], l[3]};
+        }
+    }
+
+    // ---- the (row, unit) this thread finishes at every step, per slot of the part's tpp * NC (row tile, column tile) pairs.
+    // Dense: slot = gate * PSr + i (PSr = slots per workgroup, the four gate workgroups share them in order); LIVE: row tile i,
+    // column tile `gate` (balanced for any count of live tiles)
+    const int pr = tid >> 4, pn = tid & 15;                    // row within the tile, unit within the column tile
+    // (row and unit indices are made opaque at each use in the step loop: per-slot units and 64-bit addresses hoisted out of it would otherwise
+    //  cost registers per slot and array for the whole launch, which the weights need)
+    auto fresh = [](int v) __attribute__((always_inline)) { asm volatile("" : "+v"(v)); return v; };
+    const int nslots = tpp * NC, psr = (nslots + 3) >> 2;
+    float dc_reg[PS], cnew[PS];
+    bool pok[PS];
+    int pm[PS], ptile[PS], pc[PS];
+    auto pu_of = [&](int i) __attribute__((always_inline)) { return u0 + pc[i] * 16 + fresh(pn); };
+    auto slot_of = [&](int i) __attribute__((always_inline)) { return LIVE ? i * NC + gate : gate * psr + i; };
+#pragma unroll
+    for (int i = 0; i < PS; ++i) {
+        const int slot = slot_of(i);
+        ptile[i] = slot / NC; pc[i] = slot % NC;              // row tile within the part, column tile
+        const int vrow = (tile0 + ptile[i] * TS) * 16 + pr;
+        pok[i] = i < psr && slot < nslots && vrow < M && u0 + pc[i] * 16 + pn < H;
+        pm[i] = vrow;
+        if constexpr (LIVE) pm[i] = pok[i] ? (int)g.perm[vrow] : 0;
+        dc_reg[i] = 0.0f;
+        cnew[i] = pok[i] ? g.C[(size_t)T * g.state_tstride + (size_t)pm[i] * H + pu_of(i)] : 0.0f;      // c_{T-1}
+    }
+    const int cluster = jj * NC + part;
+    gu32* const ccount = (gu32*)g.sync + (kChainSyncBytes / 4) + cluster * 32;
+    const __amdgpu_buffer_rsrc_t rsEx = __builtin_amdgcn_make_buffer_rsrc(g.ex, 0, g.ncg * NC * 4 * tpp * NC * 1024, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsImg = __builtin_amdgcn_make_buffer_rsrc(g.img, 0, (int)(8 * img_floats * 4), 0x00020000);
+    GridSync gs{(gu32*)g.sync, g.status, g.fault, g.spin_limit, g.ncg, false, 4u * NC};
+    __syncthreads();
+
+    // live row tiles of this part at step t (dense: all)
+    auto live_tiles = [&](int t) __attribute__((always_inline)) {
+        if constexpr (!LIVE) return TPP;
+        else {
+            int n = g.nlive ? g.nlive[t] : M;
+            n = n < M ? n : M;
+            int nl = (((n + 15) >> 4) - part + 3) >> 2;
+            nl = nl < 0 ? 0 : (nl > TPP ? TPP : nl);
+            return __builtin_amdgcn_readfirstlane(nl);
+        }
+    };
+
+    float sg[PS][4], cprev[PS], dx[PS];
+    auto load_step = [&](int t, int nl) __attribute__((always_inline)) {        // operands of step t's pointwise part (independent of the recurrence)
+#pragma unroll
+        for (int i = 0; i < PS; ++i) {
+            const bool ok = pok[i] && i < nl;
+            const int m_ = fresh(pm[i]);
+            const float* gp = g.gates + (size_t)t * g.gates_tstride + (size_t)m_ * 4 * H + pu_of(i);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) sg[i][q] = ok ? gp[(size_t)q * H] : 0.0f;
+            cprev[i] = ok ? g.C[(size_t)t * g.state_tstride + (size_t)m_ * H + pu_of(i)] : 0.0f;
+            dx[i] = (ok && g.dext && t >= g.dext_t0) ? g.dext[(size_t)(t - g.dext_t0) * g.dext_tstride + (size_t)m_ * g.ld_ext + pu_of(i)] : 0.0f;
+            if constexpr (LIVE) cnew[i] = ok ? g.C[(size_t)(t + 1) * g.state_tstride + (size_t)m_ * H + pu_of(i)] : 0.0f;      // (a tile that joins at this step has no c_t from the step before)
+        }
+    };
+    const size_t exc = (size_t)cluster * 4 * nslots;              // tiles of this cluster's exchange before its own
+    // dz_{t+1}[:, gate block] @ slice^T for NL row tiles, the partial tiles handed to the cluster's exchange: the only part of a
+    // step that is instantiated per count of live tiles
+    auto product = [&](auto nl_, const int t) __attribute__((always_inline)) {
+        constexpr int NL = decltype(nl_)::value;
+        constexpr int DPW = NL * CG / 4;                       // DMA instructions per wave per chunk
+        const float* acur = g.img + (size_t)((t + 1) & 1) * 4 * img_floats + (size_t)gate * img_floats;
+        const __amdgpu_buffer_rsrc_t rsA =
+            __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(acur + (size_t)tile0 * NG * 256), 0, ((TPP - 1) * TS + 1) * NG * 1024, 0x00020000);
+        // chunk c = groups c*CG ..; piece p = gq * NL + i; wave w issues pieces w, w + 4, .. (static: CG * NL / 4 each)
+        auto issue_chunk = [&](auto c_) __attribute__((always_inline)) {
+            constexpr int c = decltype(c_)::value;
+            float* dstb = Ab + (c % NBUF) * CHF;
+            static_for<0, DPW>([&](auto q_) {
+                constexpr int q = decltype(q_)::value;
+                const int p = pwave + 4 * q;
+                const int gq = p / NL, i = p % NL;
+                const int vo = (tile0 + i * TS) * 16 < M ? lane * 16 : (int)0x80000000u;          // row tiles beyond the problem: zeros
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (lds_ptr4)(dstb + (gq * TPP + i) * 256), 16, vo, (i * TS * NG + c * CG + gq) * 1024, 0, 16);   // aux 16 = sc1
+            });
+        };
+        f32x4 acc[NL];
+#pragma unroll
+        for (int i = 0; i < NL; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+        static_for<0, NBUF - 1>([&](auto c_) { issue_chunk(c_); });
+        static_for<0, NCH>([&](auto c_) {
+            constexpr int c = decltype(c_)::value;
+            constexpr int issued = c + NBUF - 1 < NCH ? c + NBUF - 1 : NCH;
+            constexpr int later = issued - (c + 1);
+            static_assert(later * DPW <= 63, "vmcnt range");
+            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(later * DPW) : "memory");
+            __syncthreads();
+            if constexpr (c + NBUF - 1 < NCH) issue_chunk(std::integral_constant<int, c + NBUF - 1>{});
+            const u32x4v* ab = reinterpret_cast<const u32x4v*>(Ab + (c % NBUF) * CHF) + lane;
+            // turn v = (k-step s, tile group gr): tiles GS gr .. of k-step c CS + s
+            constexpr int NGR = (NL + GS - 1) / GS, NV = CS * NGR;
+            u32x4v ahi[GS], alo[GS];
+            auto read = [&](auto v_, u32x4v (&f)[GS], auto plane_) __attribute__((always_inline)) {
+                constexpr int v = decltype(v_)::value, s = v / NGR, i0 = (v % NGR) * GS, n = NL - i0 < GS ? NL - i0 : GS;
+#pragma unroll
+                for (int i = 0; i < n; ++i) f[i] = ab[((2 * s + decltype(plane_)::value) * TPP + i0 + i) * 64];
+            };
+            using I0 = std::integral_constant<int, 0>;
+            using I1 = std::integral_constant<int, 1>;
+            read(I0{}, alo, I1{}); read(I0{}, ahi, I0{});
+            static_for<0, NV>([&](auto v_) {
+                constexpr int v = decltype(v_)::value, ks = c * CS + v / NGR, i0 = (v % NGR) * GS, n = NL - i0 < GS ? NL - i0 : GS;
+                const bf16x8 bh = __builtin_bit_cast(bf16x8, bhi[ks]), bw = __builtin_bit_cast(bf16x8, blo[ks]);
+                __builtin_amdgcn_sched_barrier(0);
+                static_for<0, n>([&](auto i_) {
+                    constexpr int i = decltype(i_)::value;
+                    acc[i0 + i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, alo[i]), bh, acc[i0 + i], 0, 0, 0);
+                });
+                __builtin_amdgcn_sched_barrier(0);
+                if constexpr (v + 1 < NV) read(std::integral_constant<int, v + 1>{}, alo, I1{});
+                static_for<0, n>([&](auto i_) {
+                    constexpr int i = decltype(i_)::value;
+                    acc[i0 + i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, ahi[i]), bw, acc[i0 + i], 0, 0, 0);
+                });
+                static_for<0, n>([&](auto i_) {
+                    constexpr int i = decltype(i_)::value;
+                    acc[i0 + i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, ahi[i]), bh, acc[i0 + i], 0, 0, 0);
+                });
+                __builtin_amdgcn_sched_barrier(0);
+                if constexpr (v + 1 < NV) read(std::integral_constant<int, v + 1>{}, ahi, I0{});
+            });
+        });
+        __syncthreads();                                          // (everybody is done with the ring before the exchange tiles reuse zb / the next step's DMA)
+        // ---- partial tiles -> the cluster's exchange [gate][row tile of the part][column tile] (row-major 16 x 16, one
+        // write-through 16-byte store per lane)
+#pragma unroll
+        for (int i = 0; i < NL; ++i) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) zb[(lq * 4 + r) * ZS + l15] = acc[i][r];
+            __builtin_amdgcn_wave_barrier();
+            const f32x4 row = *reinterpret_cast<const f32x4*>(zb + (lane >> 2) * ZS + (lane & 3) * 4);
+            __builtin_amdgcn_wave_barrier();
+            bstore16_sc1(rsEx, __builtin_bit_cast(u32x4v, row), (int)(((exc + (size_t)gate * nslots + (size_t)i * NC + pwave) * 256 + lane * 4) * 4), 0);
+        }
+    };
+
+    int nl = live_tiles(T - 1);
+    load_step(T - 1, nl);
+    unsigned arrival = 0, carrival = 0;                        // grid-wide hand-offs so far; exchanges of this cluster so far
+    for (int t = T - 1; t >= 0; --t) {
+        float dh[PS];
+#pragma unroll
+        for (int i = 0; i < PS; ++i) dh[i] = 0.0f;
+        const bool mul = t < T - 1 && nl > 0;                   // (uniform over the cluster: the four gate workgroups of a part agree)
+        if (t < T - 1) {
+            gs.wait_all(arrival, pwave, lane);
+            ++arrival;
+            if (mul) {
+                if constexpr (LIVE) {
+                    bool done = false;
+                    static_for<1, TPP + 1>([&](auto k_) {
+                        if (!done && nl == decltype(k_)::value) { product(k_, t); done = true; }
+                    });
+                } else {
+                    product(std::integral_constant<int, TPP>{}, t);
+                }
+                gs.arrive_one(ccount, tid);
+            }
+        }
+        // the rows' dropout stream ids, per step and under the exchange's wait rather than in registers for the whole launch
+        uint32_t vid[PS], sid[PS];
+#pragma unroll
+        for (int i = 0; i < PS; ++i) {
+            const bool ok = g.keep < 1.0f && pok[i];
+            const int m_ = fresh(pm[i]);
+            vid[i] = ok ? (uint32_t)g.video_id[m_] : 0u;
+            sid[i] = ok ? (uint32_t)g.sample_id[m_] : 0u;
+        }
+        if (mul) {
+            gs.wait_one(ccount, 4u * (carrival + 1u), pwave, lane);
+            ++carrival;
+#pragma unroll
+            for (int i = 0; i < PS; ++i) {
+                float s_ = 0.0f;
+                if (i < nl) {
+#pragma unroll
+                    for (int q = 0; q < 4; ++q)
+                        s_ += __uint_as_float(__hip_atomic_load((const gu32*)(g.ex + (exc + (size_t)q * nslots + slot_of(i)) * 256 + tid), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+                }
+                dh[i] = s_;
+            }
+        }
+        // ---- BasicLSTMCell backward pointwise (the expressions of lstm_bwd_pointwise_kernel), one (row, unit) per thread and slot
+        float dzv[PS][4];
+#pragma unroll
+        for (int i = 0; i < PS; ++i) {
+            float d = dx[i];
+            if (g.keep < 1.0f && g.dext && t >= g.dext_t0)
+                d = (d / g.keep) * dropout_keep01(g.seed_lo, g.seed_hi, vid[i], sid[i], g.drop_code0 + (uint32_t)t, (uint32_t)pu_of(i), g.keep);
+            const float dht = dh[i] + d;
+            const float si = sg[i][0], tj = sg[i][1], sf = sg[i][2], so = sg[i][3];
+            const float tc = dm_tanhf(cnew[i]);
+            const float dc = dht * so * (1.f - tc * tc) + dc_reg[i];
+            dzv[i][0] = dc * tj * si * (1.f - si);
+            dzv[i][1] = dc * si * (1.f - tj * tj);
+            dzv[i][2] = dc * cprev[i] * sf * (1.f - sf);
+            dzv[i][3] = dht * tc * so * (1.f - so);
+            if (i < nl) dc_reg[i] = dc * sf;                     // (a tile that has not joined yet keeps dc = 0: its operands above are zeros)
+            if constexpr (!LIVE) cnew[i] = cprev[i];             // c_{t-1} is the next step's c_t
+        }
+        if (t > 0) {
+            // ---- dz_t -> the four gate images of the other parity, split, regrouped through LDS so that every thread writes ONE 16-byte
+            // fragment slot: thread (gate q = tid / 64, slot L = tid % 64) takes plane L / 32 (hi, lo), row L % 16, units 8 ((L / 16) & 1) + e
+            const size_t inext = (size_t)(t & 1) * 4 * img_floats;
+#pragma unroll
+            for (int i = 0; i < PS; ++i) {
+                if (!(i < nl)) continue;                         // (uniform over the workgroup)
+                __syncthreads();
+#pragma unroll
+                for (int q = 0; q < 4; ++q) dzl[(q * 16 + pr) * 17 + pn] = pok[i] ? dzv[i][q] : 0.0f;
+                __syncthreads();
+                const int q = tid >> 6, L = tid & 63, r = L & 15, k8 = (L >> 4) & 1, plane = L >> 5;
+                const float* zr = dzl + (q * 16 + r) * 17 + 8 * k8;
+                uint32_t h[4], l[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) split2(zr[2 * e], zr[2 * e + 1], h[e], l[e]);
+                const u32x4v wh = {h[0], h[1], h[2], h[3]}, wl = {l[0], l[1], l[2], l[3]};
+                const int kg = jj * NC + pc[i];                  // 16-unit group of the image's k: half (kg & 1) of k-step kg / 2
+                const size_t dst = inext + (size_t)q * img_floats +
+                                   ((size_t)((tile0 + ptile[i] * TS) * NG + (kg & ~1) + plane) * 64 + ((kg & 1) * 2 + k8) * 16 + r) * 4;
+                bstore16_sc1(rsImg, plane ? wl : wh, (int)(dst * 4), 0);
+            }
+            gs.arrive(tid);
+        }
+        // ---- history: dZ[t] (read by the weight-gradient contractions after the launch), then the next step's operands
+#pragma unroll
+        for (int i = 0; i < PS; ++i) {
+            if (!pok[i] || !(i < nl)) continue;
+            float* zp = g.dZ + (size_t)t * g.dz_tstride + (size_t)fresh(pm[i]) * 4 * H + pu_of(i);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) zp[(size_t)q * H] = dzv[i][q];
+        }
+        if (t > 0) {
+            nl = live_tiles(t - 1);
+            load_step(t - 1, nl);
+        }
+    }
+}
+
 // ---- backward recurrence: configurations, eligibility, launcher
 typedef void (*BwdFn)(const BwdChainArgs);
-struct BwdCfg { int ng, tmw, nc; BwdFn fn; const char* name; BwdFn fn_live; const char* name_live; };     // fn_live: the live-row variant of the register-weights form
+struct BwdCfg {
+    int ng, tmw, nc; BwdFn fn; const char* name;
+    BwdFn fn_live; const char* name_live;            // the live-row variant of the register-weights form
+    BwdFn fn_split, fn_split_live;                   // ... and both on split-bf16 operands (the same profiler rows: one of the two runs per shape and mode)
+};
 const BwdCfg kBwd[] = {
     {8, 1, 1, lstm_bwd_chain_kernel<8, 1, 1>, "bchain(ng8,m64)"},     {8, 2, 1, lstm_bwd_chain_kernel<8, 2, 1>, "bchain(ng8,m128)"},
     {8, 4, 1, lstm_bwd_chain_kernel<8, 4, 1>, "bchain(ng8,m256)"},    {64, 1, 1, lstm_bwd_chain_kernel<64, 1, 1>, "bchain(ng64,m64)"},
@@ -767,8 +1080,10 @@ const BwdCfg kBwd[] = {
     // 32 units x half the row tiles per workgroup (tmw = row tiles per wave of a part): 257 .. 384 rows
     {64, 3, 2, lstm_bwd_chain_kernel<64, 3, 2>, "bchain2(ng64,m384)"},
     // weights in registers, 64 units x a gate x a quarter of the row tiles per workgroup (tmw = row tiles per part)
-    {64, 5, 4, lstm_bwd_chain4_kernel<64, 5>, "bchain4(ng64,m320)", lstm_bwd_chain4_live_kernel<64, 5>, "bchain4(ng64,m320)[live]"},
-    {64, 6, 4, lstm_bwd_chain4_kernel<64, 6>, "bchain4(ng64,m384)", lstm_bwd_chain4_live_kernel<64, 6>, "bchain4(ng64,m384)[live]"},
+    {64, 5, 4, lstm_bwd_chain4_kernel<64, 5>, "bchain4(ng64,m320)", lstm_bwd_chain4_live_kernel<64, 5>, "bchain4(ng64,m320)[live]",
+     lstm_bwd_chain4_split_kernel<64, 5, false>, lstm_bwd_chain4_split_kernel<64, 5, true>},
+    {64, 6, 4, lstm_bwd_chain4_kernel<64, 6>, "bchain4(ng64,m384)", lstm_bwd_chain4_live_kernel<64, 6>, "bchain4(ng64,m384)[live]",
+     lstm_bwd_chain4_split_kernel<64, 6, false>, lstm_bwd_chain4_split_kernel<64, 6, true>},
 };
 constexpr int kNumBwd = (int)(sizeof(kBwd) / sizeof(kBwd[0]));
 int bwd_lds_bytes(const BwdCfg& c)
@@ -797,7 +1112,7 @@ int bwd_cfg(int M, int H)
         if (kBwd[i].ng == ng && kBwd[i].tmw == tmw && kBwd[i].nc == nc) return i;
     return -1;
 }
-struct BwdDev { std::once_flag once; bool ok = false; int per_cu[kNumBwd] = {}; };
+struct BwdDev { std::once_flag once; bool ok = false; int per_cu[kNumBwd] = {}; int per_cu_split[kNumBwd] = {}; };
 constexpr int kMaxDev = 32;
 BwdDev g_bdev[kMaxDev];
 BwdDev* bwd_dev_state()
@@ -812,9 +1127,17 @@ BwdDev* bwd_dev_state()
             ok = hipFuncSetAttribute(reinterpret_cast<const void*>(c.fn), hipFuncAttributeMaxDynamicSharedMemorySize, bwd_lds_bytes(c)) == hipSuccess;
             if (ok && c.fn_live)
                 ok = hipFuncSetAttribute(reinterpret_cast<const void*>(c.fn_live), hipFuncAttributeMaxDynamicSharedMemorySize, bwd_lds_bytes(c)) == hipSuccess;
+            for (BwdFn f : {c.fn_split, c.fn_split_live})
+                if (ok && f) ok = hipFuncSetAttribute(reinterpret_cast<const void*>(f), hipFuncAttributeMaxDynamicSharedMemorySize, bwd_lds_bytes(c)) == hipSuccess;
             int n = 0;
             if (ok && hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, reinterpret_cast<const void*>(c.fn), 256, bwd_lds_bytes(c)) == hipSuccess)
                 d.per_cu[i] = n;
+            // (the split forms: the smaller of the dense and the live-row kernel's, which takes more registers -- both are one wave per SIMD by
+            //  attribute today, so the two agree)
+            int nd = 0, nv = 0;
+            if (ok && c.fn_split && hipOccupancyMaxActiveBlocksPerMultiprocessor(&nd, reinterpret_cast<const void*>(c.fn_split), 256, bwd_lds_bytes(c)) == hipSuccess &&
+                hipOccupancyMaxActiveBlocksPerMultiprocessor(&nv, reinterpret_cast<const void*>(c.fn_split_live), 256, bwd_lds_bytes(c)) == hipSuccess)
+                d.per_cu_split[i] = nd < nv ? nd : nv;
         }
         d.ok = ok;
     });
@@ -838,6 +1161,17 @@ bool bwd_chain_eligible(int M, int H)
     if (ci < 0) return false;
     const int nc = kBwd[ci].nc, ncg = (H + 16 * nc - 1) / (16 * nc);
     return (long)b->per_cu[ci] * d->num_cus >= 4L * nc * ncg;   // every ACTIVE workgroup fits on the chip at once
+}
+
+// the split-bf16 form of the recurrence serves the shape: the register-weights form does (above 256 rows), and its split kernels fit the chip
+bool bwd_chain_split_serves(int M, int H)
+{
+    if (!bwd_chain_eligible(M, H) || !bwd_four_parts(M, H)) return false;
+    const int ci = bwd_cfg(M, H);
+    BwdDev* b = bwd_dev_state();
+    ChainHost hst;
+    if (ci < 0 || !kBwd[ci].fn_split || !b || !chain_host(&hst)) return false;
+    return (long)b->per_cu_split[ci] * hst.num_cus >= 4L * kBwd[ci].nc * ((H + 16 * kBwd[ci].nc - 1) / (16 * kBwd[ci].nc));
 }
 
 bool bwd_chain_live_capable(int M, int H)
@@ -903,6 +1237,8 @@ hipError_t launch_lstm_bwd_chain(const BwdChainLaunch& a, hipStream_t st)
     k.video_id = a.video_id; k.sample_id = a.sample_id;
     k.img = a.img; k.ex = a.ex; k.sync = a.sync;
     const bool live = a.perm && a.nlive && c.fn_live;
+    if (a.split && !bwd_chain_split_serves(a.M, a.H)) return hipErrorInvalidValue;
+    const BwdFn fn = a.split ? (live ? c.fn_split_live : c.fn_split) : (live ? c.fn_live : c.fn);
     if (live) { k.perm = a.perm; k.nlive = a.nlive; }
     k.status = hst.status_dev; k.fault = hst.fault; k.spin_limit = hst.spin_limit;
     int nc_, tmw_, tpp_, ncg_;
@@ -931,7 +1267,7 @@ hipError_t launch_lstm_bwd_chain(const BwdChainLaunch& a, hipStream_t st)
         if (pe != hipSuccess) return pe;
         (void)hipEventRecord(e0, st);
     }
-    hipLaunchKernelGGL(live ? c.fn_live : c.fn, grid, dim3(256), bwd_lds_bytes(c), st, k);
+    hipLaunchKernelGGL(fn, grid, dim3(256), bwd_lds_bytes(c), st, k);
     if (prof) {
         (void)hipEventRecord(e1, st);
         prof_record(6, pci, live ? c.name_live : c.name, live ? 0.0 : flops, e0, e1);     // (live rows: the executed count lives on the device -- no rate is claimed)

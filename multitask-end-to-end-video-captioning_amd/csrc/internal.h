@@ -166,8 +166,10 @@ struct BwdChainLaunch {
     const int32_t* video_id; const int32_t* sample_id;
     float* img; float* ex; unsigned* sync;             // scratch, sizes from bwd_chain_scratch (16-byte aligned)
     const int32_t* perm; const int32_t* nlive;         // optional, as ChainArgs: step t runs virtual rows 0 .. nlive[t]-1 only (their dZ rows are the only ones written)
+    bool split;                                        // dz @ Whh^T as three bf16 products on split operands (only where bwd_chain_split_serves)
 };
 bool bwd_chain_eligible(int M, int H);               // the shape fits the persistent form on this device
+bool bwd_chain_split_serves(int M, int H);           // ... in its register-weights form (above 256 rows), which has split-bf16 kernels
 bool bwd_chain_auto(int M, int H);                   // ... and it is the faster form there (chosen when the caller does not say)
 void bwd_chain_scratch(int H, int M, size_t* img_floats, size_t* ex_floats, size_t* sync_bytes);
 hipError_t launch_lstm_bwd_chain(const BwdChainLaunch& a, hipStream_t st);

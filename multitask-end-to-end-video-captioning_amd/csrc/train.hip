@@ -273,7 +273,7 @@ struct BwdScratch { float* slab; float* dc; float* bimg; float* bex; unsigned* b
 hipError_t lstm_recurrence_bwd(const float* W, int kw0, const float* gates, const float* C, const float* dext, size_t dext_tstride,
                                int ld_ext, int dext_t0, float* dZ, int M, int H, int T, float keep, uint64_t seed, uint32_t drop_code0,
                                const int32_t* video_id, const int32_t* sample_id, const BwdScratch& sc, int persistent, hipStream_t st,
-                               const int32_t* perm = nullptr, const int32_t* nlive = nullptr)
+                               const int32_t* perm = nullptr, const int32_t* nlive = nullptr, bool split = false)
 {
     const size_t MH = (size_t)M * H;
     const bool can = sc.bimg && sc.bex && sc.bsync && bwd_chain_eligible(M, H) && !(reinterpret_cast<uintptr_t>(W) & 15);
@@ -288,6 +288,7 @@ hipError_t lstm_recurrence_bwd(const float* W, int kw0, const float* gates, cons
         a.video_id = video_id; a.sample_id = sample_id;
         a.img = sc.bimg; a.ex = sc.bex; a.sync = sc.bsync;
         a.perm = perm; a.nlive = nlive;
+        a.split = split && bwd_chain_split_serves(M, H);      // (the other persistent forms have no split kernels: fp32 there)
         return launch_lstm_bwd_chain(a, st);
     }
     const SlabPlan sp = slab_plan(M, H);
@@ -515,10 +516,10 @@ size_t s2vt_lstm_recurrence_bwd_scratch_bytes(int32_t M, int32_t H)
     return c.off;
 }
 
-int s2vt_lstm_recurrence_bwd(const float* W, int32_t kw0, const float* gates, const float* C_hist, const float* dext, int64_t dext_tstride,
-                             int32_t ld_ext, int32_t dext_t0, float* dZ, int32_t M, int32_t H, int32_t T, float keep, uint64_t seed,
-                             const int32_t* video_id, const int32_t* sample_id, uint32_t drop_code0, int32_t persistent, void* scratch,
-                             size_t scratch_bytes, s2vt_stream stream)
+static int recurrence_bwd_entry(const float* W, int32_t kw0, const float* gates, const float* C_hist, const float* dext, int64_t dext_tstride,
+                               int32_t ld_ext, int32_t dext_t0, float* dZ, int32_t M, int32_t H, int32_t T, float keep, uint64_t seed,
+                               const int32_t* video_id, const int32_t* sample_id, uint32_t drop_code0, int32_t persistent, void* scratch,
+                               size_t scratch_bytes, s2vt_stream stream, bool split)
 {
     if (!W || !gates || !C_hist || !dZ || M <= 0 || H <= 0 || T < 0 || kw0 < 0 || persistent < -1 || persistent > 1 || !scratch) return S2VT_E_BADARG;
     if (dext && (ld_ext < H || dext_t0 < 0)) return S2VT_E_BADARG;
@@ -533,9 +534,28 @@ int s2vt_lstm_recurrence_bwd(const float* W, int32_t kw0, const float* gates, co
     sc.bimg = c.take<float>(imgf); sc.bex = c.take<float>(exf); sc.bsync = c.take<unsigned>(syncb / 4);
     if (!c.ok()) return S2VT_E_WORKSPACE;
     if (persistent == 1 && !bwd_chain_eligible(M, H)) return S2VT_E_BADARG;
+    if (split && (persistent != 1 || !bwd_chain_split_serves(M, H) || (reinterpret_cast<uintptr_t>(W) & 15))) return S2VT_E_BADARG;
     HIP_TRY(lstm_recurrence_bwd(W, kw0, gates, C_hist, dext, (size_t)dext_tstride, ld_ext, dext_t0, dZ, M, H, T, keep, seed, drop_code0, video_id,
-                                sample_id, sc, persistent, S(stream)));
+                                sample_id, sc, persistent, S(stream), nullptr, nullptr, split));
     return S2VT_OK;
+}
+
+int s2vt_lstm_recurrence_bwd(const float* W, int32_t kw0, const float* gates, const float* C_hist, const float* dext, int64_t dext_tstride,
+                             int32_t ld_ext, int32_t dext_t0, float* dZ, int32_t M, int32_t H, int32_t T, float keep, uint64_t seed,
+                             const int32_t* video_id, const int32_t* sample_id, uint32_t drop_code0, int32_t persistent, void* scratch,
+                             size_t scratch_bytes, s2vt_stream stream)
+{
+    return recurrence_bwd_entry(W, kw0, gates, C_hist, dext, dext_tstride, ld_ext, dext_t0, dZ, M, H, T, keep, seed, video_id, sample_id, drop_code0,
+                                persistent, scratch, scratch_bytes, stream, false);
+}
+
+int s2vt_lstm_recurrence_bwd_split(const float* W, int32_t kw0, const float* gates, const float* C_hist, const float* dext, int64_t dext_tstride,
+                                   int32_t ld_ext, int32_t dext_t0, float* dZ, int32_t M, int32_t H, int32_t T, float keep, uint64_t seed,
+                                   const int32_t* video_id, const int32_t* sample_id, uint32_t drop_code0, int32_t persistent, void* scratch,
+                                   size_t scratch_bytes, s2vt_stream stream)
+{
+    return recurrence_bwd_entry(W, kw0, gates, C_hist, dext, dext_tstride, ld_ext, dext_t0, dZ, M, H, T, keep, seed, video_id, sample_id, drop_code0,
+                                persistent, scratch, scratch_bytes, stream, true);
 }
 
 size_t s2vt_train_workspace_bytes(const s2vt_dims* d, int32_t B, int32_t N)
@@ -543,6 +563,18 @@ size_t s2vt_train_workspace_bytes(const s2vt_dims* d, int32_t B, int32_t N)
     if (!dims_ok_res(d) || B <= 0 || N <= 0 || N % B) return 0;      // (the residual model's unroll needs no region of its own)
     Carver c(nullptr, 0);
     return carve_train(c, d, B, N, nullptr);
+}
+
+int s2vt_train_workspace_dz2(const s2vt_dims* d, int32_t B, int32_t N, size_t* offset, size_t* floats)
+{
+    if (!dims_ok_res(d) || B <= 0 || N <= 0 || N % B || !offset || !floats) return S2VT_E_BADARG;
+    alignas(256) static char origin[256];                             // (a base to measure from: nothing is read or written through it)
+    Carver c(origin, 0);
+    TrainWs w;
+    carve_train(c, d, B, N, &w);
+    *offset = (size_t)(reinterpret_cast<const char*>(w.dZ2) - origin);
+    *floats = (size_t)(d->n_video_lstm_step + d->n_caption_lstm_step) * N * 4 * d->lstm_dim;
+    return S2VT_OK;
 }
 
 int s2vt_teacher_forced_fwd(const s2vt_dims* d, const s2vt_params* p, const float* video, int32_t B, int32_t N,
@@ -821,6 +853,13 @@ static int split_grad_mode(int N)
 {
     static const int on = [] { const char* e = getenv("S2VT_SPLIT_GRADS"); return e ? atoi(e) : 1; }();
     return on && N > 256 ? kGradSplit : kGradFp32;
+}
+// ... and LSTM2's backward recurrence with them, where its register-weights form serves the shape (bwd_chain_split_serves: above 256 rows).
+// S2VT_BCHAIN_SPLIT=0 (dev knob, read once): the fp32 recurrence beside the split products.
+static bool split_recurrence()
+{
+    static const bool on = [] { const char* e = getenv("S2VT_BCHAIN_SPLIT"); return !(e && e[0] == '0'); }();
+    return on;
 }
 
 // Phases of the backward (the ABI's `phase`, 0 to 4), for data-parallel callers that start a slice's all-reduce as soon as its gradients
@@ -1152,7 +1191,7 @@ static int bptt_bwd_body(const s2vt_dims* d, const s2vt_params* p, const s2vt_pa
         if (live_rows && Tc <= 128 && N <= 1024) HIP_TRY(launch_row_order(live_rows, n_live, N, Tv, Tc, w.perm, w.nlive, st));
         if (dwout_deferred) chain_gate_arm(&gate);
         const hipError_t re = lstm_recurrence_bwd(p->lstm2_W, H + E, w.G2, w.C2, w.dO2, NH, H, Tv, w.dZ2, N, H, T, keep, seed, 512u, video_id, sample_id, sc, -1, st,
-                                                  rec_live ? w.perm : nullptr, rec_live ? w.nlive : nullptr);
+                                                  rec_live ? w.perm : nullptr, rec_live ? w.nlive : nullptr, split && split_recurrence());
         chain_gate_arm(nullptr);
         HIP_TRY(re);
         if (dwout_deferred) {

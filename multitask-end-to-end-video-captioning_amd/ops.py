@@ -164,10 +164,13 @@ def lstm_recurrence_fwd(W, kw0, b, h0, c0, T, cinit=None, cinit_steps=0, keep=1.
 
 
 def lstm_recurrence_bwd(W, kw0, gates, C_hist, dext=None, dext_t0=0, keep=1.0, seed=0, video_id=None, sample_id=None, drop_code0=0,
-                        persistent=-1):
+                        persistent=-1, precision="fp32"):
     """Back-propagation through lstm_recurrence_fwd's unroll: returns dZ [T, M, 4H].  gates [T, M, 4H] activated, C_hist
     [T+1, M, H], dext [T - dext_t0, M, H] = gradient w.r.t. the (dropped) outputs of steps dext_t0 .. T-1 or None.
-    persistent: 1 = the one-launch form, 0 = per-step launches, -1 = auto."""
+    persistent: 1 = the one-launch form, 0 = per-step launches, -1 = auto.
+    precision: "fp32", or "split" = dz @ Whh^T as three bf16 products on split operands (persistent = 1 above 256 rows only:
+    S2VT_E_BADARG elsewhere)."""
+    assert precision in ("fp32", "split")
     _chk_f32(W, gates, C_hist, dext)
     T, M, H4 = gates.shape
     H = H4 // 4
@@ -177,9 +180,9 @@ def lstm_recurrence_bwd(W, kw0, gates, C_hist, dext=None, dext_t0=0, keep=1.0, s
     dZ = torch.empty((T, M, 4 * H), dtype=torch.float32, device=W.device)
     nb = lib().s2vt_lstm_recurrence_bwd_scratch_bytes(M, H)
     ws = workspace(nb, W.device, "bchain")
-    check(lib().s2vt_lstm_recurrence_bwd(_ptr(W), kw0, _ptr(gates), _ptr(C_hist), _ptr(dext), M * H, H, dext_t0, _ptr(dZ), M, H, T, float(keep),
-                                         seed, _ptr(video_id), _ptr(sample_id), drop_code0, persistent, _ptr(ws), ws.numel(), _stream()),
-          "s2vt_lstm_recurrence_bwd")
+    name = "s2vt_lstm_recurrence_bwd_split" if precision == "split" else "s2vt_lstm_recurrence_bwd"
+    check(getattr(lib(), name)(_ptr(W), kw0, _ptr(gates), _ptr(C_hist), _ptr(dext), M * H, H, dext_t0, _ptr(dZ), M, H, T, float(keep),
+                               seed, _ptr(video_id), _ptr(sample_id), drop_code0, persistent, _ptr(ws), ws.numel(), _stream()), name)
     return dZ
 
 
@@ -403,6 +406,13 @@ def softmax_nll_fwd_bwd_split(logits, target, coef, smoothing, dims: Dims, B: in
     if rc != 1:
         check(rc, "s2vt_softmax_nll_fwd_bwd_split")
     return nll, lp, rc == 0
+
+
+def train_workspace_dz2(dims: Dims, B: int, N: int, ws):
+    """View [T, N, 4H] of LSTM2's pre-activation gradients in the training workspace `ws` after LSTM2's phase of bptt_bwd."""
+    off, n = C.c_size_t(), C.c_size_t()
+    check(lib().s2vt_train_workspace_dz2(C.byref(dims), B, N, C.byref(off), C.byref(n)), "s2vt_train_workspace_dz2")
+    return ws[off.value:off.value + 4 * n.value].view(torch.float32).view(-1, N, 4 * dims.lstm_dim)
 
 
 def split_grad_dlogits_planes(dims: Dims, B: int, N: int, R: int, device):

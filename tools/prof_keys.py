@@ -35,6 +35,10 @@ def prof_key(kname):
     if m:
         ng, tpp = [int(x) for x in m.groups()]
         return f"6:bchain4(ng{ng},m{tpp * 64})[live]"
+    m = re.search(r"lstm_bwd_chain4_split_kernel<(\d+), (\d+), (true|false)>", kname)
+    if m:                                                   # the split-bf16 form of bchain4: the same profiler rows (one of the two runs per shape and mode)
+        ng, tpp = int(m.group(1)), int(m.group(2))
+        return f"6:bchain4(ng{ng},m{tpp * 64})" + ("[live]" if m.group(3) == "true" else "")
     m = re.search(r"lstm_chain4_kernel<(\d+), (\d+)>", kname)
     if m:
         ng, tpp = [int(x) for x in m.groups()]
