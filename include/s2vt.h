@@ -798,6 +798,65 @@ int s2vt_lstm_recurrence_fwd(const float* W, int32_t kw0, const float* b, const 
                              int32_t cinit_steps, float* C_hist, float* H_hist, float* gates, float* out, int32_t M, int32_t H,
                              int32_t T, float keep, uint64_t seed, const int32_t* video_id, const int32_t* sample_id,
                              uint32_t drop_code0, int32_t persistent, void* scratch, size_t scratch_bytes, s2vt_stream stream);
+/* ---- two such recurrences on the same rows behind one call: LSTM1 of the bidirectional captioner (bidirection_tf_s2vt.py:113-121,
+ * static_bidirectional_rnn over the frames and the zero padding; the cell has no DropoutWrapper).  Each direction is described in
+ * CHAIN-STEP order: step t = 0 .. T-1 reads slot t of its C_hist / H_hist ([T+1, M, H], slot 0 = the initial state), writes slot
+ * t + 1 and gates[t] ([T, M, 4H] activated, or NULL; gates == cinit is refused: the window moves, the gates must not overwrite it).  Its carried partial covers the window of steps
+ * [cinit_t0, cinit_t0 + cinit_steps): step t continues from cinit + (t - cinit_t0) * cinit_tstride (rows ldcinit apart); cinit_tstride
+ * may be negative.  The forward direction takes the hoisted frame products as a prefix (t0 = 0, steps = Tv); the backward direction
+ * consumes time T-1 .. 0, so its slot k + 1 is the state after time T-1-k and the frame products are a suffix read backwards
+ * (t0 = Tc, steps = Tv, cinit = the product of frame Tv-1, cinit_tstride = -(one frame's stride)).
+ * persistent = 1: ONE persistent launch advances both directions behind one grid hand-off per step -- a workgroup keeps the
+ * [H x 16] slices of both cells in LDS and a wave interleaves the two MFMA chains (M <= 64, H % 4 == 0, H <= 1024, H / 4 <= the
+ * CU count; S2VT_E_BADARG otherwise, S2VT_E_ALIGN when a W is not 16-byte aligned); 0: per-step launches of the fused cell kernel;
+ * -1: the one-launch form when the shape fits, else one s2vt_lstm_recurrence_fwd per direction (cut in two at cinit_t0, the first
+ * part's last slot being the second part's slot 0: nothing is copied); 2: that pair of persistent recurrences, asked for by name
+ * (S2VT_E_BADARG where s2vt_lstm_recurrence_fwd's persistent form does not serve the shape).  Every form gives the bits of two
+ * s2vt_lstm_recurrence_fwd calls.  scratch: s2vt_lstm_birecurrence_scratch_bytes(H) bytes, 256-byte aligned. */
+typedef struct s2vt_lstm_dir {
+    const float* W; int32_t kw0; const float* b;      /* the cell's matrix [kw0 + H, 4H] (its recurrent rows start at kw0) and bias [4H] */
+    const float* cinit; int64_t cinit_tstride; int32_t ldcinit; int32_t cinit_t0; int32_t cinit_steps;   /* carried partial; cinit NULL = none */
+    float* C_hist; float* H_hist; float* gates;
+} s2vt_lstm_dir;
+size_t s2vt_lstm_birecurrence_scratch_bytes(int32_t H);
+int s2vt_lstm_birecurrence_fwd(const s2vt_lstm_dir* fw, const s2vt_lstm_dir* bw, int32_t M, int32_t H, int32_t T, int32_t persistent,
+                               void* scratch, size_t scratch_bytes, s2vt_stream stream);
+/* ---- the bidirectional captioner (bidirection_tf_s2vt.py:48-216) as library calls on one caller-owned workspace.  LSTM1 is the pair of
+ * recurrences above over T = Tv + Tc steps (frames, then zero padding; no DropoutWrapper, no word ever enters it); LSTM2 reads
+ * [fw ; bw ; embed ; h2].  d: the usual dims (reserved = 0; label_dim unused).  Rows are time-major (row t * B + b).  lstm1_form: the
+ * `persistent` argument of s2vt_lstm_birecurrence_fwd (-1: the library's choice).  Argument errors return S2VT_E_BADARG, the size functions 0;
+ * both answer without a GPU.
+ * s2vt_bidir_teacher_forced_fwd: build_model's logits (:113-156) for caption [B, Tc] -> logits_out [Tc * B, V]; keep = LSTM2's DropoutWrapper
+ *   (Philox codes 512 + step, video_id / sample_id [B] needed when keep < 1); leaves in the workspace what the backward needs.
+ * s2vt_bidir_bptt_bwd: given dlogits [Tc * B, V] (s2vt_softmax_nll_fwd_bwd's output) ADDS the fp32 gradient products of all eleven
+ *   variables into `grads` (the caller zeroes them; Wemb's gradient is dense); same keep / seed / ids as the forward call on the same workspace.
+ * s2vt_bidir_decode_greedy: build_generator's arithmetic (:187-215) for B videos -> ids_out [B, Tc] (and, optionally, logits_out
+ *   [B, Tc, V]): LSTM1 and [fw ; bw] @ W2[:2H] once per video, LSTM2's Tv encode steps as one recurrence, then per decode step ONE fused cell
+ *   launch that continues from the hoisted partial with the fed word's Wemb rows gathered as an operand, and the pick launch.
+ *   unshifted_softmax != 0: the pick is argmax(exp(l) / sum exp(l)) as :211-212 write it (s2vt_softmax_unshifted_argmax), else argmax(l). */
+typedef struct s2vt_bidir_params {
+    float* Wemb;            /* [V, E] */
+    float* encode_image_W;  /* [D, E] */
+    float* encode_image_b;  /* [E] */
+    float* lstm1_fw_W;      /* [E + H, 4H]  s2vt/LSTM1/bidirectional_rnn/fw/basic_lstm_cell/weights (name recalled from TF 1.1) */
+    float* lstm1_fw_b;      /* [4H] */
+    float* lstm1_bw_W;      /* [E + H, 4H]  .../bw/... */
+    float* lstm1_bw_b;      /* [4H] */
+    float* lstm2_W;         /* [2H + E + H, 4H] rows [fw ; bw ; embed ; h2] */
+    float* lstm2_b;         /* [4H] */
+    float* embed_word_W;    /* [H, V] */
+    float* embed_word_b;    /* [V] */
+} s2vt_bidir_params;
+size_t s2vt_bidir_workspace_bytes(const s2vt_dims* d, int32_t B);
+int s2vt_bidir_teacher_forced_fwd(const s2vt_dims* d, const s2vt_bidir_params* p, const float* video, int32_t B, const int32_t* caption, float keep,
+                                  uint64_t seed, const int32_t* video_id, const int32_t* sample_id, int32_t lstm1_form, float* logits_out, void* workspace,
+                                  size_t workspace_bytes, s2vt_stream stream);
+int s2vt_bidir_bptt_bwd(const s2vt_dims* d, const s2vt_bidir_params* p, const s2vt_bidir_params* grads, const float* video, int32_t B,
+                        const float* dlogits, float keep, uint64_t seed, const int32_t* video_id, const int32_t* sample_id, void* workspace,
+                        size_t workspace_bytes, s2vt_stream stream);
+size_t s2vt_bidir_decode_workspace_bytes(const s2vt_dims* d, int32_t B);
+int s2vt_bidir_decode_greedy(const s2vt_dims* d, const s2vt_bidir_params* p, const float* video, int32_t B, int32_t unshifted_softmax, int32_t video_base,
+                             int32_t lstm1_form, int32_t* ids_out, float* logits_out, void* workspace, size_t workspace_bytes, s2vt_stream stream);
 /* ---- back-propagation through that recurrence (tf.gradients through the unroll, reinforcement_multisampling_tf_s2vt.py:650):
  * for t = T-1 .. 0:  dh = dext_t (through the DropoutWrapper mask, Philox code drop_code0 + t; dext_t = dext + (t - dext_t0) *
  * dext_tstride, rows ld_ext apart, for t >= dext_t0; dext NULL = none) + dZ[t+1] @ W[kw0 : kw0 + H, :]^T;  dZ[t] ([T, M, 4H],

@@ -54,6 +54,22 @@ class Operand(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class LstmDir(C.Structure):
+    """s2vt_lstm_dir: one direction of s2vt_lstm_birecurrence_fwd, in chain-step order."""
+    _fields_ = [("W", C.c_void_p), ("kw0", C.c_int32), ("b", C.c_void_p), ("cinit", C.c_void_p), ("cinit_tstride", C.c_int64),
+                ("ldcinit", C.c_int32), ("cinit_t0", C.c_int32), ("cinit_steps", C.c_int32), ("C_hist", C.c_void_p),
+                ("H_hist", C.c_void_p), ("gates", C.c_void_p)]
+
+
+BIDIR_PARAM_FIELDS = ("Wemb", "encode_image_W", "encode_image_b", "lstm1_fw_W", "lstm1_fw_b", "lstm1_bw_W", "lstm1_bw_b", "lstm2_W", "lstm2_b",
+                      "embed_word_W", "embed_word_b")
+
+
+class BidirParams(C.Structure):
+    """s2vt_bidir_params: the variables of bidirection_tf_s2vt.py:63-83 as device pointers."""
+    _fields_ = [(n, C.c_void_p) for n in BIDIR_PARAM_FIELDS]
+
+
 def lib_path() -> str:
     return os.environ.get("S2VT_LIB") or os.path.join(_HERE, "libs2vt_hip.so")   # S2VT_LIB: dev A/B builds only
 
@@ -61,6 +77,8 @@ def lib_path() -> str:
 _vp, _i32, _i64, _u32, _u64, _f32, _sz = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_uint64, C.c_float, C.c_size_t
 _DP, _PP, _OP = C.POINTER(Dims), C.POINTER(Params), C.POINTER(Operand)
 _AP = C.POINTER(AttnParams)
+_LD = C.POINTER(LstmDir)
+_BP = C.POINTER(BidirParams)
 
 # name -> (restype, argtypes); every symbol include/s2vt.h declares
 SIGNATURES = {
@@ -171,6 +189,13 @@ SIGNATURES = {
     "s2vt_lstm_recurrence_scratch_bytes": (_sz, [_i32]),
     "s2vt_lstm_recurrence_fwd": (C.c_int, [_vp, _i32, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _u64, _vp, _vp,
                                            _u32, _i32, _vp, _sz, _vp]),
+    "s2vt_lstm_birecurrence_scratch_bytes": (_sz, [_i32]),
+    "s2vt_lstm_birecurrence_fwd": (C.c_int, [_LD, _LD, _i32, _i32, _i32, _i32, _vp, _sz, _vp]),
+    "s2vt_bidir_workspace_bytes": (_sz, [_DP, _i32]),
+    "s2vt_bidir_teacher_forced_fwd": (C.c_int, [_DP, _BP, _vp, _i32, _vp, _f32, _u64, _vp, _vp, _i32, _vp, _vp, _sz, _vp]),
+    "s2vt_bidir_bptt_bwd": (C.c_int, [_DP, _BP, _BP, _vp, _i32, _vp, _f32, _u64, _vp, _vp, _vp, _sz, _vp]),
+    "s2vt_bidir_decode_workspace_bytes": (_sz, [_DP, _i32]),
+    "s2vt_bidir_decode_greedy": (C.c_int, [_DP, _BP, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
     "s2vt_lstm_recurrence_bwd_scratch_bytes": (_sz, [_i32, _i32]),
     "s2vt_lstm_recurrence_bwd": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _i32, _i32, _i32, _f32, _u64, _vp, _vp, _u32, _i32,
                                            _vp, _sz, _vp]),

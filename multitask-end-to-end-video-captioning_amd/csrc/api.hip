@@ -373,7 +373,7 @@ size_t carve_sample(Carver& c, const s2vt_dims* d, int B, int R, SampleWs* w)
     return c.off;
 }
 
-hipError_t lstm_recurrence(const float* W, int kw0, const float* bias, const float* cinit, size_t cinit_tstride, int ldcinit,
+hipError_t lstm_recurrence(const float* W, int kw0, const float* bias, const float* cinit, long long cinit_tstride, int ldcinit,
                            int cinit_steps, float* C, float* Hh, size_t state_tstride, float* gates, size_t gates_tstride,
                            float* out, size_t out_tstride, int M, int H, int T, float keep, const NoiseIds& ids,
                            uint32_t drop_code0, float* chain_abuf, unsigned* chain_sync, hipStream_t st, const int32_t* perm, const int32_t* nlive)
@@ -397,7 +397,7 @@ hipError_t lstm_recurrence(const float* W, int kw0, const float* bias, const flo
         hipError_t e = lstm_call(&s1, 1, W, bias, C + (size_t)t * state_tstride, 0, C + (size_t)(t + 1) * state_tstride,
                                  Hh + (size_t)(t + 1) * state_tstride, out ? out + (size_t)t * out_tstride : nullptr,
                                  gates ? gates + (size_t)t * gates_tstride : nullptr, M, H, keep, ids, drop_code0 + (uint32_t)t, -1, st,
-                                 (cinit && t < cinit_steps) ? cinit + (size_t)t * cinit_tstride : nullptr, ldcinit, 0);
+                                 (cinit && t < cinit_steps) ? cinit + (long long)t * cinit_tstride : nullptr, ldcinit, 0);
         if (e != hipSuccess) return e;
     }
     return hipSuccess;

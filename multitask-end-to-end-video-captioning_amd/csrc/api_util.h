@@ -221,7 +221,7 @@ struct SampleWs : SampleEnc {
 
 // One LSTM recurrence of T steps on M rows: ONE persistent launch when the shape fits (chain_eligible), else T
 // per-step launches of the fused cell kernel.  Histories: step t reads slot t of C / Hh and writes slot t + 1.
-hipError_t lstm_recurrence(const float* W, int kw0, const float* bias, const float* cinit, size_t cinit_tstride, int ldcinit,
+hipError_t lstm_recurrence(const float* W, int kw0, const float* bias, const float* cinit, long long cinit_tstride, int ldcinit,
                            int cinit_steps, float* C, float* Hh, size_t state_tstride, float* gates, size_t gates_tstride,
                            float* out, size_t out_tstride, int M, int H, int T, float keep, const NoiseIds& ids,
                            uint32_t drop_code0, float* chain_abuf, unsigned* chain_sync, hipStream_t st, const int32_t* perm = nullptr,

@@ -137,7 +137,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int m = (tb + i) * 16 + lq * 4 + r;
-                    ci[c][i][r] = (g.cinit && t < g.cinit_steps && tok[i] && m < M) ? g.cinit[(size_t)t * g.cinit_tstride + (size_t)m * g.ldcinit + ccol] : 0.0f;
+                    ci[c][i][r] = (g.cinit && t < g.cinit_steps && tok[i] && m < M) ? g.cinit[(long long)t * g.cinit_tstride + (long long)m * g.ldcinit + ccol] : 0.0f;
                 }
         }
     };
@@ -387,7 +387,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     auto load_cinit = [&](int t) __attribute__((always_inline)) {
         if (g.cinit && t < g.cinit_steps) {                       // (uniform)
             const __amdgpu_buffer_rsrc_t rsC =
-                __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(g.cinit + (size_t)t * g.cinit_tstride), 0, (int)0x80000000u, 0x00020000);
+                __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(g.cinit + (long long)t * g.cinit_tstride), 0, (int)0x80000000u, 0x00020000);
 #pragma unroll
             for (int i = 0; i < TPP; ++i)
 #pragma unroll
@@ -678,7 +678,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     auto load_cinit = [&](int t, int nl) __attribute__((always_inline)) {
         if (g.cinit && t < g.cinit_steps) {                       // (uniform)
             const __amdgpu_buffer_rsrc_t rsC =
-                __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(g.cinit + (size_t)t * g.cinit_tstride), 0, (int)0x80000000u, 0x00020000);
+                __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(g.cinit + (long long)t * g.cinit_tstride), 0, (int)0x80000000u, 0x00020000);
 #pragma unroll
             for (int i = 0; i < TPP; ++i)
 #pragma unroll

@@ -112,7 +112,7 @@ hipError_t launch_sgd(float* theta, const float* g, int64_t n, const float* sums
 struct ChainArgs {
     const float* W; int ldw; int kw0;                 // full cell matrix [*, 4H] (ldw floats per row); the recurrent rows start at kw0
     const float* bias;                                 // [4H]
-    const float* cinit; size_t cinit_tstride; int ldcinit; int cinit_steps;   // carried partial of step t < cinit_steps: cinit + t*tstride, rows ldcinit apart; NULL = none
+    const float* cinit; long long cinit_tstride; int ldcinit; int cinit_steps;   // carried partial of step t < cinit_steps: cinit + t*tstride (signed: a caller may walk its partials backwards), rows ldcinit apart; NULL = none
     const float* h0; const float* c0;                  // initial state [M, H] or NULL = zeros
     float* C; float* Hh; size_t state_tstride;         // state histories: step t writes slot t + 1 (C + (t+1)*state_tstride)
     float* gates; size_t gates_tstride;                // optional activated gates [T][M][4H] (si | tj | sf | so)

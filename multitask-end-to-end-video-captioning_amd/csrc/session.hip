@@ -282,7 +282,7 @@ int s2vt_lstm_recurrence_fwd(const float* W, int32_t kw0, const float* b, const 
     }
     NoiseIds ids{video_id, sample_id, seed};
     const size_t MH = (size_t)M * H;
-    HIP_TRY(lstm_recurrence(W, kw0, b, cinit, (size_t)cinit_tstride, ldcinit, cinit ? cinit_steps : 0, C_hist, H_hist, MH, gates, 4 * MH, out,
+    HIP_TRY(lstm_recurrence(W, kw0, b, cinit, (long long)cinit_tstride, ldcinit, cinit ? cinit_steps : 0, C_hist, H_hist, MH, gates, 4 * MH, out,
                             MH, M, H, T, keep, ids, drop_code0, abuf, sync, S(stream)));
     return S2VT_OK;
 }

@@ -163,6 +163,99 @@ def lstm_recurrence_fwd(W, kw0, b, h0, c0, T, cinit=None, cinit_steps=0, keep=1.
     return Ch, Hh, gates, out
 
 
+def lstm_dir(W, kw0, b, h0, c0, T, cinit=None, cinit_t0=0, reverse=False, want_gates=True) -> _lib.LstmDir:
+    """One direction of lstm_birecurrence_fwd, in chain-step order: histories [T+1, M, H] with slot 0 = (c0, h0); cinit
+    [steps, M, 4H] is the carried partial of chain steps cinit_t0 .. cinit_t0 + steps - 1, consumed last slice first if
+    `reverse` (the backward direction reads the frame products in descending time).  The tensors ride on the struct as
+    .C / .H / .gates."""
+    _chk_f32(W, b, h0, c0, cinit)
+    M, H = h0.shape
+    dev = W.device
+    Ch = torch.empty((T + 1, M, H), dtype=torch.float32, device=dev); Hh = torch.empty_like(Ch)
+    Ch[0].copy_(c0); Hh[0].copy_(h0)
+    gates = torch.empty((T, M, 4 * H), dtype=torch.float32, device=dev) if want_gates else None
+    d = _lib.LstmDir()
+    d.W, d.kw0, d.b = W.data_ptr(), int(kw0), b.data_ptr()
+    if cinit is not None:
+        assert cinit.dim() == 3 and cinit.shape[1] == M and cinit.stride(2) == 1
+        steps = cinit.shape[0]
+        d.cinit = cinit.data_ptr() + (4 * (steps - 1) * cinit.stride(0) if reverse else 0)
+        d.cinit_tstride = -cinit.stride(0) if reverse else cinit.stride(0)
+        d.ldcinit, d.cinit_t0, d.cinit_steps = cinit.stride(1), int(cinit_t0), steps
+    d.C_hist, d.H_hist, d.gates = Ch.data_ptr(), Hh.data_ptr(), None if gates is None else gates.data_ptr()
+    d.C, d.H, d.gates_t = Ch, Hh, gates
+    d._keep = (W, b, cinit)         # the struct holds raw pointers: keep the tensors alive with it
+    return d
+
+
+def lstm_birecurrence_fwd(fw: _lib.LstmDir, bw: _lib.LstmDir, persistent=-1):
+    """Both LSTM1 directions of the bidirectional captioner (s2vt_lstm_birecurrence_fwd): fills the histories of the two
+    lstm_dir() descriptions.  persistent: 1 = one persistent launch for both directions (M <= 64), 0 = per-step launches,
+    2 = one persistent recurrence per direction, -1 = the library's choice.  Every form gives the bits of two lstm_recurrence_fwd calls."""
+    T, M, H = fw.C.shape[0] - 1, fw.C.shape[1], fw.C.shape[2]
+    assert bw.C.shape == fw.C.shape
+    nb = lib().s2vt_lstm_birecurrence_scratch_bytes(H)
+    ws = workspace(nb, fw.C.device, "bichain")
+    check(lib().s2vt_lstm_birecurrence_fwd(C.byref(fw), C.byref(bw), M, H, T, persistent, _ptr(ws), ws.numel(), _stream()),
+          "s2vt_lstm_birecurrence_fwd")
+    return (fw.C, fw.H, fw.gates_t), (bw.C, bw.H, bw.gates_t)
+
+
+def make_bidir_params(tensors: dict) -> _lib.BidirParams:
+    """tensors: name -> contiguous CUDA fp32 tensor for every name in _lib.BIDIR_PARAM_FIELDS (s2vt_bidir_params)."""
+    p = _lib.BidirParams()
+    for n in _lib.BIDIR_PARAM_FIELDS:
+        t = tensors[n]
+        _chk_f32(t)
+        assert t.is_contiguous()
+        setattr(p, n, t.data_ptr())
+    p._keep = tensors
+    return p
+
+
+def bidir_workspace(dims: Dims, B: int, device):
+    nb = lib().s2vt_bidir_workspace_bytes(C.byref(dims), B)
+    assert nb > 0
+    return torch.empty(nb, dtype=torch.uint8, device=device)
+
+
+def bidir_teacher_forced_fwd(dims: Dims, params, video, caption, ws, keep=1.0, seed=0, video_id=None, sample_id=None, lstm1_form=-1, out=None):
+    """build_model's logits of the bidirectional captioner, time-major [Tc * B, V] (s2vt_bidir_teacher_forced_fwd); ws keeps the state
+    bidir_bptt_bwd needs."""
+    _chk_f32(video)
+    B = video.shape[0]
+    assert video.is_contiguous() and caption.is_cuda and caption.dtype == torch.int32 and caption.is_contiguous()
+    if out is None:
+        out = torch.empty((dims.n_caption_lstm_step * B, dims.n_words), dtype=torch.float32, device=video.device)
+    check(lib().s2vt_bidir_teacher_forced_fwd(C.byref(dims), C.byref(params), _ptr(video), B, _ptr(caption), float(keep), seed, _ptr(video_id),
+                                              _ptr(sample_id), lstm1_form, _ptr(out), _ptr(ws), ws.numel(), _stream()), "s2vt_bidir_teacher_forced_fwd")
+    return out
+
+
+def bidir_bptt_bwd(dims: Dims, params, grads, video, dlogits, ws, keep=1.0, seed=0, video_id=None, sample_id=None):
+    """Adds the gradient products of all eleven variables into `grads` (a make_bidir_params of zeroed tensors)."""
+    _chk_f32(video, dlogits)
+    assert dlogits.is_contiguous()
+    check(lib().s2vt_bidir_bptt_bwd(C.byref(dims), C.byref(params), C.byref(grads), _ptr(video), video.shape[0], _ptr(dlogits), float(keep), seed,
+                                    _ptr(video_id), _ptr(sample_id), _ptr(ws), ws.numel(), _stream()), "s2vt_bidir_bptt_bwd")
+
+
+def bidir_decode_greedy(dims: Dims, params, video, unshifted_softmax=False, video_base=0, want_logits=False, lstm1_form=-1, ids=None, logits=None):
+    """Greedy decode of B videos (s2vt_bidir_decode_greedy): ids int32 [B, Tc] (and logits [B, Tc, V])."""
+    _chk_f32(video)
+    assert video.is_contiguous()
+    B = video.shape[0]
+    if ids is None:
+        ids = torch.empty((B, dims.n_caption_lstm_step), dtype=torch.int32, device=video.device)
+    if want_logits and logits is None:
+        logits = torch.empty((B, dims.n_caption_lstm_step, dims.n_words), dtype=torch.float32, device=video.device)
+    nb = lib().s2vt_bidir_decode_workspace_bytes(C.byref(dims), B)
+    ws = workspace(nb, video.device, "bidir_decode")
+    check(lib().s2vt_bidir_decode_greedy(C.byref(dims), C.byref(params), _ptr(video), B, int(bool(unshifted_softmax)), int(video_base), lstm1_form,
+                                         _ptr(ids), _ptr(logits), _ptr(ws), ws.numel(), _stream()), "s2vt_bidir_decode_greedy")
+    return (ids, logits) if want_logits else ids
+
+
 def lstm_recurrence_bwd(W, kw0, gates, C_hist, dext=None, dext_t0=0, keep=1.0, seed=0, video_id=None, sample_id=None, drop_code0=0,
                         persistent=-1, precision="fp32"):
     """Back-propagation through lstm_recurrence_fwd's unroll: returns dZ [T, M, 4H].  gates [T, M, 4H] activated, C_hist

@@ -441,6 +441,18 @@ def write_checkpoint_v1(path: str, variables: dict, compress=True):
 
 
 # ------------------------------------------------------------------------------------------------ entry point
+# Variable -> checkpoint name of bidirection_tf_s2vt.py's graph (bidirection.Video_Caption_Generator.save / restore).  The LSTM1 scopes are
+# those of tf.contrib.rnn.static_bidirectional_rnn under variable_scope("s2vt/LSTM1") (bidirection_tf_s2vt.py:114-117) with BasicLSTMCell's
+# `weights` / `biases`.  They are RECALLED from TF 1.1, which is not vendored here, and no checkpoint written by that script has been seen.
+BIDIRECTION_TF_NAMES = {
+    "Wemb": "Wemb", "encode_image_W": "encode_image_W", "encode_image_b": "encode_image_b",
+    "lstm1_fw_W": "s2vt/LSTM1/bidirectional_rnn/fw/basic_lstm_cell/weights", "lstm1_fw_b": "s2vt/LSTM1/bidirectional_rnn/fw/basic_lstm_cell/biases",
+    "lstm1_bw_W": "s2vt/LSTM1/bidirectional_rnn/bw/basic_lstm_cell/weights", "lstm1_bw_b": "s2vt/LSTM1/bidirectional_rnn/bw/basic_lstm_cell/biases",
+    "lstm2_W": "s2vt/LSTM2/basic_lstm_cell/weights", "lstm2_b": "s2vt/LSTM2/basic_lstm_cell/biases",
+    "embed_word_W": "embed_word_W", "embed_word_b": "embed_word_b",
+}
+
+
 def read_checkpoint(path: str) -> dict:
     """{variable name: ndarray} of a TensorFlow checkpoint given as the reference gives it to the Saver: a V2 prefix
     (`…/model-6` with `model-6.index` beside it) or a V1 file.  Also accepts this repository's own `.npz` dumps."""

@@ -6,6 +6,9 @@ Per step the reference runs sess.run([train_op, tf_loss]) on build_model (label-
 batch-mean rule, weight decay, clip 10, Adam, lr 1e-3 halved every 5000 steps); here that is
 Video_Caption_Generator.xe_update.  One process per GPU under torch.distributed.run for data parallel.
 
+--bidirectional trains the bidirectional captioner of bidirection_tf_s2vt.py by that script's rule (train_bidirectional: SGD, clip_by_norm 10 per
+variable, lr 0.01 halved every 10000 steps).
+
 --scheduled-sampling P trains as generate_words_tf_s2vt.py does instead (Video_Caption_Generator.scheduled_update): the unroll decodes and
 a per-row coin feeds the ground-truth word with probability P / 1.00001 (the script writes P = 0.5), or, with --ss-k K, with the inverse
 sigmoid schedule K / (K + exp(step / K)) of its commented line :134; --optimizer sgd is that script's GradientDescentOptimizer."""
@@ -113,6 +116,59 @@ def train(cfg: Config, train_corpus: Corpus, test_corpus: Corpus | None = None, 
     return model, history
 
 
+def train_bidirectional(cfg: Config, train_corpus: Corpus, model=None, log=print, resume=None):
+    """train() of bidirection_tf_s2vt.py (:336-428) on the bidirectional captioner (bidirection.Video_Caption_Generator): per step
+    sess.run([train_op, tf_loss]) there is xe_update here -- plain softmax cross-entropy x mask x loss_weight (20) / sum(mask) + weight decay,
+    GradientDescentOptimizer behind tf.clip_by_norm(grad, cfg.clip_norm) PER VARIABLE, lr = cfg.start_learning_rate * 0.5^(step // cfg.decay_steps)
+    (the script: 0.01, 10000) -- and a version-1 checkpoint `<model_name>-<epoch>` under the TF names per epoch.  One process, one GPU (the
+    script is; data parallel is not built for this model).  Returns (model, history)."""
+    import os
+    from . import bidirection
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise ValueError("--bidirectional trains in one process: data parallel is not built for the bidirectional captioner")
+    wordtoix, ixtoword = hostglue.preProBuildWordVocab(train_corpus.vocabulary)
+    B = cfg.batch_size
+    if model is None:
+        model = bidirection.Video_Caption_Generator(cfg.dim_image, len(wordtoix), cfg.word_dim, cfg.lstm_dim, B, cfg.n_video_lstm_step + cfg.n_caption_lstm_step,
+                                                    cfg.n_video_lstm_step, cfg.n_caption_lstm_step, bias_init_vector=None, seed=cfg.seed)
+    if resume:
+        model.restore(resume)
+        log(f"resumed: {resume} at step {model.global_step}")
+    model.global_step = getattr(model, "global_step", 0)
+    rng = random.Random(cfg.seed)
+    caps = train_corpus.captions
+    history = []
+    steplog = StepLog(cfg.step_log)
+    dev = model.device
+    for epoch in range(cfg.n_epochs):
+        losses = []
+        for it, idx in enumerate(epoch_batches(len(caps), B, rng)):
+            if cfg.max_steps_per_epoch and it >= cfg.max_steps_per_epoch:
+                break
+            t0 = time.time()
+            ind, mask = hostglue.sentence_padding_toix(caps[idx, 1].tolist(), wordtoix, cfg.n_caption_lstm_step)
+            feats = torch.as_tensor(np.asarray(train_corpus.features.batch(caps[idx, 0], pinned=False), np.float32)).to(dev)
+            lr = learning_rate(cfg, model.global_step)
+            step = model.global_step
+            loss = model.xe_update(feats, torch.as_tensor(np.asarray(ind, np.int32)).to(dev), torch.as_tensor(np.asarray(mask, np.float32)).to(dev),
+                                   lr=lr, clip_norm=cfg.clip_norm, seed=cfg.seed + 104729 * step)
+            if not np.isfinite(loss):
+                raise FloatingPointError(f"bidirectional captioner, step {step}: the loss is {loss}")
+            losses.append(loss)
+            secs = time.time() - t0
+            log(f"idx: {it * B} rate: {lr:g} Epoch: {epoch} loss: {loss:.5f} Elapsed time: {secs:.3f}")
+            steplog.write(kind="step", epoch=epoch, step=step + 1, lr=lr, loss=loss, seconds=secs)
+        os.makedirs(cfg.model_path, exist_ok=True)
+        ck = os.path.join(cfg.model_path, f"{cfg.model_name}-{epoch}")
+        model.save(ck, tf_version=1)                                  # :368, :426: Saver(write_version=1), global_step = epoch
+        entry = {"epoch": epoch, "loss": float(np.mean(losses)) if losses else None, "checkpoint": ck}
+        history.append(entry)
+        steplog.write(kind="epoch", bidirectional=True, **entry)
+        log(f"Epoch {epoch} is done: {entry}")
+    steplog.close()
+    return model, history
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--train-sents", required=True); ap.add_argument("--train-feats", required=True)
@@ -126,10 +182,21 @@ def main(argv=None):
                     "ground-truth word with probability P / 1.00001, the model's own argmax otherwise (the script writes 0.5)")
     ap.add_argument("--ss-k", type=float, metavar="K", help="with scheduled sampling: P = K / (K + exp(step / K)) (the script's k_value = 5000)")
     ap.add_argument("--residual", action="store_true", help="the residual captioner of residual_tf_s2vt.py: out1 + out2 into the vocabulary projection")
+    ap.add_argument("--bidirectional", action="store_true", help="the bidirectional captioner of bidirection_tf_s2vt.py with its own training rule: "
+                    "plain SGD, tf.clip_by_norm 10 per variable, lr 0.01 halved every 10000 steps, loss_weight 20, batch 32, d = 1024, Tv = 25 "
+                    "(train_bidirectional)")
     ap.add_argument("--optimizer", choices=("adam", "sgd"), default="adam", help="sgd: the scheduled-sampling script's GradientDescentOptimizer")
     a = ap.parse_args(argv)
     if a.ss_k is not None and a.scheduled_sampling is None:
         a.scheduled_sampling = 0.5
+    if a.bidirectional:
+        if a.scheduled_sampling is not None or a.residual or a.grad_precision or a.optimizer != "adam":
+            ap.error("--bidirectional has one training rule (the script's); it does not combine with --scheduled-sampling, --residual, --grad-precision or --optimizer")
+        # the script's "Train Parameters" (bidirection_tf_s2vt.py:233-252)
+        cfg = Config(dim_image=1024, n_video_lstm_step=25, n_caption_lstm_step=35, n_epochs=a.epochs, batch_size=a.batch_size, start_learning_rate=0.01,
+                     decay_steps=10000, clip_norm=10.0, model_path=a.model_path, model_name="bimodel")
+        train_bidirectional(cfg, Corpus(a.train_sents, a.train_feats, vocabulary_file=a.vocab), resume=a.resume)
+        return
     if a.optimizer != "adam" and a.scheduled_sampling is None:
         ap.error("--optimizer sgd is wired for --scheduled-sampling only")
     cfg = Config(n_epochs=a.epochs, batch_size=a.batch_size, model_path=a.model_path, model_name=f"batch_size{a.batch_size}_s2vt_model",
