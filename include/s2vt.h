@@ -857,6 +857,37 @@ int s2vt_bidir_bptt_bwd(const s2vt_dims* d, const s2vt_bidir_params* p, const s2
 size_t s2vt_bidir_decode_workspace_bytes(const s2vt_dims* d, int32_t B);
 int s2vt_bidir_decode_greedy(const s2vt_dims* d, const s2vt_bidir_params* p, const float* video, int32_t B, int32_t unshifted_softmax, int32_t video_base,
                              int32_t lstm1_form, int32_t* ids_out, float* logits_out, void* workspace, size_t workspace_bytes, s2vt_stream stream);
+/* ---- the self-critical REINFORCE stage on that model (reinforcement_multisampling_tf_s2vt.py:227-339 applied to it).  No word enters LSTM1,
+ * so both LSTM1 directions and [fw ; bw] @ W2[:2H] depend on the video only: the samples of a video share them.  Rows are SAMPLE-MAJOR (row
+ * s * B + j is sample s of video j; the video of row n is n % B) and `video` is always the B distinct blocks [B, Tv, D], never tiled.  Same
+ * conventions as above: caller-owned 256-byte-aligned workspace, S2VT_E_BADARG / S2VT_E_ALIGN / S2VT_E_WORKSPACE before any launch, size
+ * functions 0 on bad shapes (S >= 1, K >= 0, K + with_greedy >= 1, S * B * T within int).
+ * s2vt_bidir_sample: K multinomial captions per video -> sampled_out [K * B, Tc] and (with_greedy) the greedy one -> greedy_out [B, Tc], int32.
+ *   LSTM1, the hoisted partial and LSTM2's Tv encode steps run on B rows; the Tc decode steps on R = (K + with_greedy) * B rows, each the fused
+ *   cell launch of s2vt_bidir_decode_greedy continuing from the video's slice of the partial (row % B), then s2vt_vocab_pick: Gumbel-max over
+ *   Philox counters (video_base + j, s, step), the greedy block last with sample id -1 (s2vt_sample's convention).  No dropout, <bos> = 1 fed at
+ *   step 0, no host round trip.  K = 0 with greedy equals s2vt_bidir_decode_greedy(unshifted_softmax = 0).  A NULL output is legal where its
+ *   block does not exist (sampled_out at K = 0, greedy_out without with_greedy).
+ * s2vt_bidir_teacher_forced_fwd_rows: caption [S * B, Tc], video_id / sample_id [S * B] -> logits_out [Tc * S * B, V] (row t * N + n),
+ *   bit-identical to s2vt_bidir_teacher_forced_fwd on the S-times tiled block: LSTM1 and its input products on B rows, the 2H-row part of
+ *   LSTM2's partial on T * B rows and continued per row with the fed word's Wemb rows, LSTM2 / DropoutWrapper / vocabulary projection on S * B rows.
+ * s2vt_bidir_bptt_bwd_rows: the backward of that call on the same workspace, ADDING into `grads` as s2vt_bidir_bptt_bwd does.  LSTM2's
+ *   pre-activation gradients are summed over the samples of a video (ascending s, one owning thread per element, no atomics); lstm2_W's
+ *   two H-row blocks, lstm2_b, the gradient into [fw ; bw] and all of LSTM1 / encode_image_* run on T * B (B) rows from that sum. */
+size_t s2vt_bidir_sample_workspace_bytes(const s2vt_dims* d, int32_t B, int32_t K, int32_t with_greedy);
+int s2vt_bidir_sample(const s2vt_dims* d, const s2vt_bidir_params* p, const float* video, int32_t B, int32_t K, int32_t with_greedy, uint64_t seed,
+                      int32_t video_base, int32_t lstm1_form, int32_t* sampled_out, int32_t* greedy_out, void* workspace, size_t workspace_bytes,
+                      s2vt_stream stream);
+/* The sample sum on its own: out[(t * B + b) * C + c] = sum_s dz[((t * S + s) * B + b) * C + c], s ascending, no atomics (two runs give equal
+ * bits).  C % 4 == 0 and 16-byte aligned pointers (S2VT_E_ALIGN): the kernel moves 16 bytes per lane. */
+int s2vt_bidir_sample_sum(const float* dz, float* out, int32_t T, int32_t B, int32_t S, int32_t C, s2vt_stream stream);
+size_t s2vt_bidir_rows_workspace_bytes(const s2vt_dims* d, int32_t B, int32_t S);
+int s2vt_bidir_teacher_forced_fwd_rows(const s2vt_dims* d, const s2vt_bidir_params* p, const float* video, int32_t B, int32_t S, const int32_t* caption,
+                                       float keep, uint64_t seed, const int32_t* video_id, const int32_t* sample_id, int32_t lstm1_form, float* logits_out,
+                                       void* workspace, size_t workspace_bytes, s2vt_stream stream);
+int s2vt_bidir_bptt_bwd_rows(const s2vt_dims* d, const s2vt_bidir_params* p, const s2vt_bidir_params* grads, const float* video, int32_t B, int32_t S,
+                             const float* dlogits, float keep, uint64_t seed, const int32_t* video_id, const int32_t* sample_id, void* workspace,
+                             size_t workspace_bytes, s2vt_stream stream);
 /* ---- back-propagation through that recurrence (tf.gradients through the unroll, reinforcement_multisampling_tf_s2vt.py:650):
  * for t = T-1 .. 0:  dh = dext_t (through the DropoutWrapper mask, Philox code drop_code0 + t; dext_t = dext + (t - dext_t0) *
  * dext_tstride, rows ld_ext apart, for t >= dext_t0; dext NULL = none) + dZ[t+1] @ W[kw0 : kw0 + H, :]^T;  dZ[t] ([T, M, 4H],

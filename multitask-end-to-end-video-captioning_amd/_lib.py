@@ -196,6 +196,12 @@ SIGNATURES = {
     "s2vt_bidir_bptt_bwd": (C.c_int, [_DP, _BP, _BP, _vp, _i32, _vp, _f32, _u64, _vp, _vp, _vp, _sz, _vp]),
     "s2vt_bidir_decode_workspace_bytes": (_sz, [_DP, _i32]),
     "s2vt_bidir_decode_greedy": (C.c_int, [_DP, _BP, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "s2vt_bidir_sample_workspace_bytes": (_sz, [_DP, _i32, _i32, _i32]),
+    "s2vt_bidir_sample": (C.c_int, [_DP, _BP, _vp, _i32, _i32, _i32, _u64, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "s2vt_bidir_sample_sum": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp]),
+    "s2vt_bidir_rows_workspace_bytes": (_sz, [_DP, _i32, _i32]),
+    "s2vt_bidir_teacher_forced_fwd_rows": (C.c_int, [_DP, _BP, _vp, _i32, _i32, _vp, _f32, _u64, _vp, _vp, _i32, _vp, _vp, _sz, _vp]),
+    "s2vt_bidir_bptt_bwd_rows": (C.c_int, [_DP, _BP, _BP, _vp, _i32, _i32, _vp, _f32, _u64, _vp, _vp, _vp, _sz, _vp]),
     "s2vt_lstm_recurrence_bwd_scratch_bytes": (_sz, [_i32, _i32]),
     "s2vt_lstm_recurrence_bwd": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _i32, _i32, _i32, _f32, _u64, _vp, _vp, _u32, _i32,
                                            _vp, _sz, _vp]),

@@ -638,3 +638,284 @@ int s2vt_bidir_decode_greedy(const s2vt_dims* d, const s2vt_bidir_params* p, con
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The self-critical REINFORCE stage (reinforcement_multisampling_tf_s2vt.py:227-339 on this model).  No word ever enters LSTM1, so
+// both LSTM1 directions, their histories and [fw ; bw] @ W2[:2H] depend on the video only: the S sample rows of a video share them,
+// forward and backward.  Rows are sample-major (row s * B + j is sample s of video j, the video of row n is n % B) and the feature
+// block is never tiled.  What sees a per-sample operand (the fed word, LSTM2's state, its dropout noise, the logits) runs on
+// N = S * B rows; what only sees the video runs on B rows, and its gradient is the sum over the video's S rows (the sample sum).
+namespace {
+
+// sampler set-up (t < 0): noise ids and <bos> of the R = (K + greedy) * B decode rows, the greedy block last with sample id -1
+// (s2vt_sample's convention); step t: the picks into sampled [K * B, Tc] / greedy [B, Tc]
+__global__ void bidir_sample_ids_kernel(int B, int K, int R, int Tc, int t, int32_t video_base, int32_t* tok, int32_t* sampled, int32_t* greedy,
+                                        int32_t* vid, int32_t* sid)
+{
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= R) return;
+    const int s = r / B;
+    if (t < 0) { vid[r] = video_base + r % B; sid[r] = s < K ? s : -1; tok[r] = 1; return; }
+    if (s < K) sampled[(size_t)r * Tc + t] = tok[r];
+    else greedy[(size_t)(r - K * B) * Tc + t] = tok[r];
+}
+// fed[t * N + n] = the word row n is fed at decode step t: <bos>, then the previous word (clamped as bidir_index_kernel does)
+__global__ void bidir_rows_fed_kernel(int N, int Tc, int V, const int32_t* caption, int32_t* fed)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)Tc * N) return;
+    const int t = (int)(i / N), n = (int)(i % N);
+    const int w = t == 0 ? 1 : caption[(size_t)n * Tc + t - 1];
+    fed[i] = w < 0 ? 0 : (w >= V ? V - 1 : w);
+}
+// out[t][n][:] = in[t][n % B][:] for t < T: the encode steps' partial of the N rows (no word is fed there: the shared chain is the whole one)
+__global__ __launch_bounds__(256) void bidir_tile_rows_kernel(const f32x4* __restrict__ in, f32x4* __restrict__ out, int T, int B, int N, int C4)
+{
+    const size_t total = (size_t)T * N * C4;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+        const size_t row = i / C4;
+        const int c = (int)(i % C4), t = (int)(row / N), n = (int)(row % N);
+        out[i] = in[((size_t)t * B + n % B) * C4 + c];
+    }
+}
+// The sample sum: out[t * B + b][:] = sum_s in[t * N + s * B + b][:], ascending s, one owning thread per output element, no atomics (two
+// runs give equal bits).  HBM-bound: 16-byte loads, consecutive lanes on consecutive 16 bytes of a row, four samples in flight.
+__global__ __launch_bounds__(256) void bidir_sample_sum_kernel(const f32x4* __restrict__ in, f32x4* __restrict__ out, int TB, int B, int S, int C4)
+{
+    const size_t total = (size_t)TB * C4, BC = (size_t)B * C4;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+        const size_t row = i / C4;
+        const int c = (int)(i % C4);
+        const f32x4* src = in + ((row / B) * S * B + row % B) * C4 + c;      // row t * N + b; sample s lies s * B rows on
+        f32x4 acc = src[0];
+        int s = 1;
+        for (; s + 4 <= S; s += 4) {
+            const f32x4 v0 = src[(size_t)s * BC], v1 = src[(size_t)(s + 1) * BC], v2 = src[(size_t)(s + 2) * BC], v3 = src[(size_t)(s + 3) * BC];
+            acc += v0; acc += v1; acc += v2; acc += v3;
+        }
+        for (; s < S; ++s) acc += src[(size_t)s * BC];
+        out[i] = acc;
+    }
+}
+unsigned grid_for(size_t total) { const size_t nb = (total + 255) / 256; return (unsigned)(nb < 1 ? 1 : (nb > (1u << 20) ? (1u << 20) : nb)); }
+
+// the rows drivers' workspace: the B-row workspace of the plain drivers (LSTM1's side, the shared partial in b.P2, the sample sum in
+// b.dZ2, dd / dZ1 / demb) and LSTM2's side at N rows behind it
+struct BiRowsWs {
+    BiWs b;
+    int32_t* fed;
+    float *P2, *G2, *C2, *H2, *O2, *dO2, *dZ2, *dE;
+    void* bchain;
+    size_t bchain_bytes;
+};
+bool bidir_rows_ok(const s2vt_dims* d, int B, int S)
+{
+    if (!bidir_dims_ok(d, B) || S < 1) return false;
+    const long long T = (long long)d->n_video_lstm_step + d->n_caption_lstm_step;
+    return (long long)S * B <= 0x7fffffffLL / T;                 // S * B, and every row count T * S * B of a product, within int
+}
+size_t bidir_rows_carve(const s2vt_dims* d, int B, int S, void* base, size_t cap, BiRowsWs* w)
+{
+    const size_t H = d->lstm_dim, E = d->word_dim, Tv = d->n_video_lstm_step, Tc = d->n_caption_lstm_step, T = Tv + Tc, N = (size_t)S * B, NH = N * H;
+    BiRowsWs t;
+    std::memset(&t, 0, sizeof(t));
+    Carver c(base, cap);
+    c.off = bidir_carve(d, B, base, cap, &t.b, true);
+    t.fed = c.take<int32_t>(Tc * N);
+    t.P2 = c.take<float>(T * 4 * NH); t.G2 = c.take<float>(T * 4 * NH);
+    t.C2 = c.take<float>((T + 1) * NH); t.H2 = c.take<float>((T + 1) * NH); t.O2 = c.take<float>(T * NH);
+    t.dO2 = c.take<float>(Tc * NH); t.dZ2 = c.take<float>(T * 4 * NH); t.dE = c.take<float>(Tc * N * E);
+    t.bchain_bytes = s2vt_lstm_recurrence_bwd_scratch_bytes((int32_t)N, (int32_t)H);
+    t.bchain = c.take<char>(t.bchain_bytes);
+    if (w) *w = t;
+    return c.off;
+}
+size_t bidir_sample_carve(const s2vt_dims* d, int B, int R, void* base, size_t cap, BiWs* w, float** st, float** out2, unsigned long long** packed,
+                          int32_t** iw)
+{
+    const size_t RH = (size_t)R * d->lstm_dim;
+    Carver c(base, cap);
+    c.off = bidir_carve(d, B, base, cap, w, false);
+    float* a = c.take<float>(4 * RH);                          // c | h, two parities
+    float* o = c.take<float>(RH);
+    unsigned long long* k = c.take<unsigned long long>(R);
+    int32_t* i = c.take<int32_t>(3 * (size_t)R);
+    if (st) { *st = a; *out2 = o; *packed = k; *iw = i; }
+    return c.off;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t s2vt_bidir_sample_workspace_bytes(const s2vt_dims* d, int32_t B, int32_t K, int32_t with_greedy)
+{
+    if (!bidir_dims_ok(d, B) || K < 0 || (K == 0 && !with_greedy) || ((long long)K + 1) * B > 0x7fffffffLL) return 0;
+    return bidir_sample_carve(d, B, (K + (with_greedy ? 1 : 0)) * B, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr);
+}
+
+int s2vt_bidir_sample(const s2vt_dims* d, const s2vt_bidir_params* p, const float* video, int32_t B, int32_t K, int32_t with_greedy, uint64_t seed,
+                      int32_t video_base, int32_t lstm1_form, int32_t* sampled_out, int32_t* greedy_out, void* workspace, size_t workspace_bytes,
+                      s2vt_stream stream)
+{
+    if (!bidir_dims_ok(d, B) || !bidir_params_ok(p) || !video || !workspace || K < 0 || (K == 0 && !with_greedy) || (K > 0 && !sampled_out) ||
+        (with_greedy && !greedy_out) || ((long long)K + 1) * B > 0x7fffffffLL || lstm1_form < -1 || lstm1_form > 2)
+        return S2VT_E_BADARG;
+    if (reinterpret_cast<uintptr_t>(workspace) & 255u) return S2VT_E_ALIGN;
+    const int H = d->lstm_dim, E = d->word_dim, Tv = d->n_video_lstm_step, Tc = d->n_caption_lstm_step, T = Tv + Tc, V = d->n_words;
+    const int R = (K + (with_greedy ? 1 : 0)) * B;
+    const size_t BH = (size_t)B * H, RH = (size_t)R * H;
+    BiWs w;
+    float *st, *out2;
+    unsigned long long* packed;
+    int32_t* iw;
+    if (bidir_sample_carve(d, B, R, workspace, workspace_bytes, &w, &st, &out2, &packed, &iw) > workspace_bytes) return S2VT_E_WORKSPACE;
+    int32_t *tok = iw, *vid = iw + R, *sid = iw + 2 * (size_t)R;
+    hipStream_t hs = S(stream);
+    const unsigned nb = (unsigned)((R + 255) / 256);
+    hipLaunchKernelGGL(bidir_sample_ids_kernel, dim3(nb), dim3(256), 0, hs, B, K, R, Tc, -1, video_base, tok, sampled_out, greedy_out, vid, sid);
+    HIP_TRY(hipGetLastError());
+    // once per VIDEO: LSTM1, [fw ; bw] @ W2[:2H] for all T steps, LSTM2's Tv encode steps
+    RC_TRY(bidir_lstm1(d, p, video, B, nullptr, w, lstm1_form, stream));
+    s2vt_operand o1[2] = {{w.H1[0] + BH, nullptr, H, H, 0, 0}, {w.H1[1] + BH, w.rev, H, H, 0, 0}};
+    RC_TRY(s2vt_gemm(o1, 2, p->lstm2_W, 4 * H, nullptr, nullptr, 0, w.P2, 4 * H, T * B, 4 * H, 0, -1, stream));
+    HIP_TRY(hipMemsetAsync(w.C2, 0, BH * 4, hs));
+    HIP_TRY(hipMemsetAsync(w.H2, 0, BH * 4, hs));
+    RC_TRY(s2vt_lstm_recurrence_fwd(p->lstm2_W, 2 * H + E, p->lstm2_b, w.P2, (int64_t)B * 4 * H, 4 * H, Tv, w.C2, w.H2, nullptr, nullptr, B, H, Tv, 1.0f, 0,
+                                    nullptr, nullptr, 0u, -1, w.chain, w.chain_bytes, stream));
+    // Tc decode steps on the R rows: every row's chain goes on from ITS VIDEO's slice of the hoisted partial (row % B); step 0 reads the
+    // video's encoder state the same way
+    const float* cprev = w.C2 + (size_t)Tv * BH;
+    const float* hprev = w.H2 + (size_t)Tv * BH;
+    const NoiseIds none{nullptr, nullptr, 0};
+    for (int t = 0; t < Tc; ++t) {
+        float* cn = st + (size_t)(t & 1) * 2 * RH;
+        float* hn = cn + RH;
+        const int mod = t == 0 ? B : 0;
+        ASeg segs[2] = {make_seg(p->Wemb, E, E, 2 * H, 0, tok), make_seg(hprev, H, H, 2 * H + E, mod)};
+        HIP_TRY(lstm_call(segs, 2, p->lstm2_W, p->lstm2_b, cprev, mod, cn, hn, out2, nullptr, R, H, 1.0f, none, 0u, -1, hs,
+                          w.P2 + (size_t)(Tv + t) * B * 4 * H, 4 * H, B));
+        HIP_TRY(hipMemsetAsync(packed, 0, (size_t)R * 8, hs));                      // the pick is an atomicMax on a zeroed word per row
+        RC_TRY(s2vt_vocab_pick(out2, H, p->embed_word_W, p->embed_word_b, R, H, V, vid, sid, t, seed, packed, tok, nullptr, -1, stream));
+        hipLaunchKernelGGL(bidir_sample_ids_kernel, dim3(nb), dim3(256), 0, hs, B, K, R, Tc, t, 0, tok, sampled_out, greedy_out, vid, sid);
+        HIP_TRY(hipGetLastError());
+        cprev = cn; hprev = hn;
+    }
+    return S2VT_OK;
+}
+
+int s2vt_bidir_sample_sum(const float* dz, float* out, int32_t T, int32_t B, int32_t S, int32_t C, s2vt_stream stream)
+{
+    if (!dz || !out || T < 1 || B < 1 || S < 1 || C < 4 || (C & 3) || (long long)S * B > 0x7fffffffLL / T) return S2VT_E_BADARG;
+    if ((reinterpret_cast<uintptr_t>(dz) | reinterpret_cast<uintptr_t>(out)) & 15u) return S2VT_E_ALIGN;
+    hipLaunchKernelGGL(bidir_sample_sum_kernel, dim3(grid_for((size_t)T * B * (C / 4))), dim3(256), 0, s2vt_api::S(stream), reinterpret_cast<const f32x4*>(dz),
+                       reinterpret_cast<f32x4*>(out), T * B, B, S, C / 4);
+    HIP_TRY(hipGetLastError());
+    return S2VT_OK;
+}
+
+size_t s2vt_bidir_rows_workspace_bytes(const s2vt_dims* d, int32_t B, int32_t S)
+{
+    return bidir_rows_ok(d, B, S) ? bidir_rows_carve(d, B, S, nullptr, 0, nullptr) : 0;
+}
+
+int s2vt_bidir_teacher_forced_fwd_rows(const s2vt_dims* d, const s2vt_bidir_params* p, const float* video, int32_t B, int32_t S, const int32_t* caption,
+                                       float keep, uint64_t seed, const int32_t* video_id, const int32_t* sample_id, int32_t lstm1_form, float* logits_out,
+                                       void* workspace, size_t workspace_bytes, s2vt_stream stream)
+{
+    if (!bidir_rows_ok(d, B, S) || !bidir_params_ok(p) || !video || !caption || !logits_out || !workspace || !(keep > 0.0f) || keep > 1.0f ||
+        (keep < 1.0f && (!video_id || !sample_id)) || lstm1_form < -1 || lstm1_form > 2)
+        return S2VT_E_BADARG;
+    if (reinterpret_cast<uintptr_t>(workspace) & 255u) return S2VT_E_ALIGN;
+    BiRowsWs w;
+    if (bidir_rows_carve(d, B, S, workspace, workspace_bytes, &w) > workspace_bytes) return S2VT_E_WORKSPACE;
+    const int H = d->lstm_dim, E = d->word_dim, Tv = d->n_video_lstm_step, Tc = d->n_caption_lstm_step, T = Tv + Tc, V = d->n_words, N = S * B;
+    const size_t BH = (size_t)B * H, NH = (size_t)N * H;
+    hipStream_t hs = s2vt_api::S(stream);
+    // per VIDEO: LSTM1 and [fw ; bw] @ W2[:2H] for all T steps, on T * B rows
+    RC_TRY(bidir_lstm1(d, p, video, B, nullptr, w.b, lstm1_form, stream));
+    s2vt_operand o1[2] = {{w.b.H1[0] + BH, nullptr, H, H, 0, 0}, {w.b.H1[1] + BH, w.b.rev, H, H, 0, 0}};
+    RC_TRY(s2vt_gemm(o1, 2, p->lstm2_W, 4 * H, nullptr, nullptr, 0, w.b.P2, 4 * H, T * B, 4 * H, 0, -1, stream));
+    // per ROW: the encode steps' partial is the video's; a decode step's chain goes on from the video's slice with the fed word's rows of
+    // Wemb (continuing a chain from a carried partial is exact: the bits of the one three-segment product on the tiled block)
+    hipLaunchKernelGGL(bidir_rows_fed_kernel, dim3(grid_for((size_t)Tc * N)), dim3(256), 0, hs, N, Tc, V, caption, w.fed);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(bidir_tile_rows_kernel, dim3(grid_for((size_t)Tv * N * H)), dim3(256), 0, hs, reinterpret_cast<const f32x4*>(w.b.P2),
+                       reinterpret_cast<f32x4*>(w.P2), Tv, B, N, H);
+    HIP_TRY(hipGetLastError());
+    for (int t = 0; t < Tc; ++t) {
+        GemmArgs a;
+        std::memset(&a, 0, sizeof(a));
+        a.seg[0] = make_seg(p->Wemb, E, E, 2 * H, 0, w.fed + (size_t)t * N);
+        a.nseg = 1;
+        a.W = p->lstm2_W; a.ldw = 4 * H; a.M = N; a.N = 4 * H;
+        a.cinit = w.b.P2 + (size_t)(Tv + t) * B * 4 * H; a.ldcinit = 4 * H; a.cinit_rowmod = B;
+        a.C = w.P2 + (size_t)(Tv + t) * N * 4 * H; a.ldc = 4 * H;
+        HIP_TRY(launch_gemm(a, EPI_STORE, -1, hs));
+    }
+    HIP_TRY(hipMemsetAsync(w.C2, 0, NH * 4, hs));
+    HIP_TRY(hipMemsetAsync(w.H2, 0, NH * 4, hs));
+    // LSTM2 over all T steps on the N rows; its DropoutWrapper on its own Philox codes, keyed per row
+    RC_TRY(s2vt_lstm_recurrence_fwd(p->lstm2_W, 2 * H + E, p->lstm2_b, w.P2, (int64_t)N * 4 * H, 4 * H, T, w.C2, w.H2, w.G2, w.O2, N, H, T, keep, seed,
+                                    video_id, sample_id, 512u, -1, w.b.chain, w.b.chain_bytes, stream));
+    s2vt_operand o{w.O2 + (size_t)Tv * NH, nullptr, H, H, 0, 0};
+    return s2vt_gemm(&o, 1, p->embed_word_W, V, p->embed_word_b, nullptr, 0, logits_out, V, Tc * N, V, 0, -1, stream);
+}
+
+int s2vt_bidir_bptt_bwd_rows(const s2vt_dims* d, const s2vt_bidir_params* p, const s2vt_bidir_params* grads, const float* video, int32_t B, int32_t S,
+                             const float* dlogits, float keep, uint64_t seed, const int32_t* video_id, const int32_t* sample_id, void* workspace,
+                             size_t workspace_bytes, s2vt_stream stream)
+{
+    if (!bidir_rows_ok(d, B, S) || !bidir_params_ok(p) || !bidir_params_ok(grads) || !video || !dlogits || !workspace || !(keep > 0.0f) || keep > 1.0f ||
+        (keep < 1.0f && (!video_id || !sample_id)))
+        return S2VT_E_BADARG;
+    if (reinterpret_cast<uintptr_t>(workspace) & 255u) return S2VT_E_ALIGN;
+    BiRowsWs r;
+    if (bidir_rows_carve(d, B, S, workspace, workspace_bytes, &r) > workspace_bytes) return S2VT_E_WORKSPACE;
+    const BiWs& w = r.b;
+    const int H = d->lstm_dim, E = d->word_dim, Tv = d->n_video_lstm_step, Tc = d->n_caption_lstm_step, T = Tv + Tc, V = d->n_words, D = d->dim_image;
+    const int N = S * B;
+    const size_t BH = (size_t)B * H, NH = (size_t)N * H;
+    const s2vt_bidir_params* g = grads;
+    hipStream_t hs = s2vt_api::S(stream);
+    // ---- what sees a per-sample operand: N rows
+    RC_TRY(s2vt_gemm_tn(r.O2 + (size_t)Tv * NH, H, nullptr, dlogits, V, g->embed_word_W, V, Tc * N, H, V, 1, stream));
+    RC_TRY(s2vt_colsum(dlogits, V, Tc * N, V, g->embed_word_b, stream));
+    s2vt_operand dl{dlogits, nullptr, V, V, 0, 0};
+    RC_TRY(s2vt_gemm_nt(&dl, 1, p->embed_word_W, V, nullptr, nullptr, 0, r.dO2, H, Tc * N, H, 0, -1, stream));
+    RC_TRY(s2vt_lstm_recurrence_bwd(p->lstm2_W, 2 * H + E, r.G2, r.C2, r.dO2, (int64_t)NH, H, Tv, r.dZ2, N, H, T, keep, seed, video_id, sample_id, 512u, -1,
+                                    r.bchain, r.bchain_bytes, stream));
+    float* gW2 = g->lstm2_W;
+    const float* dZ2d = r.dZ2 + (size_t)Tv * N * 4 * H;
+    RC_TRY(s2vt_gemm_tn(p->Wemb, E, r.fed, dZ2d, 4 * H, gW2 + (size_t)2 * H * 4 * H, 4 * H, Tc * N, E, 4 * H, 1, stream));
+    RC_TRY(s2vt_gemm_tn(r.H2, H, nullptr, r.dZ2, 4 * H, gW2 + (size_t)(2 * H + E) * 4 * H, 4 * H, T * N, H, 4 * H, 1, stream));
+    s2vt_operand zd{dZ2d, nullptr, 4 * H, 4 * H, 0, 0};
+    RC_TRY(s2vt_gemm_nt(&zd, 1, p->lstm2_W + (size_t)2 * H * 4 * H, 4 * H, nullptr, nullptr, 0, r.dE, E, Tc * N, E, 0, -1, stream));
+    RC_TRY(s2vt_embed_scatter_add(r.dE, E, r.fed, Tc * N, E, g->Wemb, stream));
+    // ---- the sample sum, then what sees the video only: T * B rows
+    RC_TRY(s2vt_bidir_sample_sum(r.dZ2, w.dZ2, T, B, S, 4 * H, stream));
+    RC_TRY(s2vt_gemm_tn(w.H1[0] + BH, H, nullptr, w.dZ2, 4 * H, gW2, 4 * H, T * B, H, 4 * H, 1, stream));
+    RC_TRY(s2vt_gemm_tn(w.H1[1] + BH, H, w.rev, w.dZ2, 4 * H, gW2 + (size_t)H * 4 * H, 4 * H, T * B, H, 4 * H, 1, stream));
+    RC_TRY(s2vt_colsum(w.dZ2, 4 * H, T * B, 4 * H, g->lstm2_b, stream));
+    s2vt_operand z{w.dZ2, nullptr, 4 * H, 4 * H, 0, 0}, zr{w.dZ2, w.rev, 4 * H, 4 * H, 0, 0};
+    RC_TRY(s2vt_gemm_nt(&z, 1, p->lstm2_W, 4 * H, nullptr, nullptr, 0, w.dd[0], H, T * B, H, 0, -1, stream));
+    RC_TRY(s2vt_gemm_nt(&zr, 1, p->lstm2_W + (size_t)H * 4 * H, 4 * H, nullptr, nullptr, 0, w.dd[1], H, T * B, H, 0, -1, stream));
+    // ---- LSTM1 on B rows, as s2vt_bidir_bptt_bwd
+    const float* W1[2] = {p->lstm1_fw_W, p->lstm1_bw_W};
+    float* gW1[2] = {g->lstm1_fw_W, g->lstm1_bw_W};
+    float* gb1[2] = {g->lstm1_fw_b, g->lstm1_bw_b};
+    for (int k = 0; k < 2; ++k) {
+        RC_TRY(s2vt_lstm_recurrence_bwd(W1[k], E, w.G1[k], w.C1[k], w.dd[k], (int64_t)BH, H, 0, w.dZ1, B, H, T, 1.0f, 0, nullptr, nullptr, 0u, -1, w.bchain,
+                                        w.bchain_bytes, stream));
+        const float* dZf = w.dZ1 + (size_t)(k ? Tc : 0) * B * 4 * H;            // the steps that saw a frame
+        RC_TRY(s2vt_gemm_tn(w.emb, E, k ? w.framesb : w.tm, dZf, 4 * H, gW1[k], 4 * H, Tv * B, E, 4 * H, 1, stream));
+        RC_TRY(s2vt_gemm_tn(w.H1[k], H, nullptr, w.dZ1, 4 * H, gW1[k] + (size_t)E * 4 * H, 4 * H, T * B, H, 4 * H, 1, stream));
+        RC_TRY(s2vt_colsum(w.dZ1, 4 * H, T * B, 4 * H, gb1[k], stream));
+        s2vt_operand f{dZf, k ? w.srcb : w.srcf, 4 * H, 4 * H, 0, 0};
+        RC_TRY(s2vt_gemm_nt(&f, 1, W1[k], 4 * H, nullptr, k ? w.demb[0] : nullptr, k ? E : 0, w.demb[k], E, B * Tv, E, 0, -1, stream));
+    }
+    RC_TRY(s2vt_gemm_tn(video, D, nullptr, w.demb[1], E, g->encode_image_W, E, B * Tv, D, E, 1, stream));
+    return s2vt_colsum(w.demb[1], E, B * Tv, E, g->encode_image_b, stream);
+}
+
+}  // extern "C"

@@ -256,6 +256,64 @@ def bidir_decode_greedy(dims: Dims, params, video, unshifted_softmax=False, vide
     return (ids, logits) if want_logits else ids
 
 
+def bidir_sample(dims: Dims, params, video, K: int, seed: int = 0, video_base: int = 0, with_greedy: bool = True, lstm1_form=-1, out=None, ids=None):
+    """K multinomial captions per video (+ the greedy one) of the bidirectional captioner (s2vt_bidir_sample): (sampled [K * B, Tc] | None,
+    greedy [B, Tc] | None) int32, sample-major rows.  out / ids: windows for the sampled / greedy block."""
+    _chk_f32(video)
+    assert video.is_contiguous() and K >= 0 and (K > 0 or with_greedy)
+    B, Tc = video.shape[0], dims.n_caption_lstm_step
+    if K > 0 and out is None:
+        out = torch.empty((K * B, Tc), dtype=torch.int32, device=video.device)
+    if with_greedy and ids is None:
+        ids = torch.empty((B, Tc), dtype=torch.int32, device=video.device)
+    nb = lib().s2vt_bidir_sample_workspace_bytes(C.byref(dims), B, int(K), int(bool(with_greedy)))
+    assert nb > 0
+    ws = workspace(nb, video.device, "bidir_sample")
+    check(lib().s2vt_bidir_sample(C.byref(dims), C.byref(params), _ptr(video), B, int(K), int(bool(with_greedy)), int(seed), int(video_base), lstm1_form,
+                                  _ptr(out if K > 0 else None), _ptr(ids if with_greedy else None), _ptr(ws), ws.numel(), _stream()), "s2vt_bidir_sample")
+    return (out if K > 0 else None), (ids if with_greedy else None)
+
+
+def bidir_sample_sum(dz, B: int, S: int, out=None):
+    """dz [T, S * B, C] (sample-major rows) -> [T, B, C]: the sum over a video's S rows in ascending s, no atomics (s2vt_bidir_sample_sum)."""
+    _chk_f32(dz, out)
+    T, N, Cc = dz.shape
+    assert N == S * B and dz.is_contiguous()
+    if out is None:
+        out = torch.empty((T, B, Cc), dtype=torch.float32, device=dz.device)
+    check(lib().s2vt_bidir_sample_sum(_ptr(dz), _ptr(out), T, B, S, Cc, _stream()), "s2vt_bidir_sample_sum")
+    return out
+
+
+def bidir_rows_workspace(dims: Dims, B: int, S: int, device):
+    nb = lib().s2vt_bidir_rows_workspace_bytes(C.byref(dims), B, S)
+    assert nb > 0
+    return torch.empty(nb, dtype=torch.uint8, device=device)
+
+
+def bidir_teacher_forced_fwd_rows(dims: Dims, params, video, caption, ws, keep=1.0, seed=0, video_id=None, sample_id=None, lstm1_form=-1, out=None):
+    """The teacher-forced logits of the N = S * B sample-major rows caption [N, Tc] on the B videos video [B, Tv, D], time-major [Tc * N, V]
+    (s2vt_bidir_teacher_forced_fwd_rows): the bits of bidir_teacher_forced_fwd on the S-times tiled block; ws (bidir_rows_workspace) keeps
+    the state bidir_bptt_bwd_rows needs."""
+    _chk_f32(video)
+    B, N = video.shape[0], caption.shape[0]
+    assert video.is_contiguous() and caption.is_cuda and caption.dtype == torch.int32 and caption.is_contiguous() and N % B == 0 and N >= B
+    if out is None:
+        out = torch.empty((dims.n_caption_lstm_step * N, dims.n_words), dtype=torch.float32, device=video.device)
+    check(lib().s2vt_bidir_teacher_forced_fwd_rows(C.byref(dims), C.byref(params), _ptr(video), B, N // B, _ptr(caption), float(keep), seed, _ptr(video_id),
+                                                   _ptr(sample_id), lstm1_form, _ptr(out), _ptr(ws), ws.numel(), _stream()),
+          "s2vt_bidir_teacher_forced_fwd_rows")
+    return out
+
+
+def bidir_bptt_bwd_rows(dims: Dims, params, grads, video, S, dlogits, ws, keep=1.0, seed=0, video_id=None, sample_id=None):
+    """The backward of bidir_teacher_forced_fwd_rows on the same ws: adds the gradient products of all eleven variables into `grads`."""
+    _chk_f32(video, dlogits)
+    assert dlogits.is_contiguous() and video.is_contiguous()
+    check(lib().s2vt_bidir_bptt_bwd_rows(C.byref(dims), C.byref(params), C.byref(grads), _ptr(video), video.shape[0], int(S), _ptr(dlogits), float(keep),
+                                         seed, _ptr(video_id), _ptr(sample_id), _ptr(ws), ws.numel(), _stream()), "s2vt_bidir_bptt_bwd_rows")
+
+
 def lstm_recurrence_bwd(W, kw0, gates, C_hist, dext=None, dext_t0=0, keep=1.0, seed=0, video_id=None, sample_id=None, drop_code0=0,
                         persistent=-1, precision="fp32"):
     """Back-propagation through lstm_recurrence_fwd's unroll: returns dZ [T, M, 4H].  gates [T, M, 4H] activated, C_hist

@@ -210,6 +210,83 @@ def train(cfg: Config, train_corpus: Corpus, test_corpus: Corpus | None = None, 
     return model, history
 
 
+def train_bidirectional(cfg: Config, train_corpus: Corpus, test_corpus: Corpus | None = None, model=None, restore=None, resume=None, log=print):
+    """The loop of train() on the bidirectional captioner (bidirection_rl.Reinforce_Caption_Generator): per step model.sample (K multinomial
+    captions + the greedy one, LSTM1 once per video), CIDEr-D of both on the host under the queued teacher-forced forward, model.reinforce_update
+    (LSTM1's side of the forward and the backward on B rows), a step-log record; per epoch a checkpoint `<model_name>-<epoch>` under the TF
+    names with Adam's slots and the counter as g_step.  restore: an XE checkpoint of train_xe --bidirectional (variables only, the counters start at
+    zero as the reference's optimistic restore leaves them); resume: a checkpoint of THIS driver.  One process, one GPU: data parallel is not
+    built for this model.  Returns (model, history)."""
+    import os
+    import torch
+    from . import bidirection_rl
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise ValueError("--bidirectional trains in one process: data parallel is not built for the bidirectional captioner")
+    if cfg.residual or cfg.mix_baseline is not None or cfg.stop_at_eos:
+        raise ValueError("the bidirectional captioner has no residual form, no mixed baseline and no early-exit sampler")
+    wordtoix, ixtoword = hostglue.preProBuildWordVocab(train_corpus.vocabulary)
+    K, B = cfg.multisample, cfg.batch_size
+    if model is None:
+        model = bidirection_rl.Reinforce_Caption_Generator(cfg.dim_image, len(wordtoix), cfg.word_dim, cfg.lstm_dim, B, cfg.n_video_lstm_step + cfg.n_caption_lstm_step,
+                                                           cfg.n_video_lstm_step, cfg.n_caption_lstm_step, bias_init_vector=None, seed=cfg.seed, multisample=K)
+    if restore:
+        model.restore(restore)
+        log(f"restored: {restore}")
+    if resume:
+        model.restore(resume)
+        log(f"resumed: {resume} at step {model.global_step}")
+    scorer = reward.CiderD(train_corpus.index.refs_by_video(), wordtoix)
+    test_scorer = reward.CiderD(test_corpus.index.refs_by_video(), wordtoix) if test_corpus is not None else None
+    rng = random.Random(cfg.seed)
+    caps = train_corpus.captions
+    history = []
+    steplog = StepLog(cfg.step_log)
+    if test_corpus is not None:
+        log(f"before train: ciderD {greedy_eval(model, test_corpus, ixtoword, test_scorer, B)[1]}")
+    for epoch in range(cfg.n_epochs):
+        losses, adv = [], []
+        for it, idx in enumerate(epoch_batches(len(caps), B, rng)):
+            if cfg.max_steps_per_epoch and it >= cfg.max_steps_per_epoch:
+                break
+            t0 = time.time()
+            vid = caps[idx, 0]
+            rows = np.asarray([train_corpus.index.row[v] for v in vid], np.int32)
+            video = model._dev(train_corpus.features.batch(vid), torch.float32)
+            lr = learning_rate(cfg, model.global_step)
+            rb = {}
+
+            def step():
+                samples, greedy_words = model.sample(video, K, True, seed=cfg.seed + 7919 * (model.global_step + 1))
+                s_host, g_host = samples.cpu().numpy(), greedy_words.cpu().numpy()
+                model.check_health()            # the ids just came to the host: a starved recurrence is caught before it is scored
+
+                def rewards():                  # runs on the host while the GPU does the teacher-forced forward
+                    rb["r"] = scorer.score_ids(s_host, np.tile(rows, K))                 # [K*B], sample-major like the ids
+                    rb["b"] = scorer.score_ids(g_host, rows)                            # [B]
+                    return rb["r"], hostglue.tile_baseline(rb["b"], K)
+                return model.reinforce_update(video, samples, None, None, None, lr=lr, clip_norm=cfg.clip_norm, reward_fn=rewards)
+            st, loss = run_step(model, step, log)
+            if not np.isfinite(loss):
+                raise FloatingPointError(f"bidirectional captioner, REINFORCE step {model.global_step}: the loss is {loss}")
+            rm, bm = float(rb["r"].mean()), float(rb["b"].mean())
+            losses.append(loss); adv.append(rm - bm)
+            secs = time.time() - t0
+            log(f"idx: {it * B} rate: {lr:g} Epoch: {epoch} loss: {loss:.5f} r: {rm:.4f} b: {bm:.4f} Elapsed time: {secs:.3f}")
+            steplog.write(kind="step", epoch=epoch, step=model.global_step, lr=lr, loss=loss, reward=rm, baseline=bm, seconds=secs)
+        entry = {"epoch": epoch, "loss": float(np.mean(losses)) if losses else None, "r_minus_b": float(np.mean(adv)) if adv else None}
+        if test_corpus is not None:
+            _, entry["ciderD"] = greedy_eval(model, test_corpus, ixtoword, test_scorer, B)
+        model.check_health()
+        os.makedirs(cfg.model_path, exist_ok=True)
+        entry["checkpoint"] = os.path.join(cfg.model_path, f"{cfg.model_name}-{epoch}")
+        model.save(entry["checkpoint"], tf_version=2)          # the REINFORCE script's Saver writes V2 (reinforcement_multisampling_tf_s2vt.py:661)
+        history.append(entry)
+        steplog.write(kind="epoch", bidirectional=True, **entry)
+        log(f"Epoch {epoch} is done: {entry}")
+    steplog.close()
+    return model, history
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--train-sents", required=True); ap.add_argument("--train-feats", required=True)
@@ -226,7 +303,19 @@ def main(argv=None):
     ap.add_argument("--residual", action="store_true", help="the residual captioner of residual_tf_s2vt.py: out1 + out2 into the vocabulary projection")
     ap.add_argument("--grad-precision", choices=("fp32", "bf16"), help="the backward's gradient contractions on bf16 operands (non-parity "
                     "fast mode, DESIGN.md §3); default: S2VT_GRAD_PRECISION, else fp32")
+    ap.add_argument("--bidirectional", action="store_true", help="the bidirectional captioner of bidirection_tf_s2vt.py (d = 1024, Tv = 25) under this "
+                    "script's self-critical stage: LSTM1 runs once per video, the samples share it (train_bidirectional); --restore takes a "
+                    "train_xe --bidirectional checkpoint")
     a = ap.parse_args(argv)
+    if a.bidirectional:
+        if a.residual or a.mix_baseline is not None or a.stop_at_eos or a.attr_vocab or a.grad_precision:
+            ap.error("--bidirectional does not combine with --residual, --mix-baseline, --stop-at-eos, --attr-vocab or --grad-precision")
+        cfg = rl_config(dim_image=1024, n_video_lstm_step=25, n_caption_lstm_step=35, n_epochs=a.epochs, batch_size=a.batch_size, multisample=a.samples,
+                        model_path=a.model_path, model_name="reinforce_bimodel")
+        tr = Corpus(a.train_sents, a.train_feats, vocabulary_file=a.vocab)
+        te = Corpus(a.test_sents, a.test_feats, vocabulary=tr.vocabulary) if a.test_sents and a.test_feats else None
+        train_bidirectional(cfg, tr, te, restore=a.restore, resume=a.resume)
+        return
     cfg = rl_config(n_epochs=a.epochs, batch_size=a.batch_size, multisample=a.samples, model_path=a.model_path, stop_at_eos=a.stop_at_eos,
                     alpha=a.alpha, lambda_loss=a.lambda_loss, mix_baseline=a.mix_baseline, residual=a.residual)
     tr = Corpus(a.train_sents, a.train_feats, vocabulary_file=a.vocab)
