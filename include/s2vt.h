@@ -192,6 +192,54 @@ int s2vt_vocab_pick(const float* out2, int32_t ld, const float* W, const float* 
                     unsigned long long* packed, int32_t* tokens_out, float* logits_out, int32_t tile_cfg,
                     s2vt_stream stream);
 
+/* ---- the tile tables behind every tile_cfg argument, and the live-row forms of the three calls above -----------------
+ * A seam for tests and tuning: no kernels of its own.  kind is the profiler's kernel_class: 0 = STORE contraction (s2vt_gemm), 1 = fused
+ * LSTM cell, 2 = vocab logits + pick, 4 = STORE with the weights transposed (s2vt_gemm_nt).  s2vt_tile_count: the entries of that table
+ * (tile_cfg in [0, count) forces one, anything else is the library's choice), or S2VT_E_BADARG for another kind.  s2vt_tile_info: entry
+ * tile_cfg of the table -- rows x cols of the workgroup's tile (cols per gate for the cell tiles), its name as s2vt_prof_collect reports it,
+ * and which forms it has.  An entry without the form a launch needs hands the launch to entry `fallback` of the same table (-1: it has every
+ * form it can be asked for): has_scalar == 0 and operands off the fast path, or has_live == 0 and a live-row launch.  Kind 4 has no live-row
+ * form at all. */
+typedef struct s2vt_tile_desc {
+    int32_t rows;
+    int32_t cols;
+    int32_t fallback;
+    int32_t has_scalar;
+    int32_t has_live;
+    int32_t reserved;
+    char name[32];
+} s2vt_tile_desc;
+int s2vt_tile_count(int kind);
+int s2vt_tile_info(int kind, int tile_cfg, s2vt_tile_desc* out);
+
+/* Live-row launches: what the early-exit samplers (S2VT_SAMPLE_STOP_AT_EOS) issue per decode step, one launch at a time.  The arguments
+ * of s2vt_gemm / s2vt_lstm_cell_fwd_res / s2vt_vocab_pick keep their meaning, with M the CAPACITY -- the caller's row count, the rows of
+ * every per-row array -- and two more:
+ *   live    device, int32: distinct row indices in [0, M) in ascending order (what the samplers' row lists hold); only the first
+ *           min(*n_live, M) entries are read.  NULL: the rows are 0 .. min(*n_live, M) - 1.
+ *   n_live  device, int32: the number of live rows, read by the kernel (no host round trip).  NULL: all M entries of `live`.
+ * Both NULL: S2VT_E_BADARG.  Row r = live[i] is computed exactly as row r of the dense call: every per-row access -- the segments (before
+ * their own rowmod / rowidx), Cinit, c_prev / h_prev (before state_rowmod), the residual operand, video_id / sample_id, and every output --
+ * uses row r of the caller's arrays.  Rows that are not listed are neither read nor written.  Bit-identical to the dense call on the
+ * listed rows.  The other argument checks are those of the dense entries (M == 0: S2VT_OK, nothing is launched).  Fast path: as for
+ * the dense calls, except that with a list a plain segment is addressed from its base by the caller's row, so all M of its rows must fit
+ * a 2 GiB window (a dense call's operand is addressed per tile); a larger one takes the scalar path with identical results.
+ *   s2vt_lstm_cell_fwd_live: res may be NULL (the plain cell); otherwise as in s2vt_lstm_cell_fwd_res.
+ *   s2vt_vocab_pick_live: packed[r * pick_stride] is row r's word (pick_stride >= 1 64-bit words apart; the samplers keep one word per
+ *     128-byte line, pick_stride = 16), zero on entry for the listed rows; there is no tokens_out -- the word's low half is ~token. */
+int s2vt_gemm_live(const s2vt_operand* segs, int32_t nseg, const float* W, int32_t ldw, const float* bias, const float* Cinit,
+                   int32_t ldcinit, float* C, int32_t ldc, int32_t M, int32_t N, int32_t act_tanh, const int32_t* live,
+                   const int32_t* n_live, int32_t tile_cfg, s2vt_stream stream);
+int s2vt_lstm_cell_fwd_live(const s2vt_operand* x0, const s2vt_operand* x1, const float* h_prev, const float* c_prev,
+                            int32_t state_rowmod, const float* W, const float* b, const s2vt_operand* res, float* c_new, float* h_new,
+                            float* out, float* gates, int32_t M, int32_t H, float keep, uint64_t seed, const int32_t* video_id,
+                            const int32_t* sample_id, uint32_t drop_code, const int32_t* live, const int32_t* n_live, int32_t tile_cfg,
+                            s2vt_stream stream);
+int s2vt_vocab_pick_live(const float* out2, int32_t ld, const float* W, const float* b, int32_t M, int32_t H, int32_t V,
+                         const int32_t* video_id, const int32_t* sample_id, int32_t step, uint64_t seed, unsigned long long* packed,
+                         int32_t pick_stride, float* logits_out, const int32_t* live, const int32_t* n_live, int32_t tile_cfg,
+                         s2vt_stream stream);
+
 /* ---- frame embedding (tf_s2vt.py:97-101): emb[B*Tv, E] = video[B*Tv, d] @ encode_image_W + b */
 int s2vt_frame_embed_fwd(const s2vt_dims* d, const s2vt_params* p, const float* video, int32_t B, float* emb,
                          s2vt_stream stream);

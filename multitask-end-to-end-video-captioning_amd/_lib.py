@@ -49,6 +49,15 @@ class ProfRow(C.Structure):
                 ("total_flops", C.c_double), ("name", C.c_char * 32)]
 
 
+class TileDesc(C.Structure):
+    """s2vt_tile_desc: one entry of a tile table (s2vt_tile_info)."""
+    _fields_ = [("rows", C.c_int32), ("cols", C.c_int32), ("fallback", C.c_int32), ("has_scalar", C.c_int32), ("has_live", C.c_int32),
+                ("reserved", C.c_int32), ("name", C.c_char * 32)]
+
+
+TILE_STORE, TILE_LSTM, TILE_PICK, TILE_STORE_NT = 0, 1, 2, 4      # `kind` of s2vt_tile_count / s2vt_tile_info = the profiler's kernel_class
+
+
 class Operand(C.Structure):
     _fields_ = [("ptr", C.c_void_p), ("rowidx", C.c_void_p), ("ld", C.c_int32), ("k", C.c_int32), ("rowmod", C.c_int32),
                 ("reserved", C.c_int32)]
@@ -99,6 +108,12 @@ SIGNATURES = {
     "s2vt_lstm_cell_fwd_res": (C.c_int, [_OP, _OP, _vp, _vp, _i32, _vp, _vp, _OP, _vp, _vp, _vp, _vp, _i32, _i32, _f32, _u64, _vp,
                                          _vp, _u32, _i32, _vp]),
     "s2vt_vocab_pick": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _i32, _u64, _vp, _vp, _vp, _i32, _vp]),
+    "s2vt_tile_count": (C.c_int, [C.c_int]),
+    "s2vt_tile_info": (C.c_int, [C.c_int, C.c_int, C.POINTER(TileDesc)]),
+    "s2vt_gemm_live": (C.c_int, [_OP, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp]),
+    "s2vt_lstm_cell_fwd_live": (C.c_int, [_OP, _OP, _vp, _vp, _i32, _vp, _vp, _OP, _vp, _vp, _vp, _vp, _i32, _i32, _f32, _u64, _vp,
+                                          _vp, _u32, _vp, _vp, _i32, _vp]),
+    "s2vt_vocab_pick_live": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _i32, _u64, _vp, _i32, _vp, _vp, _vp, _i32, _vp]),
     "s2vt_frame_embed_fwd": (C.c_int, [_DP, _PP, _vp, _i32, _vp, _vp]),
     "s2vt_sample_workspace_bytes": (_sz, [_DP, _i32, _i32, _i32]),
     "s2vt_sample": (C.c_int, [_DP, _PP, _vp, _i32, _i32, _i32, _u64, _i32, _vp, _vp, _sz, _vp]),

@@ -185,7 +185,7 @@ int s2vt_math_eval(int fn, const float* x, float* y, int64_t n, s2vt_stream stre
 // C = act([segs] @ W + bias) continuing Cinit; W as [k][n] rows (ldw >= N) or, w_transposed, as [n][k] rows (ldw >= the segments' K)
 static int gemm_impl(const s2vt_operand* segs, int32_t nseg, const float* W, int32_t ldw, const float* bias, const float* Cinit,
                      int32_t ldcinit, float* C, int32_t ldc, int32_t M, int32_t N, int32_t act_tanh, int32_t tile_cfg,
-                     s2vt_stream stream, bool w_transposed)
+                     s2vt_stream stream, bool w_transposed, const int32_t* live = nullptr, const int32_t* n_live = nullptr)
 {
     if (!segs || nseg < 1 || nseg > 3 || !W || !C || M < 0 || N <= 0 || ldc < N || (!w_transposed && ldw < N)) return S2VT_E_BADARG;
     if (Cinit && ldcinit < N) return S2VT_E_BADARG;
@@ -198,7 +198,7 @@ static int gemm_impl(const s2vt_operand* segs, int32_t nseg, const float* W, int
     }
     if (w_transposed && ldw < kw) return S2VT_E_BADARG;
     if (M == 0) return S2VT_OK;
-    HIP_TRY(store_call(a, nseg, W, ldw, bias, C, ldc, M, N, act_tanh ? 1 : 0, tile_cfg, S(stream), Cinit, ldcinit, w_transposed));
+    HIP_TRY(store_call(a, nseg, W, ldw, bias, C, ldc, M, N, act_tanh ? 1 : 0, tile_cfg, S(stream), Cinit, ldcinit, w_transposed, live, n_live));
     return S2VT_OK;
 }
 
@@ -225,11 +225,21 @@ int s2vt_gemm(const s2vt_operand* segs, int32_t nseg, const float* W, int32_t ld
     return gemm_impl(segs, nseg, W, ldw, bias, Cinit, ldcinit, C, ldc, M, N, act_tanh, tile_cfg, stream, false);
 }
 
+// ---- the live-row forms of the single-op calls (GemmArgs::omap / m_dev): what the early-exit samplers launch, one launch at a time
+int s2vt_gemm_live(const s2vt_operand* segs, int32_t nseg, const float* W, int32_t ldw, const float* bias, const float* Cinit,
+                   int32_t ldcinit, float* C, int32_t ldc, int32_t M, int32_t N, int32_t act_tanh, const int32_t* live,
+                   const int32_t* n_live, int32_t tile_cfg, s2vt_stream stream)
+{
+    if (!live && !n_live) return S2VT_E_BADARG;
+    return gemm_impl(segs, nseg, W, ldw, bias, Cinit, ldcinit, C, ldc, M, N, act_tanh, tile_cfg, stream, false, live, n_live);
+}
+
 // res != NULL: the residual form, out[m] = dropout(h'[m]) + res[row(m)]
 static int lstm_cell_impl(const s2vt_operand* x0, const s2vt_operand* x1, const float* h_prev, const float* c_prev,
                           int32_t state_rowmod, const float* W, const float* b, float* c_new, float* h_new, float* out,
                           float* gates, int32_t M, int32_t H, float keep, uint64_t seed, const int32_t* video_id,
-                          const int32_t* sample_id, uint32_t drop_code, int32_t tile_cfg, s2vt_stream stream, const s2vt_operand* res)
+                          const int32_t* sample_id, uint32_t drop_code, int32_t tile_cfg, s2vt_stream stream, const s2vt_operand* res,
+                          const int32_t* live = nullptr, const int32_t* n_live = nullptr)
 {
     if (!h_prev || !c_prev || !W || !b || !c_new || !h_new || M < 0 || H <= 0) return S2VT_E_BADARG;
     if (keep < 1.0f && (!video_id || !sample_id || !out || !(keep > 0.0f))) return S2VT_E_BADARG;
@@ -248,7 +258,7 @@ static int lstm_cell_impl(const s2vt_operand* x0, const s2vt_operand* x1, const 
     ASeg r;
     if (res) seg_from_operand(r, res, 0);
     HIP_TRY(lstm_call(a, n, W, b, c_prev, state_rowmod, c_new, h_new, out, gates, M, H, keep, ids, drop_code, tile_cfg,
-                      S(stream), nullptr, 0, 0, nullptr, nullptr, res ? &r : nullptr));
+                      S(stream), nullptr, 0, 0, live, n_live, res ? &r : nullptr));
     return S2VT_OK;
 }
 
@@ -271,6 +281,18 @@ int s2vt_lstm_cell_fwd_res(const s2vt_operand* x0, const s2vt_operand* x1, const
                           tile_cfg, stream, res);
 }
 
+int s2vt_lstm_cell_fwd_live(const s2vt_operand* x0, const s2vt_operand* x1, const float* h_prev, const float* c_prev,
+                            int32_t state_rowmod, const float* W, const float* b, const s2vt_operand* res, float* c_new, float* h_new,
+                            float* out, float* gates, int32_t M, int32_t H, float keep, uint64_t seed, const int32_t* video_id,
+                            const int32_t* sample_id, uint32_t drop_code, const int32_t* live, const int32_t* n_live, int32_t tile_cfg,
+                            s2vt_stream stream)
+{
+    if (!live && !n_live) return S2VT_E_BADARG;
+    if (res && (!res->ptr || !out || res->k != H || res->ld < H || res->rowmod < 0)) return S2VT_E_BADARG;
+    return lstm_cell_impl(x0, x1, h_prev, c_prev, state_rowmod, W, b, c_new, h_new, out, gates, M, H, keep, seed, video_id, sample_id, drop_code,
+                          tile_cfg, stream, res, live, n_live);
+}
+
 int s2vt_vocab_pick(const float* out2, int32_t ld, const float* W, const float* b, int32_t M, int32_t H, int32_t V,
                     const int32_t* video_id, const int32_t* sample_id, int32_t step, uint64_t seed,
                     unsigned long long* packed, int32_t* tokens_out, float* logits_out, int32_t tile_cfg,
@@ -285,6 +307,34 @@ int s2vt_vocab_pick(const float* out2, int32_t ld, const float* W, const float* 
         hipLaunchKernelGGL(unpack_ids_kernel, dim3((M + 255) / 256), dim3(256), 0, S(stream), packed, tokens_out, M, 1, 1);
         HIP_TRY(hipGetLastError());
     }
+    return S2VT_OK;
+}
+
+int s2vt_vocab_pick_live(const float* out2, int32_t ld, const float* W, const float* b, int32_t M, int32_t H, int32_t V,
+                         const int32_t* video_id, const int32_t* sample_id, int32_t step, uint64_t seed, unsigned long long* packed,
+                         int32_t pick_stride, float* logits_out, const int32_t* live, const int32_t* n_live, int32_t tile_cfg,
+                         s2vt_stream stream)
+{
+    if (!out2 || !W || !b || !video_id || !sample_id || !packed || M < 0 || H <= 0 || V <= 0 || ld < H || pick_stride < 1 || (!live && !n_live))
+        return S2VT_E_BADARG;
+    if (M == 0) return S2VT_OK;
+    NoiseIds ids{video_id, sample_id, seed};
+    HIP_TRY(pick_call(out2, ld, W, b, M, H, V, ids, step, packed, logits_out, tile_cfg, S(stream), pick_stride, live, n_live));
+    return S2VT_OK;
+}
+
+// the tile tables of fwd.hip as a caller of the tile_cfg arguments sees them
+static bool tile_kind_ok(int kind) { return kind == EPI_STORE || kind == EPI_LSTM || kind == EPI_PICK || kind == EPI_STORE_NT; }
+
+int s2vt_tile_count(int kind) { return tile_kind_ok(kind) ? gemm_num_cfgs(kind) : S2VT_E_BADARG; }
+
+int s2vt_tile_info(int kind, int tile_cfg, s2vt_tile_desc* out)
+{
+    GemmCfgInfo g;
+    if (!out || !tile_kind_ok(kind) || !gemm_cfg_info(kind, tile_cfg, &g)) return S2VT_E_BADARG;
+    std::memset(out, 0, sizeof(*out));
+    out->rows = g.BM; out->cols = g.CG; out->fallback = g.fallback; out->has_scalar = g.has_scalar; out->has_live = g.has_live;
+    std::strncpy(out->name, g.name, sizeof(out->name) - 1);
     return S2VT_OK;
 }
 

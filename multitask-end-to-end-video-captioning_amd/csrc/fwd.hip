@@ -187,7 +187,9 @@ bool can_vec(const GemmArgs& a, bool bt)
         const ASeg& sg = a.seg[s];
         if (sg.kw + sg.k > (int)krows) krows = (size_t)(sg.kw + sg.k);
         if (!sg.ptr || sg.k <= 0 || sg.rowidx || sg.rowkey) continue;
-        const size_t rows = sg.rowmod > 0 ? (size_t)sg.rowmod : 256;    // plain segments are addressed per tile (<= 256 rows)
+        // plain segments are addressed per tile (<= 256 rows) -- but under a live-row list from the operand's base by the caller's row
+        // (gemm_mfma.h seg_base / row_offsets: orow(m)), so there the offsets span all a.M rows
+        const size_t rows = sg.rowmod > 0 ? (size_t)sg.rowmod : (a.omap ? (size_t)a.M : 256);
         if (rows * sg.ld * 4 >= (1ull << 31)) return false;
     }
     if ((bt ? (size_t)a.N : krows) * a.ldw * 4 >= (1ull << 31)) return false;
@@ -345,6 +347,15 @@ const char* gemm_cfg_name(int epi, int cfg)
     int n;
     const CfgEntry* t = table(epi, &n);
     return (cfg >= 0 && cfg < n) ? t[cfg].name : "?";
+}
+
+bool gemm_cfg_info(int epi, int cfg, GemmCfgInfo* out)
+{
+    int n;
+    const CfgEntry* t = table(epi, &n);
+    if (cfg < 0 || cfg >= n || !out) return false;
+    *out = GemmCfgInfo{t[cfg].name, t[cfg].BM, t[cfg].CG, t[cfg].fallback, t[cfg].scalar != nullptr, t[cfg].vec_om != nullptr};
+    return true;
 }
 
 hipError_t launch_gemm(const GemmArgs& a, int epi, int cfg, hipStream_t st)

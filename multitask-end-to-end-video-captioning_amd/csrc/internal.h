@@ -24,6 +24,10 @@ hipError_t prof_events(hipEvent_t* e0, hipEvent_t* e1);
 int prof_collect(ProfRow* rows, int max_rows);
 int gemm_num_cfgs(int epi);
 const char* gemm_cfg_name(int epi, int cfg);
+// one entry of a tile table as launch_gemm sees it: rows x columns (per group) of the workgroup's tile, the entry that takes the launch when
+// this one lacks the form asked for (-1: none), whether it has a scalar form and a live-row form (GemmArgs::omap / m_dev) of its own
+struct GemmCfgInfo { const char* name; int BM, CG, fallback; bool has_scalar, has_live; };
+bool gemm_cfg_info(int epi, int cfg, GemmCfgInfo* out);
 
 // C[Kout, N] (+)= sum_m A[row(m), k] * B[m, n]   (weight gradients; order-free, fp32 MFMA)
 struct TnArgs {

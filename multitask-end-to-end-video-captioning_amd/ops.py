@@ -355,6 +355,64 @@ def vocab_pick(out2, W, b, video_id, sample_id, step, seed, want_logits=False, t
     return tok, logits, packed
 
 
+def tile_count(kind: int) -> int:
+    """Entries of a tile table (kind = the profiler's kernel_class: _lib.TILE_STORE / TILE_LSTM / TILE_PICK / TILE_STORE_NT)."""
+    n = lib().s2vt_tile_count(kind)
+    if n < 0:
+        check(n, "s2vt_tile_count")
+    return n
+
+
+def tile_info(kind: int, tile_cfg: int) -> dict:
+    """Entry tile_cfg of a tile table: rows, cols, name, fallback (-1: none), has_scalar, has_live."""
+    d = _lib.TileDesc()
+    check(lib().s2vt_tile_info(kind, tile_cfg, C.byref(d)), "s2vt_tile_info")
+    return dict(rows=d.rows, cols=d.cols, name=d.name.decode(), fallback=d.fallback, has_scalar=bool(d.has_scalar), has_live=bool(d.has_live))
+
+
+def _chk_live(live, n_live):
+    for t in (live, n_live):
+        if t is not None:
+            assert t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()
+
+
+def gemm_live(segs, W, out, live=None, n_live=None, bias=None, cinit=None, act_tanh=False, tile_cfg=-1):
+    """s2vt_gemm on the rows live[0 .. n_live) of `out` ([M, N]: M is the capacity); the other rows of `out` are left as they are."""
+    _chk_f32(W, bias, cinit, out)
+    _chk_live(live, n_live)
+    assert W.dim() == 2 and W.stride(1) == 1 and out.stride(1) == 1
+    M, N = out.shape[0], W.shape[1]
+    arr = (Operand * len(segs))(*segs)
+    check(lib().s2vt_gemm_live(arr, len(segs), _ptr(W), W.stride(0), _ptr(bias), _ptr(cinit), 0 if cinit is None else cinit.stride(0),
+                               _ptr(out), out.stride(0), M, N, int(act_tanh), _ptr(live), _ptr(n_live), tile_cfg, _stream()), "s2vt_gemm_live")
+    return out
+
+
+def lstm_cell_fwd_live(x0, x1, h_prev, c_prev, W, b, c_new, h_new, out, gates=None, live=None, n_live=None, state_rowmod=0, keep=1.0, seed=0,
+                       video_id=None, sample_id=None, drop_code=0, tile_cfg=-1, res=None):
+    """The cell step (plain, or residual when res is given) on the rows live[0 .. n_live) of c_new / h_new / out / gates ([M, .])."""
+    _chk_f32(h_prev, c_prev, W, b, c_new, h_new, out, gates)
+    _chk_live(live, n_live)
+    M, H = c_new.shape[0], W.shape[1] // 4
+    check(lib().s2vt_lstm_cell_fwd_live(None if x0 is None else C.byref(x0), None if x1 is None else C.byref(x1), _ptr(h_prev), _ptr(c_prev),
+                                        state_rowmod, _ptr(W), _ptr(b), None if res is None else C.byref(res), _ptr(c_new), _ptr(h_new),
+                                        _ptr(out), _ptr(gates), M, H, float(keep), seed, _ptr(video_id), _ptr(sample_id), drop_code,
+                                        _ptr(live), _ptr(n_live), tile_cfg, _stream()), "s2vt_lstm_cell_fwd_live")
+    return c_new, h_new, out, gates
+
+
+def vocab_pick_live(out2, W, b, video_id, sample_id, step, seed, packed, live=None, n_live=None, pick_stride=1, logits=None, tile_cfg=-1):
+    """s2vt_vocab_pick on the rows live[0 .. n_live): packed[r * pick_stride] (zero on entry for those rows) receives row r's word,
+    whose low half is ~token; logits (optional, [M, V]) its logits."""
+    _chk_f32(out2, W, b, logits)
+    _chk_live(live, n_live)
+    M, H = out2.shape
+    check(lib().s2vt_vocab_pick_live(_ptr(out2), out2.stride(0), _ptr(W), _ptr(b), M, H, W.shape[1], _ptr(video_id), _ptr(sample_id), step,
+                                     seed, _ptr(packed), pick_stride, _ptr(logits), _ptr(live), _ptr(n_live), tile_cfg, _stream()),
+          "s2vt_vocab_pick_live")
+    return packed, logits
+
+
 def frame_embed_fwd(dims: Dims, params: Params, video):
     _chk_f32(video)
     B = video.shape[0]

@@ -10,7 +10,9 @@ kernel that loads outside its input reads a NaN, which poisons the result the te
 Index arrays that a kernel follows to an address (rowidx, video_id, sample_id) take `fill=<a valid index>`: their guards then hold
 that in-range integer instead of the NaN bits, so that a read past the array can never become a wild address; assert_intact()
 compares with the same value.  int64 windows (the packed pick words) are guarded with the 32-bit sentinel in both halves.
-reset() puts the sentinel back into the window as well, for an output that several launches write in turn.
+reset() puts the sentinel back into the window as well, for an output that several launches write in turn; image(rows, values) is
+then what the whole allocation must hold after a launch that writes those rows of the window only, and assert_image() compares with it
+in one go (rows the launch must leave alone, pads and guards alike).
 
 A plain module (not a conftest, no fixtures); works on CPU tensors as well, where tests/test_guardband_cpu.py checks it."""
 import ctypes
@@ -81,6 +83,31 @@ class Guarded:
     def bits(self):
         """The window's bit patterns as a host integer array."""
         return self._iview.cpu().numpy()
+
+    def image(self, rows=None, values=None):
+        """The bits of the WHOLE allocation after reset() and a launch that wrote `values` ([len(rows), cols] floats, or integers given as
+        their bits) into the window's `rows` and nothing else -- sentinels everywhere else, the window's other rows included."""
+        img = torch.full_like(self._ibuf, self._sentinel)
+        if rows is not None and len(rows):
+            v = np.ascontiguousarray(values)
+            itype = {8: np.int64, 4: np.int32, 2: np.int16}[img.element_size()]
+            v = v.view(itype) if v.dtype.itemsize == img.element_size() else v.astype(itype)
+            v = torch.as_tensor(v).reshape(len(rows), self.cols).to(img.device)
+            win = img[self.lead:self.lead + self.rows * self.ld].view(self.rows, self.ld)[:, :self.cols]
+            win[torch.as_tensor(np.asarray(rows, np.int64), device=img.device)] = v
+        return img
+
+    def assert_image(self, img, what=""):
+        """The allocation holds exactly img (one comparison on the device); names the first element that does not."""
+        if torch.equal(self._ibuf, img):
+            return
+        diff = self._ibuf != img
+        off = int(diff.nonzero()[0, 0])
+        rel = off - self.lead
+        inside = 0 <= rel < self.rows * self.ld and rel % self.ld < self.cols
+        where = f"window row {rel // self.ld}, column {rel % self.ld}" if inside else self._where(off)
+        raise AssertionError(f"{self.name} {what}: {int(diff.sum())} element(s) differ, the first at flat offset {off}: {where}; "
+                             f"bits {int(self._ibuf[off]):#x}, expected {int(img[off]):#x} (sentinel {self._sentinel:#x})")
 
     def _where(self, off):
         if off < self.lead:

@@ -115,12 +115,13 @@ def test_gemm_all_tiles_guarded(gpu, gemm_refs, form, M, K, N, variant):
     assert gA.aligned16 == (variant != "mis:A") and gW.aligned16 == (variant != "mis:W") and out.aligned16 == (variant != "mis:C")
     scalar = kind in ("odd-ld", "mis") and target in ("A", "W")               # what can_vec() refuses; C / Cinit / bias are scalar accesses
     segs = (type(_operand(gA)) * 1)(_operand(gA))
-    for cfg in range(-1, 12):
+    n_cfgs = gpu.tile_count(4 if nt else 0)
+    for cfg in range(-1, n_cfgs + 1):                                         # every entry of the table; the count itself = out of range = auto
         for mode in ("bias", "tanh", "cinit"):
             out.reset()
             call = lambda: fn(segs, 1, gW.ptr, gW.ld, None if mode == "cinit" else gb.ptr, gCi.ptr if mode == "cinit" else None,
                               gCi.ld if mode == "cinit" else 0, out.ptr, out.ld, M, N, int(mode == "tanh"), cfg, st)
-            if cfg >= 8 and mode == "bias":
+            if 8 <= cfg < n_cfgs and mode == "bias":
                 want = STORE_NAMES[STORE_FALLBACK[cfg] if scalar else cfg]
                 assert _tile_of(gpu, 4 if nt else 0, call) == ("nt" if nt else "") + want, (cfg, variant)
             else:
@@ -242,7 +243,7 @@ def lstm_refs(oracle):
 @pytest.mark.parametrize("variant", ["dense", "strided", "odd-ld:x0", "mis:x0"])
 @pytest.mark.parametrize("M,E,H", LSTM_SHAPES)
 def test_lstm_cell_all_tiles_guarded(gpu, lstm_refs, M, E, H, variant):
-    """Every entry of fwd.hip kLstm (and -1 / 19 = auto): c_new, h_new, out and gates bit for bit against oracle.lstm1_step, nothing
+    """Every entry of fwd.hip kLstm (and -1 / the table's size = auto): c_new, h_new, out and gates bit for bit against oracle.lstm1_step, nothing
     written in rows >= M.  W, b, c_prev and h_prev have no stride argument; x0 takes the layouts."""
     L, st = _lib(), gpu._stream()
     r = lstm_refs[(M, E, H)]
@@ -255,7 +256,7 @@ def test_lstm_cell_all_tiles_guarded(gpu, lstm_refs, M, E, H, variant):
     outs = [Guarded(M, H, name=n) for n in ("c_new", "h_new", "out")] + [Guarded(M, 4 * H, name="gates")]
     x0 = _operand(gx)
     for keep, code in LSTM_KEEP:
-        for cfg in range(-1, 19):
+        for cfg in range(-1, gpu.tile_count(1) + 1):
             for o in outs:
                 o.reset()
             rc = L.s2vt_lstm_cell_fwd(C.byref(x0), None, gh.ptr, gc.ptr, 0, gW.ptr, gb.ptr, outs[0].ptr, outs[1].ptr, outs[2].ptr, outs[3].ptr,
@@ -287,7 +288,7 @@ def pick_refs(oracle):
 @pytest.mark.parametrize("variant", ["dense", "strided", "odd-ld:out2", "mis:out2"])
 @pytest.mark.parametrize("M,H,V", PICK_SHAPES)
 def test_vocab_pick_all_tiles_guarded(gpu, pick_refs, M, H, V, variant):
-    """Every entry of fwd.hip kPick (and -1 / 15 = auto), with and without logits_out: ids and logits bit for bit against
+    """Every entry of fwd.hip kPick (and -1 / the table's size = auto), with and without logits_out: ids and logits bit for bit against
     oracle.pick_tokens; packed (one 8-byte word per row, zero on entry), tokens_out and logits_out keep their guards."""
     import torch
     L, st = _lib(), gpu._stream()
@@ -299,7 +300,7 @@ def test_vocab_pick_all_tiles_guarded(gpu, pick_refs, M, H, V, variant):
     gvid, gsid = _index(r["vid"], 0, "video_id"), _index(r["sid"], 0, "sample_id")
     packed = Guarded(1, M, dtype=torch.int64, name="packed")
     tok, logits = Guarded(1, M, dtype=torch.int32, name="tokens_out"), Guarded(M, V, name="logits_out")
-    for cfg in range(-1, 16):
+    for cfg in range(-1, gpu.tile_count(2) + 1):
         for want_logits in (True, False):
             packed.reset(); packed.view.zero_(); tok.reset(); logits.reset()
             rc = L.s2vt_vocab_pick(go.ptr, go.ld, gW.ptr, gb.ptr, M, H, V, gvid.ptr, gsid.ptr, 5, 2024, packed.ptr, tok.ptr,

@@ -49,7 +49,7 @@ def test_gemm_bitwise_all_tiles(gpu, oracle, M, K, N):
     b = rng.standard_normal(N).astype(np.float32)
     ref = oracle.bias_add(oracle.gemm_chain(A, W), b)
     dA, dW, db = _dev(A), _dev(W), _dev(b)
-    for cfg in range(-1, 12):                           # every entry of fwd.hip kStore (64x96, 96x96, 96x128; 8-11: the LDS-DMA ring tiles)
+    for cfg in range(-1, gpu.tile_count(0) + 1):        # every entry of fwd.hip kStore (8-11: the LDS-DMA ring tiles); the count itself = out of range = auto
         C = gpu.gemm([gpu.operand(dA)], dW, db, M=M, tile_cfg=cfg).cpu().numpy()
         assert np.array_equal(C, ref), f"tile cfg {cfg}"
     ref_t = oracle.det_tanh(ref)
@@ -92,7 +92,7 @@ def test_lstm_cell_bitwise(gpu, oracle, M, E, H):
     for keep, code in ((1.0, 0), (0.9, 258), (0.5, 600)):
         mask = None if keep >= 1 else oracle.dropout_mask(77, vid, sid, code, keep, H)
         rc, rh, rout, rg, _ = oracle.lstm1_step(p, x, c, h, mask, keep, want_gates=True)
-        for cfg in range(-1, 18):                     # every tile of the table (12-16: the LDS-DMA ring tiles of round 6), 17 = out of range = auto
+        for cfg in range(-1, gpu.tile_count(1) + 1):  # every entry of fwd.hip kLstm (12 and up: the LDS-DMA ring tiles); the count itself = out of range = auto
             gc, gh, gout, gg = gpu.lstm_cell_fwd(gpu.operand(_dev(x)), None, _dev(h), _dev(c), _dev(W), _dev(b), M, keep=keep,
                                                  seed=77, video_id=_dev(vid), sample_id=_dev(sid), drop_code=code,
                                                  want_gates=True, tile_cfg=cfg)
@@ -113,7 +113,7 @@ def test_vocab_pick_bitwise(gpu, oracle, M, H, V):
     vid = rng.integers(0, 500, M).astype(np.int32); sid = rng.integers(-1, 4, M).astype(np.int32)
     logits = oracle.xw_plus_b(o2, W, b)
     ref = oracle.pick_tokens(logits, vid, sid, 5, 2024)
-    for cfg in range(-1, 16):                          # every entry of fwd.hip kPick (7-14: LDS-DMA ring); 15 = out of range = auto
+    for cfg in range(-1, gpu.tile_count(2) + 1):       # every entry of fwd.hip kPick (7 and up: LDS-DMA ring); the count itself = out of range = auto
         tok, gl, _ = gpu.vocab_pick(_dev(o2), _dev(W), _dev(b), _dev(vid), _dev(sid), 5, 2024, want_logits=True, tile_cfg=cfg)
         assert np.array_equal(gl.cpu().numpy(), logits), cfg
         assert np.array_equal(tok.cpu().numpy(), ref), cfg
@@ -124,7 +124,7 @@ def test_vocab_pick_ties_lowest_index(gpu, oracle):
     o2 = np.zeros((M, H), np.float32); W = np.zeros((H, V), np.float32); b = np.zeros(V, np.float32)
     b[[40, 41, 200, 299]] = 3.0                        # exact ties across lanes, sub-tiles and tiles
     vid = np.zeros(M, np.int32); sid = -np.ones(M, np.int32)
-    for cfg in range(-1, 16):                          # every entry of fwd.hip kPick (7-14: LDS-DMA ring); 15 = out of range = auto
+    for cfg in range(-1, gpu.tile_count(2) + 1):       # every entry of fwd.hip kPick (7 and up: LDS-DMA ring); the count itself = out of range = auto
         tok, _, _ = gpu.vocab_pick(_dev(o2), _dev(W), _dev(b), _dev(vid), _dev(sid), 0, 1, tile_cfg=cfg)
         assert tok.cpu().numpy().tolist() == [40] * M
 
@@ -185,7 +185,7 @@ def test_gemm_nt_bitwise_all_tiles(gpu, oracle, M, K, N):
     b = rng.standard_normal(N).astype(np.float32)
     ref = oracle.bias_add(oracle.gemm_chain(A, np.ascontiguousarray(Wt.T)), b)
     dA, dWt, db = _dev(A), _dev(Wt), _dev(b)
-    for cfg in range(-1, 12):                           # (8-11: the LDS-DMA ring tiles with the W^T image)
+    for cfg in range(-1, gpu.tile_count(4) + 1):        # every entry of fwd.hip kStoreNT (8-11: the LDS-DMA ring tiles with the W^T image) + auto
         C = gpu.gemm_nt([gpu.operand(dA)], dWt, db, M=M, tile_cfg=cfg).cpu().numpy()
         assert np.array_equal(C, ref), f"tile cfg {cfg}"
     if K >= 8 and K % 8 == 0:                           # two K segments + a carried partial

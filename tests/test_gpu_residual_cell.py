@@ -8,7 +8,6 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
-N_CFGS = 19                                  # entries of fwd.hip kLstm; N_CFGS itself = out of range = the library's choice, as -1
 # (M, E, H): one ragged tile; exact 64-row tiles; a ragged last tile of every row count; two 96-row tiles + 8 rows; the bench width
 SHAPES = [(5, 3, 4), (64, 32, 64), (70, 12, 20), (200, 8, 36), (96, 500, 1000)]
 
@@ -44,7 +43,7 @@ def test_cell_with_residual_operand_all_tiles(gpu, oracle, M, E, H):
         pc, ph, pout, pg = gpu.lstm_cell_fwd(gpu.operand(dx), None, dh, dc, dW, db, M, keep=keep, seed=77, video_id=dvid, sample_id=dsid,
                                              drop_code=code, want_gates=True)
         assert np.array_equal(pout.cpu().numpy(), rout)
-        for cfg in range(-1, N_CFGS + 1):
+        for cfg in range(-1, gpu.tile_count(1) + 1):       # every entry of fwd.hip kLstm; the count itself = out of range = the library's choice, as -1
             name, given, mod, idx, rows = variants[(cfg + 1) % len(variants)] if H >= 1000 else (None,) * 5
             for v in (variants if name is None else [(name, given, mod, idx, rows)]):       # (the widest shape: the variants take turns)
                 name, given, mod, idx, rows = v
@@ -61,10 +60,9 @@ def test_cell_with_residual_operand_all_tiles(gpu, oracle, M, E, H):
 
 def test_operand_and_state_broadcast_over_sample_blocks(gpu, oracle):
     """The single-op call as the sampler's first step uses it: the state and the residual operand of B videos broadcast over the sample
-    blocks (state_rowmod, res rowmod).  No single-op entry point takes a live-row list, so the live-row (OM) residual instantiations are
-    launched through the early-exit sampler only: tests/test_gpu_residual_sample.py::test_stop_at_eos..., vector path on the issue's
-    shapes (32-row tile above 64 rows, the cost model's tile below) and scalar path on `odd-dims`.  Of the 62 residual instantiations the
-    live-row forms of the OTHER tiles (those the early-exit mode does not pick) are compiled and have no launch in the suite."""
+    blocks (state_rowmod, res rowmod).  The live-row (OM) residual instantiations -- what the early-exit sampler launches for the tiles it
+    picks, tests/test_gpu_residual_sample.py::test_stop_at_eos... -- are launched for EVERY tile of the table, vector and scalar path, through
+    s2vt_lstm_cell_fwd_live in tests/test_gpu_live_tiles.py::test_cell_tiles."""
     M, E, H, B = 12, 6, 20, 3
     W, b, x, c, h, vid, sid, _ = _inputs(M, E, H)
     p = {"lstm1_W": W, "lstm1_b": b}

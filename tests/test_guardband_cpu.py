@@ -119,3 +119,31 @@ def test_reset_poisons_the_window():
     g.reset()
     assert (g.bits() == SENTINEL32).all() and np.isnan(g.numpy()).all()
     g.assert_intact()
+
+
+@pytest.mark.parametrize("dtype,ld", [(torch.float32, 9), (torch.int32, 6), (torch.int64, 16)])
+def test_image_is_the_whole_allocation_after_writing_some_rows(dtype, ld):
+    """image(rows, values): those rows of the window, the sentinel everywhere else -- the window's other rows included; assert_image
+    passes on exactly that and names a row that was written though it is not listed, a listed row that was not, and a guard."""
+    cols = 6 if dtype != torch.int64 else 1
+    g = Guarded(5, cols, ld=ld, dtype=dtype, lead=65, device="cpu")
+    vals = np.arange(2 * cols).reshape(2, cols).astype({torch.float32: np.float32, torch.int32: np.int32, torch.int64: np.int64}[dtype])
+    img = g.image([1, 3], vals)
+    assert img.numel() == g._buf.numel() and int((img != g._sentinel).sum()) == 2 * cols
+    assert torch.equal(g.image(), torch.full_like(g._ibuf, g._sentinel)) and torch.equal(g.image([], vals[:0]), g.image())
+    g.reset()
+    g.assert_image(g.image())
+    g.view[torch.tensor([1, 3])] = torch.as_tensor(vals)
+    g.assert_image(img)
+    g.assert_intact()
+    g.view[4, 0] = 7                                                   # a row that is not listed
+    with pytest.raises(AssertionError, match="window row 4, column 0"):
+        g.assert_image(img)
+    g.reset()
+    g.view[1] = torch.as_tensor(vals[0])                               # row 3 was never written
+    with pytest.raises(AssertionError, match="window row 3, column 0"):
+        g.assert_image(img)
+    g.view[3] = torch.as_tensor(vals[1])
+    g._ibuf[64] = 0                                                    # the last guard element in front of the window
+    with pytest.raises(AssertionError, match="lead guard, 1 element"):
+        g.assert_image(img)

@@ -137,6 +137,72 @@ def test_lstm_cell_fwd_res_argument_checks():
     assert L.s2vt_lstm_cell_fwd_res(None, None, ONE, ONE, 0, ONE, ONE, ctypes.byref(good), ONE, ONE, ONE, None, 0, H, 1.0, 0, None, None, 0, -1, None) == 0   # M = 0: nothing to do
 
 
+def test_live_row_entries_argument_checks():
+    """s2vt_gemm_live, s2vt_lstm_cell_fwd_live, s2vt_vocab_pick_live: the dense entries' refusals, the residual operand's, and a row list
+    and a count that are both absent -- all before any device work; M == 0 is nothing to do."""
+    L = s2vt_amd.lib()
+    H, M, K, N, V = 8, 4, 6, 12, 20
+    seg = lambda ptr=256, ld=K, k=K: (_lib.Operand * 1)(_lib.Operand(ptr, None, ld, k, 0, 0))
+    gemm = lambda segs=seg(), nseg=1, W=ONE, ldw=N, C=ONE, ldc=N, M=M, live=ONE, n_live=ONE, ldci=N, Cinit=None: L.s2vt_gemm_live(
+        segs, nseg, W, ldw, None, Cinit, ldci, C, ldc, M, N, 0, live, n_live, -1, None)
+    assert gemm(segs=None) == BADARG and gemm(W=None) == BADARG and gemm(C=None) == BADARG          # NULL operands
+    assert gemm(nseg=0) == BADARG and gemm(nseg=4) == BADARG and gemm(M=-1) == BADARG
+    assert gemm(live=None, n_live=None) == BADARG                                                   # neither a list nor a count
+    assert gemm(segs=seg(ld=K - 1)) == BADARG                                                       # ld < k
+    assert gemm(ldw=N - 1) == BADARG and gemm(ldc=N - 1) == BADARG and gemm(Cinit=ONE, ldci=N - 1) == BADARG
+    assert gemm(M=0) == 0 and gemm(M=0, live=None) == 0 and gemm(M=0, n_live=None) == 0
+
+    good = _lib.Operand(256, None, H, H, 0, 0)
+    x0 = _lib.Operand(256, None, K, K, 0, 0)
+    def cell(res=None, out=ONE, h=ONE, c=ONE, W=ONE, b=ONE, cn=ONE, hn=ONE, M=M, live=ONE, n_live=ONE, x=x0, keep=1.0, vid=None):
+        return L.s2vt_lstm_cell_fwd_live(ctypes.byref(x), None, h, c, 0, W, b, res, cn, hn, out, None, M, H, keep, 0, vid, vid, 0, live, n_live, -1, None)
+    for name in ("h", "c", "W", "b", "cn", "hn"):
+        assert cell(**{name: None}) == BADARG, name                                                 # NULL operands
+    assert cell(live=None, n_live=None) == BADARG
+    assert cell(x=_lib.Operand(256, None, K - 1, K, 0, 0)) == BADARG                                # ld < k
+    assert cell(keep=0.5) == BADARG and cell(keep=0.5, vid=ONE, out=None) == BADARG                 # dropout needs the ids and `out`
+    assert cell(M=-1) == BADARG
+    # the residual operand: optional here, checked as s2vt_lstm_cell_fwd_res checks it when given
+    assert cell(ctypes.byref(_lib.Operand(None, None, H, H, 0, 0))) == BADARG                       # res->ptr NULL
+    assert cell(ctypes.byref(_lib.Operand(256, None, H, H - 1, 0, 0))) == BADARG                    # k != H
+    assert cell(ctypes.byref(_lib.Operand(256, None, H, H + 4, 0, 0))) == BADARG
+    assert cell(ctypes.byref(_lib.Operand(256, None, H - 1, H, 0, 0))) == BADARG                    # ld < H
+    assert cell(ctypes.byref(_lib.Operand(256, None, H, H, -1, 0))) == BADARG                       # rowmod < 0
+    assert cell(ctypes.byref(good), out=None) == BADARG                                             # out NULL
+    assert cell(M=0) == 0 and cell(ctypes.byref(good), M=0) == 0 and cell(M=0, live=None) == 0 and cell(M=0, n_live=None) == 0
+
+    def pick(o2=ONE, ld=H, W=ONE, b=ONE, vid=ONE, sid=ONE, packed=ONE, stride=16, M=M, live=ONE, n_live=ONE, H=H, V=V):
+        return L.s2vt_vocab_pick_live(o2, ld, W, b, M, H, V, vid, sid, 0, 0, packed, stride, None, live, n_live, -1, None)
+    for name in ("o2", "W", "b", "vid", "sid", "packed"):
+        assert pick(**{name: None}) == BADARG, name                                                 # NULL operands
+    assert pick(live=None, n_live=None) == BADARG
+    assert pick(ld=H - 1) == BADARG and pick(stride=0) == BADARG and pick(stride=-1) == BADARG
+    assert pick(M=-1) == BADARG and pick(H=0, ld=0) == BADARG and pick(V=0) == BADARG
+    assert pick(M=0) == 0 and pick(M=0, live=None) == 0 and pick(M=0, n_live=None) == 0
+
+
+def test_tile_tables_are_described_without_a_gpu():
+    from s2vt_amd import ops
+    L = s2vt_amd.lib()
+    assert L.s2vt_tile_count(3) == BADARG and L.s2vt_tile_count(-1) == BADARG and L.s2vt_tile_count(5) == BADARG
+    d = _lib.TileDesc()
+    assert L.s2vt_tile_info(0, 0, None) == BADARG and L.s2vt_tile_info(3, 0, ctypes.byref(d)) == BADARG
+    assert ops.tile_count(_lib.TILE_STORE) == ops.tile_count(_lib.TILE_STORE_NT)                    # index-compatible tables
+    for kind in (_lib.TILE_STORE, _lib.TILE_LSTM, _lib.TILE_PICK, _lib.TILE_STORE_NT):
+        n = ops.tile_count(kind)
+        assert n >= 8 and L.s2vt_tile_info(kind, n, ctypes.byref(d)) == BADARG and L.s2vt_tile_info(kind, -1, ctypes.byref(d)) == BADARG
+        infos = [ops.tile_info(kind, i) for i in range(n)]
+        assert len({t["name"] for t in infos}) == n
+        for t in infos:
+            assert t["rows"] % 16 == 0 and t["rows"] > 0 and t["cols"] % 16 == 0 and t["cols"] > 0
+            assert t["has_scalar"] == (t["fallback"] < 0)                                           # only the LDS-DMA entries lack a scalar form
+            if t["fallback"] >= 0:                                                                  # a fallback has every form its table has
+                f = infos[t["fallback"]]
+                assert f["fallback"] < 0 and f["has_scalar"] and (f["has_live"] or kind == _lib.TILE_STORE_NT)
+            assert t["has_live"] or t["fallback"] >= 0 or kind == _lib.TILE_STORE_NT
+        assert not any(t["has_live"] for t in infos) if kind == _lib.TILE_STORE_NT else any(t["has_live"] for t in infos)
+
+
 def _model(residual, **kw):
     from s2vt_amd import model as M
     return M.Video_Caption_Generator(16, 11, 3, 4, 2, 5, 2, 3, device="cpu", seed=5, residual=residual, **kw)
