@@ -181,6 +181,24 @@ int s2vt_lstm_cell_fwd_res(const s2vt_operand* x0, const s2vt_operand* x1, const
                            float* out, float* gates, int32_t M, int32_t H, float keep, uint64_t seed, const int32_t* video_id,
                            const int32_t* sample_id, uint32_t drop_code, int32_t tile_cfg, s2vt_stream stream);
 
+/* The gathered-state form of the cell, one decode step of a beam search: every launch row reads its state and its carried partial
+ * through index arrays (device, int32 [M]), with no gathered copy of either.
+ *   z[m] = Cinit[cinit_rowidx[m]] + [x0 ; x1 ; h_prev[state_rowidx[m]]] @ W, the chain continued from the partial in ascending k, then the
+ *   bias and the pointwise cell on c_prev[state_rowidx[m]]; there is no dropout (a decode step never drops), `out` does not exist.
+ * state_rowidx NULL: row m of h_prev / c_prev.  Cinit NULL: the chain starts from +0 (cinit_rowidx is ignored); cinit_rowidx NULL: row m
+ * of Cinit (rows ldcinit >= 4H floats apart).  Indices are NOT checked: every one must name a row of its array.  With identity maps and no
+ * Cinit the results are s2vt_lstm_cell_fwd's, bit for bit.
+ * With state_rowidx another workgroup may own the source row of a launch row, so the state cannot be advanced in place: c_new / h_new
+ * [M, H] must not overlap ANY part of c_prev / h_prev (equal pointers are S2VT_E_BADARG; partial overlap is the caller's to avoid).
+ * S2VT_E_BADARG also for NULL h_prev / c_prev / W / b / c_new / h_new, M < 0, H <= 0, ldcinit < 4H with Cinit.  M == 0: S2VT_OK.
+ * tile_cfg as in s2vt_lstm_cell_fwd (kind 1 of s2vt_tile_count).  Every cell tile has this form on the 16-byte path.  Off it (H % 4 != 0
+ * or unaligned operands) one tile has none: a launch forced onto gw16x16u(1x4)k64 runs gw16x16u(1x4), the 32-deep tile of the same 16 rows,
+ * as the tiles with has_scalar == 0 hand theirs to `fallback`; s2vt_tile_info does not report it, and the results are the same bits. */
+int s2vt_lstm_cell_fwd_gather(const s2vt_operand* x0, const s2vt_operand* x1, const float* h_prev, const float* c_prev,
+                              const int32_t* state_rowidx, const float* Cinit, int32_t ldcinit, const int32_t* cinit_rowidx, const float* W,
+                              const float* b, float* c_new, float* h_new, float* gates, int32_t M, int32_t H, int32_t tile_cfg,
+                              s2vt_stream stream);
+
 /* ---- vocab logits + token pick, one decode step ---------------------------------------------
  * logits = out2 @ embed_word_W + embed_word_b (tf_s2vt.py:153); token = tf.argmax(logits,1) for
  * rows with sample_id < 0 (tf_s2vt.py:262) or one draw of tf.multinomial(log_softmax(logits),1)
@@ -926,6 +944,29 @@ size_t s2vt_bidir_sample_workspace_bytes(const s2vt_dims* d, int32_t B, int32_t 
 int s2vt_bidir_sample(const s2vt_dims* d, const s2vt_bidir_params* p, const float* video, int32_t B, int32_t K, int32_t with_greedy, uint64_t seed,
                       int32_t video_base, int32_t lstm1_form, int32_t* sampled_out, int32_t* greedy_out, void* workspace, size_t workspace_bytes,
                       s2vt_stream stream);
+/* ---- batched beam search on that model: the s2vt_beam_* family (above) for the bidirectional captioner, same conventions as the other
+ * s2vt_bidir_* drivers (size function 0 on bad shapes; 1 <= beam <= 16).  No word enters LSTM1, so every hypothesis of a video shares both
+ * LSTM1 directions and [fw ; bw] @ W2[:2H]; only the fused LSTM2 cell launch and the vocabulary product run on the R <= B * beam rows.
+ * s2vt_bidir_beam_encode: exactly the once-per-video prefix of s2vt_bidir_sample -- LSTM1, the 2H-row partial of all T steps, LSTM2's Tv
+ *   encode steps as one recurrence.  S2VT_E_CHAIN_TIMEOUT while a chain fault is pending.
+ * s2vt_bidir_beam_step: s2vt_beam_step's semantics -- decode step t (0 <= t < Tc) for R live hypotheses; hypothesis m continues video
+ *   video_of_row[m] from row parent[m] of step t - 1 (t = 0: the video's encoder state, parent ignored) with word[m] (<bos> = 1 at t = 0).
+ *   The three int32 [R] arrays are device pointers; indices out of range are clamped, not reported.  A parent is clamped into
+ *   [0, B * beam), the parity buffer's rows, not into step t - 1's R (which the call does not know): one at or past that R cannot fault,
+ *   but it reads a row that an earlier step or nothing wrote, and the row's results mean nothing.  R == 0: S2VT_OK.  Steps are issued in
+ *   order.  Writes top_ids / top_logp [R, k] (s2vt_vocab_topk of the step's logits; 1 <= k <= 16, k <= n_words) and, when logits_out is
+ *   given, the logits [R, V].  Launches: one index kernel (the clamped [3][R] block into the workspace), ONE gathered-state cell launch (Wemb
+ *   rows by word, h / c by parent, the partial of step Tv + t by video -- no gathered copy of state or partial), the vocabulary product
+ *   on h', the top-k.  LSTM2's state lives in two parity buffers [B * beam, H] (c | h): step t writes parity t & 1 and reads the other, so
+ *   issuing step t twice gives the same bits.
+ * Workspace: s2vt_bidir_decode_workspace_bytes' encode part, then 4 * B * beam * H floats of state, B * beam * V of logits and 3 * B * beam
+ * int32, each rounded up to 256 bytes. */
+size_t s2vt_bidir_beam_workspace_bytes(const s2vt_dims* d, int32_t B, int32_t beam);
+int s2vt_bidir_beam_encode(const s2vt_dims* d, const s2vt_bidir_params* p, const float* video, int32_t B, int32_t beam, int32_t lstm1_form,
+                           void* workspace, size_t workspace_bytes, s2vt_stream stream);
+int s2vt_bidir_beam_step(const s2vt_dims* d, const s2vt_bidir_params* p, int32_t B, int32_t beam, int32_t t, int32_t R, const int32_t* video_of_row,
+                         const int32_t* parent, const int32_t* word, int32_t k, int32_t* top_ids, float* top_logp, float* logits_out,
+                         void* workspace, size_t workspace_bytes, s2vt_stream stream);
 /* The sample sum on its own: out[(t * B + b) * C + c] = sum_s dz[((t * S + s) * B + b) * C + c], s ascending, no atomics (two runs give equal
  * bits).  C % 4 == 0 and 16-byte aligned pointers (S2VT_E_ALIGN): the kernel moves 16 bytes per lane. */
 int s2vt_bidir_sample_sum(const float* dz, float* out, int32_t T, int32_t B, int32_t S, int32_t C, s2vt_stream stream);

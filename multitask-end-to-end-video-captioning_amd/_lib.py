@@ -113,6 +113,7 @@ SIGNATURES = {
     "s2vt_gemm_live": (C.c_int, [_OP, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp]),
     "s2vt_lstm_cell_fwd_live": (C.c_int, [_OP, _OP, _vp, _vp, _i32, _vp, _vp, _OP, _vp, _vp, _vp, _vp, _i32, _i32, _f32, _u64, _vp,
                                           _vp, _u32, _vp, _vp, _i32, _vp]),
+    "s2vt_lstm_cell_fwd_gather": (C.c_int, [_OP, _OP, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "s2vt_vocab_pick_live": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _i32, _u64, _vp, _i32, _vp, _vp, _vp, _i32, _vp]),
     "s2vt_frame_embed_fwd": (C.c_int, [_DP, _PP, _vp, _i32, _vp, _vp]),
     "s2vt_sample_workspace_bytes": (_sz, [_DP, _i32, _i32, _i32]),
@@ -213,6 +214,9 @@ SIGNATURES = {
     "s2vt_bidir_decode_greedy": (C.c_int, [_DP, _BP, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
     "s2vt_bidir_sample_workspace_bytes": (_sz, [_DP, _i32, _i32, _i32]),
     "s2vt_bidir_sample": (C.c_int, [_DP, _BP, _vp, _i32, _i32, _i32, _u64, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "s2vt_bidir_beam_workspace_bytes": (_sz, [_DP, _i32, _i32]),
+    "s2vt_bidir_beam_encode": (C.c_int, [_DP, _BP, _vp, _i32, _i32, _i32, _vp, _sz, _vp]),
+    "s2vt_bidir_beam_step": (C.c_int, [_DP, _BP, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
     "s2vt_bidir_sample_sum": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "s2vt_bidir_rows_workspace_bytes": (_sz, [_DP, _i32, _i32]),
     "s2vt_bidir_teacher_forced_fwd_rows": (C.c_int, [_DP, _BP, _vp, _i32, _i32, _vp, _f32, _u64, _vp, _vp, _i32, _vp, _vp, _sz, _vp]),

@@ -1,11 +1,13 @@
 """Beam-search captions for a test set from a checkpoint (the test() of final_beam_search.py:504-545 / e2e_beam_search.py, batched):
 
     python -m s2vt_amd.beam_eval --checkpoint CKPT --test-sents SENTS --test-feats FEATS --vocab VOCAB \
-        [--beam 3] [--lnf 0.0] [--batch-size 64] [--n-caption-lstm-step 35] [--out captions.txt] [--model auto|s2vt|attention]
+        [--beam 3] [--lnf 0.0] [--batch-size 64] [--n-caption-lstm-step 35] [--out captions.txt] [--model auto|s2vt|attention|bidirectional]
 
 The checkpoint is loaded with optimistic_restore (an .npz dump or a TensorFlow checkpoint); the model's dimensions are read from
 its variables, Tv from the feature file.  The model class is read off the variable names too: a checkpoint that holds embed_att_Wa
-is the temporal-attention captioner (original_attention.py:64-86), any other the S2VT model; --model overrides the detection.  Writes one `video_id<TAB>sentence` line per test video, as the reference does (the
+is the temporal-attention captioner (original_attention.py:64-86), one that holds the forward LSTM1 cell of bidirection_tf_s2vt.py's
+static_bidirectional_rnn (bidirection.TF_NAMES["lstm1_fw_W"]) the bidirectional captioner -- an XE or a REINFORCE checkpoint of it --, any
+other the S2VT model; --model overrides the detection.  Writes one `video_id<TAB>sentence` line per test video, as the reference does (the
 caption cut at its first <eos>, <bos> / <eos> dropped), and prints the mean CIDEr-D against the test set's references."""
 from __future__ import annotations
 
@@ -44,13 +46,18 @@ def read_captions(path) -> dict:
 
 
 def model_kind(variable_names, choice="auto") -> str:
-    """"attention" or "s2vt" for a checkpoint's variable names (any iterable of names, e.g. the dict read_checkpoint returns):
-    embed_att_Wa exists only in the temporal-attention captioner.  `choice` other than "auto" wins."""
+    """"attention", "bidirectional" or "s2vt" for a checkpoint's variable names (any iterable of names, e.g. the dict read_checkpoint
+    returns): embed_att_Wa exists only in the temporal-attention captioner, the forward LSTM1 cell of a bidirectional_rnn scope only in the
+    bidirectional one.  `choice` other than "auto" wins."""
     if choice != "auto":
-        if choice not in ("s2vt", "attention"):
-            raise ValueError(f"model: {choice!r} (auto, s2vt or attention)")
+        if choice not in ("s2vt", "attention", "bidirectional"):
+            raise ValueError(f"model: {choice!r} (auto, s2vt, attention or bidirectional)")
         return choice
-    return "attention" if "embed_att_Wa" in set(variable_names) else "s2vt"
+    names = set(variable_names)
+    if "embed_att_Wa" in names:
+        return "attention"
+    from .tfckpt import BIDIRECTION_TF_NAMES
+    return "bidirectional" if BIDIRECTION_TF_NAMES["lstm1_fw_W"] in names else "s2vt"
 
 
 def main(argv=None):
@@ -62,7 +69,7 @@ def main(argv=None):
     ap.add_argument("--batch-size", type=int, default=64)
     ap.add_argument("--n-caption-lstm-step", type=int, default=35)
     ap.add_argument("--out", default="beam_captions.txt")
-    ap.add_argument("--model", choices=("auto", "s2vt", "attention"), default="auto")
+    ap.add_argument("--model", choices=("auto", "s2vt", "attention", "bidirectional"), default="auto")
     ap.add_argument("--residual", action="store_true", help="decode as the residual captioner of residual_tf_s2vt.py (an S2VT checkpoint "
                     "does not say which script trained it)")
     a = ap.parse_args(argv)
@@ -80,11 +87,17 @@ def main(argv=None):
         raise SystemExit(f"checkpoint vocabulary has {V} words, {a.vocab} gives {len(wordtoix)}")
     Tv = corpus.features.features.shape[1]
     Tc = a.n_caption_lstm_step
-    if model_kind(raw, a.model) == "attention":
+    kind = model_kind(raw, a.model)
+    if kind == "attention":
         from . import attention as A
         if a.residual:
             raise SystemExit("--residual is an S2VT variant; this checkpoint is an attention model")
         model = A.Attention_Caption_Generator(D, V, E, a.batch_size, Tv, Tc, 1.0, bias_init_vector=None)    # dim_hidden = Wemb.shape[1] (:65)
+    elif kind == "bidirectional":
+        from . import bidirection_beam as BB
+        if a.residual:
+            raise SystemExit("--residual is an S2VT variant; this checkpoint is a bidirectional model")
+        model = BB.Beam_Caption_Generator(D, V, E, H, a.batch_size, Tv + Tc, Tv, Tc, bias_init_vector=None)
     else:
         model = M.Video_Caption_Generator(D, V, E, H, a.batch_size, Tv + Tc, Tv, Tc, bias_init_vector=None, residual=a.residual)
     optimistic_restore(model, a.checkpoint)

@@ -293,6 +293,32 @@ int s2vt_lstm_cell_fwd_live(const s2vt_operand* x0, const s2vt_operand* x1, cons
                           tile_cfg, stream, res, live, n_live);
 }
 
+// ---- the gathered-state form of the cell (GemmArgs::cinit_rowidx / cprev_rowidx): what the bidirectional beam step launches
+int s2vt_lstm_cell_fwd_gather(const s2vt_operand* x0, const s2vt_operand* x1, const float* h_prev, const float* c_prev,
+                              const int32_t* state_rowidx, const float* Cinit, int32_t ldcinit, const int32_t* cinit_rowidx, const float* W,
+                              const float* b, float* c_new, float* h_new, float* gates, int32_t M, int32_t H, int32_t tile_cfg,
+                              s2vt_stream stream)
+{
+    if (!h_prev || !c_prev || !W || !b || !c_new || !h_new || M < 0 || H <= 0) return S2VT_E_BADARG;
+    if (Cinit && ldcinit < 4 * H) return S2VT_E_BADARG;
+    if (state_rowidx && (c_new == c_prev || h_new == h_prev)) return S2VT_E_BADARG;   // another workgroup owns the source row: in place is a race
+    ASeg a[3];
+    int kw = 0, n = 0;
+    const s2vt_operand* xs[2] = {x0, x1};
+    for (int i = 0; i < 2; ++i) {
+        if (!xs[i]) continue;
+        if (xs[i]->k < 0 || (xs[i]->ptr && xs[i]->ld < xs[i]->k)) return S2VT_E_BADARG;
+        seg_from_operand(a[n++], xs[i], kw);
+        kw += xs[i]->k;
+    }
+    a[n++] = make_seg(h_prev, H, H, kw, 0, state_rowidx);
+    if (M == 0) return S2VT_OK;
+    // no index at all: the plain twin (same bits); an index on either operand: the GS twin, whose other index may be NULL
+    HIP_TRY(lstm_call(a, n, W, b, c_prev, 0, c_new, h_new, nullptr, gates, M, H, 1.0f, NoiseIds{nullptr, nullptr, 0}, 0u, tile_cfg, S(stream), Cinit,
+                      Cinit ? ldcinit : 0, 0, nullptr, nullptr, nullptr, Cinit ? cinit_rowidx : nullptr, state_rowidx));
+    return S2VT_OK;
+}
+
 int s2vt_vocab_pick(const float* out2, int32_t ld, const float* W, const float* b, int32_t M, int32_t H, int32_t V,
                     const int32_t* video_id, const int32_t* sample_id, int32_t step, uint64_t seed,
                     unsigned long long* packed, int32_t* tokens_out, float* logits_out, int32_t tile_cfg,

@@ -92,7 +92,8 @@ struct NoiseIds {
 inline hipError_t lstm_call(const ASeg* segs, int nseg, const float* W, const float* b, const float* c_prev, int cprev_rowmod,
                      float* c_new, float* h_new, float* out, float* gates, int M, int H, float keep, const NoiseIds& ids,
                      uint32_t drop_code, int cfg, hipStream_t st, const float* cinit = nullptr, int ldcinit = 0,
-                     int cinit_rowmod = 0, const int* omap = nullptr, const int* m_dev = nullptr, const ASeg* res = nullptr)
+                     int cinit_rowmod = 0, const int* omap = nullptr, const int* m_dev = nullptr, const ASeg* res = nullptr,
+                     const int* cinit_rowidx = nullptr, const int* cprev_rowidx = nullptr)
 {
     GemmArgs a;
     std::memset(&a, 0, sizeof(a));
@@ -106,6 +107,7 @@ inline hipError_t lstm_call(const ASeg* segs, int nseg, const float* W, const fl
     a.cinit = cinit; a.ldcinit = ldcinit; a.cinit_rowmod = cinit_rowmod;   // a carried partial chain (hoisted input products)
     a.omap = omap; a.m_dev = m_dev;                                          // live-row launch (gemm_mfma.h)
     if (res) { a.res = res->ptr; a.res_rowidx = res->rowidx; a.res_ld = res->ld; a.res_rowmod = res->rowmod; }   // residual form: out += res[row(m)]
+    a.cinit_rowidx = cinit_rowidx; a.cprev_rowidx = cprev_rowidx;            // gathered-state form (gemm_mfma.h, GS): row -> partial, row -> c_prev
     return launch_gemm(a, EPI_LSTM, cfg, st);
 }
 

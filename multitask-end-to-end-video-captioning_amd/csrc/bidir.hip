@@ -919,3 +919,125 @@ int s2vt_bidir_bptt_bwd_rows(const s2vt_dims* d, const s2vt_bidir_params* p, con
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Batched beam search on this model (final_beam_search.py:201-294 for B videos at once, as beam.hip runs it for the S2VT models).  What a
+// hypothesis shares with its video -- both LSTM1 directions, [fw ; bw] @ W2[:2H], LSTM2's encode steps -- is s2vt_bidir_sample's prefix; a
+// decode step is that driver's fused cell launch in its gathered-state form (gemm_mfma.h, GS): the Wemb rows by word, h / c by parent and
+// the partial by video are all read through index arrays, so nothing is copied into dense scratch first.
+namespace {
+
+constexpr int kBeamTopkMax = 16;
+
+// the clamped indices of the step's R rows: idx[0][m] = video (the partial's row), idx[1][m] = the state's row (t = 0: the video, in the
+// encode history's slot Tv; else the parent, a row of the other parity buffer), idx[2][m] = the word.  Indices are device data the host
+// does not see here: out-of-range values are clamped into range, so nothing is read outside the workspace or the embedding table.
+__global__ void bidir_beam_index_kernel(const int32_t* video_of_row, const int32_t* parent, const int32_t* word, int t, int R, int B, int Rmax, int V,
+                                        int32_t* idx)
+{
+    const int m = blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= R) return;
+    int vid = video_of_row[m];
+    vid = vid < 0 ? 0 : (vid >= B ? B - 1 : vid);
+    int src = vid;
+    if (t > 0) {
+        const int par = parent[m];
+        src = par < 0 ? 0 : (par >= Rmax ? Rmax - 1 : par);
+    }
+    const int wd = word[m];
+    idx[m] = vid;
+    idx[(size_t)Rmax + m] = src;
+    idx[2 * (size_t)Rmax + m] = wd < 0 ? 0 : (wd >= V ? V - 1 : wd);
+}
+
+struct BiBeamWs {
+    BiWs b;                             // the decode workspace's encode part (bidir_carve, no gates)
+    float* st;                          // LSTM2 state of the hypotheses, two parities of (c | h) [Rmax][H]
+    float* logits;                      // [Rmax][V] (when the caller does not ask for them)
+    int32_t* idx;                       // [3][Rmax]
+};
+bool bidir_beam_shape_ok(const s2vt_dims* d, int B, int beam)
+{
+    return bidir_dims_ok(d, B) && beam >= 1 && beam <= kBeamTopkMax && (int64_t)B * beam <= 0x7fffffffLL / 4;
+}
+size_t bidir_beam_carve(const s2vt_dims* d, int B, int beam, void* base, size_t cap, BiBeamWs* w)
+{
+    const size_t Rmax = (size_t)B * beam, H = d->lstm_dim, V = d->n_words;
+    BiBeamWs t;
+    Carver c(base, cap);
+    c.off = bidir_carve(d, B, base, cap, &t.b, false);
+    t.st = c.take<float>(4 * Rmax * H);
+    t.logits = c.take<float>(Rmax * V);
+    t.idx = c.take<int32_t>(3 * Rmax);
+    if (w) *w = t;
+    return c.off;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t s2vt_bidir_beam_workspace_bytes(const s2vt_dims* d, int32_t B, int32_t beam)
+{
+    return bidir_beam_shape_ok(d, B, beam) ? bidir_beam_carve(d, B, beam, nullptr, 0, nullptr) : 0;
+}
+
+int s2vt_bidir_beam_encode(const s2vt_dims* d, const s2vt_bidir_params* p, const float* video, int32_t B, int32_t beam, int32_t lstm1_form,
+                           void* workspace, size_t workspace_bytes, s2vt_stream stream)
+{
+    if (!bidir_beam_shape_ok(d, B, beam) || !bidir_params_ok(p) || !video || !workspace || lstm1_form < -1 || lstm1_form > 2) return S2VT_E_BADARG;
+    if (reinterpret_cast<uintptr_t>(workspace) & 255u) return S2VT_E_ALIGN;
+    BiBeamWs bw;
+    if (bidir_beam_carve(d, B, beam, workspace, workspace_bytes, &bw) > workspace_bytes) return S2VT_E_WORKSPACE;
+    if (chain_fault()) return S2VT_E_CHAIN_TIMEOUT;
+    const BiWs& w = bw.b;
+    const int H = d->lstm_dim, E = d->word_dim, Tv = d->n_video_lstm_step, Tc = d->n_caption_lstm_step, T = Tv + Tc;
+    const size_t BH = (size_t)B * H;
+    hipStream_t hs = s2vt_api::S(stream);
+    // once per VIDEO, as s2vt_bidir_sample: LSTM1, [fw ; bw] @ W2[:2H] for all T steps, LSTM2's Tv encode steps
+    RC_TRY(bidir_lstm1(d, p, video, B, nullptr, w, lstm1_form, stream));
+    s2vt_operand o1[2] = {{w.H1[0] + BH, nullptr, H, H, 0, 0}, {w.H1[1] + BH, w.rev, H, H, 0, 0}};
+    RC_TRY(s2vt_gemm(o1, 2, p->lstm2_W, 4 * H, nullptr, nullptr, 0, w.P2, 4 * H, T * B, 4 * H, 0, -1, stream));
+    HIP_TRY(hipMemsetAsync(w.C2, 0, BH * 4, hs));
+    HIP_TRY(hipMemsetAsync(w.H2, 0, BH * 4, hs));
+    return s2vt_lstm_recurrence_fwd(p->lstm2_W, 2 * H + E, p->lstm2_b, w.P2, (int64_t)B * 4 * H, 4 * H, Tv, w.C2, w.H2, nullptr, nullptr, B, H, Tv, 1.0f, 0,
+                                    nullptr, nullptr, 0u, -1, w.chain, w.chain_bytes, stream);
+}
+
+int s2vt_bidir_beam_step(const s2vt_dims* d, const s2vt_bidir_params* p, int32_t B, int32_t beam, int32_t t, int32_t R, const int32_t* video_of_row,
+                         const int32_t* parent, const int32_t* word, int32_t k, int32_t* top_ids, float* top_logp, float* logits_out,
+                         void* workspace, size_t workspace_bytes, s2vt_stream stream)
+{
+    if (!bidir_beam_shape_ok(d, B, beam) || !bidir_params_ok(p) || !video_of_row || !parent || !word || !top_ids || !top_logp || !workspace)
+        return S2VT_E_BADARG;
+    if (t < 0 || t >= d->n_caption_lstm_step || R < 0 || R > B * beam || k < 1 || k > kBeamTopkMax || k > d->n_words) return S2VT_E_BADARG;
+    if (reinterpret_cast<uintptr_t>(workspace) & 255u) return S2VT_E_ALIGN;
+    BiBeamWs bw;
+    if (bidir_beam_carve(d, B, beam, workspace, workspace_bytes, &bw) > workspace_bytes) return S2VT_E_WORKSPACE;
+    if (R == 0) return S2VT_OK;
+    const BiWs& w = bw.b;
+    const int H = d->lstm_dim, E = d->word_dim, Tv = d->n_video_lstm_step, V = d->n_words, Rmax = B * beam;
+    const size_t BH = (size_t)B * H, RH = (size_t)Rmax * H;
+    hipStream_t hs = s2vt_api::S(stream);
+    // 1. the clamped [3][R] indices
+    hipLaunchKernelGGL(bidir_beam_index_kernel, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, hs, video_of_row, parent, word, (int)t, (int)R, (int)B,
+                       Rmax, V, bw.idx);
+    HIP_TRY(hipGetLastError());
+    const int32_t *vid = bw.idx, *src = bw.idx + Rmax, *wd = bw.idx + 2 * (size_t)Rmax;
+    // 2. the fused cell launch, gathered-state form: step t writes parity t & 1 and reads the other (step 0: slot Tv of the encode history)
+    float* cn = bw.st + (size_t)(t & 1) * 2 * RH;
+    float* hn = cn + RH;
+    const float* cprev = t == 0 ? w.C2 + (size_t)Tv * BH : bw.st + (size_t)((t - 1) & 1) * 2 * RH;
+    const float* hprev = t == 0 ? w.H2 + (size_t)Tv * BH : cprev + RH;
+    ASeg segs[2] = {make_seg(p->Wemb, E, E, 2 * H, 0, wd), make_seg(hprev, H, H, 2 * H + E, 0, src)};
+    HIP_TRY(lstm_call(segs, 2, p->lstm2_W, p->lstm2_b, cprev, 0, cn, hn, nullptr, nullptr, R, H, 1.0f, NoiseIds{nullptr, nullptr, 0}, 0u, -1, hs,
+                      w.P2 + (size_t)(Tv + t) * B * 4 * H, 4 * H, 0, nullptr, nullptr, nullptr, vid, src));
+    // 3. vocabulary logits from h' (no dropout, no residual: no separate `out`), 4. top-k words and their log-probabilities
+    float* logits = logits_out ? logits_out : bw.logits;
+    ASeg so = make_seg(hn, H, H, 0);
+    HIP_TRY(store_call(&so, 1, p->embed_word_W, V, p->embed_word_b, logits, V, R, V, 0, -1, hs));
+    HIP_TRY(launch_vocab_topk(logits, V, R, V, k, top_ids, top_logp, hs));
+    return S2VT_OK;
+}
+
+}  // extern "C"

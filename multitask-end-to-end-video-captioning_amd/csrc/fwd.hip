@@ -22,10 +22,13 @@ struct CfgEntry {
     int fallback;                 // LDS-DMA entries (vector path only): the table index of the register-staged tile that takes the launch
                                   // when the operands are not 16-byte aligned (-1: this entry has a scalar form of its own)
     KernelFn res[4];              // cell-step tiles: the residual forms (GemmArgs::res) of vec, scalar, vec_om, scalar_om
+    KernelFn gs[2];               // cell-step tiles: the gathered-state forms (GemmArgs::cinit_rowidx / cprev_rowidx) of vec, scalar; no live-row or residual twin
+    int gs_fallback = -1;         // an entry with a scalar form but no scalar GS twin: the table index of the tile that takes a gathered launch off
+                                  // the vector path (-1: every plain form of this entry has its GS twin)
 };
 
-template <int WM, int WN, int TM, int TN, int NG, int EPI, int BKT = 32, int PW = 0, bool BT = false>
-constexpr CfgEntry make_entry(const char* name)
+template <int WM, int WN, int TM, int TN, int NG, int EPI, int BKT = 32, int PW = 0, bool BT = false, bool GS_SCALAR = true>
+constexpr CfgEntry make_entry(const char* name, int gs_fallback = -1)
 {
     using C = GemmCfg<WM, WN, TM, TN, NG, EPI, true, BKT, PW, BT>;
     KernelFn om = nullptr, om_s = nullptr;
@@ -34,13 +37,18 @@ constexpr CfgEntry make_entry(const char* name)
         om_s = gemm_kernel<WM, WN, TM, TN, NG, EPI, false, BKT, PW, BT, true>;
     }
     CfgEntry e{name, gemm_kernel<WM, WN, TM, TN, NG, EPI, true, BKT, PW, BT>,
-               gemm_kernel<WM, WN, TM, TN, NG, EPI, false, BKT, PW, BT>, C::BM, C::CG, C::NT, C::LDS_FLOATS * 4, om, om_s, -1, {nullptr, nullptr, nullptr, nullptr}};
+               gemm_kernel<WM, WN, TM, TN, NG, EPI, false, BKT, PW, BT>, C::BM, C::CG, C::NT, C::LDS_FLOATS * 4, om, om_s, -1, {nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr}};
     if constexpr (EPI == EPI_LSTM || EPI == EPI_LSTM_GW) {
+        e.gs[0] = gemm_kernel<WM, WN, TM, TN, NG, EPI, true, BKT, PW, BT, false, 0, false, true>;
+        // GS_SCALAR false: no scalar GS twin; gs_fallback names the tile that takes a gathered launch off the vector path -- one of the
+        // same rows, so that no launch lands on a tile sized for another M
+        if constexpr (GS_SCALAR) e.gs[1] = gemm_kernel<WM, WN, TM, TN, NG, EPI, false, BKT, PW, BT, false, 0, false, true>;
         e.res[0] = gemm_kernel<WM, WN, TM, TN, NG, EPI, true, BKT, PW, BT, false, 0, true>;
         e.res[1] = gemm_kernel<WM, WN, TM, TN, NG, EPI, false, BKT, PW, BT, false, 0, true>;
         e.res[2] = gemm_kernel<WM, WN, TM, TN, NG, EPI, true, BKT, PW, BT, true, 0, true>;
         e.res[3] = gemm_kernel<WM, WN, TM, TN, NG, EPI, false, BKT, PW, BT, true, 0, true>;
     }
+    e.gs_fallback = GS_SCALAR ? -1 : gs_fallback;
     return e;
 }
 // LDS-DMA ring tiles (gemm_mfma.h, DM > 0): PW loader waves issue buffer_load ... lds pieces DM stages deep, the MFMA waves only read
@@ -52,8 +60,9 @@ constexpr CfgEntry make_dma_entry(const char* name, int fallback)
     KernelFn om = nullptr;
     if constexpr (EPI == EPI_LSTM || EPI == EPI_LSTM_GW || EPI == EPI_PICK) om = gemm_kernel<WM, WN, TM, TN, NG, EPI, true, BKT, PW, BT, true, DM>;
     CfgEntry e{name, gemm_kernel<WM, WN, TM, TN, NG, EPI, true, BKT, PW, BT, false, DM>, nullptr, C::BM, C::CG, C::NT, C::LDS_FLOATS * 4, om,
-               nullptr, fallback, {nullptr, nullptr, nullptr, nullptr}};
+               nullptr, fallback, {nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr}};
     if constexpr (EPI == EPI_LSTM || EPI == EPI_LSTM_GW) {
+        e.gs[0] = gemm_kernel<WM, WN, TM, TN, NG, EPI, true, BKT, PW, BT, false, DM, false, true>;
         e.res[0] = gemm_kernel<WM, WN, TM, TN, NG, EPI, true, BKT, PW, BT, false, DM, true>;
         e.res[2] = gemm_kernel<WM, WN, TM, TN, NG, EPI, true, BKT, PW, BT, true, DM, true>;
     }
@@ -103,7 +112,9 @@ const CfgEntry kLstm[] = {
     make_entry<1, 4, 4, 1, 4, EPI_LSTM_GW>("gw64x16u(1x4)"),
     make_entry<1, 4, 5, 1, 4, EPI_LSTM_GW>("gw80x16u(1x4)"),
     make_entry<2, 4, 3, 1, 4, EPI_LSTM_GW>("gw96x16u(2x4)"),
-    make_entry<1, 4, 1, 1, 4, EPI_LSTM_GW, 64>("gw16x16u(1x4)k64"),
+    // (its scalar GS twin takes 83 VGPRs against the plain twin's 64, five waves per SIMD against seven, wherever its indices are loaded: it
+    //  gets none, and a gathered launch off the vector path goes to entry 3, the 32-deep tile of the same 16 rows, which gives the same bits)
+    make_entry<1, 4, 1, 1, 4, EPI_LSTM_GW, 64, 0, false, false>("gw16x16u(1x4)k64", 3),
     // + 4 loader waves (the MFMA waves issue no loads / LDS stores): 3-5 % over the plain tiles at M = 320 / 384
     make_entry<1, 4, 5, 1, 4, EPI_LSTM_GW, 32, 4>("gw80x16u(1x4)+4"),
     make_entry<1, 4, 6, 1, 4, EPI_LSTM_GW, 32, 4>("gw96x16u(1x4)+4"),
@@ -258,7 +269,7 @@ void set_lds_attrs()
         int n;
         const CfgEntry* t = table(epi, &n);
         for (int i = 0; i < n; ++i) {
-            for (KernelFn fn : {t[i].vec, t[i].scalar, t[i].vec_om, t[i].scalar_om, t[i].res[0], t[i].res[1], t[i].res[2], t[i].res[3]}) {
+            for (KernelFn fn : {t[i].vec, t[i].scalar, t[i].vec_om, t[i].scalar_om, t[i].res[0], t[i].res[1], t[i].res[2], t[i].res[3], t[i].gs[0], t[i].gs[1]}) {
                 if (!fn) continue;
                 const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
                                                          t[i].lds_bytes);
@@ -377,6 +388,9 @@ hipError_t launch_gemm(const GemmArgs& a, int epi, int cfg, hipStream_t st)
         cfg = cfg == 2 ? 8 : 9;
     if (t[cfg].fallback >= 0 && !can_vec(a, epi == EPI_STORE_NT)) cfg = t[cfg].fallback;       // LDS-DMA tiles: aligned operands only
     if ((a.omap || a.m_dev) && !t[cfg].vec_om && t[cfg].fallback >= 0) cfg = t[cfg].fallback;  // ... and (store) no live-row form: their register-staged twin
+    const bool gathered = a.cinit_rowidx || a.cprev_rowidx;
+    if (gathered && !t[cfg].gs[0] && t[cfg].fallback >= 0) cfg = t[cfg].fallback;              // ... and a tile without a gathered-state form, likewise
+    if (gathered && t[cfg].gs_fallback >= 0 && !can_vec(a, false)) cfg = t[cfg].gs_fallback;   // ... and one without the scalar GS twin, off the vector path
     const CfgEntry& e = t[cfg];
     if (a.M <= 0 || a.N <= 0) return hipSuccess;
     const int mt = ceil_div(a.M, e.BM), nt = ceil_div(a.N, e.CG);
@@ -418,6 +432,11 @@ hipError_t launch_gemm(const GemmArgs& a, int epi, int cfg, hipStream_t st)
     if (a.res) {                                                       // residual cell step: the RES twin of whichever form was chosen
         if (epi != EPI_LSTM || !a.out) return hipErrorInvalidValue;
         fn = e.res[(fn == e.vec || fn == e.vec_om ? 0 : 1) + ((a.omap || a.m_dev) ? 2 : 0)];
+        if (!fn) return hipErrorInvalidValue;
+    }
+    if (gathered) {                                                    // gathered state: the GS twin; it has no live-row or residual combination
+        if (epi != EPI_LSTM || a.omap || a.m_dev || a.res) return hipErrorInvalidValue;
+        fn = e.gs[fn == e.vec ? 0 : 1];
         if (!fn) return hipErrorInvalidValue;
     }
     const int pcls = epi;                                              // profiler class (0 store, 1 LSTM, 2 pick, 3 = TN kernel, 4 store with W^T)

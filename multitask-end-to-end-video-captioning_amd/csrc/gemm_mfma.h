@@ -95,6 +95,10 @@ struct GemmArgs {
     const int* res_rowidx;
     int res_ld;
     int res_rowmod;
+    // gathered-state form of the cell launches (the GS instantiations: a beam step, whose rows continue from arbitrary videos and parents).
+    // Each is applied AFTER the operand's own rowmod, as ASeg::rowidx is; NULL: none.  The A segments have their own rowidx.
+    const int* cinit_rowidx;    // row of cinit for launch row m
+    const int* cprev_rowidx;    // row of c_prev for launch row m
 };
 
 // ---- loads the compiler does not schedule (cdna_hip_programming.md §5.7): hipcc sinks ordinary prefetch loads next
@@ -221,10 +225,11 @@ struct GemmCfg {
     static_assert(DM == 0 || (PW > 0 && VEC), "LDS-DMA ring: loader waves, aligned operands");
 };
 
-template <int WM, int WN, int TM, int TN, int NG, int EPI, bool VEC, int BKT = 32, int PW = 0, bool BT = false, bool OM = false, int DM = 0, bool RES = false>
+template <int WM, int WN, int TM, int TN, int NG, int EPI, bool VEC, int BKT = 32, int PW = 0, bool BT = false, bool OM = false, int DM = 0, bool RES = false, bool GS = false>
 __global__ __launch_bounds__(64 * (WM * WN + PW)) void gemm_kernel(const GemmArgs g)
 {
     static_assert(!RES || EPI == EPI_LSTM || EPI == EPI_LSTM_GW, "residual operand: cell epilogues only");
+    static_assert(!GS || ((EPI == EPI_LSTM || EPI == EPI_LSTM_GW) && !OM && !RES), "gathered state: plain cell launches only");
     using Cfg = GemmCfg<WM, WN, TM, TN, NG, EPI, VEC, BKT, PW, BT, DM>;
     constexpr int BK = Cfg::BK, KQ = Cfg::KQ, RS = Cfg::RS, PL = Cfg::PL, ABUF = Cfg::ABUF;   // (BK shadows the namespace-scope default)
     constexpr int NG4 = Cfg::NG4, SWZ_SHIFT = Cfg::SWZ_SHIFT;
@@ -328,6 +333,7 @@ __global__ __launch_bounds__(64 * (WM * WN + PW)) void gemm_kernel(const GemmArg
                     if (m < MM && cok) {
                         m = orow(m);
                         if (g.cinit_rowmod > 0) m %= g.cinit_rowmod;
+                        if constexpr (GS) { if (g.cinit_rowidx) m = g.cinit_rowidx[m]; }     // (a dependent load ahead of the K loop; one per row)
                         v[r] = g.cinit[(size_t)m * g.ldcinit + col];
                     }
                 }
@@ -359,7 +365,49 @@ __global__ __launch_bounds__(64 * (WM * WN + PW)) void gemm_kernel(const GemmArg
                 ep_vid[i][r] = mok ? g.video_id[orow(m)] : 0;
             }
     }
+    // GS: the c_prev row of every (row, unit) pair this thread finishes -- EPI_LSTM: its TM x 4 accumulator rows; EPI_LSTM_GW: row
+    // (tid + it * NT) / CG of pass `it` of the epilogue's loop.  -1: no such row.  They are index loads the c_prev loads depend on, so
+    // they belong here with the other epilogue operands -- except in the five twins where holding them across the K loop costs an
+    // occupancy step against the plain twin (kernel-resource-usage, profiles/NOTES.md): the register-staged scalar gate-per-wave tiles
+    // up to 64 rows and the 80-row tile with loader waves on the vector path load them in the epilogue (GS_LATE).  The list is one
+    // compiler's register allocation (ROCm 7.2's hipcc), not a property of the tiles; either placement computes the same bits, so a stale
+    // list costs occupancy only.  Nothing in the build checks it: after a toolchain change, redo the table in profiles/NOTES.md.
+    constexpr int GWP = (BM * CG + NT - 1) / NT;
+    constexpr bool GS_LATE = GS && Cfg::GW && DM == 0 && ((!VEC && PW == 0 && BM <= 64) || (VEC && PW > 0 && BM == 80));
+    int ep_cp[GS && !Cfg::GW ? TM : 1][4], ep_cpg[GS && Cfg::GW && !GS_LATE ? GWP : 1];
+    auto cprev_row = [&](int m) __attribute__((always_inline)) {
+        int rr = -1;
+        if (m < MM) {
+            rr = g.cprev_rowmod > 0 ? m % g.cprev_rowmod : m;
+            if (g.cprev_rowidx) rr = g.cprev_rowidx[rr];
+        }
+        return rr;
+    };
+    if constexpr (GS && !GS_LATE) {
+        if constexpr (Cfg::GW) {
+#pragma unroll
+            for (int it = 0; it < GWP; ++it) {
+                const int pidx = tid + it * NT;
+                ep_cpg[it] = pidx < BM * CG ? cprev_row(m0 + pidx / CG) : -1;
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < TM; ++i)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) ep_cp[i][r] = mma_wave ? cprev_row(m0 + (wm * TM + i) * 16 + lq * 4 + r) : -1;
+        }
+    }
     auto pin_epilogue_operands = [&]() __attribute__((always_inline)) {
+        if constexpr (GS && Cfg::GW && !GS_LATE) {
+#pragma unroll
+            for (int it = 0; it < GWP; ++it) asm volatile("" : "+v"(ep_cpg[it]));
+        }
+        if constexpr (GS && !Cfg::GW) {
+#pragma unroll
+            for (int i = 0; i < TM; ++i)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) asm volatile("" : "+v"(ep_cp[i][r]));
+        }
         if constexpr (EPI == EPI_STORE || EPI == EPI_PICK) {
 #pragma unroll
             for (int j = 0; j < TN; ++j) asm volatile("" : "+v"(ep_bias[j]));
@@ -1093,7 +1141,9 @@ __global__ __launch_bounds__(64 * (WM * WN + PW)) void gemm_kernel(const GemmArg
                     const float sf = dm_sigmoidf(zf + 1.0f);
                     const float so = dm_sigmoidf(zo);
                     const size_t o = (size_t)mo * H + u;
-                    const size_t op = (size_t)(g.cprev_rowmod > 0 ? mo % g.cprev_rowmod : mo) * H + u;
+                    size_t op;
+                    if constexpr (GS) op = (size_t)ep_cp[i][r] * H + u;
+                    else op = (size_t)(g.cprev_rowmod > 0 ? mo % g.cprev_rowmod : mo) * H + u;
                     const float t1 = g.c_prev[op] * sf;
                     const float t2 = si * tj;
                     const float c = t1 + t2;
@@ -1146,7 +1196,19 @@ __global__ __launch_bounds__(64 * (WM * WN + PW)) void gemm_kernel(const GemmArg
             const float sf = dm_sigmoidf(zf + 1.0f);
             const float so = dm_sigmoidf(zo);
             const size_t o = (size_t)mo * H + u;
-            const size_t op = (size_t)(g.cprev_rowmod > 0 ? mo % g.cprev_rowmod : mo) * H + u;
+            size_t op;
+            if constexpr (GS_LATE) {
+                op = (size_t)cprev_row(m) * H + u;
+            } else if constexpr (GS) {
+                const int it = (pidx - tid) / NT;                  // the pass of this loop: selects among the rows loaded ahead of the K loop
+                int rr = ep_cpg[0];
+#pragma unroll
+                for (int k = 1; k < GWP; ++k)
+                    if (it == k) rr = ep_cpg[k];
+                op = (size_t)rr * H + u;
+            } else {
+                op = (size_t)(g.cprev_rowmod > 0 ? mo % g.cprev_rowmod : mo) * H + u;
+            }
             const float t1 = g.c_prev[op] * sf;
             const float t2 = si * tj;
             const float c = t1 + t2;

@@ -401,6 +401,27 @@ def lstm_cell_fwd_live(x0, x1, h_prev, c_prev, W, b, c_new, h_new, out, gates=No
     return c_new, h_new, out, gates
 
 
+def lstm_cell_fwd_gather(x0, x1, h_prev, c_prev, W, b, M, state_rowidx=None, cinit=None, cinit_rowidx=None, want_gates=False, tile_cfg=-1,
+                         c_new=None, h_new=None, gates=None):
+    """The gathered-state cell step (s2vt_lstm_cell_fwd_gather): launch row m continues h_prev / c_prev row state_rowidx[m] and the carried
+    partial cinit row cinit_rowidx[m] (int32 device arrays of M entries; None: row m), no dropout.  Returns (c_new, h_new, gates | None),
+    [M, H] / [M, 4H]; given outputs are written in place and must not overlap the state they are gathered from."""
+    _chk_f32(h_prev, c_prev, W, b, cinit, c_new, h_new, gates)
+    _chk_live(state_rowidx, cinit_rowidx)
+    H = W.shape[1] // 4
+    dev = W.device
+    c_new = torch.empty((M, H), dtype=torch.float32, device=dev) if c_new is None else c_new
+    h_new = torch.empty((M, H), dtype=torch.float32, device=dev) if h_new is None else h_new
+    if gates is None and want_gates:
+        gates = torch.empty((M, 4 * H), dtype=torch.float32, device=dev)
+    assert cinit is None or (cinit.dim() == 2 and cinit.stride(1) == 1)
+    check(lib().s2vt_lstm_cell_fwd_gather(None if x0 is None else C.byref(x0), None if x1 is None else C.byref(x1), _ptr(h_prev), _ptr(c_prev),
+                                          _ptr(state_rowidx), _ptr(cinit), 0 if cinit is None else cinit.stride(0), _ptr(cinit_rowidx), _ptr(W),
+                                          _ptr(b), _ptr(c_new), _ptr(h_new), _ptr(gates), int(M), H, tile_cfg, _stream()),
+          "s2vt_lstm_cell_fwd_gather")
+    return c_new, h_new, gates
+
+
 def vocab_pick_live(out2, W, b, video_id, sample_id, step, seed, packed, live=None, n_live=None, pick_stride=1, logits=None, tile_cfg=-1):
     """s2vt_vocab_pick on the rows live[0 .. n_live): packed[r * pick_stride] (zero on entry for those rows) receives row r's word,
     whose low half is ~token; logits (optional, [M, V]) its logits."""
@@ -1280,6 +1301,45 @@ class BeamDecoder:
         check(lib().s2vt_beam_step(C.byref(self.dims), C.byref(params), self._B, self.beam, int(t), R, _ptr(dev[0]), _ptr(dev[1]),
                                    _ptr(dev[2]), int(k), _ptr(out[0]), _ptr(out[1]), _ptr(logits), _ptr(self.ws), self.ws.numel(),
                                    _stream()), "s2vt_beam_step")
+        host = out.cpu().numpy()                                                # the one device-to-host copy
+        ids, logp = host[0], host[1].view(np.float32)
+        return (ids, logp, logits) if want_logits else (ids, logp)
+
+
+class BidirBeamDecoder:
+    """s2vt_bidir_beam_workspace_bytes / s2vt_bidir_beam_encode / s2vt_bidir_beam_step: BeamDecoder for the bidirectional captioner (same
+    interface; params: make_bidir_params).  encode runs what a video's hypotheses share -- both LSTM1 directions, their products into
+    LSTM2, LSTM2's encode steps -- once per batch; a step is one gathered-state cell launch, the vocabulary product and the top-k.  Steps
+    are issued in order t = 0, 1, ...; at t = 0 the parent row is ignored and the word row holds <bos>."""
+
+    def __init__(self, dims: Dims, max_B: int, beam: int, device="cuda", lstm1_form=-1):
+        self.dims, self.max_B, self.beam, self.device, self.lstm1_form = dims, int(max_B), int(beam), torch.device(device), int(lstm1_form)
+        nbytes = lib().s2vt_bidir_beam_workspace_bytes(C.byref(dims), self.max_B, self.beam)
+        if not nbytes:
+            raise ValueError(f"bidirectional beam decoder: bad shape (B={max_B}, beam={beam}; 1 <= beam <= 16, n_caption_lstm_step <= 128)")
+        self.ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        assert self.ws.data_ptr() % 256 == 0
+        self._B = 0
+
+    def encode(self, params, video):
+        _chk_f32(video)
+        assert video.is_contiguous() and video.shape[0] <= self.max_B
+        self._B = video.shape[0]
+        check(lib().s2vt_bidir_beam_encode(C.byref(self.dims), C.byref(params), _ptr(video), self._B, self.beam, self.lstm1_form, _ptr(self.ws),
+                                           self.ws.numel(), _stream()), "s2vt_bidir_beam_encode")
+
+    def step(self, params, t: int, rows, k: int, want_logits=False):
+        """rows: int32 [3, R] host array (video of each row, parent row of step t - 1, word).  Returns numpy (ids [R, k],
+        logp [R, k]) and, with want_logits, the step's logits [R, V] on the device."""
+        import numpy as np
+        rows = np.ascontiguousarray(rows, dtype=np.int32)
+        R = rows.shape[1]
+        dev = torch.from_numpy(rows).to(self.device)                            # the one host-to-device copy
+        out = torch.empty((2, R, k), dtype=torch.int32, device=self.device)    # ids, then the bits of logp
+        logits = torch.empty((R, self.dims.n_words), dtype=torch.float32, device=self.device) if want_logits else None
+        check(lib().s2vt_bidir_beam_step(C.byref(self.dims), C.byref(params), self._B, self.beam, int(t), R, _ptr(dev[0]), _ptr(dev[1]),
+                                         _ptr(dev[2]), int(k), _ptr(out[0]), _ptr(out[1]), _ptr(logits), _ptr(self.ws), self.ws.numel(),
+                                         _stream()), "s2vt_bidir_beam_step")
         host = out.cpu().numpy()                                                # the one device-to-host copy
         ids, logp = host[0], host[1].view(np.float32)
         return (ids, logp, logits) if want_logits else (ids, logp)
