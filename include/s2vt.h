@@ -491,7 +491,8 @@ int s2vt_gemm_bf16_nt(const uint16_t* A, int32_t lda, const uint16_t* B, int32_t
  * fp32 body (the gated side-stream overlap); so does every shape when the environment sets S2VT_SPLIT_GRADS=0 (read once) -- then
  * bit-identical to s2vt_bptt_bwd_live.  Deterministic, no atomics.  split_ws: a scratch of its own (256-byte aligned) of
  * s2vt_split_grad_workspace_bytes(d, B, N) bytes (0 on bad arguments): about twice the bf16 mode's -- 0.7 GB at BASELINE
- * configs[2], several GB at the reference defaults (B 256, K 8, 35 caption steps). */
+ * configs[2], several GB at the reference defaults (B 256, K 8, 35 caption steps).  It is held to that size in every mode: the
+ * fp32 body never touches it, but a smaller one is S2VT_E_WORKSPACE there as well. */
 size_t s2vt_split_grad_workspace_bytes(const s2vt_dims* d, int32_t B, int32_t N);
 int s2vt_bptt_bwd_split(const s2vt_dims* d, const s2vt_params* p, const s2vt_params* grads, const float* video, int32_t B,
                         int32_t N, const float* dlogits, int32_t caption_steps, const int32_t* live_rows, int32_t n_live, float keep,

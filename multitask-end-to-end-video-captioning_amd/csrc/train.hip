@@ -1122,7 +1122,7 @@ static int bptt_bwd_body(const s2vt_dims* d, const s2vt_params* p, const s2vt_pa
     if (!dims_ok_res(d) || !params_ok(p) || !params_ok(grads) || !video || !workspace || B <= 0 || N <= 0 || N % B)
         return S2VT_E_BADARG;
     if (reinterpret_cast<uintptr_t>(workspace) & 255u) return S2VT_E_ALIGN;
-    if (bf16 && (reinterpret_cast<uintptr_t>(bf16_ws) & 255u)) return S2VT_E_ALIGN;
+    if (bf16_ws && (reinterpret_cast<uintptr_t>(bf16_ws) & 255u)) return S2VT_E_ALIGN;
     if (chain_fault()) return S2VT_E_CHAIN_TIMEOUT;
     if (caption_steps < 1 || caption_steps > d->n_caption_lstm_step) return S2VT_E_BADARG;
     if (live_rows && (n_live > caption_steps * N || ((d->lstm_dim | d->word_dim) & 3))) return S2VT_E_BADARG;
@@ -1134,9 +1134,11 @@ static int bptt_bwd_body(const s2vt_dims* d, const s2vt_params* p, const s2vt_pa
     carve_train(c, d, B, N, &w);
     if (!c.ok()) return S2VT_E_WORKSPACE;
     Bf16Ws bw{};
-    if (bf16) {
+    // (a scratch that came with the call is held to its declared size in every mode: s2vt_bptt_bwd_split's fp32 body -- N <= 256 rows,
+    //  or S2VT_SPLIT_GRADS=0 -- never touches split_ws, but a caller whose scratch is too small learns it at the first shape, not the first large one)
+    if (bf16_ws) {
         Carver cb(bf16_ws, bf16_ws_bytes);
-        carve_bf16(cb, d, B, N, &bw, split);
+        carve_bf16(cb, d, B, N, &bw, split || !bf16);
         if (!cb.ok()) return S2VT_E_WORKSPACE;
     }
     hipStream_t st = S(stream);

@@ -14,6 +14,11 @@ reset() puts the sentinel back into the window as well, for an output that sever
 then what the whole allocation must hold after a launch that writes those rows of the window only, and assert_image() compares with it
 in one go (rows the launch must leave alone, pads and guards alike).
 
+GuardedWorkspace is the byte form for a driver's `void* workspace, size_t bytes`: a 256-byte aligned window of exactly nbytes between
+two SENTINEL32 guards.  Its window is NOT pre-filled: a workspace holds index arrays and counters, and by the rule above a place an
+index could be read from must hold a valid index -- so a test dirties the window with a real call of the same driver on other inputs,
+and then runs the call under test on it.  snapshot() / assert_unchanged() compare a byte range of the window bit for bit.
+
 A plain module (not a conftest, no fixtures); works on CPU tensors as well, where tests/test_guardband_cpu.py checks it."""
 import ctypes
 
@@ -126,3 +131,62 @@ class Guarded:
             got = int(self._ibuf[off]) & {torch.int64: 0xFFFFFFFFFFFFFFFF, torch.int32: 0xFFFFFFFF, torch.int16: 0xFFFF}[self._itype]
             raise AssertionError(f"{self.name}: write outside the window at flat offset {off} (window starts at {self.lead}): "
                                  f"{self._where(off)}; bits {got:#x}, sentinel {self._sentinel:#x}; {int(changed.sum())} element(s) changed")
+
+
+WS_ALIGN = 256                   # what every driver asks of its workspace pointer (S2VT_E_ALIGN otherwise)
+WS_MIN_LEAD = 256                # guard bytes in front of the window, at least
+WS_MIN_TAIL = 4096               # guard bytes behind it, at least
+
+
+class GuardedWorkspace:
+    """One flat uint8 allocation: [lead guard | window of exactly nbytes, 256-byte aligned | tail guard], guards of SENTINEL32 words."""
+
+    def __init__(self, nbytes, device="cuda", name="workspace", tail=WS_MIN_TAIL):
+        nbytes = int(nbytes)
+        assert nbytes > 0 and nbytes % WS_ALIGN == 0, f"{name}: a workspace size is a positive multiple of 256 bytes, got {nbytes}"
+        assert tail >= WS_MIN_TAIL and tail % 4 == 0
+        self.nbytes, self.name, self.tail = nbytes, name, int(tail)
+        self._buf = torch.empty(WS_MIN_LEAD + WS_ALIGN + nbytes + self.tail, dtype=torch.uint8, device=device)
+        base = self._buf.data_ptr()
+        assert base % 4 == 0
+        self.lead = WS_MIN_LEAD + (-(base + WS_MIN_LEAD)) % WS_ALIGN          # the lead that puts the window on a 256-byte boundary
+        self._buf = self._buf[:self.lead + nbytes + self.tail]
+        self._front = self._buf[:self.lead].view(torch.int32)
+        self._back = self._buf[self.lead + nbytes:].view(torch.int32)
+        self._front.fill_(SENTINEL32)
+        self._back.fill_(SENTINEL32)
+        self.window = self._buf[self.lead:self.lead + nbytes]
+        assert self.window.data_ptr() % WS_ALIGN == 0 and self.lead >= WS_MIN_LEAD and self.window.numel() == nbytes
+
+    @property
+    def ptr(self):
+        return ctypes.c_void_p(self.window.data_ptr())
+
+    def as_uint8(self, nbytes=None):
+        """The window (or its first nbytes) as a uint8 tensor: what the ws= parameters of ops take, numel() being the byte count they pass."""
+        return self.window if nbytes is None else self.window[:int(nbytes)]
+
+    def assert_intact(self):
+        """Both guards still hold the sentinel; names the byte offset, relative to the window, of the first word that does not."""
+        for words, start, label in ((self._back, self.nbytes, "behind the window's end"), (self._front, -self.lead, "in front of the window")):
+            bad = words != SENTINEL32
+            if bool(bad.any()):
+                i = int(bad.nonzero()[0, 0])
+                off = start + 4 * i
+                dist = off - self.nbytes if start >= 0 else -off
+                raise AssertionError(f"{self.name}: write outside the {self.nbytes}-byte window at window offset {off} ({dist} byte(s) {label}); "
+                                     f"bits {int(words[i]) & 0xFFFFFFFF:#x}, sentinel {SENTINEL32:#x}; {int(bad.sum())} word(s) changed")
+
+    def snapshot(self):
+        return self.window.clone()
+
+    def assert_unchanged(self, snapshot, lo=0, hi=None, what=""):
+        """Bytes [lo, hi) of the window equal the snapshot's (one comparison on the device); names the first offset that differs."""
+        hi = self.nbytes if hi is None else int(hi)
+        assert 0 <= lo <= hi <= self.nbytes and snapshot.numel() == self.nbytes
+        if lo == hi or torch.equal(self.window[lo:hi], snapshot[lo:hi]):
+            return
+        diff = self.window[lo:hi] != snapshot[lo:hi]
+        off = lo + int(diff.nonzero()[0, 0])
+        raise AssertionError(f"{self.name} {what}: {int(diff.sum())} byte(s) of [{lo}, {hi}) changed, the first at window offset {off} "
+                             f"({off - lo} past {lo}): {int(self.window[off]):#04x}, was {int(snapshot[off]):#04x}")

@@ -1,10 +1,12 @@
 """tests/guardband.py on CPU tensors: an untouched buffer passes, one planted element in the lead, the tail or a row pad fails and is
-located, the window round-trips, and lead % 4 == 1 really gives a 4-byte but not 16-byte aligned window."""
+located, the window round-trips, and lead % 4 == 1 really gives a 4-byte but not 16-byte aligned window.  Then GuardedWorkspace, the
+byte window of a driver's workspace, and the four workspace checks of tests/workspace_contract.py on fake drivers."""
 import numpy as np
 import pytest
 import torch
 
-from guardband import SENTINEL16, SENTINEL32, SENTINEL64, Guarded
+import workspace_contract as wc
+from guardband import SENTINEL16, SENTINEL32, SENTINEL64, Guarded, GuardedWorkspace
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.int32, torch.bfloat16])
@@ -147,3 +149,193 @@ def test_image_is_the_whole_allocation_after_writing_some_rows(dtype, ld):
     g._ibuf[64] = 0                                                    # the last guard element in front of the window
     with pytest.raises(AssertionError, match="lead guard, 1 element"):
         g.assert_image(img)
+
+
+# ---- GuardedWorkspace: the byte window of a driver's `void* workspace, size_t bytes`
+def test_workspace_window_is_exact_aligned_and_between_two_guards():
+    g = GuardedWorkspace(768, device="cpu", name="ws")
+    assert g.nbytes == 768 and g.as_uint8().numel() == 768 and g.as_uint8().dtype == torch.uint8
+    assert g.ptr.value == g.as_uint8().data_ptr() and g.ptr.value % 256 == 0
+    assert g.lead >= 256 and g.tail >= 4096 and g._buf.numel() == g.lead + 768 + g.tail
+    assert g.window.data_ptr() == g._buf.data_ptr() + g.lead
+    assert (g._front == SENTINEL32).all() and (g._back == SENTINEL32).all() and g._front.numel() * 4 == g.lead
+    g.assert_intact()
+    g.window.fill_(0xFF)                                               # the window is the caller's to dirty
+    g.assert_intact()
+    assert g.as_uint8(512).numel() == 512 and g.as_uint8(512).data_ptr() == g.ptr.value
+    for bad in (0, 100, 257):
+        with pytest.raises(AssertionError):
+            GuardedWorkspace(bad, device="cpu")
+
+
+@pytest.mark.parametrize("word,where", [(0, "0 byte(s) behind the window's end"), (1023, "4092 byte(s) behind"), (-1, "4 byte(s) in front of the window")])
+def test_workspace_guard_writes_are_located(word, where):
+    g = GuardedWorkspace(512, device="cpu", name="ws")
+    (g._back if word >= 0 else g._front)[word] = 0
+    with pytest.raises(AssertionError) as e:
+        g.assert_intact()
+    assert where in str(e.value) and "ws" in str(e.value)
+
+
+def test_workspace_snapshot_compares_a_byte_range():
+    g = GuardedWorkspace(1024, device="cpu", name="ws")
+    g.window.copy_(torch.arange(1024) % 251)
+    snap = g.snapshot()
+    g.assert_unchanged(snap, 0, 1024)
+    g.window[300] ^= 1
+    g.assert_unchanged(snap, 0, 300); g.assert_unchanged(snap, 301, 1024); g.assert_unchanged(snap, 512)
+    with pytest.raises(AssertionError, match=r"first at window offset 300 \(44 past 256\)"):
+        g.assert_unchanged(snap, 256, 1024, "tail")
+    assert snap.data_ptr() != g.window.data_ptr()
+
+
+# ---- the four workspace checks (tests/workspace_contract.py) on fake drivers: half-built ones are rejected, the correct one passes
+class _Refused(Exception):
+    pass
+
+
+def _declared(n):
+    return (4 * n + 255) // 256 * 256
+
+
+def _word(ws, byte_off):
+    """One int32 at byte_off from the start of the view `ws`, outside it if byte_off says so (what a kernel's stray store does)."""
+    base = ws.view(torch.int32)
+    return base.as_strided((1,), (1,), base.storage_offset() + byte_off // 4)
+
+
+def _fake_driver(bug=None):
+    """out[j] = 2 * sum_i x[i, j], accumulated in the workspace: it zeroes its n accumulators, adds the rows, doubles.  declared = 4 n bytes
+    rounded up to 256."""
+    def driver(x, out, ws):
+        n = x.shape[1]
+        stray = n == SMALL_N                                            # the stray stores: a tail that only this width has
+        if bug == "zeroes_before_refusing":
+            ws.zero_()
+        if ws.numel() < _declared(n) and bug != "never_refuses":
+            raise _Refused
+        acc = ws.view(torch.float32)[:n] if ws.numel() >= 4 * n else torch.zeros(n)
+        if bug != "no_zeroing":
+            acc.zero_()
+        for row in x:
+            acc += row
+        if bug == "stores_at_end" and stray:
+            _word(ws, _declared(n)).fill_(7)
+        if bug == "stores_in_front" and stray:
+            _word(ws, -4).fill_(7)
+        if bug == "stores_inside_rounding" and stray:                          # past 4 n bytes, inside the declared 256-byte rounding: no overrun
+            _word(ws, 4 * n).fill_(7)
+        if bug == "stores_past_declared" and stray:                            # 8 bytes behind the declared end
+            _word(ws, _declared(n) + 8).fill_(7)
+        out.copy_(2 * acc)
+    return driver
+
+
+class _FakeFamily:
+    def __init__(self, bug=None):
+        self.driver = _fake_driver(bug)
+        self.stages = [self.stage]
+
+    def inputs(self, n, variant):
+        return (torch.arange(3 * n, dtype=torch.float32).reshape(3, n) + 1) * (1 + 2 * variant)
+
+    def stage(self, env, n, x, state):
+        out = env.empty(n)
+        self.driver(x, out, env.ws(_declared(n), "fake"))
+        state["out"] = out
+
+    def check(self, n, x, state):
+        assert torch.equal(state["out"], 2 * x.double().sum(0).float())
+
+    def refused(self, e):
+        return isinstance(e, _Refused)
+
+
+SMALL_N, LARGE_N = 100, 400      # 400 of 512 declared bytes; 1600 of 1792
+
+
+def _all_checks(fam):
+    wc.exact_and_dirty(fam, SMALL_N, "cpu")
+    wc.shrink(fam, SMALL_N, LARGE_N, "cpu")
+    wc.containment(fam, SMALL_N, LARGE_N, "cpu")
+    wc.refusal(fam, SMALL_N, "cpu")
+
+
+def test_workspace_checks_accept_a_correct_driver():
+    _all_checks(_FakeFamily())
+    _all_checks(_FakeFamily("stores_inside_rounding"))                 # its own bytes
+
+
+@pytest.mark.parametrize("bug,check,message", [
+    ("stores_at_end", "A", r"window offset 512 \(0 byte\(s\) behind the window's end\)"),
+    ("stores_in_front", "A", r"4 byte\(s\) in front of the window"),
+    ("stores_past_declared", "A", r"8 byte\(s\) behind the window's end"),
+    ("stores_at_end", "C", r"first at window offset 512 \(0 past 512\)"),
+    ("stores_past_declared", "C", r"byte\(s\) of \[512, 1792\) changed, the first at window offset 520"),
+    ("no_zeroing", "A", None), ("no_zeroing", "B", None), ("no_zeroing", "C", None),
+    ("never_refuses", "D", r"accepted fake with 256 of 512 bytes"),
+    ("zeroes_before_refusing", "D", r"after stage 0 refused fake: \d+ byte\(s\) of \[0, 512\) changed"),
+])
+def test_workspace_checks_reject_a_half_built_driver(bug, check, message):
+    fam = _FakeFamily(bug)
+    run = {"A": lambda: wc.exact_and_dirty(fam, SMALL_N, "cpu"), "B": lambda: wc.shrink(fam, SMALL_N, LARGE_N, "cpu"),
+           "C": lambda: wc.containment(fam, SMALL_N, LARGE_N, "cpu"), "D": lambda: wc.refusal(fam, SMALL_N, "cpu")}[check]
+    with pytest.raises(AssertionError, match=message):
+        run()
+
+
+def test_a_store_inside_the_larger_window_is_invisible_to_shrink_but_not_to_containment():
+    """B hands the driver the larger byte count, so a store 8 bytes past the smaller shape's declared end is inside what it was given;
+    only C, which declares the smaller size on the same window, sees it."""
+    fam = _FakeFamily("stores_past_declared")
+    wc.shrink(fam, SMALL_N, LARGE_N, "cpu")
+    with pytest.raises(AssertionError, match="behind the 512 bytes declared for the smaller shape"):
+        wc.containment(fam, SMALL_N, LARGE_N, "cpu")
+
+
+def test_a_scratch_documented_as_unused_must_be_accepted_and_left_alone():
+    """unused(shape): check D then wants the short buffer accepted and not one byte of it written"""
+    class Unused(_FakeFamily):
+        def unused(self, n):
+            return {"fake"}
+    wc.refusal(Unused("never_refuses"), SMALL_N, "cpu")                # (short of its accumulators it works beside the buffer)
+    with pytest.raises(_Refused):
+        wc.refusal(Unused(), SMALL_N, "cpu")
+
+    class Touches(Unused):
+        def stage(self, env, n, x, state):
+            ws = env.ws(_declared(n), "fake")
+            if ws.numel() < _declared(n):
+                ws[:4] = 0
+            state["out"] = env.empty(n)
+    with pytest.raises(AssertionError, match="documented as unused in this form"):
+        wc.refusal(Touches("never_refuses"), SMALL_N, "cpu")
+
+
+def test_a_smaller_shape_that_needs_more_bytes_gets_a_regrown_window_of_stale_data():
+    """a size function need not grow with the shape: B and C then run on a new exact window that holds the old one's bytes, repeated"""
+    class Inverted(_FakeFamily):
+        def stage(self, env, n, x, state):                             # the fewer columns, the more bytes
+            out = env.empty(n)
+            self.driver(x, out, env.ws(_declared(n) + (2048 if n == SMALL_N else 0), "fake")[:_declared(n)])
+            state["out"] = out
+    for check in (wc.shrink, wc.containment):
+        env = check(Inverted(), SMALL_N, LARGE_N, "cpu")
+        assert env.regrown == {"fake"} and env.windows["fake"].nbytes == _declared(SMALL_N) + 2048
+        env.assert_intact()
+    with pytest.raises(AssertionError):                                # stale data is still stale there
+        wc.shrink(Inverted("no_zeroing"), SMALL_N, LARGE_N, "cpu")
+
+
+def test_refusal_check_sees_an_output_written_by_a_refusing_driver():
+    class Writes(_FakeFamily):
+        def stage(self, env, n, x, state):
+            out = env.empty(n)
+            ws = env.ws(_declared(n), "fake")
+            if ws.numel() < _declared(n):
+                out[0] = 0
+            self.driver(x, out, ws)
+            state["out"] = out
+    wc.exact_and_dirty(Writes(), SMALL_N, "cpu")
+    with pytest.raises(AssertionError, match="wrote an output"):
+        wc.refusal(Writes(), SMALL_N, "cpu")
