@@ -282,6 +282,24 @@ int s2vt_sample_ex(const s2vt_dims* d, const s2vt_params* p, const float* video,
                    uint64_t seed, int32_t video_base, int32_t flags, int32_t* ids_out, void* workspace, size_t workspace_bytes,
                    s2vt_stream stream);
 
+/* s2vt_sample with the vocabulary pick screened: per decode step the split-bf16 product of the step's rows with
+ * embed_word_W gives approximate logits, a proven margin (2^-10 |h| max|W[:, v]| per 1024 reduction steps, plus the Gumbel screen's)
+ * keeps the columns of a row that can still win it, and only those get the exact ascending-k fp32 chain and the exact Gumbel
+ * expression.  ids_out is bit-identical to s2vt_sample's.  workspace / workspace_bytes: s2vt_sample's, carved and left as s2vt_sample
+ * leaves it.  screen_ws (256-byte aligned): a scratch of its own of s2vt_sample_screen_workspace_bytes bytes -- a 256-byte head block,
+ * the hi / lo planes of embed_word_W^T [V][pad(H)] (bf16, pad = up to a multiple of 64), embed_word_W^T in fp32 [V][H up to a
+ * multiple of 4] (a surviving column is read as one row), the hi / lo planes of the step's rows [R][pad(H)] and the approximate logits
+ * [R][V up to a multiple of 4] fp32, each region rounded up to 256 bytes: about 118 MB at V = 12000, H = 1000, R = 384.  The head block holds, per call: uint64 survivors summed over rows and steps (byte 0), uint32 the most survivors of one row
+ * (byte 8), uint32 rows that took every column because a key, norm or margin was not finite (byte 12).
+ * ..._workspace_bytes returns 0 where the path does not serve the call -- (K + with_greedy) * B <= 64 rows (the persistent decode
+ * loop's shapes), lstm_dim > 2048, a residual model, bad arguments, 257 - 384 rows while S2VT_DECLOOP=2 or S2VT_DEC4=1 asks for the
+ * opt-in fragment-order forms there, or S2VT_PICK_SCREEN=0 in the environment (read once) -- and
+ * s2vt_sample_screened then returns S2VT_E_BADARG.  Other errors as s2vt_sample; S2VT_E_WORKSPACE for either block too small. */
+size_t s2vt_sample_screen_workspace_bytes(const s2vt_dims* d, int32_t B, int32_t K, int32_t with_greedy);
+int s2vt_sample_screened(const s2vt_dims* d, const s2vt_params* p, const float* video, int32_t B, int32_t K, int32_t with_greedy,
+                         uint64_t seed, int32_t video_base, int32_t* ids_out, void* workspace, size_t workspace_bytes, void* screen_ws,
+                         size_t screen_bytes, s2vt_stream stream);
+
 /* ---- mixed sampler: build_mix_sample of reinforce_multitask_e2e_attribute_by_groudtruth_greedy_s2vt.py:512-599 (built at :828, run
  * beside build_sampler on the same batch at :957-960), whose reward is that script's baseline.  A greedy decode in which the word fed
  * back at step t >= 1 is the ground-truth word caption[b][t - 1] with probability p_gt and the row's own argmax of step t - 1 otherwise

@@ -119,6 +119,8 @@ SIGNATURES = {
     "s2vt_sample_workspace_bytes": (_sz, [_DP, _i32, _i32, _i32]),
     "s2vt_sample": (C.c_int, [_DP, _PP, _vp, _i32, _i32, _i32, _u64, _i32, _vp, _vp, _sz, _vp]),
     "s2vt_sample_ex": (C.c_int, [_DP, _PP, _vp, _i32, _i32, _i32, _u64, _i32, _i32, _vp, _vp, _sz, _vp]),
+    "s2vt_sample_screen_workspace_bytes": (_sz, [_DP, _i32, _i32, _i32]),
+    "s2vt_sample_screened": (C.c_int, [_DP, _PP, _vp, _i32, _i32, _i32, _u64, _i32, _vp, _vp, _sz, _vp, _sz, _vp]),
     "s2vt_sample_mix_workspace_bytes": (_sz, [_DP, _i32, _i32]),
     "s2vt_sample_mix": (C.c_int, [_DP, _PP, _vp, _i32, _vp, _f32, _i32, _u64, _i32, _vp, _vp, _sz, _vp]),
     "s2vt_vocab_topk": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),

@@ -547,6 +547,7 @@ struct SampleDecode {
     size_t BH, enc;          // enc: where sample_encode left the encoder state, slot Tv of the c2e / h2e history
     Dec4Geom q4;
     const SampleMix* mix = nullptr;   // mixed mode: the argmax block at rows [K B, K B + B) is fed ground-truth words by coin
+    const PickScreenWs* screen = nullptr;   // s2vt_sample_screened: the pick of step_launches is the screened one (pick_screen.hip), same packed picks
 
     unsigned long long* picks(int t) const { return w.packed + (size_t)t * R * kPickStride; }     // the packed picks of step t [R]
     const float* partial(int t) const { return w.P2 + (size_t)(Tv + t) * 4 * BH; }                // the out1 partial of step t [B][4H]
@@ -639,6 +640,7 @@ struct SampleDecode {
         // residual model: the cell launch also writes out1 + h' (out1 = slot Tv + t + 1 of LSTM1's history, row % B), and the pick reads that
         if (w.out2) { s.out = w.out2; s.out1 = w.h1 + (size_t)(Tv + t + 1) * BH; s.out1_rowmod = B; }
         HIP_CHECK(lstm2_step(s, st));
+        if (screen) return launch_pick_screen_step(w.h2[nxt], H, p->embed_word_W, p->embed_word_b, R, H, V, w.vid, w.sid, seed, t, picks(t), kPickStride, *screen, st);
         return pick_call(w.out2 ? w.out2 : w.h2[nxt], H, p->embed_word_W, p->embed_word_b, R, H, V, ids(), t, picks(t), nullptr, pick_cfg, st, kPickStride, s.live, s.n_live);
     }
 };
@@ -650,15 +652,16 @@ struct SampleDecode {
 // mixed mode (one more argmax block in front of the greedy one): the other two read the fed word from the packed picks.  The residual
 // model (w.out2) takes the last form too: the other two project h2, not out1 + h2 (extending them is open).
 int sample_decode(const s2vt_dims* d, const s2vt_params* p, int B, int K, int with_greedy, uint64_t seed, int video_base,
-                  int32_t* ids_out, const SampleWs& w, s2vt_stream stream, int stop_at_eos, const SampleMix* mix)
+                  int32_t* ids_out, const SampleWs& w, s2vt_stream stream, int stop_at_eos, const SampleMix* mix, const PickScreenWs* screen)
 {
     const int H = d->lstm_dim, E = d->word_dim, V = d->n_words, Tv = d->n_video_lstm_step, Tc = d->n_caption_lstm_step;
     const int R = (K + (mix ? 1 : 0) + (with_greedy ? 1 : 0)) * B;
     hipStream_t st = S(stream);
-    SampleDecode s{p, w, B, K, R, seed, video_base, stop_at_eos != 0, st, H, E, V, Tv, Tc, (size_t)B * H, (size_t)Tv * B * H, {}, mix};
+    SampleDecode s{p, w, B, K, R, seed, video_base, stop_at_eos != 0, st, H, E, V, Tv, Tc, (size_t)B * H, (size_t)Tv * B * H, {}, mix, screen};
     HIP_TRY(s.open());
-    const bool loop1 = !stop_at_eos && !mix && !w.out2 && w.wemb_p && (B & 15) == 0 && decode_loop_eligible(R, H, E, V) && chain_operands_ok(p->embed_word_W, V, w.himg[0]);
-    const bool dec4 = !stop_at_eos && !mix && !w.out2 && (loop1 || (w.wemb_p && decode4_eligible(R, H, E)));
+    if (screen) HIP_TRY(launch_pick_screen_prepare(p->embed_word_W, H, V, *screen, st));      // embed_word_W is constant over the Tc steps
+    const bool loop1 = !screen && !stop_at_eos && !mix && !w.out2 && w.wemb_p && (B & 15) == 0 && decode_loop_eligible(R, H, E, V) && chain_operands_ok(p->embed_word_W, V, w.himg[0]);
+    const bool dec4 = !screen && !stop_at_eos && !mix && !w.out2 && (loop1 || (w.wemb_p && decode4_eligible(R, H, E)));
     if (dec4) HIP_TRY(s.pack_fragments());
     if (loop1) {
         HIP_TRY(s.persistent_loop());
@@ -715,6 +718,63 @@ int s2vt_sample(const s2vt_dims* d, const s2vt_params* p, const float* video, in
                 s2vt_stream stream)
 {
     return s2vt_sample_ex(d, p, video, B, K, with_greedy, seed, video_base, 0, ids_out, workspace, workspace_bytes, stream);
+}
+
+// ---- the screened form of s2vt_sample (pick_screen.hip).  Its scratch is a block of its own: the sampler workspace and its carve stay as
+// they are (train.hip and session.hip carve it again).
+static bool pick_screen_enabled()
+{
+    static const bool on = [] { const char* e = getenv("S2VT_PICK_SCREEN"); return !(e && e[0] == '0'); }();
+    return on;
+}
+
+// head block (counters, nwmax), W^T planes, W^T in fp32, row planes, approximate logits; 0: the path does not serve the shape
+static size_t carve_pick_screen(Carver& c, const s2vt_dims* d, int R, PickScreenWs* s)
+{
+    const size_t H = d->lstm_dim, V = d->n_words, Hp = bf16_pad((int)H), ldl = (V + 3) & ~(size_t)3, ldt = (H + 3) & ~(size_t)3;
+    if (R <= 64 || H > (size_t)kPickScreenMaxH) return 0;                 // <= 64 rows: the persistent decode loop's shapes
+    PickScreenWs t;
+    char* head = c.take<char>(kPickScreenHeadBytes);
+    t.counters = reinterpret_cast<unsigned long long*>(head);
+    t.nwmax = reinterpret_cast<float*>(head ? head + 16 : nullptr);
+    t.Wh = c.take<uint16_t>(V * Hp); t.Wl = c.take<uint16_t>(V * Hp);
+    t.Wt = c.take<float>(V * ldt);
+    t.hh = c.take<uint16_t>((size_t)R * Hp); t.hl = c.take<uint16_t>((size_t)R * Hp);
+    t.L = c.take<float>((size_t)R * ldl);
+    t.Hp = (int)Hp; t.ldl = (int)ldl; t.ldt = (int)ldt;
+    if (s) *s = t;
+    return c.off;
+}
+
+size_t s2vt_sample_screen_workspace_bytes(const s2vt_dims* d, int32_t B, int32_t K, int32_t with_greedy)
+{
+    if (!dims_ok(d) || B <= 0 || K < 0 || !pick_screen_enabled()) return 0;
+    if ((long long)(K + (with_greedy ? 1 : 0)) * B > 0x7fffffffll) return 0;
+    const int R = (K + (with_greedy ? 1 : 0)) * B;
+    if (sampler_knobs().frag_big && R > 256 && R <= 384) return 0;       // the opt-in fragment-order forms were asked for: they keep the call
+    Carver c(nullptr, 0);
+    return carve_pick_screen(c, d, R, nullptr);
+}
+
+int s2vt_sample_screened(const s2vt_dims* d, const s2vt_params* p, const float* video, int32_t B, int32_t K, int32_t with_greedy,
+                         uint64_t seed, int32_t video_base, int32_t* ids_out, void* workspace, size_t workspace_bytes, void* screen_ws,
+                         size_t screen_bytes, s2vt_stream stream)
+{
+    if (!dims_ok(d) || !sampler_params_ok(p) || !video || !ids_out || !workspace || !screen_ws || B <= 0 || K < 0 || (K == 0 && !with_greedy))
+        return S2VT_E_BADARG;
+    if (s2vt_sample_screen_workspace_bytes(d, B, K, with_greedy) == 0) return S2VT_E_BADARG;      // not a call this path serves
+    if ((reinterpret_cast<uintptr_t>(workspace) | reinterpret_cast<uintptr_t>(screen_ws)) & 255u) return S2VT_E_ALIGN;
+    if (chain_fault()) return S2VT_E_CHAIN_TIMEOUT;
+    const int R = (K + (with_greedy ? 1 : 0)) * B;
+    Carver c(workspace, workspace_bytes), cs(screen_ws, screen_bytes);
+    SampleWs w;
+    PickScreenWs sw;
+    carve_sample(c, d, B, R, &w);
+    carve_pick_screen(cs, d, R, &sw);
+    if (!c.ok() || !cs.ok()) return S2VT_E_WORKSPACE;
+    int rc = sample_encode(d, p, video, B, w, stream);
+    if (rc != S2VT_OK) return rc;
+    return sample_decode(d, p, B, K, with_greedy, seed, video_base, ids_out, w, stream, 0, nullptr, &sw);
 }
 
 // mixed sampler: carve_sample for R = (1 + with_greedy) * B rows, then the fed words [R]

@@ -239,7 +239,8 @@ struct SampleMix {
     int32_t* word;           // [R]: the words fed at the current step, behind carve_sample's regions
 };
 int sample_decode(const s2vt_dims* d, const s2vt_params* p, int B, int K, int with_greedy, uint64_t seed, int video_base,
-                  int32_t* ids_out, const SampleWs& w, s2vt_stream stream, int stop_at_eos = 0, const SampleMix* mix = nullptr);
+                  int32_t* ids_out, const SampleWs& w, s2vt_stream stream, int stop_at_eos = 0, const SampleMix* mix = nullptr,
+                  const PickScreenWs* screen = nullptr);      // screen: the pick of every step is the screened one (per-step launches only)
 
 // One LSTM2 step of the decoding stage on M rows (sampler loop, beam step).  What the callers differ in is data: where the hoisted
 // out1 partial of a row lies, how its word is gathered, where its state lives, and the early-exit mode's row list and tile.

@@ -576,7 +576,8 @@ hipError_t launch_x3(const uint16_t* Ah, const uint16_t* Al, int lda, const uint
     }
     if (prof) {
         (void)hipEventRecord(e1, st);
-        prof_record(cls, 16, cls == 3 ? "x3_128x128(dma) wgrad" : "x3_128x128(dma) dgrad", 2.0 * M * (double)N * Kp, e0, e1);
+        prof_record(cls, 16, cls == 2 ? "x3_128x128(dma) pick screen" : cls == 3 ? "x3_128x128(dma) wgrad" : "x3_128x128(dma) dgrad",
+                    2.0 * M * (double)N * Kp, e0, e1);
     }
     return hipGetLastError();
 }

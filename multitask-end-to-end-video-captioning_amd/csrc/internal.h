@@ -350,7 +350,7 @@ hipError_t launch_gemm_bf16_nt(const uint16_t* A, int lda, const uint16_t* B, in
                                int mfma, hipStream_t st);
 // C[M,N] (+)= Ah Bh^T + Ah Bl^T + Al Bh^T: split-bf16 operands (hi / lo planes with the layout rules of launch_gemm_bf16_nt), fp32
 // accumulation, no atomics.  part: optional split-K scratch of part_floats floats (gemm_bf16x3_part_floats(M, N, Kp) for the full
-// split; fewer -> no split); cls: the launch profiler's class (3 weight gradients, 4 data gradients)
+// split; fewer -> no split); cls: the launch profiler's class (2 the sampler's pick screen, 3 weight gradients, 4 data gradients)
 hipError_t launch_gemm_bf16x3_nt(const uint16_t* Ah, const uint16_t* Al, int lda, const uint16_t* Bh, const uint16_t* Bl, int ldb, float* C, int ldc,
                                  int M, int N, int Kp, int accumulate, float* part, size_t part_floats, int cls, hipStream_t st);
 size_t gemm_bf16x3_part_floats(int M, int N, int Kp);
@@ -366,6 +366,26 @@ hipError_t launch_gemm_bf16x3_tn(const uint16_t* Ah, const uint16_t* Al, int lda
 bool softmax_nll_split_ok(const float* logits, int ld, int V, const uint16_t* hi, const uint16_t* lo, int ldp);
 hipError_t launch_softmax_nll_split(const float* logits, int ld, int R, int V, const int32_t* target, const float* coef, float smoothing, float* nll,
                                     float* lp_t, uint16_t* hi, uint16_t* lo, int ldp, hipStream_t st, const float* smooth_rows = nullptr);
+
+// ---- the sampler's screened vocabulary pick (pick_screen.hip): split-bf16 approximate logits screen the columns of a row, the survivors
+// get the exact fp32 chain and Gumbel expression -- the packed picks are those of launch_gemm(EPI_PICK), bit for bit
+constexpr int kPickScreenMaxH = 2048;                 // the resolve kernel stages h and a column of W in LDS
+constexpr size_t kPickScreenHeadBytes = 256;          // counters + nwmax: the scratch's first block, zeroed by ..._prepare
+struct PickScreenWs {
+    unsigned long long* counters;                     // [0] survivors summed over rows and steps; then uint32 most survivors of a row, uint32 rows that took every column
+    float* nwmax;                                     // max_v |W[:, v]|_2, rounded up (byte 16 of the head block)
+    uint16_t *Wh, *Wl;                                // hi / lo planes of embed_word_W^T [V][Hp]
+    float* Wt;                                        // embed_word_W^T in fp32 [V][ldt], zeros past H: a survivor's column as one row
+    uint16_t *hh, *hl;                                // hi / lo planes of the step's rows [R][Hp]
+    float* L;                                         // approximate logits [R][ldl]; the resolve kernel leaves its fast keys there
+    int Hp, ldl, ldt;                                 // bf16_pad(H); V rounded up to 4; H rounded up to 4
+};
+// once per sampler call: zero the head block, cast W^T, transpose W, take the column norms' maximum
+hipError_t launch_pick_screen_prepare(const float* W, int H, int V, const PickScreenWs& s, hipStream_t st);
+// one decode step's pick on R rows h[R][H]: cast, product (profiler class 2), resolve; pick zeroed beforehand, as for EPI_PICK
+hipError_t launch_pick_screen_step(const float* h, int ldh, const float* W, const float* bias, int R, int H, int V, const int32_t* vid,
+                                   const int32_t* sid, uint64_t seed, int step, unsigned long long* pick, int pick_stride, const PickScreenWs& s,
+                                   hipStream_t st);
 
 // order-free NN contraction for the backward data path with optional split-K slabs:
 // slab s (blockIdx.y) holds the partial over its K range at C + s * slab_stride.

@@ -1,0 +1,292 @@
+// pick_screen.hip -- the sampler's screened vocabulary pick: approximate logits from the split-bf16 product
+// (bwd_bf16.hip, gemm_bf16x3_nt) select, under a proven margin, the few columns of a row that can still win it; only those get the
+// exact ascending-k fp32 chain and the exact Gumbel expression of the PICK epilogue (gemm_mfma.h).  The packed pick a row ends with is
+// the maximum exact key over a set of columns that contains the exact winner: the ids are those of the fp32 pick, bit for bit.
+//
+// Why the winner survives: with e >= |exact key - fast key| for every column, w the exact winner and f the fast argmax,
+//     fast_w >= exact_w - e >= exact_f - e >= fast_f - 2 e.
+// e = m + kGumbelScreenMargin + slack, m = C |h| max_v |W[:, v]|: the three kept products of hi = bf16(x), lo = bf16(x - hi) miss at
+// most 3 * 2^-18 |h_k w_k| per term, the fp32 chain is within K 2^-24 sum |h_k w_k| of the true sum, and 3 K roundings of the bf16
+// MFMA accumulation within 2^-22 relative each add 3 K 2^-22 sum |h_k w_k|; sum |h_k w_k| <= |h| |w| -- below C = 2^-10 for K <= 1024,
+// scaled by ceil(K / 1024) above.  slack covers the roundings of (logit + bias) + noise on either side.
+#include <hip/hip_runtime.h>
+
+#include "detmath.h"
+#include "internal.h"
+
+namespace s2vt {
+namespace {
+
+constexpr int kResThreads = 512, kResWaves = kResThreads / 64;
+constexpr int kResChunk = 4 * kResThreads, kResList = 2 * kResChunk;   // columns keyed per pass (one group of 4 per thread); survivors listed at most
+
+// Once per sampler call: Wt[v][k] = W[k][v] (fp32, rows ldt apart, zeros for H <= k < ldt) -- a survivor's column of W is then one
+// contiguous row instead of H cache lines -- and nwmax = max_v |W[:, v]|_2 rounded up, as the bits of a non-negative float folded with an
+// integer atomicMax (a non-finite norm has the larger bits and wins: the resolve kernel then takes every column).  64 columns per
+// workgroup, 64 x 64 tiles through LDS; wave w sums the squares of rows k = w (mod 4), the four partials are added in a fixed order.
+__global__ __launch_bounds__(256) void pick_screen_prepare_kernel(const float* __restrict__ W, int ldw, int H, int V, float* __restrict__ Wt, int ldt,
+                                                                  uint32_t* __restrict__ nwmax)
+{
+    __shared__ float t[64][65];
+    __shared__ float part[4][64];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, c0 = blockIdx.x * 64, col = c0 + lane;
+    const int vv = tid >> 2, q = tid & 3;                    // the transposed store: column c0 + vv, k quarter q of the tile
+    float s = 0.0f;
+    for (int k0 = 0; k0 < ldt; k0 += 64) {
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            const int kk = w + 4 * j;
+            const float x = k0 + kk < H && col < V ? W[(size_t)(k0 + kk) * ldw + col] : 0.0f;
+            s += x * x;
+            t[kk][lane] = x;
+        }
+        __syncthreads();
+        if (c0 + vv < V)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int kk = q * 16 + i * 4;
+                if (k0 + kk < ldt)                              // (ldt % 4 == 0: the four floats lie inside the row)
+                    *reinterpret_cast<float4*>(Wt + (size_t)(c0 + vv) * ldt + k0 + kk) = make_float4(t[kk][vv], t[kk + 1][vv], t[kk + 2][vv], t[kk + 3][vv]);
+            }
+        __syncthreads();
+    }
+    part[w][lane] = s;
+    __syncthreads();
+    if (w == 0) {
+        // (the sum of squares is within (H / 4 + 4) 2^-24 relative of the true one, its root within half of that: 1.001 rounds up)
+        float n = col < V ? sqrtf((part[0][lane] + part[1][lane]) + (part[2][lane] + part[3][lane])) * 1.001f : 0.0f;
+        uint32_t b = __float_as_uint(n);
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const uint32_t o = (uint32_t)__shfl_xor((int)b, off, 64);
+            b = o > b ? o : b;
+        }
+        if (lane == 0) atomicMax(nwmax, b);
+    }
+}
+
+struct PickResolveArgs {
+    float* L; int ldl;                       // approximate logits [R][ldl], ldl % 4 == 0, 16-byte aligned rows; left holding the fast keys
+    const float* bias;                       // [V]
+    const float* h; int ldh;                 // the step's fp32 rows [R][H]
+    const float* Wt; int ldt;                // embed_word_W^T [V][ldt], ldt % 4 == 0, zeros past H
+    const int32_t* vid; const int32_t* sid;
+    uint32_t seed_lo, seed_hi; int step;
+    unsigned long long* pick; int pick_stride;
+    const float* nwmax;
+    unsigned long long* counters;            // PickScreenWs::counters
+    int H, V; float C;
+};
+
+// v = L~ + bias and the fast key of columns c0 .. c0 + 3 (c0 % 4 == 0): one Philox block, counter (col >> 2, video, sample, step) as the
+// PICK epilogue's; argmax rows (sid < 0) carry no noise.  Columns >= V come back as 0 and are not looked at.
+__device__ __forceinline__ void screen_keys4(const PickResolveArgs& a, const float* Lr, int c0, int vid, int sid, float (&v)[4],
+                                             float (&ka)[4])
+{
+    float l[4];
+    if (c0 + 4 <= a.V) {
+        const float4 x = *reinterpret_cast<const float4*>(Lr + c0);
+        l[0] = x.x; l[1] = x.y; l[2] = x.z; l[3] = x.w;
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) l[j] = c0 + j < a.V ? Lr[c0 + j] : 0.0f;
+    }
+    u32x4 blk = {0u, 0u, 0u, 0u};
+    if (sid >= 0) blk = philox4x32_10((uint32_t)c0 >> 2, (uint32_t)vid, (uint32_t)sid, (uint32_t)a.step, a.seed_lo, a.seed_hi);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        v[j] = l[j] + (c0 + j < a.V ? a.bias[c0 + j] : 0.0f);
+        ka[j] = sid >= 0 ? v[j] + gumbel_fast_from_word(pick_word(blk, (uint32_t)j)) : v[j];
+    }
+}
+
+// The exact keys of the listed columns, one survivor per wave at a time, folded into *best.  Lane l holds terms k = l CH .. l CH + CH - 1
+// of the row (registers, once) and of the column (its row of Wt); the chain then walks the lanes in order:
+// every lane continues the running sum with its own CH terms, and lane l's result is the one carried on -- one ascending-k fmaf chain
+// from +0, the PICK epilogue's instruction sequence, then + bias, + noise, + 0.  (Terms past H are 0 * 0: they leave the sum as it is.)
+template <int CH>
+__device__ __forceinline__ void resolve_listed(const PickResolveArgs& a, const float* hs, const int* list, int n, int wave, int lane, int vid,
+                                               int sid, unsigned long long* best)
+{
+    float hr[CH];
+#pragma unroll
+    for (int i = 0; i < CH; ++i) hr[i] = lane * CH + i < a.H ? hs[lane * CH + i] : 0.0f;
+    const int nl = (a.H + CH - 1) / CH;
+    for (int s = wave; s < n; s += kResWaves) {
+        const int col = list[s];
+        float wr[CH];
+#pragma unroll
+        for (int i = 0; i < CH; i += 4) {
+            const int k = lane * CH + i;
+            const float4 x = k < a.ldt ? *reinterpret_cast<const float4*>(a.Wt + (size_t)col * a.ldt + k) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            wr[i] = x.x; wr[i + 1] = x.y; wr[i + 2] = x.z; wr[i + 3] = x.w;
+        }
+        float acc = 0.0f;
+        for (int l = 0; l < nl; ++l) {
+            float x = acc;
+#pragma unroll
+            for (int i = 0; i < CH; ++i) x = __builtin_fmaf(hr[i], wr[i], x);
+            acc = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), l));
+        }
+        float v = acc + a.bias[col];
+        if (sid >= 0) {
+            const u32x4 blk = philox4x32_10((uint32_t)col >> 2, (uint32_t)vid, (uint32_t)sid, (uint32_t)a.step, a.seed_lo, a.seed_hi);
+            v = v + gumbel_from_word(pick_word(blk, (uint32_t)col & 3u));
+        }
+        v = v + 0.0f;  // -0 -> +0 so that the integer order equals the float order
+        if (lane == 0) atomicMax(best, ((unsigned long long)orderable(v) << 32) | (uint32_t)(~(uint32_t)col));
+    }
+}
+
+// One workgroup per row; no grid-wide waits, every loop bounded by V or H.  Pass 1 keys every column and takes the row's fast maximum,
+// the largest magnitude and |h|, and leaves the keys where the logits were; pass 2 reads them back, counts the survivors, lists them in LDS
+// and resolves them.  A row with more survivors than the list holds goes chunk by chunk instead: no survivor is ever dropped.  A row with a
+// non-finite key, norm or margin takes every column (slow, equal).
+__global__ __launch_bounds__(kResThreads) void pick_resolve_kernel(PickResolveArgs a)
+{
+    __shared__ float hs[kPickScreenMaxH];
+    __shared__ int list[kResList];
+    __shared__ int nlist;
+    __shared__ float red[3][kResWaves];
+    __shared__ int nwave[kResWaves];
+    __shared__ unsigned long long best;
+    const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int sid = a.sid[row], vid = a.vid[row];
+    float* const Lr = a.L + (size_t)row * a.ldl;
+    const float inf = __builtin_inff();
+
+    float mx = -inf, amax = 0.0f, ss = 0.0f;
+    int bad = 0;
+    for (int c0 = tid * 4; c0 < a.V; c0 += kResChunk) {
+        float v[4], ka[4];
+        screen_keys4(a, Lr, c0, vid, sid, v, ka);
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (c0 + j < a.V) {
+                mx = fmaxf(mx, ka[j]);
+                amax = fmaxf(amax, fmaxf(fabsf(v[j]), fabsf(ka[j])));
+                bad |= !(fabsf(ka[j]) < inf);
+            }
+        // the fast keys take the logits' place: pass 2 reads them back (each thread its own) instead of drawing the noise again
+        if (c0 + 4 <= a.V) *reinterpret_cast<float4*>(Lr + c0) = make_float4(ka[0], ka[1], ka[2], ka[3]);
+        else
+            for (int j = 0; c0 + j < a.V; ++j) Lr[c0 + j] = ka[j];
+    }
+    for (int k = tid; k < a.H; k += kResThreads) {
+        const float x = a.h[(size_t)row * a.ldh + k];
+        hs[k] = x;
+        ss += x * x;
+    }
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        mx = fmaxf(mx, __shfl_xor(mx, off, 64));
+        amax = fmaxf(amax, __shfl_xor(amax, off, 64));
+        ss += __shfl_xor(ss, off, 64);
+    }
+    if (lane == 0) { red[0][wave] = mx; red[1][wave] = amax; red[2][wave] = ss; }
+    if (tid == 0) { best = 0ull; nlist = 0; }
+    bad = __syncthreads_or(bad);
+    float rmx = red[0][0], rabs = red[1][0], sq = red[2][0];
+#pragma unroll
+    for (int w = 1; w < kResWaves; ++w) { rmx = fmaxf(rmx, red[0][w]); rabs = fmaxf(rabs, red[1][w]); sq += red[2][w]; }
+    const float nh = sqrtf(sq) * 1.001f;
+    const float m = a.C * nh * *a.nwmax;
+    // the roundings of (logit + bias) + noise, on the fast and on the exact side: each within 2^-24 of a value no larger than rabs + m
+    const float slack = (rabs + m + 1.0f) * 9.5367431640625e-07f;          // 2^-20
+    const float margin = 2.0f * (m + kGumbelScreenMargin + slack);
+    const bool all = bad || !(margin < inf);
+    const float thr = rmx - margin;
+    const int need = (a.H + 63) / 64;                                      // terms per lane of the chain
+
+    auto resolve = [&](int n) {
+        if (need <= 4) resolve_listed<4>(a, hs, list, n, wave, lane, vid, sid, &best);
+        else if (need <= 8) resolve_listed<8>(a, hs, list, n, wave, lane, vid, sid, &best);
+        else if (need <= 16) resolve_listed<16>(a, hs, list, n, wave, lane, vid, sid, &best);
+        else resolve_listed<32>(a, hs, list, n, wave, lane, vid, sid, &best);
+    };
+    // f(column) for every survivor among the four columns at c0 (this thread's own keys of pass 1)
+    auto survivors4 = [&](int c0, auto&& f) {
+        float ka[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        if (c0 + 4 <= a.V) {
+            const float4 x = *reinterpret_cast<const float4*>(Lr + c0);
+            ka[0] = x.x; ka[1] = x.y; ka[2] = x.z; ka[3] = x.w;
+        } else {
+            for (int j = 0; c0 + j < a.V; ++j) ka[j] = Lr[c0 + j];
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (c0 + j < a.V && (all || ka[j] >= thr)) f(c0 + j);
+    };
+    int cnt = 0;
+    for (int c0 = tid * 4; c0 < a.V; c0 += kResChunk) survivors4(c0, [&](int) { ++cnt; });
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) cnt += __shfl_xor(cnt, off, 64);
+    if (lane == 0) nwave[wave] = cnt;
+    __syncthreads();
+    unsigned total = 0;
+#pragma unroll
+    for (int w = 0; w < kResWaves; ++w) total += (unsigned)nwave[w];
+    if (total <= (unsigned)kResList) {
+        // the usual row: one list, one round
+        for (int c0 = tid * 4; c0 < a.V; c0 += kResChunk) survivors4(c0, [&](int c) { list[atomicAdd(&nlist, 1)] = c; });
+        __syncthreads();
+        resolve((int)total);
+        __syncthreads();
+    } else {
+        // more survivors than the list holds: chunk by chunk, resolving whenever the next chunk might not fit behind what is listed
+        for (int base = 0; base < a.V; base += kResChunk) {
+            if (base + tid * 4 < a.V) survivors4(base + tid * 4, [&](int c) { list[atomicAdd(&nlist, 1)] = c; });
+            __syncthreads();
+            const int n = nlist;
+            __syncthreads();                                               // (everyone has read the count before the next chunk adds to it)
+            if (n <= kResList - kResChunk && base + kResChunk < a.V) continue;
+            resolve(n);
+            __syncthreads();
+            if (tid == 0) nlist = 0;
+            __syncthreads();
+        }
+    }
+    if (tid == 0) {
+        if (best != 0ull) atomicMax(&a.pick[(size_t)row * a.pick_stride], best);
+        uint32_t* const c32 = reinterpret_cast<uint32_t*>(a.counters + 1);
+        atomicAdd(a.counters, (unsigned long long)total);
+        atomicMax(c32, total);
+        if (all) atomicAdd(c32 + 1, 1u);
+    }
+}
+
+}  // namespace
+
+hipError_t launch_pick_screen_prepare(const float* W, int H, int V, const PickScreenWs& s, hipStream_t st)
+{
+    hipError_t e = hipMemsetAsync(s.counters, 0, kPickScreenHeadBytes, st);
+    if (e != hipSuccess) return e;
+    // B operand of the NT product: the hi / lo planes of W^T, [V][bf16_pad(H)], zeros past H
+    CastTrArgs c{W, V, nullptr, H, V, s.Wh, s.Hp, s.Hp, nullptr, nullptr, nullptr, 0, s.Wl, nullptr};
+    e = launch_cast_tr_bf16(c, st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(pick_screen_prepare_kernel, dim3((V + 63) / 64), dim3(256), 0, st, W, V, H, V, s.Wt, s.ldt, reinterpret_cast<uint32_t*>(s.nwmax));
+    return hipGetLastError();
+}
+
+hipError_t launch_pick_screen_step(const float* h, int ldh, const float* W, const float* bias, int R, int H, int V, const int32_t* vid,
+                                   const int32_t* sid, uint64_t seed, int step, unsigned long long* pick, int pick_stride, const PickScreenWs& s,
+                                   hipStream_t st)
+{
+    if (R <= 0) return hipSuccess;
+    if (H > kPickScreenMaxH) return hipErrorInvalidValue;
+    hipError_t e = launch_cast_rows_bf16(h, ldh, nullptr, R, H, s.hh, s.Hp, st, s.hl);
+    if (e != hipSuccess) return e;
+    e = launch_gemm_bf16x3_nt(s.hh, s.hl, s.Hp, s.Wh, s.Wl, s.Hp, s.L, s.ldl, R, V, s.Hp, 0, nullptr, 0, 2, st);
+    if (e != hipSuccess) return e;
+    PickResolveArgs a;
+    a.L = s.L; a.ldl = s.ldl; a.bias = bias; a.h = h; a.ldh = ldh; a.Wt = s.Wt; a.ldt = s.ldt; a.vid = vid; a.sid = sid;
+    a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32); a.step = step;
+    a.pick = pick; a.pick_stride = pick_stride > 0 ? pick_stride : 1;
+    a.nwmax = s.nwmax; a.counters = s.counters; a.H = H; a.V = V;
+    a.C = 9.765625e-04f * (float)((H + 1023) / 1024);                      // 2^-10 per 1024 reduction steps
+    hipLaunchKernelGGL(pick_resolve_kernel, dim3((unsigned)R), dim3(kResThreads), 0, st, a);
+    return hipGetLastError();
+}
+
+}  // namespace s2vt

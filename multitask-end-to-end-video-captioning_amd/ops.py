@@ -485,8 +485,15 @@ def sample(dims: Dims, params: Params, video, K: int, seed: int, video_base: int
         check(L.s2vt_sample_ex(C.byref(dims), C.byref(params), _ptr(video), B, K, g, seed, video_base, 1, _ptr(ids), _ptr(ws),
                                ws.numel(), _stream()), "s2vt_sample_ex")
     else:
-        check(L.s2vt_sample(C.byref(dims), C.byref(params), _ptr(video), B, K, g, seed, video_base, _ptr(ids), _ptr(ws),
-                            ws.numel(), _stream()), "s2vt_sample")
+        # the screened pick (same ids) where the library serves the shape; its scratch is a block of its own, the sampler workspace is unchanged
+        sbytes = L.s2vt_sample_screen_workspace_bytes(C.byref(dims), B, K, g)
+        if sbytes > 0:
+            sws = workspace(sbytes, video.device, "sample_screen")
+            check(L.s2vt_sample_screened(C.byref(dims), C.byref(params), _ptr(video), B, K, g, seed, video_base, _ptr(ids), _ptr(ws),
+                                         ws.numel(), _ptr(sws), sws.numel(), _stream()), "s2vt_sample_screened")
+        else:
+            check(L.s2vt_sample(C.byref(dims), C.byref(params), _ptr(video), B, K, g, seed, video_base, _ptr(ids), _ptr(ws),
+                                ws.numel(), _stream()), "s2vt_sample")
     sample.serial += 1                                                 # the workspace is shared by every caller: a later call overwrites it
     sample.last_state = (ws, (K + g) * B, video.data_ptr(), B, sample.serial)   # for teacher_forced_fwd(sampler_state=...)
     return ids[:K * B], (ids[K * B:] if with_greedy else None)
