@@ -560,6 +560,40 @@ int s2vt_softmax_nll_fwd_bwd_split(float* logits, int32_t ld, int32_t R, int32_t
                                    const float* smoothing_rows, float* nll, float* lp_target, const s2vt_dims* d, int32_t B, int32_t N,
                                    void* split_ws, size_t split_ws_bytes, s2vt_stream stream);
 
+/* The forward form of the split-bf16 product: C[M,N] (+)= sum over k < K of A[m][k].B[k][n] with the same three products -- A by
+ * rows as in the NT form ([M][lda], lda >= bf16_pad(K), % 8 == 0), B K-major as in the TN form ([K][ldb], ldb >= N, % 8 == 0: a
+ * weight as it lies in memory, cast by rows -- no transposed copy), all planes 16-byte aligned.  A's columns in [K, bf16_pad(K)) ARE
+ * read and must be finite (s2vt_cast_bf16_split leaves zeros there); B's rows >= K are never read, its columns up to the next
+ * multiple of 128 may be; (bf16_pad(K) + 1).ldb.2 bytes must stay below 2 GiB, else S2VT_E_BADARG.  The same K steps and accumulation
+ * order as the other two forms: the same bits as either on explicitly transposed planes.  bias (optional, fp32 [N], accumulate == 0
+ * only): C = product + bias[col].  scratch as for the NT form. */
+int s2vt_gemm_bf16x3_nn(const uint16_t* Ah, const uint16_t* Al, int32_t lda, const uint16_t* Bh, const uint16_t* Bl, int32_t ldb, float* C,
+                        int32_t ldc, int32_t M, int32_t N, int32_t K, int32_t accumulate, const float* bias, void* scratch, size_t scratch_bytes,
+                        s2vt_stream stream);
+
+/* The teacher-forced forward of an UPDATE whose backward is the fused split form: s2vt_teacher_forced_fwd_live with the split
+ * workspace of (d, B, N) (s2vt_split_grad_workspace_bytes; validated like the backward's: S2VT_E_ALIGN when not 256-byte aligned,
+ * S2VT_E_WORKSPACE when short, before anything is launched).  Both recurrences, dropout, the sampler-state reuse, live rows and
+ * caption_steps are those of the live entry, bit for bit; what changes is the arithmetic of the hoisted products, by stage
+ * (s2vt_split_fwd_stage(): the env S2VT_SPLIT_FWD, read once -- 0, 1 or 2; anything else or unset = the default, 1):
+ *   1  the vocabulary logits O2.embed_word_W + b run as s2vt_gemm_bf16x3_nn on split-bf16 planes (within ~1e-6 of the product's
+ *      maximum of the fp32 chain's value, the arithmetic the backward's gradient products already use);
+ *   2  LSTM2's hoisted input partials ([O1 ; embed(prev)].lstm2_W[0:H+E], encode and decode rows) too -- LSTM2's states then differ
+ *      from the live entry's by rounding-level amounts.
+ * Where the shape does not fit (the split mode is not active for N: N <= 256 or S2VT_SPLIT_GRADS=0; lstm_dim % 8; planes beyond the
+ * K-major loader's reach) or at stage 0 the fp32 products run and the call IS s2vt_teacher_forced_fwd_live.  S2VT_SPLIT_FUSED, which
+ * picks the operand layout of the BACKWARD's products, does not change the forward.  The forward uses AT, W (and at stage 2 BT) of
+ * the split workspace and never the dlogits planes' region.  The token-deciding paths never come here.
+ * s2vt_split_fwd_active(N): the stage that applies at N unrolled rows (0: the fp32 products). */
+int s2vt_split_fwd_stage(void);
+int s2vt_split_fwd_active(int32_t N);
+int s2vt_teacher_forced_fwd_split(const s2vt_dims* d, const s2vt_params* p, const float* video, int32_t B, int32_t N,
+                                  const int32_t* caption, int32_t caption_steps, const int32_t* live_rows, int32_t n_live, float keep,
+                                  uint64_t seed, const int32_t* video_id, const int32_t* sample_id, float* logits_out,
+                                  void* workspace, size_t workspace_bytes, const void* sampler_workspace,
+                                  size_t sampler_workspace_bytes, int32_t sampler_rows, void* split_ws, size_t split_ws_bytes,
+                                  s2vt_stream stream);
+
 /* Gradient w.r.t. the frame features, for the end-to-end scripts where they are the CNN's output
  * (e2e_tf_s2vt.py:106-121,163-166: the optimizer differentiates through `video` into Inception-ResNet-v2):
  * d_video[B, Tv, dim_image] = d_emb @ encode_image_W^T, from the d_emb the preceding s2vt_bptt_bwd (phase 0 or 2)

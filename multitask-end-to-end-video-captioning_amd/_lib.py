@@ -143,7 +143,12 @@ SIGNATURES = {
     "s2vt_cast_bf16_split": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _sz, _vp]),
     "s2vt_gemm_bf16x3_nt": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _sz, _vp]),
     "s2vt_gemm_bf16x3_tn": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _sz, _vp]),
+    "s2vt_gemm_bf16x3_nn": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _sz, _vp]),
     "s2vt_split_grad_active": (C.c_int, [_i32]),
+    "s2vt_split_fwd_stage": (C.c_int, []),
+    "s2vt_split_fwd_active": (C.c_int, [_i32]),
+    "s2vt_teacher_forced_fwd_split": (C.c_int, [_DP, _PP, _vp, _i32, _i32, _vp, _i32, _vp, _i32, _f32, _u64, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _i32,
+                                                _vp, _sz, _vp]),
     "s2vt_train_workspace_dz2": (C.c_int, [_DP, _i32, _i32, C.POINTER(_sz), C.POINTER(_sz)]),
     "s2vt_split_grad_dlogits_planes": (C.c_int, [_DP, _i32, _i32, C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_i32)]),
     "s2vt_softmax_nll_fwd_bwd_split": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _f32, _vp, _vp, _vp, _DP, _i32, _i32, _vp, _sz, _vp]),

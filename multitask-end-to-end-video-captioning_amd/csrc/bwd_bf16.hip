@@ -22,13 +22,14 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 // row form: dst[r][k] = bf16(src[row(r)][k]) for k < K, 0 for K <= k < bf16_pad(K).  One 16-byte store per 8 elements.
 // SPLIT: dst the hi plane, dst_lo the lo plane (same ldd).  ones: the row is bf16_pad(K + 1) wide and column K holds 1 (hi 1, lo 0) -- as
 // the K-major operand A of gemm_bf16x3_tn it makes output row K the column sums of B (a bias gradient riding in the product).
+// width (a multiple of 8): the columns written per row, bf16_pad(K + ones) unless the caller places the row inside a wider one.
 // ---------------------------------------------------------------------------------------------
 template <bool SPLIT>
 __global__ __launch_bounds__(256) void cast_rows_bf16_kernel(const float* __restrict__ src, int ld, const int32_t* __restrict__ rowidx,
                                                              int R, int K, uint16_t* __restrict__ dst, int ldd, int vec,
-                                                             uint16_t* __restrict__ dst_lo, int ones)
+                                                             uint16_t* __restrict__ dst_lo, int ones, int width)
 {
-    const int cpr = bf16_pad(K + ones) / 8;
+    const int cpr = width / 8;
     const long total = (long)R * cpr;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
         const int r = (int)(i / cpr), k0 = (int)(i % cpr) * 8;
@@ -283,14 +284,24 @@ __global__ __launch_bounds__(256) void gemm_bf16_nt_kernel(GemmBf16Args g)
 // past K load zeros (buffer range check: the descriptor ends behind row K - 1); a tile's columns past lda / ldb come from the next
 // row and only reach outputs that are not stored.  bias (optional): output row M -- the product of A's column M, which the caller
 // filled with ones (cast_rows_bf16 ones) -- is added to bias[n] instead of a C row: the column sums of B.
+//
+// FORM = kX3NN, gemm_bf16x3_nn: C[M,N] (+)= sum_k A[m][k] B[k][n], a forward product -- A by rows ([M][lda], what cast_rows_bf16 writes) and
+// B K-major ([K][ldb], a weight as it lies in memory).  A plane's loader and fragment reads do not depend on the other operand's: loader
+// waves 4-5 and the A fragments take the NT code, loader waves 6-7 and the B fragments the TN code (both issue kX3Dma instructions per K
+// step, so the counted waits hold).  A's columns in [K, bf16_pad(K)) are read (finite by contract); B's k rows >= K load zeros, so whatever
+// A holds there adds exact zeros.  cbias (optional): C = acc + cbias[col], once per stored column -- by the reduce kernel under split-K.
 // ---------------------------------------------------------------------------------------------
 struct GemmX3Args {
     const uint16_t *Ah, *Al; int lda; const uint16_t *Bh, *Bl; int ldb; float* C; int ldc;
     int M, N, nk, nk_slab, accumulate, tiles_m, tiles_n;
     float* part;                                      // split-K slabs [slabs][Mo][N], or nullptr: the tile goes to C
     int K;                                            // TN: rows of the planes
-    float* bias; int Mo;                              // TN: optional [N] += output row M; Mo = M + (bias ? 1 : 0) output rows (NT: Mo = M)
+    float* bias; int Mo;                              // TN: optional [N] += output row M; Mo = M + (bias ? 1 : 0) output rows (NT, NN: Mo = M)
+    const float* cbias;                               // NN: optional [N], added once to every stored column (non-accumulating launches)
 };
+
+// the three forms: which of the two operands lie K-major ([K][ld], the TN loader and the transposed fragment reads)
+enum : int { kX3NT = 0, kX3TN = 1, kX3NN = 2 };
 
 constexpr int kX3BK = 32, kX3Slots = 4, kX3Plane = kTile * kX3BK;   // a plane's K step: 128 rows x 32 bf16 = 8 KB
 constexpr int kX3Lds = kX3Slots * 4 * kX3Plane * 2;                  // 128 KB: one workgroup per CU
@@ -299,9 +310,10 @@ typedef __attribute__((address_space(3))) void* x3_lds_ptr;
 typedef short i16x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) i16x4* x3_tr_ptr;
 
-template <bool TN>
+template <int FORM>
 __global__ __launch_bounds__(512) void gemm_bf16x3_kernel(GemmX3Args g)
 {
+    constexpr bool ATN = FORM == kX3TN, BTN = FORM != kX3NT;            // A's planes / B's planes K-major
     extern __shared__ __attribute__((aligned(16))) uint16_t x3lds[];   // [slot][plane][128 rows][32]
     const int nwg = g.tiles_m * g.tiles_n, orig = blockIdx.x;
     const int xcd = orig & 7, q = nwg >> 3, rem = nwg & 7;
@@ -314,13 +326,15 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_kernel(GemmX3Args g)
     if (w >= 4) {
         // ================= loader wave: plane p, 8 DMA instructions per K step
         const int p = w - 4;
+        // this plane's layout: a constant in the NT and TN forms (the branches below fold), wave-uniform in NN -- A's planes by rows, B's K-major
+        const bool TN = ATN == BTN ? ATN : p >= 2;
         const uint16_t* const plane = p == 0 ? g.Ah : p == 1 ? g.Al : p == 2 ? g.Bh : g.Bl;
         const int r0 = p < 2 ? m0 : n0, rows = p < 2 ? g.M : g.N, ld = p < 2 ? g.lda : g.ldb;
         // NT: the descriptor starts at the tile's first row; TN: at its first column, and ends behind k row K - 1
         const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(plane + (TN ? (size_t)r0 : (size_t)r0 * ld)), 0,
                                                                             TN ? (int)(((uint32_t)g.K * (uint32_t)ld - (uint32_t)r0) * 2u) : (int)kOob, 0x00020000);
         uint32_t voff[kX3Dma];
-        if constexpr (TN) {
+        if (TN) {
             // lane -> (k row lane >> 4 of a 4-row block, LDS 16-byte slot s = lane & 15): loads the 16-byte piece s & 1 of column block
             // (s >> 1) ^ swz(k), swz(k) = (k & 3) | ((k >> 1) & 4) = kr | ((b & 2) << 1) for k = 4 b + kr
             const int kr = lane >> 4, s = lane & 15;
@@ -338,7 +352,7 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_kernel(GemmX3Args g)
         }
         auto issue = [&](int ks) __attribute__((always_inline)) {
             uint16_t* const dst = x3lds + ((ks % kX3Slots) * 4 + p) * kX3Plane;
-            if constexpr (TN) {
+            if (TN) {
                 // (the K step goes into the VECTOR offset: that is the part of the address the range check sees)
                 const uint32_t koff = (uint32_t)(kbeg + ks) * kX3BK * (uint32_t)ld * 2u;
 #pragma unroll
@@ -392,7 +406,16 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_kernel(GemmX3Args g)
         for (int pl = 0; pl < 4; ++pl)
 #pragma unroll
             for (int i = 0; i < 4; ++i)
-                if constexpr (TN) {
+                if constexpr (ATN != BTN) {                                // NN: A's planes by rows, B's K-major
+                    if (pl < 2) {
+                        f[pl][i] = *reinterpret_cast<const bf16x8*>(s + pl * kX3Plane + (wr * 64 + i * 16) * kX3BK + fofs);
+                    } else {
+                        const uint16_t* const a = s + pl * kX3Plane + tofs + (((wc * 4 + i) ^ tswz) << 4);
+                        const i16x4 lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((x3_tr_ptr)a);
+                        const i16x4 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((x3_tr_ptr)(a + 4 * kTile));
+                        f[pl][i] = __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo4, hi4, 0, 1, 2, 3, 4, 5, 6, 7));
+                    }
+                } else if constexpr (ATN) {
                     const uint16_t* const a = s + pl * kX3Plane + tofs + ((((pl < 2 ? wr : wc) * 4 + i) ^ tswz) << 4);
                     const i16x4 lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((x3_tr_ptr)a);
                     const i16x4 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((x3_tr_ptr)(a + 4 * kTile));
@@ -442,8 +465,13 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_kernel(GemmX3Args g)
                 const int row = m0 + wr * 64 + i * 16 + (lane >> 4) * 4 + e, col = n0 + wc * 64 + j * 16 + (lane & 15);
                 if (row < g.M && col < g.N) {
                     float* c = out + (size_t)row * ldo + col;
-                    *c = add ? *c + acc[i][j][e] : acc[i][j][e];
-                } else if (TN && row == g.M && g.bias && col < g.N) {
+                    if constexpr (FORM == kX3NN) {
+                        const float v = !g.part && g.cbias ? acc[i][j][e] + g.cbias[col] : acc[i][j][e];
+                        *c = add ? *c + v : v;
+                    } else {
+                        *c = add ? *c + acc[i][j][e] : acc[i][j][e];
+                    }
+                } else if (FORM == kX3TN && row == g.M && g.bias && col < g.N) {
                     if (g.part) out[(size_t)row * ldo + col] = acc[i][j][e];
                     else g.bias[col] += acc[i][j][e];                      // (a bias gradient accumulates, as its weight's)
                 }
@@ -452,7 +480,7 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_kernel(GemmX3Args g)
 
 // C (+)= sum over slabs of part[s] (slab order); slab row M (Mo = M + 1 rows, gemm_bf16x3_tn's bias row) is ADDED to bias
 __global__ __launch_bounds__(256) void reduce_slabs_kernel(const float* __restrict__ part, int slabs, int M, int N, float* __restrict__ C, int ldc,
-                                                           int accumulate, int Mo, float* __restrict__ bias)
+                                                           int accumulate, int Mo, float* __restrict__ bias, const float* __restrict__ cbias)
 {
     const size_t MN = (size_t)Mo * N;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < MN; i += (size_t)gridDim.x * 256) {
@@ -461,6 +489,7 @@ __global__ __launch_bounds__(256) void reduce_slabs_kernel(const float* __restri
         const size_t r = i / N;
         if (r < (size_t)M) {
             float* c = C + r * ldc + i % N;
+            if (cbias) s = s + cbias[i % N];
             *c = accumulate ? *c + s : s;
         } else {
             bias[i % N] += s;
@@ -470,16 +499,18 @@ __global__ __launch_bounds__(256) void reduce_slabs_kernel(const float* __restri
 }  // namespace
 
 hipError_t launch_cast_rows_bf16(const float* src, int ld, const int32_t* rowidx, int R, int K, uint16_t* dst, int ldd, hipStream_t st,
-                                 uint16_t* dst_lo, int ones)
+                                 uint16_t* dst_lo, int ones, int width)
 {
     if (R <= 0 || K <= 0) return hipSuccess;
     ones = ones ? 1 : 0;
+    if (width <= 0) width = bf16_pad(K + ones);
+    if ((width & 7) || width < K + ones) return hipErrorInvalidValue;
     const int vec = !((reinterpret_cast<uintptr_t>(src) & 15) || (ld & 3));
-    const long chunks = (long)R * (bf16_pad(K + ones) / 8);
+    const long chunks = (long)R * (width / 8);
     const long blocks = (chunks + 255) / 256;
     const dim3 grid((unsigned)(blocks < 8192 ? blocks : 8192));
-    if (dst_lo) hipLaunchKernelGGL(cast_rows_bf16_kernel<true>, grid, dim3(256), 0, st, src, ld, rowidx, R, K, dst, ldd, vec, dst_lo, ones);
-    else hipLaunchKernelGGL(cast_rows_bf16_kernel<false>, grid, dim3(256), 0, st, src, ld, rowidx, R, K, dst, ldd, vec, dst_lo, ones);
+    if (dst_lo) hipLaunchKernelGGL(cast_rows_bf16_kernel<true>, grid, dim3(256), 0, st, src, ld, rowidx, R, K, dst, ldd, vec, dst_lo, ones, width);
+    else hipLaunchKernelGGL(cast_rows_bf16_kernel<false>, grid, dim3(256), 0, st, src, ld, rowidx, R, K, dst, ldd, vec, dst_lo, ones, width);
     return hipGetLastError();
 }
 
@@ -541,17 +572,17 @@ size_t gemm_bf16x3_part_floats(int M, int N, int Kp)
 }
 
 namespace {
-// the launch of either form (TN: Kp = the planes' K rows, any count; NT: Kp % 64 == 0)
-template <bool TN>
+// the launch of any form (TN, NN: Kp = the reduction length K, any count; NT: Kp % 64 == 0)
+template <int FORM>
 hipError_t launch_x3(const uint16_t* Ah, const uint16_t* Al, int lda, const uint16_t* Bh, const uint16_t* Bl, int ldb, float* C, int ldc, int M, int N,
-                     int Kp, int accumulate, float* bias, float* part, size_t part_floats, int cls, hipStream_t st)
+                     int Kp, int accumulate, float* bias, float* part, size_t part_floats, int cls, hipStream_t st, const float* cbias = nullptr)
 {
     if (M <= 0 || N <= 0) return hipSuccess;
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_bf16x3_kernel<TN>), hipFuncAttributeMaxDynamicSharedMemorySize, kX3Lds);
+    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_bf16x3_kernel<FORM>), hipFuncAttributeMaxDynamicSharedMemorySize, kX3Lds);
     if (attr != hipSuccess) return attr;
     GemmX3Args g;
     g.Ah = Ah; g.Al = Al; g.lda = lda; g.Bh = Bh; g.Bl = Bl; g.ldb = ldb; g.C = C; g.ldc = ldc; g.M = M; g.N = N;
-    g.K = Kp; g.bias = bias; g.Mo = M + (bias ? 1 : 0);
+    g.K = Kp; g.bias = bias; g.Mo = M + (bias ? 1 : 0); g.cbias = cbias;
     const int Kr = bf16_pad(Kp);
     g.nk = Kr / kX3BK; g.accumulate = accumulate;
     g.tiles_m = (g.Mo + kTile - 1) / kTile; g.tiles_n = (N + kTile - 1) / kTile;
@@ -568,15 +599,15 @@ hipError_t launch_x3(const uint16_t* Ah, const uint16_t* Al, int lda, const uint
         if (pe != hipSuccess) return pe;
         (void)hipEventRecord(e0, st);
     }
-    hipLaunchKernelGGL(gemm_bf16x3_kernel<TN>, grid, dim3(512), kX3Lds, st, g);
+    hipLaunchKernelGGL(gemm_bf16x3_kernel<FORM>, grid, dim3(512), kX3Lds, st, g);
     if (slabs > 1) {
         const size_t MN = (size_t)g.Mo * N, blocks = (MN + 255) / 256;
         hipLaunchKernelGGL(reduce_slabs_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, st, (const float*)part, slabs, M, N, C, ldc,
-                           accumulate, g.Mo, bias);
+                           accumulate, g.Mo, bias, cbias);
     }
     if (prof) {
         (void)hipEventRecord(e1, st);
-        prof_record(cls, 16, cls == 2 ? "x3_128x128(dma) pick screen" : cls == 3 ? "x3_128x128(dma) wgrad" : "x3_128x128(dma) dgrad",
+        prof_record(cls, 16, cls == 0 ? "x3_128x128(dma) fwd" : cls == 2 ? "x3_128x128(dma) pick screen" : cls == 3 ? "x3_128x128(dma) wgrad" : "x3_128x128(dma) dgrad",
                     2.0 * M * (double)N * Kp, e0, e1);
     }
     return hipGetLastError();
@@ -586,7 +617,7 @@ hipError_t launch_x3(const uint16_t* Ah, const uint16_t* Al, int lda, const uint
 hipError_t launch_gemm_bf16x3_nt(const uint16_t* Ah, const uint16_t* Al, int lda, const uint16_t* Bh, const uint16_t* Bl, int ldb, float* C, int ldc,
                                  int M, int N, int Kp, int accumulate, float* part, size_t part_floats, int cls, hipStream_t st)
 {
-    return launch_x3<false>(Ah, Al, lda, Bh, Bl, ldb, C, ldc, M, N, Kp, accumulate, nullptr, part, part_floats, cls, st);
+    return launch_x3<kX3NT>(Ah, Al, lda, Bh, Bl, ldb, C, ldc, M, N, Kp, accumulate, nullptr, part, part_floats, cls, st);
 }
 
 bool gemm_bf16x3_tn_ok(int lda, int ldb, int K)
@@ -600,7 +631,14 @@ hipError_t launch_gemm_bf16x3_tn(const uint16_t* Ah, const uint16_t* Al, int lda
                                  int M, int N, int K, int accumulate, float* bias, float* part, size_t part_floats, int cls, hipStream_t st)
 {
     if (!gemm_bf16x3_tn_ok(lda, ldb, K)) return hipErrorInvalidValue;
-    return launch_x3<true>(Ah, Al, lda, Bh, Bl, ldb, C, ldc, M, N, K, accumulate, bias, part, part_floats, cls, st);
+    return launch_x3<kX3TN>(Ah, Al, lda, Bh, Bl, ldb, C, ldc, M, N, K, accumulate, bias, part, part_floats, cls, st);
+}
+
+hipError_t launch_gemm_bf16x3_nn(const uint16_t* Ah, const uint16_t* Al, int lda, const uint16_t* Bh, const uint16_t* Bl, int ldb, float* C, int ldc,
+                                 int M, int N, int K, int accumulate, const float* cbias, float* part, size_t part_floats, int cls, hipStream_t st)
+{
+    if (!gemm_bf16x3_tn_ok(ldb, ldb, K) || lda < bf16_pad(K) || (cbias && accumulate)) return hipErrorInvalidValue;
+    return launch_x3<kX3NN>(Ah, Al, lda, Bh, Bl, ldb, C, ldc, M, N, K, accumulate, nullptr, part, part_floats, cls, st, cbias);
 }
 
 }  // namespace s2vt

@@ -330,8 +330,9 @@ __device__ __forceinline__ void split2(float a, float b, uint32_t& hi, uint32_t&
 // dst[r][k] = bf16(src[row(r)][k]) (row(r) = rowidx ? rowidx[r] : r) for k < K, zeros up to bf16_pad(K); dst 16-byte aligned, ldd % 8 == 0
 // dst_lo (optional): the split form -- dst = bf16(x) (hi), dst_lo = bf16(x - hi) (lo), same ldd
 // ones: rows bf16_pad(K + 1) wide with column K = 1 -- the operand A of launch_gemm_bf16x3_tn with a bias row
+// width (0 = bf16_pad(K + ones); a multiple of 8, >= K + ones): the columns written per row, zeros past K -- a row placed inside a wider one
 hipError_t launch_cast_rows_bf16(const float* src, int ld, const int32_t* rowidx, int R, int K, uint16_t* dst, int ldd, hipStream_t st,
-                                 uint16_t* dst_lo = nullptr, int ones = 0);
+                                 uint16_t* dst_lo = nullptr, int ones = 0, int width = 0);
 // dst[c][r] = bf16(src[row(r)][c]) for r < R, zeros for R <= r < Rp (Rp a multiple of 64; dst 16-byte aligned, ldd % 8 == 0).
 // rdst (optional): the row form as well, rdst[r][c] for c < bf16_pad(C) (8-byte aligned, rldd % 4 == 0).
 // colsum (optional): += the column sums of the fp32 input rows (fixed order, no atomics), through part[cast_tr_part_floats(Rp, C)].
@@ -361,6 +362,13 @@ size_t gemm_bf16x3_part_floats(int M, int N, int Kp);
 bool gemm_bf16x3_tn_ok(int lda, int ldb, int K);     // the planes' byte offsets fit the loader's 32 bits
 hipError_t launch_gemm_bf16x3_tn(const uint16_t* Ah, const uint16_t* Al, int lda, const uint16_t* Bh, const uint16_t* Bl, int ldb, float* C, int ldc,
                                  int M, int N, int K, int accumulate, float* bias, float* part, size_t part_floats, int cls, hipStream_t st);
+// The forward form: C[M,N] (+)= sum_k A[m][k] B[k][n] -- A by rows as in the NT form ([M][lda], lda >= bf16_pad(K); its columns in
+// [K, bf16_pad(K)) ARE read and must be finite: cast_rows_bf16 leaves zeros, or the ones column, there), B K-major as in the TN form
+// ([K][ldb], a weight as it lies in memory cast by rows; k rows >= K are never read; gemm_bf16x3_tn_ok(ldb, ldb, K) must hold).  The same
+// K steps and MFMA order again: equal bits with NT / TN on explicitly transposed planes.  cbias (optional, accumulate == 0 only): fp32 [N],
+// C = product + cbias[col].  cls 0: the forward's class of the launch profiler.
+hipError_t launch_gemm_bf16x3_nn(const uint16_t* Ah, const uint16_t* Al, int lda, const uint16_t* Bh, const uint16_t* Bl, int ldb, float* C, int ldc,
+                                 int M, int N, int K, int accumulate, const float* cbias, float* part, size_t part_floats, int cls, hipStream_t st);
 // the split softmax (aux.hip): as launch_softmax_nll, but dlogits leaves as hi / lo planes [R][ldp] (ldp >= bf16_pad(V), pad columns zero)
 // and the logits stay; false: the shape is not the register kernel's (V % 4, V > 12288, alignment) -- nothing launched
 bool softmax_nll_split_ok(const float* logits, int ld, int V, const uint16_t* hi, const uint16_t* lo, int ldp);

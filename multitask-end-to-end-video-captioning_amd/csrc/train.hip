@@ -312,7 +312,7 @@ hipError_t lstm_recurrence_bwd(const float* W, int kw0, const float* gates, cons
 // pass's workspace), its dropped output O1 for the N sample rows, and the out1 partials of LSTM2's Tv encode steps in G2.
 int unroll_front(const s2vt_dims* d, const s2vt_params* p, const float* video, int B, int N, int T, float keep, uint64_t seed,
                  const int32_t* video_id, const int32_t* sample_id, const TrainWs& w, const void* sampler_workspace,
-                 size_t sampler_workspace_bytes, int sampler_rows, s2vt_stream stream)
+                 size_t sampler_workspace_bytes, int sampler_rows, s2vt_stream stream, bool encode_partials = true)
 {
     const int H = d->lstm_dim, E = d->word_dim, Tv = d->n_video_lstm_step;
     const size_t NH = (size_t)N * H, BH = (size_t)B * H;
@@ -367,8 +367,8 @@ int unroll_front(const s2vt_dims* d, const s2vt_params* p, const float* video, i
     // DropoutWrapper(LSTM1) output for the N sample rows (tf_s2vt.py:75; code = 256 + t)
     HIP_TRY(launch_expand_dropout(w.H1 + BH, w.O1, T, B, N, H, keep, seed, 256u, video_id, sample_id, st));
     // ---- LSTM2, encode steps: the out1 rows of W2, written where the step's activated gates will go (the step kernel reads its
-    // partial, then overwrites it)
-    {
+    // partial, then overwrites it).  encode_partials = false: the caller makes them (the split forward's stage B)
+    if (encode_partials) {
         ASeg se = make_seg(w.O1, H, H, 0);                                       // encode: the word slot is the zero padding (:122)
         HIP_TRY(store_call(&se, 1, p->lstm2_W, 4 * H, nullptr, w.G2, 4 * H, Tv * N, 4 * H, 0, -1, st));
     }
@@ -607,17 +607,25 @@ int s2vt_teacher_forced_fwd_steps(const s2vt_dims* d, const s2vt_params* p, cons
                                         workspace, workspace_bytes, sampler_workspace, sampler_workspace_bytes, sampler_rows, stream);
 }
 
-int s2vt_teacher_forced_fwd_live(const s2vt_dims* d, const s2vt_params* p, const float* video, int32_t B, int32_t N,
-                                 const int32_t* caption, int32_t caption_steps, const int32_t* live_rows, int32_t n_live, float keep,
-                                 uint64_t seed, const int32_t* video_id, const int32_t* sample_id, float* logits, void* workspace,
-                                 size_t workspace_bytes, const void* sampler_workspace, size_t sampler_workspace_bytes,
-                                 int32_t sampler_rows, s2vt_stream stream)
+// The teacher-forced forward.  split_entry false: s2vt_teacher_forced_fwd_live, every product an fp32 chain.  true:
+// s2vt_teacher_forced_fwd_split -- the split workspace is validated with the other arguments (before anything is launched), and at
+// stage >= 1 the vocabulary logits, at stage 2 LSTM2's hoisted input partials too, run as split-bf16 NN products where the shape fits.
+constexpr int kSplitFwdDefault = 1;      // the highest stage that is kept as the default (profiles/NOTES.md)
+static bool split_mode_on(int N);        // (below, with the backward: S2VT_SPLIT_GRADS and the 256-row threshold)
+
+static int teacher_forced_fwd_body(const s2vt_dims* d, const s2vt_params* p, const float* video, int32_t B, int32_t N,
+                                   const int32_t* caption, int32_t caption_steps, const int32_t* live_rows, int32_t n_live, float keep,
+                                   uint64_t seed, const int32_t* video_id, const int32_t* sample_id, float* logits, void* workspace,
+                                   size_t workspace_bytes, const void* sampler_workspace, size_t sampler_workspace_bytes,
+                                   int32_t sampler_rows, s2vt_stream stream, void* split_ws, size_t split_ws_bytes, bool split_entry, int stage)
 {
     if ((live_rows == nullptr) != (n_live == 0) || n_live < 0) return S2VT_E_BADARG;
     if (!dims_ok_res(d) || !params_ok(p) || !video || !caption || !logits || !workspace || B <= 0 || N <= 0 || N % B)
         return S2VT_E_BADARG;
     if (!(keep > 0.0f) || (keep < 1.0f && (!video_id || !sample_id))) return S2VT_E_BADARG;
+    if (split_entry && !split_ws) return S2VT_E_BADARG;
     if (reinterpret_cast<uintptr_t>(workspace) & 255u) return S2VT_E_ALIGN;
+    if (split_entry && (reinterpret_cast<uintptr_t>(split_ws) & 255u)) return S2VT_E_ALIGN;
     if (chain_fault()) return S2VT_E_CHAIN_TIMEOUT;
     if (caption_steps < 1 || caption_steps > d->n_caption_lstm_step) return S2VT_E_BADARG;
     if (live_rows && (n_live > caption_steps * N || ((d->lstm_dim | d->word_dim) & 3))) return S2VT_E_BADARG;     // (packed rows move as 16-byte pieces)
@@ -629,28 +637,71 @@ int s2vt_teacher_forced_fwd_live(const s2vt_dims* d, const s2vt_params* p, const
     TrainWs w;
     carve_train(c, d, B, N, &w);
     if (!c.ok()) return S2VT_E_WORKSPACE;
+    Bf16Ws bw{};
+    if (split_entry) {
+        // (held to its declared size whatever the stage or the shape makes of it, as the backward holds it)
+        Carver cb(split_ws, split_ws_bytes);
+        carve_bf16(cb, d, B, N, &bw, true);
+        if (!cb.ok()) return S2VT_E_WORKSPACE;
+    }
     hipStream_t st = S(stream);
+    const size_t NH = (size_t)N * H;
+    const int Rd = live_rows ? n_live : Tc * N;               // decode rows of the hoisted products
+    // What runs on split-bf16: where the backward's products do (the split mode is active for N -- whichever operand layout
+    // S2VT_SPLIT_FUSED gives the backward: the forward's arithmetic does not depend on that knob), operands the casts can place (H % 8: the
+    // embedding columns start at a 16-byte boundary behind O1's), planes within the K-major loader's reach and row planes that fit their region.
+    const int K4 = bf16_pad(4 * H), Kv = bf16_pad(V), Hp1 = bf16_pad(H + 1), HEp = bf16_pad(H + E);
+    const bool split_on = split_entry && stage >= 1 && split_mode_on(N) && !(H & 7);
+    // stage A's A planes [Rd][bf16_pad(H + 1)]: AT (the fused carve counts them: always; the unfused one may be shorter), else BT
+    const size_t bt_cap = split_entry ? (size_t)(bw.AT - bw.BT) : 0, at_cap = split_entry ? (size_t)(bw.L + bw.lo_delta - bw.AT) : 0;
+    uint16_t* const o2p = (size_t)Rd * Hp1 <= at_cap ? bw.AT : (size_t)Rd * Hp1 <= bt_cap ? bw.BT : nullptr;
+    const bool split_logits = split_on && o2p && gemm_bf16x3_tn_ok(Kv, Kv, H);
+    // (stage B's A planes live in BT, unused by the fused backward and free until the backward otherwise: [rows][bf16_pad(H + E)])
+    const bool split_g2 = split_on && stage >= 2 && gemm_bf16x3_tn_ok(K4, K4, H + E) && (size_t)(Tv * N > Rd ? Tv * N : Rd) * HEp <= bt_cap;
+    auto lo = [&](uint16_t* hi) { return hi + bw.lo_delta; };
+    auto nn = [&](uint16_t* A, int lda, uint16_t* Bm, int ldb, float* Cm, int ldc, int M, int Nn, int K, const float* cbias) {
+        return launch_gemm_bf16x3_nn(A, lo(A), lda, Bm, lo(Bm), ldb, Cm, ldc, M, Nn, K, 0, cbias, bw.kpart, bw.kpart_floats, 0, st);
+    };
 
     HIP_TRY(launch_prep_caption(caption, w.prev, w.tgt, N, d->n_caption_lstm_step, st));
     {
         const int rc = unroll_front(d, p, video, B, N, T, keep, seed, video_id, sample_id, w, sampler_workspace, sampler_workspace_bytes,
-                                    sampler_rows, stream);
+                                    sampler_rows, stream, !split_g2);
         if (rc != S2VT_OK) return rc;
     }
-    const size_t NH = (size_t)N * H;
     NoiseIds ids{video_id, sample_id, seed};
+    if (split_g2) {
+        // ---- stage B: lstm2_W's input rows [H + E][4H] as K-major planes in W (the Wout cast of stage A follows in stream order), then
+        // the encode partials O1[:Tv] . lstm2_W[0:H] from row planes in BT
+        HIP_TRY(launch_cast_rows_bf16(p->lstm2_W, 4 * H, nullptr, H + E, 4 * H, bw.W, K4, st, lo(bw.W)));
+        HIP_TRY(launch_cast_rows_bf16(w.O1, H, nullptr, Tv * N, H, bw.BT, bf16_pad(H), st, lo(bw.BT)));
+        HIP_TRY(nn(bw.BT, bf16_pad(H), bw.W, K4, w.G2, 4 * H, Tv * N, 4 * H, H, nullptr));
+        // decode rows: one row-plane set [Rd][bf16_pad(H + E)] -- O1 in columns 0 .. H - 1, the previous words' embedding rows behind them
+        // (zeros up to the padded width)
+        if (live_rows) HIP_TRY(launch_gather_i32(w.prev, live_rows, n_live, w.prevp, st));
+        HIP_TRY(launch_cast_rows_bf16(w.O1 + (size_t)Tv * NH, H, live_rows, Rd, H, bw.BT, HEp, st, lo(bw.BT), 0, H));
+        HIP_TRY(launch_cast_rows_bf16(p->Wemb, E, live_rows ? w.prevp : w.prev, Rd, E, bw.BT + H, HEp, st, lo(bw.BT) + H, 0, HEp - H));
+    }
     // ---- LSTM2, decode steps: rows of W2 for [out1 ; embed(prev word)] for all steps at once
     {
         if (!live_rows) {
-            ASeg sd[2] = {make_seg(w.O1 + (size_t)Tv * NH, H, H, 0), make_seg(p->Wemb, E, E, H, 0, w.prev)};   // decode (:143)
-            HIP_TRY(store_call(sd, 2, p->lstm2_W, 4 * H, nullptr, w.G2 + (size_t)Tv * 4 * NH, 4 * H, Tc * N, 4 * H, 0, -1, st));
+            if (split_g2) {
+                HIP_TRY(nn(bw.BT, HEp, bw.W, K4, w.G2 + (size_t)Tv * 4 * NH, 4 * H, Tc * N, 4 * H, H + E, nullptr));
+            } else {
+                ASeg sd[2] = {make_seg(w.O1 + (size_t)Tv * NH, H, H, 0), make_seg(p->Wemb, E, E, H, 0, w.prev)};   // decode (:143)
+                HIP_TRY(store_call(sd, 2, p->lstm2_W, 4 * H, nullptr, w.G2 + (size_t)Tv * 4 * NH, 4 * H, Tc * N, 4 * H, 0, -1, st));
+            }
         } else {
             // live rows: the partials of the unmasked positions only (both operands gathered through the list), packed, then
             // scattered into the zeroed decode part -- a masked position's cell then steps from a zero partial: finite values
             // that feed nothing (its logits are not computed, its gradients are zeros)
-            HIP_TRY(launch_gather_i32(w.prev, live_rows, n_live, w.prevp, st));
-            ASeg sd[2] = {make_seg(w.O1 + (size_t)Tv * NH, H, H, 0, 0, live_rows), make_seg(p->Wemb, E, E, H, 0, w.prevp)};
-            HIP_TRY(store_call(sd, 2, p->lstm2_W, 4 * H, nullptr, w.dZ2p, 4 * H, n_live, 4 * H, 0, -1, st));   // (dZ2p: free until the backward)
+            if (split_g2) {
+                HIP_TRY(nn(bw.BT, HEp, bw.W, K4, w.dZ2p, 4 * H, n_live, 4 * H, H + E, nullptr));
+            } else {
+                HIP_TRY(launch_gather_i32(w.prev, live_rows, n_live, w.prevp, st));
+                ASeg sd[2] = {make_seg(w.O1 + (size_t)Tv * NH, H, H, 0, 0, live_rows), make_seg(p->Wemb, E, E, H, 0, w.prevp)};
+                HIP_TRY(store_call(sd, 2, p->lstm2_W, 4 * H, nullptr, w.dZ2p, 4 * H, n_live, 4 * H, 0, -1, st));   // (dZ2p: free until the backward)
+            }
             float* const dec = w.G2 + (size_t)Tv * 4 * NH;
             ZeroList z;
             z.add(dec, (size_t)Tc * N * 4 * H * 4);
@@ -681,9 +732,57 @@ int s2vt_teacher_forced_fwd_live(const s2vt_dims* d, const s2vt_params* p, const
     if (is_residual(d)) HIP_TRY(launch_add_inplace(w.O2 + (size_t)Tv * NH, w.O1 + (size_t)Tv * NH, (size_t)Tc * NH, st));
     // vocab logits for all Tc steps at once (tf_s2vt.py:153): rows t*N + n -- or only the LIVE ones (row r of the output is
     // row live_rows[r] of the unroll: a masked position's logits feed nothing, its loss term and gradient are exact zeros)
+    if (split_logits) {
+        // stage A: the decode rows of O2 (gathered) as row planes [Rd][bf16_pad(H + 1)] in AT -- the layout and the ones column of
+        // vocab_fused's rows1 cast; the product's K = H never multiplies that column with anything but a zero -- Wout as K-major planes
+        // [H][bf16_pad(V)] in W, and the NN product with the fp32 bias.  L is not touched: the split softmax writes the dlogits planes there next.
+        HIP_TRY(launch_cast_rows_bf16(w.O2 + (size_t)Tv * NH, H, live_rows, Rd, H, o2p, Hp1, st, lo(o2p), 1));
+        HIP_TRY(launch_cast_rows_bf16(p->embed_word_W, V, nullptr, H, V, bw.W, Kv, st, lo(bw.W)));
+        HIP_TRY(nn(o2p, Hp1, bw.W, Kv, logits, V, Rd, V, H, p->embed_word_b));
+        return S2VT_OK;
+    }
     ASeg so = make_seg(w.O2 + (size_t)Tv * NH, H, H, 0, 0, live_rows);
-    HIP_TRY(store_call(&so, 1, p->embed_word_W, V, p->embed_word_b, logits, V, live_rows ? n_live : Tc * N, V, 0, -1, st));
+    HIP_TRY(store_call(&so, 1, p->embed_word_W, V, p->embed_word_b, logits, V, Rd, V, 0, -1, st));
     return S2VT_OK;
+}
+
+int s2vt_teacher_forced_fwd_live(const s2vt_dims* d, const s2vt_params* p, const float* video, int32_t B, int32_t N,
+                                 const int32_t* caption, int32_t caption_steps, const int32_t* live_rows, int32_t n_live, float keep,
+                                 uint64_t seed, const int32_t* video_id, const int32_t* sample_id, float* logits, void* workspace,
+                                 size_t workspace_bytes, const void* sampler_workspace, size_t sampler_workspace_bytes,
+                                 int32_t sampler_rows, s2vt_stream stream)
+{
+    return teacher_forced_fwd_body(d, p, video, B, N, caption, caption_steps, live_rows, n_live, keep, seed, video_id, sample_id, logits,
+                                   workspace, workspace_bytes, sampler_workspace, sampler_workspace_bytes, sampler_rows, stream, nullptr, 0,
+                                   false, 0);
+}
+
+// S2VT_SPLIT_FWD (read once): 0 = the fp32 forward, 1 = stage A (the vocabulary logits on split-bf16), 2 = stages A and B (LSTM2's hoisted
+// input partials too).  Anything else, or unset: the default.
+int s2vt_split_fwd_stage(void)
+{
+    static const int stage = [] {
+        const char* e = getenv("S2VT_SPLIT_FWD");
+        if (e && (e[0] == '0' || e[0] == '1' || e[0] == '2') && !e[1]) return e[0] - '0';
+        return kSplitFwdDefault;
+    }();
+    return stage;
+}
+
+int s2vt_split_fwd_active(int32_t N)
+{
+    return split_mode_on(N) ? s2vt_split_fwd_stage() : 0;
+}
+
+int s2vt_teacher_forced_fwd_split(const s2vt_dims* d, const s2vt_params* p, const float* video, int32_t B, int32_t N,
+                                  const int32_t* caption, int32_t caption_steps, const int32_t* live_rows, int32_t n_live, float keep,
+                                  uint64_t seed, const int32_t* video_id, const int32_t* sample_id, float* logits, void* workspace,
+                                  size_t workspace_bytes, const void* sampler_workspace, size_t sampler_workspace_bytes,
+                                  int32_t sampler_rows, void* split_ws, size_t split_ws_bytes, s2vt_stream stream)
+{
+    return teacher_forced_fwd_body(d, p, video, B, N, caption, caption_steps, live_rows, n_live, keep, seed, video_id, sample_id, logits,
+                                   workspace, workspace_bytes, sampler_workspace, sampler_workspace_bytes, sampler_rows, stream, split_ws,
+                                   split_ws_bytes, true, s2vt_split_fwd_stage());
 }
 
 size_t s2vt_scheduled_scratch_bytes(const s2vt_dims* d, int32_t N)
@@ -854,6 +953,7 @@ static int split_grad_mode(int N)
     static const int on = [] { const char* e = getenv("S2VT_SPLIT_GRADS"); return e ? atoi(e) : 1; }();
     return on && N > 256 ? kGradSplit : kGradFp32;
 }
+static bool split_mode_on(int N) { return split_grad_mode(N) == kGradSplit; }
 // ... and LSTM2's backward recurrence with them, where its register-weights form serves the shape (bwd_chain_split_serves: above 256 rows).
 // S2VT_BCHAIN_SPLIT=0 (dev knob, read once): the fp32 recurrence beside the split products.
 static bool split_recurrence()
@@ -1356,6 +1456,19 @@ int s2vt_gemm_bf16x3_nt(const uint16_t* Ah, const uint16_t* Al, int32_t lda, con
     if ((reinterpret_cast<uintptr_t>(Ah) | reinterpret_cast<uintptr_t>(Al) | reinterpret_cast<uintptr_t>(Bh) | reinterpret_cast<uintptr_t>(Bl)) & 15)
         return S2VT_E_ALIGN;
     HIP_TRY(launch_gemm_bf16x3_nt(Ah, Al, lda, Bh, Bl, ldb, C, ldc, M, N, Kp, accumulate, static_cast<float*>(scratch), scratch_bytes / 4, 3, S(stream)));
+    return S2VT_OK;
+}
+
+int s2vt_gemm_bf16x3_nn(const uint16_t* Ah, const uint16_t* Al, int32_t lda, const uint16_t* Bh, const uint16_t* Bl, int32_t ldb, float* C,
+                        int32_t ldc, int32_t M, int32_t N, int32_t K, int32_t accumulate, const float* bias, void* scratch, size_t scratch_bytes,
+                        s2vt_stream stream)
+{
+    if (!Ah || !Al || !Bh || !Bl || !C || M < 0 || N < 0 || K < 0 || lda < bf16_pad(K) || ldb < N || ldc < N || (lda & 7) || (ldb & 7))
+        return S2VT_E_BADARG;
+    if (accumulate < 0 || accumulate > 1 || (bias && accumulate) || (scratch_bytes && !scratch) || !gemm_bf16x3_tn_ok(ldb, ldb, K)) return S2VT_E_BADARG;
+    if ((reinterpret_cast<uintptr_t>(Ah) | reinterpret_cast<uintptr_t>(Al) | reinterpret_cast<uintptr_t>(Bh) | reinterpret_cast<uintptr_t>(Bl)) & 15)
+        return S2VT_E_ALIGN;
+    HIP_TRY(launch_gemm_bf16x3_nn(Ah, Al, lda, Bh, Bl, ldb, C, ldc, M, N, K, accumulate, bias, static_cast<float*>(scratch), scratch_bytes / 4, 0, S(stream)));
     return S2VT_OK;
 }
 

@@ -670,8 +670,11 @@ class Video_Caption_Generator:
                 raise RuntimeError("reuse_sampler_state needs model.sample() on this very video tensor, with the current "
                                    "weights, as the last sampler call before the update")
             state = (ls[0], ls[1])
+        # (an update whose backward runs split-bf16 products: its forward's hoisted products on the same arithmetic, by
+        #  ops.split_fwd_stage() -- above 256 rows, as the split softmax below, but whatever S2VT_SPLIT_FUSED makes of the backward)
         logits, ws = ops.teacher_forced_fwd(self.dims, self.store.params, video, caption, N, keep, seed, vid, sid,
-                                            sampler_state=state, steps=steps, live=live)
+                                            sampler_state=state, steps=steps, live=live,
+                                            split=self.grad_precision == "fp32" and ops.split_fwd_active(N) > 0)
         if callable(coef_tm):            # host work (the reward) runs here, beside the forward just queued on the GPU
             coef_tm = coef_tm()
         target = caption.t().contiguous().view(-1) if target_tm is None else target_tm

@@ -531,8 +531,11 @@ def train_workspace(dims: Dims, B: int, N: int, device):
 
 
 def teacher_forced_fwd(dims: Dims, params: Params, video, caption, N: int, keep=1.0, seed=0, video_id=None,
-                       sample_id=None, ws=None, logits=None, sampler_state=None, steps=None, live=None):
+                       sample_id=None, ws=None, logits=None, sampler_state=None, steps=None, live=None, split=False):
     """Teacher-forced unroll on N = rep*B sample-major rows.  Returns time-major logits [Tc*N, V].
+    split=True: the forward of an update whose backward is the fused split form (s2vt_teacher_forced_fwd_split, with the split
+    workspace of (dims, B, N)): by split_fwd_stage() the vocabulary logits (stage 1) and LSTM2's hoisted input partials (stage 2)
+    run as split-bf16 products where the shape fits.  Without it every product is the bit-exact fp32 chain.
     sampler_state = (workspace tensor, rows) of the sample() call of the same step on the same video block:
     LSTM1's trajectory is taken from it instead of being recomputed.
     steps (1..Tc): unroll only the first `steps` decode steps (every later position of the batch is masked); logits
@@ -554,6 +557,14 @@ def teacher_forced_fwd(dims: Dims, params: Params, video, caption, N: int, keep=
         logits = torch.empty((R, dims.n_words), dtype=torch.float32, device=video.device)
     assert logits.shape[0] == R
     sws, srows = sampler_state if sampler_state is not None else (None, 0)
+    if split:
+        gws = split_grad_workspace(dims, B, N, video.device)
+        check(lib().s2vt_teacher_forced_fwd_split(C.byref(dims), C.byref(params), _ptr(video), B, N, _ptr(caption), steps,
+                                                  _ptr(live), 0 if live is None else live.numel(), float(keep), seed,
+                                                  _ptr(video_id), _ptr(sample_id), _ptr(logits), _ptr(ws), ws.numel(), _ptr(sws),
+                                                  0 if sws is None else sws.numel(), srows, _ptr(gws), gws.numel(), _stream()),
+              "s2vt_teacher_forced_fwd_split")
+        return logits, ws
     check(lib().s2vt_teacher_forced_fwd_live(C.byref(dims), C.byref(params), _ptr(video), B, N, _ptr(caption), steps,
                                              _ptr(live), 0 if live is None else live.numel(), float(keep), seed,
                                               _ptr(video_id), _ptr(sample_id), _ptr(logits), _ptr(ws), ws.numel(), _ptr(sws),
@@ -620,6 +631,17 @@ def split_grad_active(N: int) -> bool:
     """Whether the fp32-mode backward at N unrolled rows runs the fused split form (s2vt_split_grad_active): then
     softmax_nll_fwd_bwd_split can hand it dlogits as planes."""
     return bool(lib().s2vt_split_grad_active(int(N)))
+
+
+def split_fwd_stage() -> int:
+    """The stage of teacher_forced_fwd(split=True) (s2vt_split_fwd_stage: the env S2VT_SPLIT_FWD, read once by the library):
+    0 the fp32 forward, 1 the vocabulary logits on split-bf16, 2 LSTM2's hoisted input partials too."""
+    return int(lib().s2vt_split_fwd_stage())
+
+
+def split_fwd_active(N: int) -> int:
+    """The stage teacher_forced_fwd(split=True) runs at N unrolled rows (s2vt_split_fwd_active): 0 where the split mode is off."""
+    return int(lib().s2vt_split_fwd_active(int(N)))
 
 
 def softmax_nll_fwd_bwd_split(logits, target, coef, smoothing, dims: Dims, B: int, N: int):
@@ -764,6 +786,27 @@ def gemm_bf16x3_tn(Ah, Al, Bh, Bl, M=None, N=None, out=None, accumulate=False, s
     check(lib().s2vt_gemm_bf16x3_tn(_ptr(Ah), _ptr(Al), Ah.stride(0), _ptr(Bh), _ptr(Bl), Bh.stride(0), _ptr(out), out.stride(0), M, N, K,
                                     int(bool(accumulate)), _ptr(bias), _ptr(scratch), 0 if scratch is None else scratch.numel(), _stream()),
           "s2vt_gemm_bf16x3_tn")
+    return out
+
+
+def gemm_bf16x3_nn(Ah, Al, Bh, Bl, N=None, K=None, out=None, accumulate=False, split_k=True, bias=None):
+    """C[M, N] (+)= sum_k A[m, k] B[k, n] as Ah Bh + Ah Bl + Al Bh on split-bf16 planes: A by rows [M, >= bf16_pad(K)], B K-major
+    [K, ldb] (s2vt_gemm_bf16x3_nn; N defaults to B's width, K to its rows).  bias [N] fp32 (not with accumulate): added once per column."""
+    for t in (Ah, Al, Bh, Bl):
+        assert t.is_cuda and t.dtype == torch.bfloat16 and t.stride(1) == 1
+    assert Ah.shape == Al.shape and Bh.shape == Bl.shape and Ah.stride(0) == Al.stride(0) and Bh.stride(0) == Bl.stride(0)
+    M = Ah.shape[0]
+    K = Bh.shape[0] if K is None else int(K)
+    N = Bh.shape[1] if N is None else int(N)
+    if out is None:
+        assert not accumulate
+        out = torch.empty((M, N), dtype=torch.float32, device=Ah.device)
+    _chk_f32(out, bias)
+    assert out.shape[0] == M and out.shape[1] == N and out.stride(1) == 1
+    scratch = workspace(32 * M * N, Ah.device, "gemm_bf16x3") if split_k and M * N else None
+    check(lib().s2vt_gemm_bf16x3_nn(_ptr(Ah), _ptr(Al), Ah.stride(0), _ptr(Bh), _ptr(Bl), Bh.stride(0), _ptr(out), out.stride(0), M, N, K,
+                                    int(bool(accumulate)), _ptr(bias), _ptr(scratch), 0 if scratch is None else scratch.numel(), _stream()),
+          "s2vt_gemm_bf16x3_nn")
     return out
 
 
