@@ -527,6 +527,17 @@ int s2vt_cast_bf16_split(const float* src, int32_t ld, const int32_t* rowidx, in
  * order, when scratch holds them (4 x slabs x M x N bytes; 32 x M x N always suffices); with less it is not split. */
 int s2vt_gemm_bf16x3_nt(const uint16_t* Ah, const uint16_t* Al, int32_t lda, const uint16_t* Bh, const uint16_t* Bl, int32_t ldb, float* C,
                         int32_t ldc, int32_t M, int32_t N, int32_t Kp, int32_t accumulate, void* scratch, size_t scratch_bytes, s2vt_stream stream);
+/* s2vt_gemm_bf16x3_nt without a scratch (never split), on the workgroup tile the caller names: tile 0 = 128 x 128 (what
+ * s2vt_gemm_bf16x3_nt launches), 1 = 192 x 96; anything else is S2VT_E_BADARG and nothing is written.  Every output element keeps
+ * one accumulator, the same K steps and the same order of the three products: the two tiles give the same bits.  A seam for
+ * tests and tuning.  s2vt_gemm_bf16x3_nt_tile_choice (host only, no device needed): the tile the library's rule takes for an
+ * M x N product on `cus` compute units, one workgroup per unit -- 1 where ceil(tiles192 / cus) x 192.96 is smaller than
+ * ceil(tiles128 / cus) x 128.128, else 0; S2VT_E_BADARG unless all three are positive.  The sampler's pick screen
+ * (s2vt_sample_screened) asks this rule with the device's unit count; the env S2VT_PICK_TILE (read once) = 0 or 1 forces its
+ * tile instead.  Every other NT product of the library keeps 128 x 128. */
+int s2vt_gemm_bf16x3_nt_tile(const uint16_t* Ah, const uint16_t* Al, int32_t lda, const uint16_t* Bh, const uint16_t* Bl, int32_t ldb, float* C,
+                             int32_t ldc, int32_t M, int32_t N, int32_t Kp, int32_t accumulate, s2vt_stream stream, int32_t tile);
+int s2vt_gemm_bf16x3_nt_tile_choice(int32_t M, int32_t N, int32_t cus);
 
 /* The K-major form of s2vt_gemm_bf16x3_nt, for products that sum over the ROW index of both operands (weight gradients) without
  * transposed copies: C[M,N] (+)= sum over k < K of A[k][m].B[k][n] with the same three products, planes stored by rows -- A as

@@ -304,26 +304,88 @@ struct GemmX3Args {
 enum : int { kX3NT = 0, kX3TN = 1, kX3NN = 2 };
 
 constexpr int kX3BK = 32, kX3Slots = 4, kX3Plane = kTile * kX3BK;   // a plane's K step: 128 rows x 32 bf16 = 8 KB
-constexpr int kX3Lds = kX3Slots * 4 * kX3Plane * 2;                  // 128 KB: one workgroup per CU
+constexpr int kX3TileM = 192, kX3TileN = 96;                         // the second NT geometry
+// LDS of a tile geometry: 4 slots x (2 A planes + 2 B planes) x 64 bytes a row -- 128 KB at 128 x 128, 144 KB at 192 x 96: one workgroup per CU
+constexpr int x3_lds_bytes(int tm, int tn) { return kX3Slots * 2 * (tm + tn) * kX3BK * 2; }
 constexpr int kX3Dma = kTile / 16;                                   // DMA instructions per plane per K step (per loader wave)
 typedef __attribute__((address_space(3))) void* x3_lds_ptr;
 typedef short i16x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) i16x4* x3_tr_ptr;
 
-template <int FORM>
+// A loader wave of the NT form on a tile whose planes differ in height: the rows [r0, r0 + 16 ND) of one plane (descriptor rs starts at row
+// r0), ND DMA instructions per K step into pdst + slot * slot_elems.  ND is a constant of the plane, so the counted waits are immediates;
+// the ring, the waits and the barriers are those of the 128 x 128 loader in the kernel below.
+template <int ND>
+__device__ __forceinline__ void x3_nt_loader(__amdgpu_buffer_rsrc_t rs, int r0, int rows, int ld, uint16_t* pdst, int slot_elems, int kbeg, int nk, int lane)
+{
+    static_assert(3 * ND < 64, "vmcnt is a 6-bit counter");
+    uint32_t voff[ND];
+    const int rr = lane >> 2, kg = (lane & 3) ^ ((rr >> 2) & 3);
+#pragma unroll
+    for (int b = 0; b < ND; ++b) {
+        const int r = b * 16 + rr;
+        voff[b] = r0 + r < rows ? (uint32_t)(r * ld + kg * 8) * 2u : kOob;
+    }
+    auto issue = [&](int ks) __attribute__((always_inline)) {
+        uint16_t* const dst = pdst + (ks % kX3Slots) * slot_elems;
+        const uint32_t soff = (uint32_t)(kbeg + ks) * kX3BK * 2u;
+#pragma unroll
+        for (int b = 0; b < ND; ++b)
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (x3_lds_ptr)(dst + b * 16 * kX3BK), 16, voff[b], soff, 0, 0);
+    };
+    auto wait_younger = [](int n) __attribute__((always_inline)) {
+        if (n >= 2) wait_vmcnt<2 * ND>();
+        else if (n == 1) wait_vmcnt<ND>();
+        else wait_vmcnt<0>();
+    };
+    const int pro = min(kX3Slots, nk);
+    for (int ks = 0; ks < pro; ++ks) issue(ks);
+    if (pro - 1 >= 3) wait_vmcnt<3 * ND>();                   // K step 0 has landed
+    else wait_younger(pro - 1);
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    for (int k = 0; k < nk; ++k) {
+        wait_younger(min(k + 3, nk - 1) - (k + 1));           // K step k + 1 has landed
+        asm volatile("" ::: "memory");
+        __builtin_amdgcn_s_barrier();                         // barrier k: the MFMA waves are done reading K step k
+        asm volatile("" ::: "memory");
+        if (k + kX3Slots < nk) issue(k + kX3Slots);           // into K step k's slot
+    }
+}
+
+// BM x BN: the output tile.  128 x 128 in every form; the NT form also as 192 x 96 (2 x 2 MFMA waves of 96 x 48 = 6 x 3 fragments, 18
+// accumulators; A-plane loaders issue 12 DMA instructions per K step, B-plane loaders 6) -- the same ring, waits, K steps and MFMA order,
+// one accumulator per output element: the bits do not depend on the tile.  Unsplit launches only (g.part == nullptr).
+template <int FORM, int BM = kTile, int BN = kTile>
 __global__ __launch_bounds__(512) void gemm_bf16x3_kernel(GemmX3Args g)
 {
+    static_assert(BM == BN ? BM == kTile : FORM == kX3NT && BM % 32 == 0 && BN % 32 == 0, "K-major planes come as 128 x 128 tiles only");
     constexpr bool ATN = FORM == kX3TN, BTN = FORM != kX3NT;            // A's planes / B's planes K-major
-    extern __shared__ __attribute__((aligned(16))) uint16_t x3lds[];   // [slot][plane][128 rows][32]
+    constexpr int WM = BM / 2, WN = BN / 2, FI = WM / 16, FJ = WN / 16; // an MFMA wave's part of the tile, in rows / columns and in fragments
+    constexpr int kPlaneA = BM * kX3BK, kPlaneB = BN * kX3BK, kSlot = 2 * (kPlaneA + kPlaneB);
+    extern __shared__ __attribute__((aligned(16))) uint16_t x3lds[];   // [slot][Ah | Al | Bh | Bl][rows][32]
     const int nwg = g.tiles_m * g.tiles_n, orig = blockIdx.x;
     const int xcd = orig & 7, q = nwg >> 3, rem = nwg & 7;
     const int wgid = (xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q) + (orig >> 3);
     const int tm = wgid % g.tiles_m, tn = wgid / g.tiles_m;
-    const int m0 = tm * kTile, n0 = tn * kTile;
+    const int m0 = tm * BM, n0 = tn * BN;
     const int kbeg = blockIdx.y * g.nk_slab, nk = min(g.nk_slab, g.nk - kbeg);
     const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
 
-    if (w >= 4) {
+    if constexpr (BM != BN) {
+        if (w >= 4) {
+            // ================= loader wave of the NT form, plane p: rows / 16 DMA instructions per K step (x3_nt_loader)
+            const int p = w - 4;
+            const uint16_t* const plane = p == 0 ? g.Ah : p == 1 ? g.Al : p == 2 ? g.Bh : g.Bl;
+            const int r0 = p < 2 ? m0 : n0, rows = p < 2 ? g.M : g.N, ld = p < 2 ? g.lda : g.ldb;
+            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(plane + (size_t)r0 * ld), 0, (int)kOob, 0x00020000);
+            uint16_t* const pdst = x3lds + (p < 2 ? p * kPlaneA : 2 * kPlaneA + (p - 2) * kPlaneB);
+            if (p < 2) x3_nt_loader<BM / 16>(rs, r0, rows, ld, pdst, kSlot, kbeg, nk, lane);
+            else x3_nt_loader<BN / 16>(rs, r0, rows, ld, pdst, kSlot, kbeg, nk, lane);
+            return;
+        }
+    } else if (w >= 4) {
         // ================= loader wave: plane p, 8 DMA instructions per K step
         const int p = w - 4;
         // this plane's layout: a constant in the NT and TN forms (the branches below fold), wave-uniform in NN -- A's planes by rows, B's K-major
@@ -394,19 +456,24 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_kernel(GemmX3Args g)
     // TN: lane 4 q + pp of group gq addresses k row 8 gq + q (second read: + 4 rows, the same swz), elements 4 pp .. 4 pp + 3 of its block
     const int gq = lane >> 4, tq = (lane >> 2) & 3, tswz = tq | ((gq & 1) << 2);
     const int tofs = (gq * 8 + tq) * kTile + (lane & 3) * 4;                           // + ((column block ^ tswz) << 4) elements
-    f32x4 acc[4][4];
+    f32x4 acc[FI][FJ];
 #pragma unroll
-    for (int i = 0; i < 4; ++i)
+    for (int i = 0; i < FI; ++i)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-    // fragments of one K step: [plane][repeat]
-    auto read = [&](int ks, bf16x8 (&f)[4][4]) __attribute__((always_inline)) {
-        const uint16_t* const s = x3lds + (ks % kX3Slots) * 4 * kX3Plane;
+        for (int j = 0; j < FJ; ++j) acc[i][j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    // fragments of one K step: [plane][repeat] (FI repeats of an A plane, FJ of a B plane)
+    constexpr int FX = FI > FJ ? FI : FJ;
+    auto read = [&](int ks, bf16x8 (&f)[4][FX]) __attribute__((always_inline)) {
+        const uint16_t* const s = x3lds + (ks % kX3Slots) * kSlot;
 #pragma unroll
         for (int pl = 0; pl < 4; ++pl)
 #pragma unroll
-            for (int i = 0; i < 4; ++i)
-                if constexpr (ATN != BTN) {                                // NN: A's planes by rows, B's K-major
+            for (int i = 0; i < FX; ++i)
+                if constexpr (BM != BN) {                                  // (NT only) planes of two sizes
+                    if (i < (pl < 2 ? FI : FJ))
+                        f[pl][i] = *reinterpret_cast<const bf16x8*>(s + (pl < 2 ? pl * kPlaneA + wr * WM * kX3BK : 2 * kPlaneA + (pl - 2) * kPlaneB + wc * WN * kX3BK) +
+                                                                    i * 16 * kX3BK + fofs);
+                } else if constexpr (ATN != BTN) {                        // NN: A's planes by rows, B's K-major
                     if (pl < 2) {
                         f[pl][i] = *reinterpret_cast<const bf16x8*>(s + pl * kX3Plane + (wr * 64 + i * 16) * kX3BK + fofs);
                     } else {
@@ -424,26 +491,26 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_kernel(GemmX3Args g)
                     f[pl][i] = *reinterpret_cast<const bf16x8*>(s + pl * kX3Plane + ((pl < 2 ? wr : wc) * 64 + i * 16) * kX3BK + fofs);
                 }
     };
-    auto mul = [&](const bf16x8 (&f)[4][4]) __attribute__((always_inline)) {
-        // small products first, each pass over all 16 accumulators (no back-to-back dependent MFMAs)
+    auto mul = [&](const bf16x8 (&f)[4][FX]) __attribute__((always_inline)) {
+        // small products first, each pass over all FI x FJ accumulators (no back-to-back dependent MFMAs)
 #pragma unroll
-        for (int i = 0; i < 4; ++i)
+        for (int i = 0; i < FI; ++i)
 #pragma unroll
-            for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f[0][i], f[3][j], acc[i][j], 0, 0, 0);
+            for (int j = 0; j < FJ; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f[0][i], f[3][j], acc[i][j], 0, 0, 0);
 #pragma unroll
-        for (int i = 0; i < 4; ++i)
+        for (int i = 0; i < FI; ++i)
 #pragma unroll
-            for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f[1][i], f[2][j], acc[i][j], 0, 0, 0);
+            for (int j = 0; j < FJ; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f[1][i], f[2][j], acc[i][j], 0, 0, 0);
 #pragma unroll
-        for (int i = 0; i < 4; ++i)
+        for (int i = 0; i < FI; ++i)
 #pragma unroll
-            for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f[0][i], f[2][j], acc[i][j], 0, 0, 0);
+            for (int j = 0; j < FJ; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f[0][i], f[2][j], acc[i][j], 0, 0, 0);
     };
-    bf16x8 fa[4][4], fb[4][4];
+    bf16x8 fa[4][FX], fb[4][FX];
     __syncthreads();                                                      // K step 0 has landed
     if (nk > 0) read(0, fa);
     // barrier k publishes K step k + 1 and frees K step k's slot (its fragments are in registers: lgkmcnt(0) first)
-    auto step = [&](int k, bf16x8 (&cur)[4][4], bf16x8 (&nxt)[4][4]) __attribute__((always_inline)) {
+    auto step = [&](int k, bf16x8 (&cur)[4][FX], bf16x8 (&nxt)[4][FX]) __attribute__((always_inline)) {
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __syncthreads();
         if (k + 1 < nk) read(k + 1, nxt);
@@ -457,12 +524,12 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_kernel(GemmX3Args g)
     const int ldo = g.part ? g.N : g.ldc;
     const bool add = !g.part && g.accumulate;
 #pragma unroll
-    for (int i = 0; i < 4; ++i)
+    for (int i = 0; i < FI; ++i)
 #pragma unroll
-        for (int j = 0; j < 4; ++j)
+        for (int j = 0; j < FJ; ++j)
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                const int row = m0 + wr * 64 + i * 16 + (lane >> 4) * 4 + e, col = n0 + wc * 64 + j * 16 + (lane & 15);
+                const int row = m0 + wr * WM + i * 16 + (lane >> 4) * 4 + e, col = n0 + wc * WN + j * 16 + (lane & 15);
                 if (row < g.M && col < g.N) {
                     float* c = out + (size_t)row * ldo + col;
                     if constexpr (FORM == kX3NN) {
@@ -551,18 +618,37 @@ hipError_t launch_gemm_bf16_nt(const uint16_t* A, int lda, const uint16_t* B, in
     return hipGetLastError();
 }
 
-int gemm_bf16x3_slabs(int M, int N, int Kp)
+static int x3_cus()
 {
-    // split-K where the tiles do not fill the chip (one workgroup per CU, one round): slabs of at least 16 K steps of 32
-    const int tiles = ((M + kTile - 1) / kTile) * ((N + kTile - 1) / kTile), nk = Kp / kX3BK;
     static const int cus = [] {
         int dev = 0, n = 256;
         if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
         return n > 0 ? n : 256;
     }();
+    return cus;
+}
+
+int gemm_bf16x3_slabs(int M, int N, int Kp)
+{
+    // split-K where the tiles do not fill the chip (one workgroup per CU, one round): slabs of at least 16 K steps of 32
+    const int tiles = ((M + kTile - 1) / kTile) * ((N + kTile - 1) / kTile), nk = Kp / kX3BK, cus = x3_cus();
     int s = 1;
     while (s < 8 && tiles * (s * 2) <= cus && nk / (s * 2) >= 16) s *= 2;
     return s;
+}
+
+int gemm_bf16x3_nt_tile_choice(int M, int N, int cus)
+{
+    // one workgroup per CU with either tile: rounds of workgroups x the tile's area is the work of the longest-running CU
+    const auto up = [](long long a, long long b) { return (a + b - 1) / b; };
+    const long long t192 = up(M, kX3TileM) * up(N, kX3TileN), t128 = up(M, kTile) * up(N, kTile);
+    return up(t192, cus) * (kX3TileM * kX3TileN) < up(t128, cus) * (kTile * kTile) ? 1 : 0;
+}
+
+int gemm_bf16x3_pick_tile(int M, int N)
+{
+    static const int knob = [] { const char* e = getenv("S2VT_PICK_TILE"); return e && (e[0] == '0' || e[0] == '1') && !e[1] ? e[0] - '0' : -1; }();
+    return knob >= 0 ? knob : gemm_bf16x3_nt_tile_choice(M, N, x3_cus());
 }
 
 size_t gemm_bf16x3_part_floats(int M, int N, int Kp)
@@ -572,34 +658,37 @@ size_t gemm_bf16x3_part_floats(int M, int N, int Kp)
 }
 
 namespace {
-// the launch of any form (TN, NN: Kp = the reduction length K, any count; NT: Kp % 64 == 0)
-template <int FORM>
+// the launch of any form (TN, NN: Kp = the reduction length K, any count; NT: Kp % 64 == 0); a tile other than 128 x 128 takes no split-K scratch
+template <int FORM, int BM = kTile, int BN = kTile>
 hipError_t launch_x3(const uint16_t* Ah, const uint16_t* Al, int lda, const uint16_t* Bh, const uint16_t* Bl, int ldb, float* C, int ldc, int M, int N,
                      int Kp, int accumulate, float* bias, float* part, size_t part_floats, int cls, hipStream_t st, const float* cbias = nullptr)
 {
+    constexpr bool kWide = BM != BN;
+    constexpr int kLds = x3_lds_bytes(BM, BN), kCfg = kWide ? 17 : 16;     // (the launch profiler's tile id)
     if (M <= 0 || N <= 0) return hipSuccess;
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_bf16x3_kernel<FORM>), hipFuncAttributeMaxDynamicSharedMemorySize, kX3Lds);
+    if (kWide && part) return hipErrorInvalidValue;
+    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_bf16x3_kernel<FORM, BM, BN>), hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
     if (attr != hipSuccess) return attr;
     GemmX3Args g;
     g.Ah = Ah; g.Al = Al; g.lda = lda; g.Bh = Bh; g.Bl = Bl; g.ldb = ldb; g.C = C; g.ldc = ldc; g.M = M; g.N = N;
     g.K = Kp; g.bias = bias; g.Mo = M + (bias ? 1 : 0); g.cbias = cbias;
     const int Kr = bf16_pad(Kp);
     g.nk = Kr / kX3BK; g.accumulate = accumulate;
-    g.tiles_m = (g.Mo + kTile - 1) / kTile; g.tiles_n = (N + kTile - 1) / kTile;
+    g.tiles_m = (g.Mo + BM - 1) / BM; g.tiles_n = (N + BN - 1) / BN;
     int slabs = part ? gemm_bf16x3_slabs(g.Mo, N, Kr) : 1;
     if ((size_t)slabs * g.Mo * N > part_floats) slabs = 1;
     g.nk_slab = ((g.nk + slabs - 1) / slabs + 1) & ~1;                    // >= nk / slabs (so no more slabs than the scratch holds), even:
     slabs = g.nk_slab ? (g.nk + g.nk_slab - 1) / g.nk_slab : 1;           // the MFMA loop takes K steps in pairs
     g.part = slabs > 1 ? part : nullptr;
     const dim3 grid((unsigned)(g.tiles_m * g.tiles_n), (unsigned)slabs);
-    const bool prof = prof_wants(cls, 16);
+    const bool prof = prof_wants(cls, kCfg);
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (prof) {
         hipError_t pe = prof_events(&e0, &e1);
         if (pe != hipSuccess) return pe;
         (void)hipEventRecord(e0, st);
     }
-    hipLaunchKernelGGL(gemm_bf16x3_kernel<FORM>, grid, dim3(512), kX3Lds, st, g);
+    hipLaunchKernelGGL((gemm_bf16x3_kernel<FORM, BM, BN>), grid, dim3(512), kLds, st, g);
     if (slabs > 1) {
         const size_t MN = (size_t)g.Mo * N, blocks = (MN + 255) / 256;
         hipLaunchKernelGGL(reduce_slabs_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, st, (const float*)part, slabs, M, N, C, ldc,
@@ -607,16 +696,18 @@ hipError_t launch_x3(const uint16_t* Ah, const uint16_t* Al, int lda, const uint
     }
     if (prof) {
         (void)hipEventRecord(e1, st);
-        prof_record(cls, 16, cls == 0 ? "x3_128x128(dma) fwd" : cls == 2 ? "x3_128x128(dma) pick screen" : cls == 3 ? "x3_128x128(dma) wgrad" : "x3_128x128(dma) dgrad",
-                    2.0 * M * (double)N * Kp, e0, e1);
+        const char* const name = kWide ? (cls == 2 ? "x3_192x96(dma) pick screen" : cls == 3 ? "x3_192x96(dma) wgrad" : "x3_192x96(dma) dgrad")
+                                       : cls == 0 ? "x3_128x128(dma) fwd" : cls == 2 ? "x3_128x128(dma) pick screen" : cls == 3 ? "x3_128x128(dma) wgrad" : "x3_128x128(dma) dgrad";
+        prof_record(cls, kCfg, name, 2.0 * M * (double)N * Kp, e0, e1);
     }
     return hipGetLastError();
 }
 }  // namespace
 
 hipError_t launch_gemm_bf16x3_nt(const uint16_t* Ah, const uint16_t* Al, int lda, const uint16_t* Bh, const uint16_t* Bl, int ldb, float* C, int ldc,
-                                 int M, int N, int Kp, int accumulate, float* part, size_t part_floats, int cls, hipStream_t st)
+                                 int M, int N, int Kp, int accumulate, float* part, size_t part_floats, int cls, hipStream_t st, int tile)
 {
+    if (tile == 1 && !part) return launch_x3<kX3NT, kX3TileM, kX3TileN>(Ah, Al, lda, Bh, Bl, ldb, C, ldc, M, N, Kp, accumulate, nullptr, nullptr, 0, cls, st);
     return launch_x3<kX3NT>(Ah, Al, lda, Bh, Bl, ldb, C, ldc, M, N, Kp, accumulate, nullptr, part, part_floats, cls, st);
 }
 

@@ -351,9 +351,14 @@ hipError_t launch_gemm_bf16_nt(const uint16_t* A, int lda, const uint16_t* B, in
                                int mfma, hipStream_t st);
 // C[M,N] (+)= Ah Bh^T + Ah Bl^T + Al Bh^T: split-bf16 operands (hi / lo planes with the layout rules of launch_gemm_bf16_nt), fp32
 // accumulation, no atomics.  part: optional split-K scratch of part_floats floats (gemm_bf16x3_part_floats(M, N, Kp) for the full
-// split; fewer -> no split); cls: the launch profiler's class (2 the sampler's pick screen, 3 weight gradients, 4 data gradients)
+// split; fewer -> no split); cls: the launch profiler's class (2 the sampler's pick screen, 3 weight gradients, 4 data gradients).
+// tile: 0 = 128 x 128 workgroup tiles, 1 = 192 x 96 (launches without a scratch only: with one, 128 x 128 whatever tile says) -- the same
+// bits either way.  gemm_bf16x3_nt_tile_choice: 1 where ceil(tiles / cus) x the tile's area is smaller with 192 x 96 (host only);
+// gemm_bf16x3_pick_tile: what the pick screen's product takes -- that rule on this device's CUs, or the env S2VT_PICK_TILE (read once: 0 or 1)
 hipError_t launch_gemm_bf16x3_nt(const uint16_t* Ah, const uint16_t* Al, int lda, const uint16_t* Bh, const uint16_t* Bl, int ldb, float* C, int ldc,
-                                 int M, int N, int Kp, int accumulate, float* part, size_t part_floats, int cls, hipStream_t st);
+                                 int M, int N, int Kp, int accumulate, float* part, size_t part_floats, int cls, hipStream_t st, int tile = 0);
+int gemm_bf16x3_nt_tile_choice(int M, int N, int cus);
+int gemm_bf16x3_pick_tile(int M, int N);
 size_t gemm_bf16x3_part_floats(int M, int N, int Kp);
 // The K-major form: C[M,N] (+)= sum_k A[k][m] B[k][n] over K rows of planes stored by rows ([K][lda], [K][ldb]; lda, ldb % 8 == 0, 16-byte
 // aligned; rows >= K are never read, columns up to the next multiple of 128 may be -- they lie inside the planes or read zeros).  The
@@ -385,7 +390,7 @@ struct PickScreenWs {
     uint16_t *Wh, *Wl;                                // hi / lo planes of embed_word_W^T [V][Hp]
     float* Wt;                                        // embed_word_W^T in fp32 [V][ldt], zeros past H: a survivor's column as one row
     uint16_t *hh, *hl;                                // hi / lo planes of the step's rows [R][Hp]
-    float* L;                                         // approximate logits [R][ldl]; the resolve kernel leaves its fast keys there
+    float* L;                                         // approximate logits [R][ldl]; above 12288 columns the resolve kernel leaves its fast keys there
     int Hp, ldl, ldt;                                 // bf16_pad(H); V rounded up to 4; H rounded up to 4
 };
 // once per sampler call: zero the head block, cast W^T, transpose W, take the column norms' maximum

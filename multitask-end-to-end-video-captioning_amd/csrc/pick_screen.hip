@@ -19,6 +19,7 @@ namespace {
 
 constexpr int kResThreads = 512, kResWaves = kResThreads / 64;
 constexpr int kResChunk = 4 * kResThreads, kResList = 2 * kResChunk;   // columns keyed per pass (one group of 4 per thread); survivors listed at most
+constexpr int kResRegChunks = 6;                                       // up to 6 chunks (|V| <= 12288) a thread's fast keys stay in registers
 
 // Once per sampler call: Wt[v][k] = W[k][v] (fp32, rows ldt apart, zeros for H <= k < ldt) -- a survivor's column of W is then one
 // contiguous row instead of H cache lines -- and nwmax = max_v |W[:, v]|_2 rounded up, as the bits of a non-negative float folded with an
@@ -66,7 +67,8 @@ __global__ __launch_bounds__(256) void pick_screen_prepare_kernel(const float* _
 }
 
 struct PickResolveArgs {
-    float* L; int ldl;                       // approximate logits [R][ldl], ldl % 4 == 0, 16-byte aligned rows; left holding the fast keys
+    float* L; int ldl;                       // approximate logits [R][ldl], ldl % 4 == 0, 16-byte aligned rows; read once and left as they are
+                                             // up to 12288 columns, overwritten with the fast keys above (nothing reads either afterwards)
     const float* bias;                       // [V]
     const float* h; int ldh;                 // the step's fp32 rows [R][H]
     const float* Wt; int ldt;                // embed_word_W^T [V][ldt], ldt % 4 == 0, zeros past H
@@ -78,12 +80,9 @@ struct PickResolveArgs {
     int H, V; float C;
 };
 
-// v = L~ + bias and the fast key of columns c0 .. c0 + 3 (c0 % 4 == 0): one Philox block, counter (col >> 2, video, sample, step) as the
-// PICK epilogue's; argmax rows (sid < 0) carry no noise.  Columns >= V come back as 0 and are not looked at.
-__device__ __forceinline__ void screen_keys4(const PickResolveArgs& a, const float* Lr, int c0, int vid, int sid, float (&v)[4],
-                                             float (&ka)[4])
+// the approximate logits of columns c0 .. c0 + 3 (c0 % 4 == 0, c0 < V); columns >= V come back as 0
+__device__ __forceinline__ void load_logits4(const PickResolveArgs& a, const float* Lr, int c0, float (&l)[4])
 {
-    float l[4];
     if (c0 + 4 <= a.V) {
         const float4 x = *reinterpret_cast<const float4*>(Lr + c0);
         l[0] = x.x; l[1] = x.y; l[2] = x.z; l[3] = x.w;
@@ -91,6 +90,13 @@ __device__ __forceinline__ void screen_keys4(const PickResolveArgs& a, const flo
 #pragma unroll
         for (int j = 0; j < 4; ++j) l[j] = c0 + j < a.V ? Lr[c0 + j] : 0.0f;
     }
+}
+
+// v = L~ + bias and the fast key of columns c0 .. c0 + 3 from their logits l: one Philox block, counter (col >> 2, video, sample, step) as
+// the PICK epilogue's; argmax rows (sid < 0) carry no noise.  Columns >= V are not looked at.
+__device__ __forceinline__ void screen_keys4(const PickResolveArgs& a, const float (&l)[4], int c0, int vid, int sid, float (&v)[4],
+                                             float (&ka)[4])
+{
     u32x4 blk = {0u, 0u, 0u, 0u};
     if (sid >= 0) blk = philox4x32_10((uint32_t)c0 >> 2, (uint32_t)vid, (uint32_t)sid, (uint32_t)a.step, a.seed_lo, a.seed_hi);
 #pragma unroll
@@ -139,9 +145,13 @@ __device__ __forceinline__ void resolve_listed(const PickResolveArgs& a, const f
 }
 
 // One workgroup per row; no grid-wide waits, every loop bounded by V or H.  Pass 1 keys every column and takes the row's fast maximum,
-// the largest magnitude and |h|, and leaves the keys where the logits were; pass 2 reads them back, counts the survivors, lists them in LDS
-// and resolves them.  A row with more survivors than the list holds goes chunk by chunk instead: no survivor is ever dropped.  A row with a
-// non-finite key, norm or margin takes every column (slow, equal).
+// the largest magnitude and |h|; pass 2 counts the survivors among the keys, lists them in LDS and resolves them.  A row with more
+// survivors than the list holds goes chunk by chunk instead: no survivor is ever dropped.  A row with a non-finite key, norm or margin
+// takes every column (slow, equal).
+// A thread owns the same 4 columns of every chunk of kResChunk in every pass.  REG (|V| <= kResRegChunks chunks): its keys stay in a
+// statically indexed register array from pass 1 on -- the logits are read once, all chunks' loads issued ahead of the Philox work, and
+// nothing is written back.  Otherwise pass 1 leaves the keys where the logits were and pass 2 reads them back (each thread its own).
+template <bool REG>
 __global__ __launch_bounds__(kResThreads) void pick_resolve_kernel(PickResolveArgs a)
 {
     __shared__ float hs[kPickScreenMaxH];
@@ -157,9 +167,7 @@ __global__ __launch_bounds__(kResThreads) void pick_resolve_kernel(PickResolveAr
 
     float mx = -inf, amax = 0.0f, ss = 0.0f;
     int bad = 0;
-    for (int c0 = tid * 4; c0 < a.V; c0 += kResChunk) {
-        float v[4], ka[4];
-        screen_keys4(a, Lr, c0, vid, sid, v, ka);
+    auto fold = [&](int c0, const float (&v)[4], const float (&ka)[4]) {
 #pragma unroll
         for (int j = 0; j < 4; ++j)
             if (c0 + j < a.V) {
@@ -167,10 +175,36 @@ __global__ __launch_bounds__(kResThreads) void pick_resolve_kernel(PickResolveAr
                 amax = fmaxf(amax, fmaxf(fabsf(v[j]), fabsf(ka[j])));
                 bad |= !(fabsf(ka[j]) < inf);
             }
-        // the fast keys take the logits' place: pass 2 reads them back (each thread its own) instead of drawing the noise again
-        if (c0 + 4 <= a.V) *reinterpret_cast<float4*>(Lr + c0) = make_float4(ka[0], ka[1], ka[2], ka[3]);
-        else
-            for (int j = 0; c0 + j < a.V; ++j) Lr[c0 + j] = ka[j];
+    };
+    float kr[REG ? kResRegChunks : 1][4];                                  // REG: the fast keys of columns tid * 4 + c * kResChunk + j
+    if constexpr (REG) {
+        // every chunk's 16 bytes first, without a branch: a group that starts below V lies inside the row (ldl = V rounded up to 4; what
+        // it holds past V is not looked at), one that starts past V reads the row's last group instead
+        float4 x[kResRegChunks];
+#pragma unroll
+        for (int c = 0; c < kResRegChunks; ++c) x[c] = *reinterpret_cast<const float4*>(Lr + min(tid * 4 + c * kResChunk, a.ldl - 4));
+#pragma unroll
+        for (int c = 0; c < kResRegChunks; ++c) {
+            const int c0 = tid * 4 + c * kResChunk;
+            kr[c][0] = kr[c][1] = kr[c][2] = kr[c][3] = 0.0f;
+            if (c0 < a.V) {
+                const float l[4] = {x[c].x, x[c].y, x[c].z, x[c].w};
+                float v[4];
+                screen_keys4(a, l, c0, vid, sid, v, kr[c]);
+                fold(c0, v, kr[c]);
+            }
+        }
+    } else {
+        for (int c0 = tid * 4; c0 < a.V; c0 += kResChunk) {
+            float l[4], v[4], ka[4];
+            load_logits4(a, Lr, c0, l);
+            screen_keys4(a, l, c0, vid, sid, v, ka);
+            fold(c0, v, ka);
+            // the fast keys take the logits' place: pass 2 reads them back (each thread its own) instead of drawing the noise again
+            if (c0 + 4 <= a.V) *reinterpret_cast<float4*>(Lr + c0) = make_float4(ka[0], ka[1], ka[2], ka[3]);
+            else
+                for (int j = 0; c0 + j < a.V; ++j) Lr[c0 + j] = ka[j];
+        }
     }
     for (int k = tid; k < a.H; k += kResThreads) {
         const float x = a.h[(size_t)row * a.ldh + k];
@@ -204,10 +238,16 @@ __global__ __launch_bounds__(kResThreads) void pick_resolve_kernel(PickResolveAr
         else if (need <= 16) resolve_listed<16>(a, hs, list, n, wave, lane, vid, sid, &best);
         else resolve_listed<32>(a, hs, list, n, wave, lane, vid, sid, &best);
     };
-    // f(column) for every survivor among the four columns at c0 (this thread's own keys of pass 1)
-    auto survivors4 = [&](int c0, auto&& f) {
+    // f(column) for every survivor among this thread's four columns of chunk c (its own keys of pass 1).  REG: from the registers -- where
+    // c is not a constant (the overflow path), a select over the statically indexed array
+    auto survivors4 = [&](int c, auto&& f) {
+        const int c0 = tid * 4 + c * kResChunk;
         float ka[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-        if (c0 + 4 <= a.V) {
+        if constexpr (REG) {
+#pragma unroll
+            for (int cc = 0; cc < kResRegChunks; ++cc)
+                if (cc == c) { ka[0] = kr[cc][0]; ka[1] = kr[cc][1]; ka[2] = kr[cc][2]; ka[3] = kr[cc][3]; }
+        } else if (c0 + 4 <= a.V) {
             const float4 x = *reinterpret_cast<const float4*>(Lr + c0);
             ka[0] = x.x; ka[1] = x.y; ka[2] = x.z; ka[3] = x.w;
         } else {
@@ -217,8 +257,18 @@ __global__ __launch_bounds__(kResThreads) void pick_resolve_kernel(PickResolveAr
         for (int j = 0; j < 4; ++j)
             if (c0 + j < a.V && (all || ka[j] >= thr)) f(c0 + j);
     };
+    // the same over every chunk in which this thread has a column, in ascending order
+    auto survivors = [&](auto&& f) {
+        if constexpr (REG) {
+#pragma unroll
+            for (int c = 0; c < kResRegChunks; ++c)
+                if (tid * 4 + c * kResChunk < a.V) survivors4(c, f);
+        } else {
+            for (int c = 0; tid * 4 + c * kResChunk < a.V; ++c) survivors4(c, f);
+        }
+    };
     int cnt = 0;
-    for (int c0 = tid * 4; c0 < a.V; c0 += kResChunk) survivors4(c0, [&](int) { ++cnt; });
+    survivors([&](int) { ++cnt; });
 #pragma unroll
     for (int off = 1; off < 64; off <<= 1) cnt += __shfl_xor(cnt, off, 64);
     if (lane == 0) nwave[wave] = cnt;
@@ -228,14 +278,14 @@ __global__ __launch_bounds__(kResThreads) void pick_resolve_kernel(PickResolveAr
     for (int w = 0; w < kResWaves; ++w) total += (unsigned)nwave[w];
     if (total <= (unsigned)kResList) {
         // the usual row: one list, one round
-        for (int c0 = tid * 4; c0 < a.V; c0 += kResChunk) survivors4(c0, [&](int c) { list[atomicAdd(&nlist, 1)] = c; });
+        survivors([&](int c) { list[atomicAdd(&nlist, 1)] = c; });
         __syncthreads();
         resolve((int)total);
         __syncthreads();
     } else {
         // more survivors than the list holds: chunk by chunk, resolving whenever the next chunk might not fit behind what is listed
         for (int base = 0; base < a.V; base += kResChunk) {
-            if (base + tid * 4 < a.V) survivors4(base + tid * 4, [&](int c) { list[atomicAdd(&nlist, 1)] = c; });
+            if (base + tid * 4 < a.V) survivors4(base / kResChunk, [&](int c) { list[atomicAdd(&nlist, 1)] = c; });
             __syncthreads();
             const int n = nlist;
             __syncthreads();                                               // (everyone has read the count before the next chunk adds to it)
@@ -277,7 +327,7 @@ hipError_t launch_pick_screen_step(const float* h, int ldh, const float* W, cons
     if (H > kPickScreenMaxH) return hipErrorInvalidValue;
     hipError_t e = launch_cast_rows_bf16(h, ldh, nullptr, R, H, s.hh, s.Hp, st, s.hl);
     if (e != hipSuccess) return e;
-    e = launch_gemm_bf16x3_nt(s.hh, s.hl, s.Hp, s.Wh, s.Wl, s.Hp, s.L, s.ldl, R, V, s.Hp, 0, nullptr, 0, 2, st);
+    e = launch_gemm_bf16x3_nt(s.hh, s.hl, s.Hp, s.Wh, s.Wl, s.Hp, s.L, s.ldl, R, V, s.Hp, 0, nullptr, 0, 2, st, gemm_bf16x3_pick_tile(R, V));
     if (e != hipSuccess) return e;
     PickResolveArgs a;
     a.L = s.L; a.ldl = s.ldl; a.bias = bias; a.h = h; a.ldh = ldh; a.Wt = s.Wt; a.ldt = s.ldt; a.vid = vid; a.sid = sid;
@@ -285,7 +335,8 @@ hipError_t launch_pick_screen_step(const float* h, int ldh, const float* W, cons
     a.pick = pick; a.pick_stride = pick_stride > 0 ? pick_stride : 1;
     a.nwmax = s.nwmax; a.counters = s.counters; a.H = H; a.V = V;
     a.C = 9.765625e-04f * (float)((H + 1023) / 1024);                      // 2^-10 per 1024 reduction steps
-    hipLaunchKernelGGL(pick_resolve_kernel, dim3((unsigned)R), dim3(kResThreads), 0, st, a);
+    if (V <= kResRegChunks * kResChunk) hipLaunchKernelGGL(pick_resolve_kernel<true>, dim3((unsigned)R), dim3(kResThreads), 0, st, a);
+    else hipLaunchKernelGGL(pick_resolve_kernel<false>, dim3((unsigned)R), dim3(kResThreads), 0, st, a);
     return hipGetLastError();
 }
 

@@ -1459,6 +1459,25 @@ int s2vt_gemm_bf16x3_nt(const uint16_t* Ah, const uint16_t* Al, int32_t lda, con
     return S2VT_OK;
 }
 
+int s2vt_gemm_bf16x3_nt_tile(const uint16_t* Ah, const uint16_t* Al, int32_t lda, const uint16_t* Bh, const uint16_t* Bl, int32_t ldb, float* C,
+                             int32_t ldc, int32_t M, int32_t N, int32_t Kp, int32_t accumulate, s2vt_stream stream, int32_t tile)
+{
+    if (tile < 0 || tile > 1) return S2VT_E_BADARG;
+    if (!Ah || !Al || !Bh || !Bl || !C || M < 0 || N < 0 || Kp < 0 || Kp % kBf16K || lda < Kp || ldb < Kp || ldc < N || (lda & 7) || (ldb & 7))
+        return S2VT_E_BADARG;
+    if (accumulate < 0 || accumulate > 1) return S2VT_E_BADARG;
+    if ((reinterpret_cast<uintptr_t>(Ah) | reinterpret_cast<uintptr_t>(Al) | reinterpret_cast<uintptr_t>(Bh) | reinterpret_cast<uintptr_t>(Bl)) & 15)
+        return S2VT_E_ALIGN;
+    HIP_TRY(launch_gemm_bf16x3_nt(Ah, Al, lda, Bh, Bl, ldb, C, ldc, M, N, Kp, accumulate, nullptr, 0, 3, S(stream), tile));
+    return S2VT_OK;
+}
+
+int s2vt_gemm_bf16x3_nt_tile_choice(int32_t M, int32_t N, int32_t cus)
+{
+    if (M <= 0 || N <= 0 || cus <= 0) return S2VT_E_BADARG;
+    return gemm_bf16x3_nt_tile_choice(M, N, cus);
+}
+
 int s2vt_gemm_bf16x3_nn(const uint16_t* Ah, const uint16_t* Al, int32_t lda, const uint16_t* Bh, const uint16_t* Bl, int32_t ldb, float* C,
                         int32_t ldc, int32_t M, int32_t N, int32_t K, int32_t accumulate, const float* bias, void* scratch, size_t scratch_bytes,
                         s2vt_stream stream)

@@ -857,6 +857,31 @@ def gemm_bf16x3_nt(Ah, Al, Bh, Bl, out=None, accumulate=False, split_k=True):
     return out
 
 
+def gemm_bf16x3_nt_tile(Ah, Al, Bh, Bl, tile, out=None, accumulate=False):
+    """gemm_bf16x3_nt without split-K on the workgroup tile `tile`: 0 = 128 x 128, 1 = 192 x 96 (s2vt_gemm_bf16x3_nt_tile) -- the same bits."""
+    for t in (Ah, Al, Bh, Bl):
+        assert t.is_cuda and t.dtype == torch.bfloat16 and t.stride(1) == 1
+    assert Ah.shape == Al.shape and Bh.shape == Bl.shape and Ah.stride(0) == Al.stride(0) and Bh.stride(0) == Bl.stride(0)
+    M, Kp = Ah.shape
+    N = Bh.shape[0]
+    if out is None:
+        assert not accumulate
+        out = torch.empty((M, N), dtype=torch.float32, device=Ah.device)
+    _chk_f32(out)
+    assert out.shape[0] == M and out.shape[1] == N and out.stride(1) == 1
+    check(lib().s2vt_gemm_bf16x3_nt_tile(_ptr(Ah), _ptr(Al), Ah.stride(0), _ptr(Bh), _ptr(Bl), Bh.stride(0), _ptr(out), out.stride(0), M, N, Kp,
+                                         int(bool(accumulate)), _stream(), int(tile)), "s2vt_gemm_bf16x3_nt_tile")
+    return out
+
+
+def gemm_bf16x3_nt_tile_choice(M, N, cus):
+    """The tile the library's rule takes for an M x N NT split-bf16 product on `cus` compute units: 0 = 128 x 128, 1 = 192 x 96 (host only)."""
+    r = lib().s2vt_gemm_bf16x3_nt_tile_choice(int(M), int(N), int(cus))
+    if r < 0:
+        check(r, "s2vt_gemm_bf16x3_nt_tile_choice")
+    return r
+
+
 def gemm_bf16_nt(A, B, out=None, accumulate=False, mfma=0, n=None):
     """C[M, N] (+)= A[M, Kp] B[N, Kp]^T on bf16 operands (Kp % 64 == 0), fp32 accumulation (s2vt_gemm_bf16_nt).  `out` may be a
     row-strided fp32 view; n: columns of C when B has more rows than are wanted."""
