@@ -126,6 +126,11 @@ int s2vt_math_eval(int fn, const float* x, float* y, int64_t n, s2vt_stream stre
 /* Gumbel noise words of the sampler stream for (video, sample, step), columns [0, V). */
 int s2vt_gumbel_eval(uint64_t seed, int32_t video, int32_t sample, int32_t step, float* out, int32_t V,
                      s2vt_stream stream);
+/* Both Gumbel forms of the sampler on given Philox words: exact[i] = the fixed-sequence value that decides a token
+ * (-log(-log(u)), u = ((words[i] >> 9) + 0.5) 2^-23), fast[i] = the two-hardware-log value the pick screens compare
+ * under kGumbelScreenMargin (csrc/detmath.h).  Only the top 23 bits of a word count: 2^23 words cover the domain.
+ * NULL or n < 0: S2VT_E_BADARG; n == 0: nothing is launched. */
+int s2vt_gumbel_words_eval(const uint32_t* words, float* exact, float* fast, int64_t n, s2vt_stream stream);
 
 /* ---- tf.nn.xw_plus_b / tf.matmul over a concatenated operand -------------------------------
  * C[m, :] = act( chain over [A0[r0(m)] ; A1[r1(m)] ; A2[r2(m)]] @ W  (+ bias) ), the chain
@@ -204,7 +209,9 @@ int s2vt_lstm_cell_fwd_gather(const s2vt_operand* x0, const s2vt_operand* x1, co
  * rows with sample_id < 0 (tf_s2vt.py:262) or one draw of tf.multinomial(log_softmax(logits),1)
  * (reinforcement_multisampling_tf_s2vt.py:333-336) as Gumbel-max otherwise.  The logits stay
  * on chip unless logits_out != NULL.  packed[m] must be zero on entry; on exit it holds
- * (orderable(key) << 32) | ~token.  tokens_out (optional) receives the int32 ids. */
+ * (orderable(key) << 32) | ~token.  tokens_out (optional) receives the int32 ids.
+ * The pick is exact for |logit + bias + noise| < 16384: its screen compares fast keys under the fixed kGumbelScreenMargin
+ * (csrc/detmath.h), which must cover the rounding of logit + noise, so one ulp of a key must not exceed it (2^-10 below 16384). */
 int s2vt_vocab_pick(const float* out2, int32_t ld, const float* W, const float* b, int32_t M, int32_t H, int32_t V,
                     const int32_t* video_id, const int32_t* sample_id, int32_t step, uint64_t seed,
                     unsigned long long* packed, int32_t* tokens_out, float* logits_out, int32_t tile_cfg,

@@ -31,6 +31,15 @@ __global__ void gumbel_eval_kernel(uint32_t lo, uint32_t hi, uint32_t video, uin
     if (n < V) out[n] = gumbel_at(lo, hi, video, sample, step, (uint32_t)n);
 }
 
+__global__ void gumbel_words_eval_kernel(const uint32_t* words, float* exact, float* fast, int64_t n)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t w = words[i];
+    exact[i] = gumbel_from_word(w);
+    fast[i] = gumbel_fast_from_word(w);
+}
+
 __global__ void fill_i32_kernel(int32_t* p, int32_t v, int n)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -214,6 +223,15 @@ int s2vt_gumbel_eval(uint64_t seed, int32_t video, int32_t sample, int32_t step,
     if (!out || V <= 0) return S2VT_E_BADARG;
     hipLaunchKernelGGL(gumbel_eval_kernel, dim3((V + 255) / 256), dim3(256), 0, S(stream), (uint32_t)seed,
                        (uint32_t)(seed >> 32), (uint32_t)video, (uint32_t)sample, (uint32_t)step, out, V);
+    HIP_TRY(hipGetLastError());
+    return S2VT_OK;
+}
+
+int s2vt_gumbel_words_eval(const uint32_t* words, float* exact, float* fast, int64_t n, s2vt_stream stream)
+{
+    if (!words || !exact || !fast || n < 0 || n > (int64_t)0x7fffffff * 256) return S2VT_E_BADARG;
+    if (n == 0) return S2VT_OK;
+    hipLaunchKernelGGL(gumbel_words_eval_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, S(stream), words, exact, fast, n);
     HIP_TRY(hipGetLastError());
     return S2VT_OK;
 }

@@ -6,9 +6,11 @@
 // Why the winner survives: with e >= |exact key - fast key| for every column, w the exact winner and f the fast argmax,
 //     fast_w >= exact_w - e >= exact_f - e >= fast_f - 2 e.
 // e = m + kGumbelScreenMargin + slack, m = C |h| max_v |W[:, v]|: the three kept products of hi = bf16(x), lo = bf16(x - hi) miss at
-// most 3 * 2^-18 |h_k w_k| per term, the fp32 chain is within K 2^-24 sum |h_k w_k| of the true sum, and 3 K roundings of the bf16
-// MFMA accumulation within 2^-22 relative each add 3 K 2^-22 sum |h_k w_k|; sum |h_k w_k| <= |h| |w| -- below C = 2^-10 for K <= 1024,
-// scaled by ceil(K / 1024) above.  slack covers the roundings of (logit + bias) + noise on either side.
+// most 2^-15 |h_k w_k| per term (|lo| <= 2^-8 |x|, so the dropped lo x lo product is up to 2^-16 of the term, and |x - hi - lo| <=
+// 2^-17 |x| on either operand; measured 3.1e-5 = 1.02 x 2^-15 of sum |h_k w_k| on operands built for it, tests/test_gpu_pick_margins.py),
+// the fp32 chain is within K 2^-24 sum |h_k w_k| of the true sum, and 3 K roundings of the bf16 MFMA accumulation within 2^-22
+// relative each add 3 K 2^-22 sum |h_k w_k|; sum |h_k w_k| <= |h| |w| -- 0.84 C with C = 2^-10 at K = 1024, C scaled by ceil(K / 1024)
+// above.  slack covers the roundings of (logit + bias) + noise on either side.
 #include <hip/hip_runtime.h>
 
 #include "detmath.h"

@@ -71,6 +71,15 @@ def gumbel_eval(seed, video, sample, step, V, device="cuda"):
     return out
 
 
+def gumbel_words_eval(words):
+    """(exact, fast): gumbel_from_word and gumbel_fast_from_word of each Philox word (int32 / uint32 bits, a contiguous device tensor)."""
+    assert words.is_cuda and words.is_contiguous() and words.element_size() == 4 and not words.dtype.is_floating_point
+    exact = torch.empty(words.shape, dtype=torch.float32, device=words.device)
+    fast = torch.empty_like(exact)
+    check(lib().s2vt_gumbel_words_eval(_ptr(words), _ptr(exact), _ptr(fast), words.numel(), _stream()), "s2vt_gumbel_words_eval")
+    return exact, fast
+
+
 def gemm(segs, W, bias=None, M=None, cinit=None, act_tanh=False, tile_cfg=-1, out=None):
     """C = act([seg0 ; seg1 ; seg2] @ W + bias), continuing the chain from cinit if given."""
     _chk_f32(W, bias, cinit)

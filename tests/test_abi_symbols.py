@@ -34,6 +34,11 @@ def test_ctypes_table_matches_header():
 def test_argument_validation_without_gpu():
     L = s2vt_amd.lib()
     assert L.s2vt_math_eval(0, None, None, 4, None) == -1
+    buf = (ctypes.c_uint32 * 4)()
+    here = ctypes.cast(buf, ctypes.c_void_p)
+    assert L.s2vt_gumbel_words_eval(None, here, here, 4, None) == -1 and L.s2vt_gumbel_words_eval(here, None, here, 4, None) == -1
+    assert L.s2vt_gumbel_words_eval(here, here, None, 4, None) == -1 and L.s2vt_gumbel_words_eval(here, here, here, -1, None) == -1
+    assert L.s2vt_gumbel_words_eval(here, here, here, 0, None) == 0          # n == 0: nothing is launched
     assert L.s2vt_sample_workspace_bytes(None, 4, 2, 1) == 0
     d = _lib.Dims(16, 11, 3, 4, 2, 3, 0, 0)
     assert L.s2vt_sample_workspace_bytes(ctypes.byref(d), 4, 2, 1) > 0
