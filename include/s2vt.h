@@ -289,15 +289,18 @@ int s2vt_sample_ex(const s2vt_dims* d, const s2vt_params* p, const float* video,
                    uint64_t seed, int32_t video_base, int32_t flags, int32_t* ids_out, void* workspace, size_t workspace_bytes,
                    s2vt_stream stream);
 
-/* s2vt_sample with the vocabulary pick screened: per decode step the split-bf16 product of the step's rows with
- * embed_word_W gives approximate logits, a proven margin (2^-10 |h| max|W[:, v]| per 1024 reduction steps, plus the Gumbel screen's)
- * keeps the columns of a row that can still win it, and only those get the exact ascending-k fp32 chain and the exact Gumbel
- * expression.  ids_out is bit-identical to s2vt_sample's.  workspace / workspace_bytes: s2vt_sample's, carved and left as s2vt_sample
+/* s2vt_sample with the vocabulary pick screened: per decode step the bf16 product bf16(h) . bf16(embed_word_W) of
+ * the step's rows gives approximate logits, a proven margin (|h - bf16(h)| max|W[:, v]| + 1.004 |h| max|W[:, v] - bf16(W[:, v])|, what the
+ * two casts miss, + 2^-11 |h| max|W[:, v]| per 1024 reduction steps for the accumulation, plus the Gumbel screen's) keeps the columns of a row that can still win it, and only those get the exact ascending-k fp32 chain and the exact Gumbel
+ * expression.  ids_out is bit-identical to s2vt_sample's.  S2VT_PICK_PRODUCTS=3 in the environment (read once), or an explicit
+ * S2VT_PICK_TILE, screens on the three-product split-bf16 product instead (margin 2^-10 |h| max|W[:, v]| per 1024 steps; the lo planes
+ * of the scratch are written only then): the same ids, a slower product, fewer survivors.  workspace / workspace_bytes: s2vt_sample's, carved and left as s2vt_sample
  * leaves it.  screen_ws (256-byte aligned): a scratch of its own of s2vt_sample_screen_workspace_bytes bytes -- a 256-byte head block,
  * the hi / lo planes of embed_word_W^T [V][pad(H)] (bf16, pad = up to a multiple of 64), embed_word_W^T in fp32 [V][H up to a
  * multiple of 4] (a surviving column is read as one row), the hi / lo planes of the step's rows [R][pad(H)] and the approximate logits
  * [R][V up to a multiple of 4] fp32, each region rounded up to 256 bytes: about 118 MB at V = 12000, H = 1000, R = 384.  The head block holds, per call: uint64 survivors summed over rows and steps (byte 0), uint32 the most survivors of one row
- * (byte 8), uint32 rows that took every column because a key, norm or margin was not finite (byte 12).
+ * (byte 8), uint32 rows that took every column because a key, norm or margin was not finite (byte 12); then the two column-norm maxima the
+ * margin uses (floats, bytes 16 and 20).
  * ..._workspace_bytes returns 0 where the path does not serve the call -- (K + with_greedy) * B <= 64 rows (the persistent decode
  * loop's shapes), lstm_dim > 2048, a residual model, bad arguments, 257 - 384 rows while S2VT_DECLOOP=2 or S2VT_DEC4=1 asks for the
  * opt-in fragment-order forms there, or S2VT_PICK_SCREEN=0 in the environment (read once) -- and
@@ -545,6 +548,11 @@ int s2vt_gemm_bf16x3_nt(const uint16_t* Ah, const uint16_t* Al, int32_t lda, con
 int s2vt_gemm_bf16x3_nt_tile(const uint16_t* Ah, const uint16_t* Al, int32_t lda, const uint16_t* Bh, const uint16_t* Bl, int32_t ldb, float* C,
                              int32_t ldc, int32_t M, int32_t N, int32_t Kp, int32_t accumulate, s2vt_stream stream, int32_t tile);
 int s2vt_gemm_bf16x3_nt_tile_choice(int32_t M, int32_t N, int32_t cus);
+/* C[M,N] (+)= Ah.Bh^T over Kp: the one-product form on the hi planes alone (bf16(x), what s2vt_cast_bf16_split writes to dst; the layout
+ * rules of s2vt_gemm_bf16_nt), fp32 accumulation, 192 x 96 workgroup tiles, never split, no atomics.  |C - A.B^T| <= (2^-7 + 2^-11)
+ * ceil(Kp / 1024) |a_m| |b_n|: the product of the sampler's default pick screen, whose margin covers exactly that -- not a gradient's. */
+int s2vt_gemm_bf16x1_nt(const uint16_t* Ah, int32_t lda, const uint16_t* Bh, int32_t ldb, float* C, int32_t ldc, int32_t M, int32_t N, int32_t Kp,
+                        int32_t accumulate, s2vt_stream stream);
 
 /* The K-major form of s2vt_gemm_bf16x3_nt, for products that sum over the ROW index of both operands (weight gradients) without
  * transposed copies: C[M,N] (+)= sum over k < K of A[k][m].B[k][n] with the same three products, planes stored by rows -- A as

@@ -145,6 +145,7 @@ SIGNATURES = {
     "s2vt_gemm_bf16x3_nt": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _sz, _vp]),
     "s2vt_gemm_bf16x3_nt_tile": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32]),
     "s2vt_gemm_bf16x3_nt_tile_choice": (C.c_int, [_i32, _i32, _i32]),
+    "s2vt_gemm_bf16x1_nt": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "s2vt_gemm_bf16x3_tn": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _sz, _vp]),
     "s2vt_gemm_bf16x3_nn": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _sz, _vp]),
     "s2vt_split_grad_active": (C.c_int, [_i32]),

@@ -302,11 +302,15 @@ struct GemmX3Args {
 
 // the three forms: which of the two operands lie K-major ([K][ld], the TN loader and the transposed fragment reads)
 enum : int { kX3NT = 0, kX3TN = 1, kX3NN = 2 };
+// kX1NT: the one-product NT form, C = Ah Bh^T -- the hi planes alone (Al, Bl are neither loaded nor read), one MFMA pass per K step.  What
+// it leaves is bf16 x bf16 in fp32: a screen's product (pick_screen.hip proves the bound), never a gradient's.  192 x 96 tiles only.
+enum : int { kX1NT = 3 };
 
 constexpr int kX3BK = 32, kX3Slots = 4, kX3Plane = kTile * kX3BK;   // a plane's K step: 128 rows x 32 bf16 = 8 KB
 constexpr int kX3TileM = 192, kX3TileN = 96;                         // the second NT geometry
 // LDS of a tile geometry: 4 slots x (2 A planes + 2 B planes) x 64 bytes a row -- 128 KB at 128 x 128, 144 KB at 192 x 96: one workgroup per CU
 constexpr int x3_lds_bytes(int tm, int tn) { return kX3Slots * 2 * (tm + tn) * kX3BK * 2; }
+constexpr int x1_lds_bytes(int tm, int tn) { return kX3Slots * (tm + tn) * kX3BK * 2; }   // the hi planes alone: 72 KB at 192 x 96
 constexpr int kX3Dma = kTile / 16;                                   // DMA instructions per plane per K step (per loader wave)
 typedef __attribute__((address_space(3))) void* x3_lds_ptr;
 typedef short i16x4 __attribute__((ext_vector_type(4)));
@@ -314,8 +318,9 @@ typedef __attribute__((address_space(3))) i16x4* x3_tr_ptr;
 
 // A loader wave of the NT form on a tile whose planes differ in height: the rows [r0, r0 + 16 ND) of one plane (descriptor rs starts at row
 // r0), ND DMA instructions per K step into pdst + slot * slot_elems.  ND is a constant of the plane, so the counted waits are immediates;
-// the ring, the waits and the barriers are those of the 128 x 128 loader in the kernel below.
-template <int ND>
+// the ring, the waits and the barriers are those of the 128 x 128 loader in the kernel below.  (FORM only names the specialization: the
+// one-product kernel takes its own -- the host pass fails to look up a specialization that another kernel instantiation already took.)
+template <int ND, int FORM = kX3NT>
 __device__ __forceinline__ void x3_nt_loader(__amdgpu_buffer_rsrc_t rs, int r0, int rows, int ld, uint16_t* pdst, int slot_elems, int kbeg, int nk, int lane)
 {
     static_assert(3 * ND < 64, "vmcnt is a 6-bit counter");
@@ -357,13 +362,16 @@ __device__ __forceinline__ void x3_nt_loader(__amdgpu_buffer_rsrc_t rs, int r0, 
 // BM x BN: the output tile.  128 x 128 in every form; the NT form also as 192 x 96 (2 x 2 MFMA waves of 96 x 48 = 6 x 3 fragments, 18
 // accumulators; A-plane loaders issue 12 DMA instructions per K step, B-plane loaders 6) -- the same ring, waits, K steps and MFMA order,
 // one accumulator per output element: the bits do not depend on the tile.  Unsplit launches only (g.part == nullptr).
+// kX1NT on that geometry: a slot holds [Ah | Bh]; loader waves 4-5 take the upper and lower 96 rows of Ah (6 DMA instructions per K step
+// each), 6-7 the two 48-row halves of Bh (3 each) -- all eight waves exist and meet at the same barriers; 18 MFMAs per K step and wave.
 template <int FORM, int BM = kTile, int BN = kTile>
 __global__ __launch_bounds__(512) void gemm_bf16x3_kernel(GemmX3Args g)
 {
-    static_assert(BM == BN ? BM == kTile : FORM == kX3NT && BM % 32 == 0 && BN % 32 == 0, "K-major planes come as 128 x 128 tiles only");
-    constexpr bool ATN = FORM == kX3TN, BTN = FORM != kX3NT;            // A's planes / B's planes K-major
+    constexpr bool X1 = FORM == kX1NT;
+    static_assert(BM == BN ? BM == kTile && !X1 : (FORM == kX3NT || X1) && BM % 32 == 0 && BN % 32 == 0, "K-major planes come as 128 x 128 tiles only");
+    constexpr bool ATN = FORM == kX3TN, BTN = FORM == kX3TN || FORM == kX3NN;   // A's planes / B's planes K-major
     constexpr int WM = BM / 2, WN = BN / 2, FI = WM / 16, FJ = WN / 16; // an MFMA wave's part of the tile, in rows / columns and in fragments
-    constexpr int kPlaneA = BM * kX3BK, kPlaneB = BN * kX3BK, kSlot = 2 * (kPlaneA + kPlaneB);
+    constexpr int kPlaneA = BM * kX3BK, kPlaneB = BN * kX3BK, kSlot = (X1 ? 1 : 2) * (kPlaneA + kPlaneB);
     extern __shared__ __attribute__((aligned(16))) uint16_t x3lds[];   // [slot][Ah | Al | Bh | Bl][rows][32]
     const int nwg = g.tiles_m * g.tiles_n, orig = blockIdx.x;
     const int xcd = orig & 7, q = nwg >> 3, rem = nwg & 7;
@@ -377,13 +385,24 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_kernel(GemmX3Args g)
         if (w >= 4) {
             // ================= loader wave of the NT form, plane p: rows / 16 DMA instructions per K step (x3_nt_loader)
             const int p = w - 4;
-            const uint16_t* const plane = p == 0 ? g.Ah : p == 1 ? g.Al : p == 2 ? g.Bh : g.Bl;
-            const int r0 = p < 2 ? m0 : n0, rows = p < 2 ? g.M : g.N, ld = p < 2 ? g.lda : g.ldb;
-            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(plane + (size_t)r0 * ld), 0, (int)kOob, 0x00020000);
-            uint16_t* const pdst = x3lds + (p < 2 ? p * kPlaneA : 2 * kPlaneA + (p - 2) * kPlaneB);
-            if (p < 2) x3_nt_loader<BM / 16>(rs, r0, rows, ld, pdst, kSlot, kbeg, nk, lane);
-            else x3_nt_loader<BN / 16>(rs, r0, rows, ld, pdst, kSlot, kbeg, nk, lane);
-            return;
+            if constexpr (X1) {
+                // half (p & 1) of the hi plane of A (p < 2) or B; a half that starts past the last row loads nothing but zeros (every offset kOob)
+                const int hr = (p < 2 ? BM : BN) / 2 * (p & 1);
+                const int r0 = (p < 2 ? m0 : n0) + hr, rows = p < 2 ? g.M : g.N, ld = p < 2 ? g.lda : g.ldb;
+                const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>((p < 2 ? g.Ah : g.Bh) + (size_t)min(r0, rows) * ld), 0, (int)kOob, 0x00020000);
+                uint16_t* const pdst = x3lds + (p < 2 ? 0 : kPlaneA) + hr * kX3BK;
+                if (p < 2) x3_nt_loader<BM / 32, kX1NT>(rs, r0, rows, ld, pdst, kSlot, kbeg, nk, lane);
+                else x3_nt_loader<BN / 32, kX1NT>(rs, r0, rows, ld, pdst, kSlot, kbeg, nk, lane);
+                return;
+            } else {
+                const uint16_t* const plane = p == 0 ? g.Ah : p == 1 ? g.Al : p == 2 ? g.Bh : g.Bl;
+                const int r0 = p < 2 ? m0 : n0, rows = p < 2 ? g.M : g.N, ld = p < 2 ? g.lda : g.ldb;
+                const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(plane + (size_t)r0 * ld), 0, (int)kOob, 0x00020000);
+                uint16_t* const pdst = x3lds + (p < 2 ? p * kPlaneA : 2 * kPlaneA + (p - 2) * kPlaneB);
+                if (p < 2) x3_nt_loader<BM / 16>(rs, r0, rows, ld, pdst, kSlot, kbeg, nk, lane);
+                else x3_nt_loader<BN / 16>(rs, r0, rows, ld, pdst, kSlot, kbeg, nk, lane);
+                return;
+            }
         }
     } else if (w >= 4) {
         // ================= loader wave: plane p, 8 DMA instructions per K step
@@ -462,14 +481,17 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_kernel(GemmX3Args g)
 #pragma unroll
         for (int j = 0; j < FJ; ++j) acc[i][j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
     // fragments of one K step: [plane][repeat] (FI repeats of an A plane, FJ of a B plane)
-    constexpr int FX = FI > FJ ? FI : FJ;
-    auto read = [&](int ks, bf16x8 (&f)[4][FX]) __attribute__((always_inline)) {
+    constexpr int FX = FI > FJ ? FI : FJ, NPL = X1 ? 2 : 4;               // (kX1NT: [0] = Ah, [1] = Bh)
+    auto read = [&](int ks, bf16x8 (&f)[NPL][FX]) __attribute__((always_inline)) {
         const uint16_t* const s = x3lds + (ks % kX3Slots) * kSlot;
 #pragma unroll
-        for (int pl = 0; pl < 4; ++pl)
+        for (int pl = 0; pl < NPL; ++pl)
 #pragma unroll
             for (int i = 0; i < FX; ++i)
-                if constexpr (BM != BN) {                                  // (NT only) planes of two sizes
+                if constexpr (X1) {
+                    if (i < (pl == 0 ? FI : FJ))
+                        f[pl][i] = *reinterpret_cast<const bf16x8*>(s + (pl == 0 ? wr * WM * kX3BK : kPlaneA + wc * WN * kX3BK) + i * 16 * kX3BK + fofs);
+                } else if constexpr (BM != BN) {                                  // (NT only) planes of two sizes
                     if (i < (pl < 2 ? FI : FJ))
                         f[pl][i] = *reinterpret_cast<const bf16x8*>(s + (pl < 2 ? pl * kPlaneA + wr * WM * kX3BK : 2 * kPlaneA + (pl - 2) * kPlaneB + wc * WN * kX3BK) +
                                                                     i * 16 * kX3BK + fofs);
@@ -491,26 +513,33 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_kernel(GemmX3Args g)
                     f[pl][i] = *reinterpret_cast<const bf16x8*>(s + pl * kX3Plane + ((pl < 2 ? wr : wc) * 64 + i * 16) * kX3BK + fofs);
                 }
     };
-    auto mul = [&](const bf16x8 (&f)[4][FX]) __attribute__((always_inline)) {
-        // small products first, each pass over all FI x FJ accumulators (no back-to-back dependent MFMAs)
+    auto mul = [&](const bf16x8 (&f)[NPL][FX]) __attribute__((always_inline)) {
+        if constexpr (X1) {
 #pragma unroll
-        for (int i = 0; i < FI; ++i)
+            for (int i = 0; i < FI; ++i)
 #pragma unroll
-            for (int j = 0; j < FJ; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f[0][i], f[3][j], acc[i][j], 0, 0, 0);
+                for (int j = 0; j < FJ; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f[0][i], f[1][j], acc[i][j], 0, 0, 0);
+        } else {
+            // small products first, each pass over all FI x FJ accumulators (no back-to-back dependent MFMAs)
 #pragma unroll
-        for (int i = 0; i < FI; ++i)
+            for (int i = 0; i < FI; ++i)
 #pragma unroll
-            for (int j = 0; j < FJ; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f[1][i], f[2][j], acc[i][j], 0, 0, 0);
+                for (int j = 0; j < FJ; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f[0][i], f[3][j], acc[i][j], 0, 0, 0);
 #pragma unroll
-        for (int i = 0; i < FI; ++i)
+            for (int i = 0; i < FI; ++i)
 #pragma unroll
-            for (int j = 0; j < FJ; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f[0][i], f[2][j], acc[i][j], 0, 0, 0);
+                for (int j = 0; j < FJ; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f[1][i], f[2][j], acc[i][j], 0, 0, 0);
+#pragma unroll
+            for (int i = 0; i < FI; ++i)
+#pragma unroll
+                for (int j = 0; j < FJ; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f[0][i], f[2][j], acc[i][j], 0, 0, 0);
+        }
     };
-    bf16x8 fa[4][FX], fb[4][FX];
+    bf16x8 fa[NPL][FX], fb[NPL][FX];
     __syncthreads();                                                      // K step 0 has landed
     if (nk > 0) read(0, fa);
     // barrier k publishes K step k + 1 and frees K step k's slot (its fragments are in registers: lgkmcnt(0) first)
-    auto step = [&](int k, bf16x8 (&cur)[4][FX], bf16x8 (&nxt)[4][FX]) __attribute__((always_inline)) {
+    auto step = [&](int k, bf16x8 (&cur)[NPL][FX], bf16x8 (&nxt)[NPL][FX]) __attribute__((always_inline)) {
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __syncthreads();
         if (k + 1 < nk) read(k + 1, nxt);
@@ -663,8 +692,8 @@ template <int FORM, int BM = kTile, int BN = kTile>
 hipError_t launch_x3(const uint16_t* Ah, const uint16_t* Al, int lda, const uint16_t* Bh, const uint16_t* Bl, int ldb, float* C, int ldc, int M, int N,
                      int Kp, int accumulate, float* bias, float* part, size_t part_floats, int cls, hipStream_t st, const float* cbias = nullptr)
 {
-    constexpr bool kWide = BM != BN;
-    constexpr int kLds = x3_lds_bytes(BM, BN), kCfg = kWide ? 17 : 16;     // (the launch profiler's tile id)
+    constexpr bool kWide = BM != BN, kOne = FORM == kX1NT;
+    constexpr int kLds = kOne ? x1_lds_bytes(BM, BN) : x3_lds_bytes(BM, BN), kCfg = kOne ? 18 : kWide ? 17 : 16;     // (the launch profiler's tile id)
     if (M <= 0 || N <= 0) return hipSuccess;
     if (kWide && part) return hipErrorInvalidValue;
     static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_bf16x3_kernel<FORM, BM, BN>), hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
@@ -696,7 +725,8 @@ hipError_t launch_x3(const uint16_t* Ah, const uint16_t* Al, int lda, const uint
     }
     if (prof) {
         (void)hipEventRecord(e1, st);
-        const char* const name = kWide ? (cls == 2 ? "x3_192x96(dma) pick screen" : cls == 3 ? "x3_192x96(dma) wgrad" : "x3_192x96(dma) dgrad")
+        const char* const name = kOne ? (cls == 2 ? "x1_192x96(dma) pick screen" : "x1_192x96(dma)")
+                                 : kWide ? (cls == 2 ? "x3_192x96(dma) pick screen" : cls == 3 ? "x3_192x96(dma) wgrad" : "x3_192x96(dma) dgrad")
                                        : cls == 0 ? "x3_128x128(dma) fwd" : cls == 2 ? "x3_128x128(dma) pick screen" : cls == 3 ? "x3_128x128(dma) wgrad" : "x3_128x128(dma) dgrad";
         prof_record(cls, kCfg, name, 2.0 * M * (double)N * Kp, e0, e1);
     }
@@ -709,6 +739,12 @@ hipError_t launch_gemm_bf16x3_nt(const uint16_t* Ah, const uint16_t* Al, int lda
 {
     if (tile == 1 && !part) return launch_x3<kX3NT, kX3TileM, kX3TileN>(Ah, Al, lda, Bh, Bl, ldb, C, ldc, M, N, Kp, accumulate, nullptr, nullptr, 0, cls, st);
     return launch_x3<kX3NT>(Ah, Al, lda, Bh, Bl, ldb, C, ldc, M, N, Kp, accumulate, nullptr, part, part_floats, cls, st);
+}
+
+hipError_t launch_gemm_bf16x1_nt(const uint16_t* Ah, int lda, const uint16_t* Bh, int ldb, float* C, int ldc, int M, int N, int Kp, int accumulate, int cls,
+                                 hipStream_t st)
+{
+    return launch_x3<kX1NT, kX3TileM, kX3TileN>(Ah, nullptr, lda, Bh, nullptr, ldb, C, ldc, M, N, Kp, accumulate, nullptr, nullptr, 0, cls, st);
 }
 
 bool gemm_bf16x3_tn_ok(int lda, int ldb, int K)

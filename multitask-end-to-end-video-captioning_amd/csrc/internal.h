@@ -358,6 +358,10 @@ hipError_t launch_gemm_bf16_nt(const uint16_t* A, int lda, const uint16_t* B, in
 hipError_t launch_gemm_bf16x3_nt(const uint16_t* Ah, const uint16_t* Al, int lda, const uint16_t* Bh, const uint16_t* Bl, int ldb, float* C, int ldc,
                                  int M, int N, int Kp, int accumulate, float* part, size_t part_floats, int cls, hipStream_t st, int tile = 0);
 int gemm_bf16x3_nt_tile_choice(int M, int N, int cus);
+// C[M,N] (+)= Ah Bh^T: the one-product form on the hi planes alone (same layout rules), 192 x 96 workgroup tiles, never split.  bf16 x bf16
+// in fp32 -- |C - A B^T| up to 2^-7 of sum |a_k b_k|: the pick screen's product (its margin covers that), not a gradient's
+hipError_t launch_gemm_bf16x1_nt(const uint16_t* Ah, int lda, const uint16_t* Bh, int ldb, float* C, int ldc, int M, int N, int Kp, int accumulate, int cls,
+                                 hipStream_t st);
 int gemm_bf16x3_pick_tile(int M, int N);
 size_t gemm_bf16x3_part_floats(int M, int N, int Kp);
 // The K-major form: C[M,N] (+)= sum_k A[k][m] B[k][n] over K rows of planes stored by rows ([K][lda], [K][ldb]; lda, ldb % 8 == 0, 16-byte
@@ -380,16 +384,19 @@ bool softmax_nll_split_ok(const float* logits, int ld, int V, const uint16_t* hi
 hipError_t launch_softmax_nll_split(const float* logits, int ld, int R, int V, const int32_t* target, const float* coef, float smoothing, float* nll,
                                     float* lp_t, uint16_t* hi, uint16_t* lo, int ldp, hipStream_t st, const float* smooth_rows = nullptr);
 
-// ---- the sampler's screened vocabulary pick (pick_screen.hip): split-bf16 approximate logits screen the columns of a row, the survivors
-// get the exact fp32 chain and Gumbel expression -- the packed picks are those of launch_gemm(EPI_PICK), bit for bit
+// ---- the sampler's screened vocabulary pick (pick_screen.hip): bf16 approximate logits screen the columns of a row, the survivors
+// get the exact fp32 chain and Gumbel expression -- the packed picks are those of launch_gemm(EPI_PICK), bit for bit.  The screen's product
+// is bf16(h) bf16(W) (one product; the margin takes what the two casts miss, measured) unless the env asks for the three-product split form
+// (margin constant C = 2^-10): S2VT_PICK_PRODUCTS=3, or any explicit S2VT_PICK_TILE (a tile of the three-product kernel) -- read once
+int pick_screen_products();                           // 1 or 3
 constexpr int kPickScreenMaxH = 2048;                 // the resolve kernel stages h and a column of W in LDS
 constexpr size_t kPickScreenHeadBytes = 256;          // counters + nwmax: the scratch's first block, zeroed by ..._prepare
 struct PickScreenWs {
     unsigned long long* counters;                     // [0] survivors summed over rows and steps; then uint32 most survivors of a row, uint32 rows that took every column
-    float* nwmax;                                     // max_v |W[:, v]|_2, rounded up (byte 16 of the head block)
-    uint16_t *Wh, *Wl;                                // hi / lo planes of embed_word_W^T [V][Hp]
+    float* nwmax;                                     // [0] max_v |W[:, v]|_2, [1] max_v |W[:, v] - bf16(W[:, v])|_2, rounded up (bytes 16, 20 of the head block)
+    uint16_t *Wh, *Wl;                                // hi / lo planes of embed_word_W^T [V][Hp] (one product: Wl stays unwritten)
     float* Wt;                                        // embed_word_W^T in fp32 [V][ldt], zeros past H: a survivor's column as one row
-    uint16_t *hh, *hl;                                // hi / lo planes of the step's rows [R][Hp]
+    uint16_t *hh, *hl;                                // hi / lo planes of the step's rows [R][Hp] (one product: hl stays unwritten)
     float* L;                                         // approximate logits [R][ldl]; above 12288 columns the resolve kernel leaves its fast keys there
     int Hp, ldl, ldt;                                 // bf16_pad(H); V rounded up to 4; H rounded up to 4
 };

@@ -1472,6 +1472,16 @@ int s2vt_gemm_bf16x3_nt_tile(const uint16_t* Ah, const uint16_t* Al, int32_t lda
     return S2VT_OK;
 }
 
+int s2vt_gemm_bf16x1_nt(const uint16_t* Ah, int32_t lda, const uint16_t* Bh, int32_t ldb, float* C, int32_t ldc, int32_t M, int32_t N, int32_t Kp,
+                        int32_t accumulate, s2vt_stream stream)
+{
+    if (!Ah || !Bh || !C || M < 0 || N < 0 || Kp < 0 || Kp % kBf16K || lda < Kp || ldb < Kp || ldc < N || (lda & 7) || (ldb & 7)) return S2VT_E_BADARG;
+    if (accumulate < 0 || accumulate > 1) return S2VT_E_BADARG;
+    if ((reinterpret_cast<uintptr_t>(Ah) | reinterpret_cast<uintptr_t>(Bh)) & 15) return S2VT_E_ALIGN;
+    HIP_TRY(launch_gemm_bf16x1_nt(Ah, lda, Bh, ldb, C, ldc, M, N, Kp, accumulate, 3, S(stream)));
+    return S2VT_OK;
+}
+
 int s2vt_gemm_bf16x3_nt_tile_choice(int32_t M, int32_t N, int32_t cus)
 {
     if (M <= 0 || N <= 0 || cus <= 0) return S2VT_E_BADARG;

@@ -883,6 +883,23 @@ def gemm_bf16x3_nt_tile(Ah, Al, Bh, Bl, tile, out=None, accumulate=False):
     return out
 
 
+def gemm_bf16x1_nt(Ah, Bh, out=None, accumulate=False):
+    """C[M, N] (+)= Ah Bh^T on the bf16 hi planes alone [M | N, Kp] (Kp % 64 == 0), fp32 accumulation (s2vt_gemm_bf16x1_nt): the sampler's
+    one-product pick screen -- within 2^-7 of sum |a_k b_k|, no more."""
+    for t in (Ah, Bh):
+        assert t.is_cuda and t.dtype == torch.bfloat16 and t.stride(1) == 1
+    M, Kp = Ah.shape
+    N = Bh.shape[0]
+    if out is None:
+        assert not accumulate
+        out = torch.empty((M, N), dtype=torch.float32, device=Ah.device)
+    _chk_f32(out)
+    assert out.shape[0] == M and out.shape[1] == N and out.stride(1) == 1
+    check(lib().s2vt_gemm_bf16x1_nt(_ptr(Ah), Ah.stride(0), _ptr(Bh), Bh.stride(0), _ptr(out), out.stride(0), M, N, Kp, int(bool(accumulate)),
+                                    _stream()), "s2vt_gemm_bf16x1_nt")
+    return out
+
+
 def gemm_bf16x3_nt_tile_choice(M, N, cus):
     """The tile the library's rule takes for an M x N NT split-bf16 product on `cus` compute units: 0 = 128 x 128, 1 = 192 x 96 (host only)."""
     r = lib().s2vt_gemm_bf16x3_nt_tile_choice(int(M), int(N), int(cus))
