@@ -69,7 +69,7 @@ typedef struct s2vt_dims {
  *     bf16 / split scratch do not change.  A residual model's sampler always takes per-step launches (no persistent decode loop).
  *   Accepted, same behaviour (no logits there, or they only read what the calls above leave): s2vt_frame_embed_fwd / _bwd, s2vt_bptt_dvideo,
  *     s2vt_split_grad_dlogits_planes, s2vt_softmax_nll_fwd_bwd_split, s2vt_bf16_grad_workspace_bytes, s2vt_split_grad_workspace_bytes.
- *   Every other entry point that takes s2vt_dims (s2vt_sample_mix, s2vt_scheduled_fwd, s2vt_create and the handle calls, every s2vt_attn_*)
+ *   Every other entry point that takes s2vt_dims (s2vt_sample_mix, s2vt_scheduled_fwd, s2vt_averaged_fwd / _bptt_bwd, s2vt_create and the handle calls, every s2vt_attn_*)
  *     returns S2VT_E_BADARG (size functions: 0) when the bit is set.  Any other bit: S2VT_E_BADARG / 0 everywhere. */
 #define S2VT_MODEL_RESIDUAL 1
 
@@ -399,6 +399,42 @@ int s2vt_scheduled_fwd(const s2vt_dims* d, const s2vt_params* p, const float* vi
                        float* logits_out, int32_t* generated, int32_t* fed, float* mask, float* coef_tm, int32_t* target_tm, float* mask_sum,
                        float* mask_sum_copy, void* workspace, size_t workspace_bytes, void* scratch, size_t scratch_bytes, s2vt_stream stream);
 
+/* ---- averaged-embedding unroll: build_model of average_generate_words_tf_s2vt.py:88-165 (forward and backward) ------------------------
+ * s2vt_scheduled_fwd without the coin.  Step 0 feeds <bos> = 1 alone (:124-127); at step t >= 1 row n of LSTM2 is fed
+ *   x[n] = (Wemb[caption[n][t - 1]] + Wemb[g[n][t - 1]]) / 2   (:131-133),  g[.][t - 1] = argmax of step t - 1's logits, lowest index on ties (:156)
+ * -- in fp32 one rounded addition and an exact halving, so with both ids equal x is that row of Wemb bit for bit.  Both cells are
+ * dropout-wrapped (:138-142; keep, seed, video_id, sample_id as s2vt_teacher_forced_fwd, the ids required whatever keep says),
+ * logits = xw_plus_b(dropped out2) (:152).  The mask is the FED placeholder (:92,154), not a running mask: quirk SQ1 does not exist here.
+ * Loss (:153-164): loss_weight * sum_t sum_n xent * mask[n][t] / sum(mask) + the weight decay term; no label smoothing, no batch mean.
+ * Outputs, device memory: logits_out [Tc*N, V] time-major (:155 `probs`); generated [N, Tc] int32; coef_tm [Tc*N] = loss_weight * mask and
+ * target_tm [Tc*N] = caption, both time-major (what s2vt_softmax_nll_fwd_bwd takes, smoothing 0); *mask_sum, *mask_sum_copy = sum(mask),
+ * each may be NULL, summed in s2vt_scheduled_fwd's fixed order.  caption: device int32 [N, Tc], an id outside [0, n_words) is clamped
+ * where it is read; mask: device float [N, Tc].  One fused cell launch (the step's mean block a dense operand at kw = H), one pick launch
+ * and one small launch per step, no host round trip.
+ * workspace: the training workspace (s2vt_train_workspace_bytes, unchanged): G1 .. O2 hold the activations; prev holds the ground-truth
+ * previous words, which is NOT what LSTM2 was fed -- s2vt_bptt_bwd* on it would compute another graph's gradient.
+ * scratch: s2vt_averaged_scratch_bytes(d, N) bytes (0 on bad arguments), 256-byte aligned: the packed picks, then what the backward reads
+ * again -- Xbar [Tc*N, E] (block 0: Wemb[1] for every row) and the id pair (truth, picked) of every (step, row), (1, 1) at step 0.
+ * Errors: S2VT_E_BADARG (a NULL pointer other than the two sums, N % B != 0, keep <= 0, a model bit), S2VT_E_ALIGN, S2VT_E_WORKSPACE (a short
+ * workspace or scratch), S2VT_E_CHAIN_TIMEOUT.
+ *
+ * s2vt_averaged_bptt_bwd: s2vt_bptt_bwd on that workspace and scratch.  The argmax is not differentiable, everything else is -- no
+ * stop_gradient stands in front of the second lookup (:132): dWemb[caption[n][t-1]] += dx[n][t] / 2 and dWemb[g[n][t-1]] += dx[n][t] / 2
+ * (s2vt_embed_scatter_add2), and LSTM2's weight gradient for the word rows is Xbar^T dZ2, the mean as the operand.
+ * precision: 0 = fp32 MFMA products (s2vt_bptt_bwd's; grad_ws NULL); 1 = bf16 operands (s2vt_bptt_bwd_bf16's, grad_ws of
+ * s2vt_bf16_grad_workspace_bytes); 2 = s2vt_bptt_bwd_split's rule (split-bf16 above 256 rows, grad_ws of s2vt_split_grad_workspace_bytes;
+ * dlogits NULL = the planes s2vt_softmax_nll_fwd_bwd_split left there).  Whole pass only (no phases, steps or live rows).
+ * Errors: s2vt_bptt_bwd's, and S2VT_E_BADARG for a precision outside 0..2 or a grad_ws that does not go with it. */
+size_t s2vt_averaged_scratch_bytes(const s2vt_dims* d, int32_t N);
+int s2vt_averaged_fwd(const s2vt_dims* d, const s2vt_params* p, const float* video, int32_t B, int32_t N, const int32_t* caption, const float* mask,
+                      float loss_weight, float keep, uint64_t seed, const int32_t* video_id, const int32_t* sample_id, float* logits_out,
+                      int32_t* generated, float* coef_tm, int32_t* target_tm, float* mask_sum, float* mask_sum_copy, void* workspace,
+                      size_t workspace_bytes, void* scratch, size_t scratch_bytes, s2vt_stream stream);
+int s2vt_averaged_bptt_bwd(const s2vt_dims* d, const s2vt_params* p, const s2vt_params* grads, const float* video, int32_t B, int32_t N,
+                           const float* dlogits, float keep, uint64_t seed, const int32_t* video_id, const int32_t* sample_id, void* workspace,
+                           size_t workspace_bytes, const void* scratch, size_t scratch_bytes, int32_t precision, void* grad_ws, size_t grad_ws_bytes,
+                           s2vt_stream stream);
+
 /* Same, inside a REINFORCE step: LSTM1's state trajectory depends only on the frames and the weights, and the
  * sampler pass of the step (s2vt_sample / s2vt_encode_fwd on the SAME video block, SAME weights) has just
  * computed it.  Pass that call's workspace (and its row count R = (K + with_greedy) * B) and the trajectory and
@@ -630,6 +666,11 @@ int s2vt_bptt_dvideo(const s2vt_dims* d, const s2vt_params* p, int32_t B, int32_
 /* dWemb[idx[r], :] += dE[r, :]  -- gradient of tf.nn.embedding_lookup (tf_s2vt.py:128-134). */
 int s2vt_embed_scatter_add(const float* dE, int32_t ld, const int32_t* idx, int32_t R, int32_t E, float* dWemb,
                            s2vt_stream stream);
+/* dWemb[idx_a[r], :] += scale * dE[r, :] and dWemb[idx_b[r], :] += scale * dE[r, :] -- the gradient of a scaled sum of two lookups
+ * (average_generate_words_tf_s2vt.py:131-133, scale = 1/2); a row whose two ids are equal receives both additions.  dE [R, ld >= E];
+ * the ids must lie inside dWemb.  R = 0: nothing is launched. */
+int s2vt_embed_scatter_add2(const float* dE, int32_t ld, const int32_t* idx_a, const int32_t* idx_b, float scale, int32_t R, int32_t E,
+                            float* dWemb, s2vt_stream stream);
 
 /* ---- host glue of the REINFORCE step, on the device (decode_captions_masks, cider_evaluation.py:145-172; the objective's
  * coefficients, reinforcement_multisampling_tf_s2vt.py:641-646).

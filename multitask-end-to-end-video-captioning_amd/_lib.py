@@ -244,6 +244,11 @@ SIGNATURES = {
     "s2vt_scheduled_scratch_bytes": (_sz, [_DP, _i32]),
     "s2vt_scheduled_fwd": (C.c_int, [_DP, _PP, _vp, _i32, _i32, _vp, _f32, _u64, _f32, _f32, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                      _vp, _sz, _vp, _sz, _vp]),
+    "s2vt_averaged_scratch_bytes": (_sz, [_DP, _i32]),
+    "s2vt_averaged_fwd": (C.c_int, [_DP, _PP, _vp, _i32, _i32, _vp, _vp, _f32, _f32, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _sz,
+                                    _vp]),
+    "s2vt_averaged_bptt_bwd": (C.c_int, [_DP, _PP, _PP, _vp, _i32, _i32, _vp, _f32, _u64, _vp, _vp, _vp, _sz, _vp, _sz, _i32, _vp, _sz, _vp]),
+    "s2vt_embed_scatter_add2": (C.c_int, [_vp, _i32, _vp, _vp, _f32, _i32, _i32, _vp, _vp]),
     "s2vt_sgd_guarded": (C.c_int, [_vp, _vp, _i64, _vp, _f32, _f32, _i64, _vp, _vp]),
     "s2vt_adam_tf_guarded": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _f32, _f32, _i64, _f32, _f32, _f32, _vp, _vp]),
     "s2vt_allreduce_grads": (C.c_int, [_vp, _i64, _vp, _vp]),

@@ -501,6 +501,139 @@ struct SchedDecode {
         return hipGetLastError();
     }
 };
+
+// ---- averaged embeddings (average_generate_words_tf_s2vt.py:88-165): the scheduled unroll without the coin.  Step t >= 1 feeds LSTM2
+// the mean of two rows of Wemb, (Wemb[caption[n][t - 1]] + Wemb[argmax of step t - 1]) / 2 (:131-133) -- no row of Wemb, so every step's
+// operand is written out as a dense block Xbar[t] [N, E], which the cell launch reads at kw = H and the backward reads again.
+
+// before step 0, one thread per element of the larger of [N, Tc] and [N, E]: the ground truth as the workspace's time-major targets and
+// teacher-forced previous words, the all-argmax sample ids of the pick launches, <bos> = 1 as both ids of step 0 and Wemb[1] as every
+// row of block 0 (:124-127)
+__global__ __launch_bounds__(256) void avg_open_kernel(const int32_t* caption, const float* Wemb, int N, int Tc, int V, int E, int32_t* prev,
+                                                       int32_t* tgt, int32_t* argmax_sid, int32_t* ida, int32_t* idb, float* xbar)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const int32_t bos = clamp_word(1, V);
+    if (i < (size_t)N * Tc) {
+        const int t = (int)(i / N), n = (int)(i - (size_t)t * N);
+        tgt[i] = clamp_word(caption[(size_t)n * Tc + t], V);
+        prev[i] = t == 0 ? bos : clamp_word(caption[(size_t)n * Tc + t - 1], V);
+        if (t == 0) { argmax_sid[n] = -1; ida[n] = bos; idb[n] = bos; }
+    }
+    if (i < (size_t)N * E) xbar[i] = Wemb[(size_t)bos * E + i % E];
+}
+
+// behind the pick of step t, one thread per element of [N, E]: the row's argmax out of its packed pick (decoded as unpack_ids_kernel
+// does); the row's first thread writes generated, the step's loss coefficient loss_weight * mask (:154: the fed mask) and target, and the
+// id pair of step t + 1; every thread its element of step t + 1's mean, one rounded addition and an exact halving
+__global__ __launch_bounds__(256) void avg_step_kernel(const unsigned long long* picked, int stride, const int32_t* caption, const float* mask,
+                                                       const float* Wemb, int N, int Tc, int t, int V, int E, float loss_weight, int32_t* generated,
+                                                       float* coef_tm, int32_t* target_tm, int32_t* ida, int32_t* idb, float* xbar)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (size_t)N * E) return;
+    const int n = (int)(i / E), e = (int)(i - (size_t)n * E);
+    const unsigned long long w = picked[(size_t)n * stride];
+    const int32_t g = w ? (int32_t)(~(uint32_t)w) : 0;
+    const int32_t truth = clamp_word(caption[(size_t)n * Tc + t], V);
+    const int32_t pick = clamp_word(g, V);                  // (a pick is a column of the logits: in range already)
+    if (e == 0) {
+        generated[(size_t)n * Tc + t] = g;
+        coef_tm[(size_t)t * N + n] = loss_weight * mask[(size_t)n * Tc + t];
+        target_tm[(size_t)t * N + n] = truth;
+        if (t + 1 < Tc) { ida[(size_t)(t + 1) * N + n] = truth; idb[(size_t)(t + 1) * N + n] = pick; }
+    }
+    if (t + 1 < Tc) xbar[(size_t)(t + 1) * N * E + i] = (Wemb[(size_t)truth * E + e] + Wemb[(size_t)pick * E + e]) * 0.5f;
+}
+
+// dW[ia[r]] += scale * dE[r] and dW[ib[r]] += scale * dE[r] (twice into the same row when the two ids are equal): one wave per row
+__global__ __launch_bounds__(256) void scatter_add_rows2_kernel(const float* dE, int ld, const int32_t* ia, const int32_t* ib, float scale, int R,
+                                                                int E, float* dW, int ldw)
+{
+    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= R) return;
+    const int a = ia[r], b = ib[r];
+    for (int e = threadIdx.x & 63; e < E; e += 64) {
+        const float v = scale * dE[(size_t)r * ld + e];
+        atomicAdd(dW + (size_t)a * ldw + e, v);
+        atomicAdd(dW + (size_t)b * ldw + e, v);
+    }
+}
+hipError_t launch_scatter_add_rows2(const float* dE, int ld, const int32_t* ia, const int32_t* ib, float scale, int R, int E, float* dW, int ldw,
+                                    hipStream_t st)
+{
+    if (R <= 0) return hipSuccess;
+    hipLaunchKernelGGL(scatter_add_rows2_kernel, dim3((R + 3) / 4), dim3(256), 0, st, dE, ld, ia, ib, scale, R, E, dW, ldw);
+    return hipGetLastError();
+}
+
+// The scratch of the averaged unroll beside the training workspace: every step's packed picks (zeroed up front), the pick launches' sample
+// ids, and what the backward reads again -- Xbar [Tc N, E] and the id pair (truth, picked) [Tc N] each, time-major
+struct AvgScratch { unsigned long long* packed; int32_t* argmax_sid; float* xbar; int32_t *ida, *idb; };
+size_t carve_avg(Carver& c, const s2vt_dims* d, int N, AvgScratch* out)
+{
+    const size_t R = (size_t)d->n_caption_lstm_step * N;
+    AvgScratch s;
+    s.packed = c.take<unsigned long long>(R * kPickStride);
+    s.argmax_sid = c.take<int32_t>(N);
+    s.xbar = c.take<float>(R * d->word_dim);
+    s.ida = c.take<int32_t>(R);
+    s.idb = c.take<int32_t>(R);
+    if (out) *out = s;
+    return c.off;
+}
+
+// The decoding stage of the averaged unroll: SchedDecode's stages with the step's mean block as a dense operand at kw = H
+struct AvgDecode {
+    const s2vt_params* p; const TrainWs& w; const AvgScratch& x;
+    int N, H, E, V, Tv, Tc; float keep; NoiseIds ids; hipStream_t st;
+    const int32_t* caption; const float* mask; float loss_weight;
+    float* logits; int32_t* generated; float* coef_tm; int32_t* target_tm;
+    size_t NH;
+
+    unsigned long long* picks(int t) const { return x.packed + (size_t)t * N * kPickStride; }
+    unsigned elem_blocks() const { return (unsigned)(((size_t)N * E + 255) / 256); }
+
+    hipError_t open()
+    {
+        ZeroList z;
+        z.add(x.packed, (size_t)Tc * N * kPickStride * 8);
+        HIP_CHECK(launch_zero_regions(z, st));
+        const size_t n = (size_t)N * (Tc > E ? Tc : E);
+        hipLaunchKernelGGL(avg_open_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, caption, p->Wemb, N, Tc, V, E, w.prev, w.tgt,
+                           x.argmax_sid, x.ida, x.idb, x.xbar);
+        return hipGetLastError();
+    }
+    hipError_t decode_partials()
+    {
+        ASeg so = make_seg(w.O1 + (size_t)Tv * NH, H, H, 0);
+        return store_call(&so, 1, p->lstm2_W, 4 * H, nullptr, w.G2 + (size_t)Tv * 4 * NH, 4 * H, Tc * N, 4 * H, 0, -1, st);
+    }
+    hipError_t encode()
+    {
+        return lstm_recurrence(p->lstm2_W, H + E, p->lstm2_b, w.G2, (size_t)4 * NH, 4 * H, Tv, w.C2, w.H2, NH, w.G2, (size_t)4 * NH, w.O2, NH, N, H,
+                               Tv, keep, ids, 512u, w.chain_abuf, w.chain_sync, st);
+    }
+    hipError_t step(int t)
+    {
+        const int u = Tv + t;
+        float* const g2 = w.G2 + (size_t)u * 4 * NH;
+        ASeg s2[2] = {make_seg(x.xbar + (size_t)t * N * E, E, E, H), make_seg(w.H2 + (size_t)u * NH, H, H, H + E)};
+        HIP_CHECK(lstm_call(s2, 2, p->lstm2_W, p->lstm2_b, w.C2 + (size_t)u * NH, 0, w.C2 + (size_t)(u + 1) * NH, w.H2 + (size_t)(u + 1) * NH,
+                            w.O2 + (size_t)u * NH, g2, N, H, keep, ids, 512u + (uint32_t)u, -1, st, g2, 4 * H, 0));
+        const NoiseIds argmax{ids.video_id, x.argmax_sid, 0};
+        HIP_CHECK(pick_call(w.O2 + (size_t)u * NH, H, p->embed_word_W, p->embed_word_b, N, H, V, argmax, t, picks(t), logits + (size_t)t * N * V, -1,
+                            st, kPickStride));
+        hipLaunchKernelGGL(avg_step_kernel, dim3(elem_blocks()), dim3(256), 0, st, picks(t), kPickStride, caption, mask, p->Wemb, N, Tc, t, V, E,
+                           loss_weight, generated, coef_tm, target_tm, x.ida, x.idb, x.xbar);
+        return hipGetLastError();
+    }
+    hipError_t close(float* mask_sum, float* mask_sum_copy)
+    {
+        hipLaunchKernelGGL(sched_mask_sum_kernel, dim3(1), dim3(256), 0, st, mask, N * Tc, mask_sum, mask_sum_copy);
+        return hipGetLastError();
+    }
+};
 }  // namespace
 
 extern "C" {
@@ -826,6 +959,47 @@ int s2vt_scheduled_fwd(const s2vt_dims* d, const s2vt_params* p, const float* vi
     return S2VT_OK;
 }
 
+size_t s2vt_averaged_scratch_bytes(const s2vt_dims* d, int32_t N)
+{
+    if (!dims_ok(d) || N <= 0) return 0;
+    Carver c(nullptr, 0);
+    return carve_avg(c, d, N, nullptr);
+}
+
+int s2vt_averaged_fwd(const s2vt_dims* d, const s2vt_params* p, const float* video, int32_t B, int32_t N, const int32_t* caption, const float* mask,
+                      float loss_weight, float keep, uint64_t seed, const int32_t* video_id, const int32_t* sample_id, float* logits_out,
+                      int32_t* generated, float* coef_tm, int32_t* target_tm, float* mask_sum, float* mask_sum_copy, void* workspace,
+                      size_t workspace_bytes, void* scratch, size_t scratch_bytes, s2vt_stream stream)
+{
+    if (!dims_ok(d) || !params_ok(p) || !video || !caption || !mask || !video_id || !sample_id || !logits_out || !generated || !coef_tm ||
+        !target_tm || !workspace || !scratch || B <= 0 || N <= 0 || N % B)
+        return S2VT_E_BADARG;
+    if (!(keep > 0.0f)) return S2VT_E_BADARG;                                                  // (a NaN fails the comparison)
+    if ((reinterpret_cast<uintptr_t>(workspace) | reinterpret_cast<uintptr_t>(scratch)) & 255u) return S2VT_E_ALIGN;
+    if (chain_fault()) return S2VT_E_CHAIN_TIMEOUT;
+    const int H = d->lstm_dim, E = d->word_dim, V = d->n_words, Tv = d->n_video_lstm_step, Tc = d->n_caption_lstm_step;
+    Carver c(workspace, workspace_bytes);
+    TrainWs w;
+    carve_train(c, d, B, N, &w);
+    Carver cs(scratch, scratch_bytes);
+    AvgScratch x;
+    carve_avg(cs, d, N, &x);
+    if (!c.ok() || !cs.ok()) return S2VT_E_WORKSPACE;
+    hipStream_t st = S(stream);
+    AvgDecode s{p, w, x, N, H, E, V, Tv, Tc, keep, NoiseIds{video_id, sample_id, seed}, st, caption, mask, loss_weight,
+                logits_out, generated, coef_tm, target_tm, (size_t)N * H};
+    HIP_TRY(s.open());
+    {
+        const int rc = unroll_front(d, p, video, B, N, Tv + Tc, keep, seed, video_id, sample_id, w, nullptr, 0, 0, stream);
+        if (rc != S2VT_OK) return rc;
+    }
+    HIP_TRY(s.decode_partials());
+    HIP_TRY(s.encode());
+    for (int t = 0; t < Tc; ++t) HIP_TRY(s.step(t));
+    HIP_TRY(s.close(mask_sum, mask_sum_copy));
+    return S2VT_OK;
+}
+
 int s2vt_caption_mask(const int32_t* ids, int32_t N, int32_t Tc, float* mask, int32_t* target_tm, float* mask_sum, float* mask_sum_copy, s2vt_stream stream)
 {
     if (!ids || N <= 0 || Tc <= 0) return S2VT_E_BADARG;
@@ -987,6 +1161,10 @@ struct BpttBwd {
     size_t NH; TrainWs w; Bf16Ws bw;
     const s2vt_params *p, *grads; const float *video, *dlogits; const int32_t* live_rows; int n_live;
     float keep; uint64_t seed; const int32_t *video_id, *sample_id;
+    // The embedding operand of LSTM2's decode steps as (table, row index, table rows): row r of the operand is row emb_idx[r] of emb_tab
+    // (emb_idx NULL: row r itself).  (Wemb, prev, V) in every teacher-forced backward; (Xbar, none, Tc N) in the averaged one, whose
+    // operand is no row of Wemb -- there emb_ida / emb_idb are the two rows of Wemb each operand row is the mean of (NULL otherwise).
+    const float* emb_tab; const int32_t* emb_idx; int emb_rows; const int32_t *emb_ida, *emb_idb;
     bool bf16, split, fused;             // bf16: either bf16 mode; fused: the split mode without transposed operands (carve_bf16)
     hipStream_t st, sd, sv;              // the caller's; LSTM2's weight gradients' and the deferred dWout's; the vocab stage's dWout's
     bool gate1, gate2;                   // gated overlap beside LSTM1's / LSTM2's recurrence
@@ -1036,10 +1214,13 @@ struct BpttBwd {
         return e != hipSuccess ? e : launch_scatter_rows(packed, ld, live_rows, n, ld, dst, ld, st);
     }
     // embedding rows (gradient of tf.nn.embedding_lookup): scatter-add of the embed slice of dX2
+    // (averaged: half of each row's gradient into either row of its id pair, average_generate_words_tf_s2vt.py:131-133)
     hipError_t wemb_scatter_add() const
     {
+        if (emb_ida)
+            return launch_scatter_add_rows2(w.dX2 + (size_t)Tv * N * (H + E) + H, H + E, emb_ida, emb_idb, 0.5f, Tc * N, E, grads->Wemb, E, st);
         if (live_rows) return launch_scatter_add_rows(w.dX2p + H, H + E, w.prevp, n_live, E, grads->Wemb, E, st);
-        return launch_scatter_add_rows(w.dX2 + (size_t)Tv * N * (H + E) + H, H + E, w.prev, Tc * N, E, grads->Wemb, E, st);
+        return launch_scatter_add_rows(w.dX2 + (size_t)Tv * N * (H + E) + H, H + E, emb_idx, Tc * N, E, grads->Wemb, E, st);
     }
     // dZ2 by rows into L, [encode steps | decode steps]: the B operand of the fused LSTM2 products and dX2's A
     hipError_t cast_dz2_rows() const
@@ -1102,7 +1283,7 @@ struct BpttBwd {
         HIP_CHECK(rows(w.O1, H, nullptr, Re, H, bw.AT, Hp));
         HIP_CHECK(rows(w.O1 + (size_t)Tv * NH, H, live_rows, Rd, H, bw.AT + (size_t)Re * Hp, Hp));
         HIP_CHECK(mmt(bw.AT, Hp, bw.L, K4, grads->lstm2_W, 4 * H, H, 4 * H, Re + Rd, nullptr));
-        HIP_CHECK(rows(p->Wemb, E, live_rows ? w.prevp : w.prev, Rd, E, bw.AT, Ep));                  // Wemb [V, E] rows of the previous words
+        HIP_CHECK(rows(emb_tab, E, live_rows ? w.prevp : emb_idx, Rd, E, bw.AT, Ep));                 // Wemb [V, E] rows of the previous words
         HIP_CHECK(mmt(bw.AT, Ep, bw.L + (size_t)Re * K4, K4, grads->lstm2_W + (size_t)H * 4 * H, 4 * H, E, 4 * H, Rd, nullptr));
         HIP_CHECK(rows1(w.H2, H, nullptr, Re, H, bw.AT, Hp1));
         HIP_CHECK(rows1(w.H2 + (size_t)Tv * NH, H, live_rows, Rd, H, bw.AT + (size_t)Re * Hp1, Hp1));
@@ -1117,7 +1298,7 @@ struct BpttBwd {
         HIP_CHECK(tr(w.O1, H, nullptr, Re, H, bw.AT, Kt));
         HIP_CHECK(tr(w.O1 + (size_t)Tv * NH, H, live_rows, Rd, H, bw.AT + ke, Kt));
         HIP_CHECK(mm(bw.AT, Kt, bw.BT, Kt, grads->lstm2_W, 4 * H, H, 4 * H, Kt, 1));
-        HIP_CHECK(tr(p->Wemb, E, live_rows ? w.prevp : w.prev, Rd, E, bw.AT, Kd));                    // Wemb [V, E] rows of the previous words
+        HIP_CHECK(tr(emb_tab, E, live_rows ? w.prevp : emb_idx, Rd, E, bw.AT, Kd));                   // Wemb [V, E] rows of the previous words
         HIP_CHECK(mm(bw.AT, Kd, bw.BT + ke, Kt, grads->lstm2_W + (size_t)H * 4 * H, 4 * H, E, 4 * H, Kd, 1));
         HIP_CHECK(tr(w.H2, H, nullptr, Re, H, bw.AT, Kt));
         HIP_CHECK(tr(w.H2 + (size_t)Tv * NH, H, live_rows, Rd, H, bw.AT + ke, Kt));
@@ -1128,7 +1309,7 @@ struct BpttBwd {
         float* const gO1 = grads->lstm2_W, *const gEmb = gO1 + (size_t)H * 4 * H, *const gH2 = gO1 + (size_t)(H + E) * 4 * H;
         if (!live_rows) {
             HIP_CHECK(launch_gemm_tn(tn(w.O1, nullptr, 0, H, w.dZ2, 4 * H, gO1, 4 * H, T * N, H, 4 * H), sd));
-            HIP_CHECK(launch_gemm_tn(tn(p->Wemb, w.prev, V, E, dzd(), 4 * H, gEmb, 4 * H, Tc * N, E, 4 * H), sd));
+            HIP_CHECK(launch_gemm_tn(tn(emb_tab, emb_idx, emb_idx ? emb_rows : 0, E, dzd(), 4 * H, gEmb, 4 * H, Tc * N, E, 4 * H), sd));
             return launch_gemm_tn(tn(w.H2, nullptr, 0, H, w.dZ2, 4 * H, gH2, 4 * H, T * N, H, 4 * H, grads->lstm2_b), sd);
         }
         // Live rows: behind its first <eos> a row's dZ2 is an exact zero at every later step (zero upstream gradient, zero carried
@@ -1136,7 +1317,7 @@ struct BpttBwd {
         // dZ2 rows as a packed copy, the matching activation rows gathered through the same list.
         HIP_CHECK(launch_gemm_tn(tn(w.O1, nullptr, 0, H, w.dZ2, 4 * H, gO1, 4 * H, Re, H, 4 * H), sd));
         HIP_CHECK(launch_gemm_tn(tn(w.O1 + (size_t)Tv * NH, live_rows, Tc * N, H, w.dZ2p, 4 * H, gO1, 4 * H, Rd, H, 4 * H), sd));
-        HIP_CHECK(launch_gemm_tn(tn(p->Wemb, w.prevp, V, E, w.dZ2p, 4 * H, gEmb, 4 * H, Rd, E, 4 * H), sd));
+        HIP_CHECK(launch_gemm_tn(tn(emb_tab, w.prevp, emb_rows, E, w.dZ2p, 4 * H, gEmb, 4 * H, Rd, E, 4 * H), sd));
         HIP_CHECK(launch_gemm_tn(tn(w.H2, nullptr, 0, H, w.dZ2, 4 * H, gH2, 4 * H, Re, H, 4 * H, grads->lstm2_b), sd));
         return launch_gemm_tn(tn(w.H2 + (size_t)Tv * NH, live_rows, Tc * N, H, w.dZ2p, 4 * H, gH2, 4 * H, Rd, H, 4 * H, grads->lstm2_b), sd);
     }
@@ -1208,7 +1389,7 @@ struct BpttBwd {
 static int bptt_bwd_body(const s2vt_dims* d, const s2vt_params* p, const s2vt_params* grads, const float* video, int32_t B,
                          int32_t N, const float* dlogits, int32_t caption_steps, const int32_t* live_rows, int32_t n_live, float keep,
                          uint64_t seed, const int32_t* video_id, const int32_t* sample_id, void* workspace, size_t workspace_bytes,
-                         int32_t phase, int mode, void* bf16_ws, size_t bf16_ws_bytes, s2vt_stream stream)
+                         int32_t phase, int mode, void* bf16_ws, size_t bf16_ws_bytes, s2vt_stream stream, const AvgScratch* avg = nullptr)
 {
     const int bf16 = mode != kGradFp32;
     const bool split = mode == kGradSplit;
@@ -1226,6 +1407,7 @@ static int bptt_bwd_body(const s2vt_dims* d, const s2vt_params* p, const s2vt_pa
     if (chain_fault()) return S2VT_E_CHAIN_TIMEOUT;
     if (caption_steps < 1 || caption_steps > d->n_caption_lstm_step) return S2VT_E_BADARG;
     if (live_rows && (n_live > caption_steps * N || ((d->lstm_dim | d->word_dim) & 3))) return S2VT_E_BADARG;
+    if (avg && (live_rows || caption_steps != d->n_caption_lstm_step || is_residual(d))) return S2VT_E_BADARG;   // (the averaged unroll is whole and plain)
     // the steps the forward call unrolled (s2vt_teacher_forced_fwd_steps): later steps carry no gradient, so the
     // recurrences start from zero at step T - 1 and every contraction covers the leading T (Tc) steps only
     const int H = d->lstm_dim, E = d->word_dim, V = d->n_words, Tv = d->n_video_lstm_step, Tc = caption_steps, T = Tv + Tc;
@@ -1260,6 +1442,8 @@ static int bptt_bwd_body(const s2vt_dims* d, const s2vt_params* p, const s2vt_pa
     x.H = H; x.E = E; x.V = V; x.D = d->dim_image; x.Tv = Tv; x.Tc = Tc; x.T = T; x.B = B; x.N = N;
     x.K4 = bf16_pad(4 * H); x.Re = Tv * N; x.Rd = live_rows ? n_live : Tc * N; x.NH = NH;
     x.w = w; x.bw = bw; x.p = p; x.grads = grads; x.video = video; x.dlogits = dlogits; x.live_rows = live_rows; x.n_live = n_live;
+    x.emb_tab = avg ? avg->xbar : p->Wemb; x.emb_idx = avg ? nullptr : w.prev; x.emb_rows = avg ? Tc * N : V;
+    x.emb_ida = avg ? avg->ida : nullptr; x.emb_idb = avg ? avg->idb : nullptr;
     x.keep = keep; x.seed = seed; x.video_id = video_id; x.sample_id = sample_id; x.bf16 = bf16; x.split = split; x.fused = fused;
     x.st = st; x.sd = sd; x.sv = (phase == kAll && ss.ok && ss.mode == 1) ? sd : st;   // (phase 1: its gradients must be final on the caller's stream)
     // The side stream and its events are ONE per process: two host threads driving distinct workspaces must not interleave their
@@ -1307,7 +1491,7 @@ static int bptt_bwd_body(const s2vt_dims* d, const s2vt_params* p, const s2vt_pa
         // stream, dX2 and the embedding scatter on the caller's), so they are made on the caller's stream, ahead of the fork
         if (live_rows) {
             HIP_TRY(launch_gather_rows(w.dZ2 + (size_t)Tv * 4 * NH, 4 * H, live_rows, n_live, 4 * H, w.dZ2p, 4 * H, st));
-            HIP_TRY(launch_gather_i32(w.prev, live_rows, n_live, w.prevp, st));
+            HIP_TRY(launch_gather_i32(x.emb_idx, live_rows, n_live, w.prevp, st));
         }
         // dZ2 is complete: LSTM2's weight gradients go to the side stream, beside dX2 and LSTM1's recurrence (mode 2: beside LSTM1's
         // recurrence only -- launched below once that grid is resident; dX2 keeps the chip to itself)
@@ -1372,6 +1556,22 @@ int s2vt_bptt_bwd_split(const s2vt_dims* d, const s2vt_params* p, const s2vt_par
     if (!split_ws) return S2VT_E_BADARG;
     return bptt_bwd_body(d, p, grads, video, B, N, dlogits, caption_steps, live_rows, n_live, keep, seed, video_id, sample_id, workspace,
                          workspace_bytes, phase, split_grad_mode(N), split_ws, split_ws_bytes, stream);
+}
+
+int s2vt_averaged_bptt_bwd(const s2vt_dims* d, const s2vt_params* p, const s2vt_params* grads, const float* video, int32_t B, int32_t N,
+                           const float* dlogits, float keep, uint64_t seed, const int32_t* video_id, const int32_t* sample_id, void* workspace,
+                           size_t workspace_bytes, const void* scratch, size_t scratch_bytes, int32_t precision, void* grad_ws, size_t grad_ws_bytes,
+                           s2vt_stream stream)
+{
+    if (!dims_ok(d) || N <= 0 || !scratch || precision < 0 || precision > 2 || (precision != 0) != (grad_ws != nullptr)) return S2VT_E_BADARG;
+    if (reinterpret_cast<uintptr_t>(scratch) & 255u) return S2VT_E_ALIGN;
+    Carver cs(const_cast<void*>(scratch), scratch_bytes);
+    AvgScratch x;
+    carve_avg(cs, d, N, &x);
+    if (!cs.ok()) return S2VT_E_WORKSPACE;
+    const int mode = precision == 2 ? split_grad_mode(N) : precision == 1 ? kGradBf16 : kGradFp32;
+    return bptt_bwd_body(d, p, grads, video, B, N, dlogits, d->n_caption_lstm_step, nullptr, 0, keep, seed, video_id, sample_id, workspace,
+                         workspace_bytes, kAll, mode, grad_ws, grad_ws_bytes, stream, &x);
 }
 
 int s2vt_split_grad_active(int32_t N)
@@ -1557,6 +1757,14 @@ int s2vt_embed_scatter_add(const float* dE, int32_t ld, const int32_t* idx, int3
 {
     if (!dE || !idx || !dWemb || R < 0 || E <= 0 || ld < E) return S2VT_E_BADARG;
     HIP_TRY(launch_scatter_add_rows(dE, ld, idx, R, E, dWemb, E, S(stream)));
+    return S2VT_OK;
+}
+
+int s2vt_embed_scatter_add2(const float* dE, int32_t ld, const int32_t* idx_a, const int32_t* idx_b, float scale, int32_t R, int32_t E,
+                            float* dWemb, s2vt_stream stream)
+{
+    if (!dE || !idx_a || !idx_b || !dWemb || R < 0 || E <= 0 || ld < E) return S2VT_E_BADARG;
+    HIP_TRY(launch_scatter_add_rows2(dE, ld, idx_a, idx_b, scale, R, E, dWemb, E, S(stream)));
     return S2VT_OK;
 }
 

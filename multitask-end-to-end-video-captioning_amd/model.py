@@ -315,7 +315,7 @@ class Video_Caption_Generator:
     dim_image (it reads mean_t(video), :375).
     `residual=True` is the architecture of residual_tf_s2vt.py: at every decode step output2 = output1 + output2 ahead of the
     vocabulary projection (:149-151, :206-208, :263-265); same variables and checkpoint layout.  The flag rides in the dims of every
-    library call; mix_sample / scheduled_update and their graphs are not implemented for it and raise ValueError."""
+    library call; mix_sample / scheduled_update / averaged_update and their graphs are not implemented for it and raise ValueError."""
 
     def __init__(self, dim_image, n_words, word_dim, lstm_dim, batch_size, n_lstm_steps, n_video_lstm_step,
                  n_caption_lstm_step, bias_init_vector=None, loss_weight=1, decay_value=0.00005, dropout_rate=0.9,
@@ -1019,6 +1019,134 @@ class Video_Caption_Generator:
         st.mask, st.generated, st.fed = f["mask"], f["generated"], f["fed"]
         return st
 
+    def averaged_update(self, video, caption, caption_mask, lr, clip_norm=10.0, clip="per_variable", optimizer="sgd", video_base=0, keep=None):
+        """build_model + train_op of average_generate_words_tf_s2vt.py:88-165,358-371: scheduled sampling without the coin.  The unroll
+        decodes; step 0 feeds <bos> alone and step t >= 1 feeds LSTM2 (Wemb[caption[:, t-1]] + Wemb[argmax of step t-1]) / 2 (:131-133).  No
+        stop_gradient stands in front of the second lookup: Wemb's gradient lands, halved, on the ground-truth row and on the row the model
+        picked, and LSTM2's weight gradient reads the mean.  Loss (:153-164): per-row softmax cross entropy against caption[:, t], no label
+        smoothing, no batch mean, weighed by the FED caption_mask (no quirk SQ1 here), divided by sum(mask), plus weight decay on the
+        non-'bias' variables.
+        caption, caption_mask [N, Tc], N = rep * B sample-major rows over the B videos.
+        clip="per_variable" with optimizer="sgd" (the defaults) is the script's train(): GradientDescentOptimizer on
+        tf.clip_by_norm(grad, clip_norm) of each variable on its own (:368-371).  clip="global", or optimizer="adam" (which always clips
+        globally), goes through apply_gradients as scheduled_update does.  Data parallel: sum(mask) rides in the gradient bucket's tail slot.
+        Returns StepStats (.loss without the weight-decay term; .grad_sumsq the squared norm over all variables, before clipping) plus
+        .generated [N, Tc] int32 and, for the per-variable clip, .var_sumsq {name: device scalar}."""
+        self._refuse_residual("averaged_update")
+        if clip not in ("per_variable", "global"):
+            raise ValueError(f"clip must be 'per_variable' or 'global', got {clip!r}")
+        if optimizer not in ("adam", "sgd"):
+            raise ValueError(f"optimizer must be 'adam' or 'sgd', got {optimizer!r}")
+        video = self._dev(video, torch.float32)
+        cap = self._dev(caption, torch.int32)
+        mask = self._dev(caption_mask, torch.float32)
+        B, N = video.shape[0], cap.shape[0]
+        if N % B or cap.dim() != 2 or cap.shape[1] != self.n_caption_lstm_step or tuple(mask.shape) != tuple(cap.shape):
+            raise ValueError(f"averaged_update: caption and caption_mask must be [rep * {B}, {self.n_caption_lstm_step}], got "
+                             f"{tuple(cap.shape)} and {tuple(mask.shape)}")
+        keep = self.dropout_rate if keep is None else keep
+        vid, sid = self._row_ids(B, N // B, video_base)
+        seed = self.dropout_seed + 104729 * self.global_step
+        st_ = self.store
+        f = ops.averaged_fwd(self.dims, st_.params, video, cap, mask, N, self.loss_weight, keep, seed, vid, sid,
+                             mask_sum_copy=st_.grad[st_.numel:st_.numel + 1])
+        logits, coef, target, msum = f["logits"], f["coef_tm"], f["target_tm"], f["mask_sum"]
+        self.last_averaged = f                                   # (build_averaged_model's fetches read the logits before the softmax overwrites them)
+        if getattr(self, "_keep_averaged_logits", False):
+            f["probs"] = logits.clone()
+        dlogits = logits
+        if self.grad_precision == "fp32" and ops.split_grad_active(N):
+            nll, _, in_planes = ops.softmax_nll_fwd_bwd_split(logits, target, coef, 0.0, self.dims, B, N)
+            if in_planes:
+                dlogits = None                                   # ops.averaged_bptt_bwd: "the planes are in the split workspace"
+        else:
+            nll, _ = ops.softmax_nll_fwd_bwd(logits, target, coef, 0.0)
+        self._coef_used = coef
+        ops.zero_(st_.grad[:st_.numel])                          # (sum(mask) already sits in the tail slot)
+        self._pending, self._early = [], None
+        ops.averaged_bptt_bwd(self.dims, st_.params, st_.grads, video, N, dlogits, f["ws"], f["scratch"], keep, seed, vid, sid,
+                              precision=self.grad_precision)
+        if clip == "global" or optimizer == "adam":
+            self.apply_gradients(None, lr, clip_norm, weight_decay=self.decay_value, loss_terms=(coef, nll, msum), optimizer=optimizer)
+            var_sumsq = None
+        else:
+            var_sumsq = self._apply_per_variable(lr, clip_norm, (coef, nll, msum))
+        st = StepStats(self._loss[0], self._sumsq, msum[0])
+        st.generated, st.var_sumsq = f["generated"], var_sumsq
+        return st
+
+    def _apply_per_variable(self, lr, clip_norm, loss_terms):
+        """apply_gradients with tf.clip_by_norm per variable and plain SGD (average_generate_words_tf_s2vt.py:368-371, the bidirectional
+        script's rule): all-reduce, 1/sum(mask) and weight decay as there, then one squared norm and one guarded SGD launch per variable.
+        Leaves Adam's moments and count alone.  Returns {name: squared norm, a device scalar}; their sum is left in self._sumsq."""
+        st = self.store
+        gsum = dp.allreduce_bucket(st.grad, st.numel, None)      # (the tail slot already holds the local sum(mask))
+        scratch = torch.empty(1, dtype=torch.float32, device=self.device)
+        self._loss = torch.empty(1, dtype=torch.float32, device=self.device)
+        coef_, nll_, msum_ = loss_terms
+        ops.step_scalars(coef_, nll_, msum_, gsum, self._loss, self._gscale, scratch)
+        sumsq = torch.zeros(len(st.names), dtype=torch.float32, device=self.device)
+        for i, n in enumerate(st.names):
+            decayed = self._decay_everything() or n not in UNDECAYED
+            ops.grad_finalize(st.g[n].view(-1), st.p[n].view(-1), self._gscale, self.decay_value if decayed else 0.0, sumsq[i:i + 1])
+        self.global_step += 1
+        self._sampler_state = None
+        for i, n in enumerate(st.names):
+            ops.sgd(st.p[n].view(-1), st.g[n].view(-1), sumsq[i:i + 1], clip_norm, lr, max(1, self.adam_t), applied_step=self._applied)
+        self._sumsq = sumsq.sum().reshape(1)
+        return {n: sumsq[i] for i, n in enumerate(st.names)}
+
+    def build_averaged_model(self):
+        """The averaged-embedding graph: (loss, video, caption, caption_mask, probs) as average_generate_words_tf_s2vt.py:88-165.
+        caption_mask is an INPUT here (:92), probs a list of Tc fetches [B, V] (the logits of :155).  Fetching loss / probs evaluates the
+        forward only; minimize() builds the train_op of :368-371."""
+        self._refuse_residual("build_averaged_model")
+        B, Tc = self.batch_size, self.n_caption_lstm_step
+        video = self._video_placeholder(B)
+        caption = Placeholder("caption", (B, Tc), np.int32)
+        caption_mask = Placeholder("caption_mask", (B, Tc), np.float32)
+
+        def fetches(f, loss):
+            out = {"loss": loss}
+            pr = f["probs"].view(Tc, -1, self.n_words).cpu().numpy()
+            out.update({f"probs_{t}": pr[t] for t in range(Tc)})
+            return out
+
+        def fn(v, c, m):
+            v = self._features(v, dropout=True, draw=0)
+            c = self._dev(c, torch.int32)
+            m = self._dev(m, torch.float32)
+            n = c.shape[0]
+            vid, sid = self._row_ids(v.shape[0], n // v.shape[0], 0)
+            seed = self.dropout_seed + 104729 * self.global_step
+            f = ops.averaged_fwd(self.dims, self.store.params, v, c, m, n, self.loss_weight, self.dropout_rate, seed, vid, sid)
+            f["probs"] = f["logits"].clone()
+            nll, _ = ops.softmax_nll_fwd_bwd(f["logits"], f["target_tm"], f["coef_tm"], 0.0)
+            return fetches(f, float(torch.dot(f["coef_tm"], nll) / f["mask_sum"][0]) + self.l2_term())
+        inputs = [video, caption, caption_mask]
+        loss = Output("loss", fn, inputs)
+        probs = [Output(f"probs_{t}", fn, inputs) for t in range(Tc)]
+        loss.graph = {"kind": "build_averaged_model", "inputs": inputs, "fetches": fetches, "outputs": probs}
+        return loss, video, caption, caption_mask, probs
+
+    def _minimize_averaged(self, loss, learning_rate, clip_norm, optimizer, clip):
+        graph = loss.graph
+        lr = learning_rate.value if hasattr(learning_rate, "value") else (lambda: float(learning_rate))
+
+        def fn(v, c, m):
+            wd = self.l2_term()                                                # the l2 term of :162-164, pre-update
+            self._keep_averaged_logits = True
+            try:
+                st = self.averaged_update(self._features(v, dropout=True, draw=0), c, m, lr(), clip_norm=clip_norm, clip=clip, optimizer=optimizer)
+            finally:
+                self._keep_averaged_logits = False
+            out = graph["fetches"](self.last_averaged, float(st.loss) + wd)
+            out["train_op"] = None
+            return out
+        provides = {loss: "loss"}
+        provides.update({o: o.name for o in graph["outputs"]})
+        return Output("train_op", fn, graph["inputs"], provides=provides)
+
     @staticmethod
     def inverse_sigmoid_prob(k_value, steps):
         """The commented schedule of generate_words_tf_s2vt.py:134: p = k / (k + exp(steps / k)), in float64."""
@@ -1282,7 +1410,7 @@ class Video_Caption_Generator:
         out.value = value
         return out
 
-    def minimize(self, build_model_outputs, learning_rate, clip_norm=10.0, optimizer="adam"):
+    def minimize(self, build_model_outputs, learning_rate, clip_norm=10.0, optimizer=None, clip=None):
         """train_op of tf_s2vt.py:442-445: AdamOptimizer(learning_rate).compute_gradients(tf_loss) ->
         clip_by_global_norm(10) -> apply_gradients(global_step) -- and of multitask_e2e_attribute_s2vt.py:715-717 /
         e2e_tf_s2vt.py:533-536, the same statement over the multitask loss and over CNN + captioner.  `build_model_outputs` =
@@ -1290,8 +1418,18 @@ class Video_Caption_Generator:
         update, and the losses fetched beside it are the ones the update differentiated (same dropout masks, pre-update weights).
         The 6-tuple of build_scheduled_model() gives the train_op of generate_words_tf_s2vt.py:412-418 (optimizer="sgd" is that script's
         GradientDescentOptimizer); caption_mask and probs fetched beside it are the update's own.  optimizer="sgd" with a build_model
-        tuple is not wired (no script of the reference trains build_model that way)."""
+        tuple is not wired (no script of the reference trains build_model that way).
+        The 5-tuple of build_averaged_model() gives the train_op of average_generate_words_tf_s2vt.py:368-371; there the defaults are that
+        script's optimizer="sgd" and clip="per_variable" (tf.clip_by_norm of each gradient on its own), and clip="global" or
+        optimizer="adam" clip by the global norm.  Everywhere else optimizer defaults to "adam" and clip to the global norm, the only
+        one wired."""
         loss = build_model_outputs[0]
+        if getattr(loss, "graph", None) and loss.graph.get("kind") == "build_averaged_model":
+            return self._minimize_averaged(loss, learning_rate, clip_norm, "sgd" if optimizer is None else optimizer,
+                                           "per_variable" if clip is None else clip)
+        if clip not in (None, "global"):
+            raise ValueError("minimize(clip='per_variable') needs build_averaged_model()'s outputs")
+        optimizer = "adam" if optimizer is None else optimizer
         if getattr(loss, "graph", None) and loss.graph.get("kind") == "build_scheduled_model":
             return self._minimize_scheduled(loss, learning_rate, clip_norm, optimizer)
         if optimizer != "adam":

@@ -617,6 +617,63 @@ def scheduled_fwd(dims: Dims, params: Params, video, caption, N: int, p_gt: floa
     return out
 
 
+def averaged_fwd(dims: Dims, params: Params, video, caption, mask, N: int, loss_weight=1.0, keep=1.0, seed=0, video_id=None, sample_id=None,
+                 ws=None, mask_sum=None, mask_sum_copy=None, scratch=None):
+    """The averaged-embedding unroll of average_generate_words_tf_s2vt.py:88-165 (s2vt_averaged_fwd): the training forward decodes, and at
+    step t >= 1 LSTM2 is fed (Wemb[caption[:, t-1]] + Wemb[argmax of step t-1]) / 2; step 0 feeds <bos> alone.  caption: int32 device tensor
+    [N, Tc] (ids outside [0, n_words) are clamped by the kernel); mask: fp32 device tensor [N, Tc], the fed caption_mask; video_id /
+    sample_id [N] int32 are required.  Returns a dict: logits [Tc*N, V] time-major, generated [N, Tc] int32, coef_tm [Tc*N]
+    (= loss_weight * mask), target_tm [Tc*N] int32, mask_sum [1], ws -- the training workspace -- and scratch, which holds the mean operands
+    and the id pairs: averaged_bptt_bwd takes both (bptt_bwd on ws alone would differentiate another graph)."""
+    _chk_f32(video, mask, mask_sum, mask_sum_copy)
+    assert video.is_contiguous() and mask.is_contiguous()
+    assert caption.is_cuda and caption.dtype == torch.int32 and caption.is_contiguous()
+    Tc = dims.n_caption_lstm_step
+    assert tuple(caption.shape) == (N, Tc) and tuple(mask.shape) == (N, Tc)
+    for t in (video_id, sample_id):
+        assert t is not None and t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.numel() == N, "video_id / sample_id: int32 [N]"
+    B = video.shape[0]
+    dev = video.device
+    L = lib()
+    if ws is None:
+        ws = train_workspace(dims, B, N, dev)
+    if scratch is None:
+        nb = L.s2vt_averaged_scratch_bytes(C.byref(dims), N)
+        assert nb > 0, "bad dims / N"
+        scratch = workspace(nb, dev, "averaged")
+    out = dict(logits=torch.empty((Tc * N, dims.n_words), dtype=torch.float32, device=dev),
+               generated=torch.empty((N, Tc), dtype=torch.int32, device=dev), coef_tm=torch.empty(Tc * N, dtype=torch.float32, device=dev),
+               target_tm=torch.empty(Tc * N, dtype=torch.int32, device=dev),
+               mask_sum=torch.empty(1, dtype=torch.float32, device=dev) if mask_sum is None else mask_sum, ws=ws, scratch=scratch)
+    check(L.s2vt_averaged_fwd(C.byref(dims), C.byref(params), _ptr(video), B, N, _ptr(caption), _ptr(mask), float(loss_weight), float(keep), seed,
+                              _ptr(video_id), _ptr(sample_id), _ptr(out["logits"]), _ptr(out["generated"]), _ptr(out["coef_tm"]),
+                              _ptr(out["target_tm"]), _ptr(out["mask_sum"]), _ptr(mask_sum_copy), _ptr(ws), ws.numel(), _ptr(scratch),
+                              scratch.numel(), _stream()), "s2vt_averaged_fwd")
+    return out
+
+
+def averaged_bptt_bwd(dims: Dims, params: Params, grads: Params, video, N: int, dlogits, ws, scratch, keep=1.0, seed=0, video_id=None,
+                      sample_id=None, precision="fp32", products=None):
+    """The backward of averaged_fwd (s2vt_averaged_bptt_bwd) on its workspace and scratch; gradients are accumulated into `grads`.
+    precision "fp32": the split-bf16 products where split_grad_active(N) and fp32 MFMA below, as bptt_bwd (dlogits None: the planes
+    softmax_nll_fwd_bwd_split left); "bf16": bf16 operands.  products="fp32" forces the fp32 MFMA products at every row count."""
+    _chk_f32(video, dlogits)
+    if precision not in GRAD_PRECISIONS:
+        raise ValueError(f"precision must be one of {GRAD_PRECISIONS}, got {precision!r}")
+    B = video.shape[0]
+    assert dlogits is None or dlogits.shape[0] == dims.n_caption_lstm_step * N
+    if products == "fp32":
+        mode, gws = 0, None
+    elif precision == "bf16":
+        mode, gws = 1, bf16_grad_workspace(dims, B, N, video.device)
+    else:
+        mode, gws = 2, split_grad_workspace(dims, B, N, video.device)
+    assert dlogits is not None or mode == 2
+    check(lib().s2vt_averaged_bptt_bwd(C.byref(dims), C.byref(params), C.byref(grads), _ptr(video), B, N, _ptr(dlogits), float(keep), seed,
+                                       _ptr(video_id), _ptr(sample_id), _ptr(ws), ws.numel(), _ptr(scratch), scratch.numel(), mode, _ptr(gws),
+                                       0 if gws is None else gws.numel(), _stream()), "s2vt_averaged_bptt_bwd")
+
+
 def softmax_nll_fwd_bwd(logits, target, coef, smoothing=0.0):
     """In place: logits <- coef * (softmax - q).  Returns (nll [R], lp_target [R]).  smoothing: a float, or a CUDA fp32
     tensor [R] with one label-smoothing value per row."""
@@ -1560,6 +1617,17 @@ def embed_scatter_add(dE, idx, dWemb):
     assert dE.dim() == 2 and dE.stride(1) == 1 and dWemb.is_contiguous() and dWemb.shape[1] == dE.shape[1]
     check(lib().s2vt_embed_scatter_add(_ptr(dE), dE.stride(0), _ptr(idx), dE.shape[0], dE.shape[1], _ptr(dWemb), _stream()),
           "s2vt_embed_scatter_add")
+
+
+def embed_scatter_add2(dE, idx_a, idx_b, dWemb, scale=0.5):
+    """dWemb[idx_a[r], :] += scale * dE[r, :] and dWemb[idx_b[r], :] += scale * dE[r, :] (s2vt_embed_scatter_add2; both additions land when
+    the two ids are equal): dE [R, E] may be a row-strided view, dWemb [V, E] is contiguous."""
+    _chk_f32(dE, dWemb)
+    for idx in (idx_a, idx_b):
+        assert idx.dtype == torch.int32 and idx.is_cuda and idx.is_contiguous() and idx.numel() == dE.shape[0]
+    assert dE.dim() == 2 and dE.stride(1) == 1 and dWemb.is_contiguous() and dWemb.shape[1] == dE.shape[1]
+    check(lib().s2vt_embed_scatter_add2(_ptr(dE), dE.stride(0), _ptr(idx_a), _ptr(idx_b), float(scale), dE.shape[0], dE.shape[1], _ptr(dWemb),
+                                        _stream()), "s2vt_embed_scatter_add2")
 
 
 def global_norm_clip(g, clip_norm: float):

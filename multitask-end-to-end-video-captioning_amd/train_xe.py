@@ -11,7 +11,11 @@ variable, lr 0.01 halved every 10000 steps).
 
 --scheduled-sampling P trains as generate_words_tf_s2vt.py does instead (Video_Caption_Generator.scheduled_update): the unroll decodes and
 a per-row coin feeds the ground-truth word with probability P / 1.00001 (the script writes P = 0.5), or, with --ss-k K, with the inverse
-sigmoid schedule K / (K + exp(step / K)) of its commented line :134; --optimizer sgd is that script's GradientDescentOptimizer."""
+sigmoid schedule K / (K + exp(step / K)) of its commented line :134; --optimizer sgd is that script's GradientDescentOptimizer.
+
+--averaged-embedding trains as average_generate_words_tf_s2vt.py does (Video_Caption_Generator.averaged_update): the unroll decodes and
+LSTM2 is fed the mean of the ground-truth word's and the model's own argmax's embedding, with that script's rule -- SGD behind
+tf.clip_by_norm 10 per variable, loss_weight 20, lr halved every 40000 steps -- unless --optimizer adam is given (Adam behind the global clip)."""
 from __future__ import annotations
 
 import argparse
@@ -27,8 +31,10 @@ from .train_common import (Config, Corpus, DataParallel, StepLog, epoch_batches,
 
 
 def train(cfg: Config, train_corpus: Corpus, test_corpus: Corpus | None = None, model=None, log=print, resume=None,
-          grad_precision=None, scheduled_sampling=None, ss_k=None, optimizer="adam"):
-    """scheduled_sampling: None = cross entropy; a probability = scheduled sampling with that true-word probability (ss_k: the inverse
+          grad_precision=None, scheduled_sampling=None, ss_k=None, optimizer="adam", averaged_embedding=False):
+    """averaged_embedding: averaged_update instead of xe_update (optimizer "sgd": behind the per-variable clip, the script's train();
+    "adam": behind the global clip); a model built here then takes the script's loss_weight = 20.
+    scheduled_sampling: None = cross entropy; a probability = scheduled sampling with that true-word probability (ss_k: the inverse
     sigmoid schedule on the step counter instead).  Its mask comes from the model's own picks, so a batch in which every row emits <eos>
     at step 0 has sum(mask) = 0 and a 0/0 loss, as in the reference: the run stops there, before another checkpoint is written.
     cfg.batch_size is the GLOBAL batch; data parallel as in train_rl.train (shards of each shuffled batch, Q1's per-step
@@ -43,9 +49,11 @@ def train(cfg: Config, train_corpus: Corpus, test_corpus: Corpus | None = None, 
         model = M.Video_Caption_Generator(cfg.dim_image, len(wordtoix), cfg.word_dim, cfg.lstm_dim, B,
                                           cfg.n_video_lstm_step + cfg.n_caption_lstm_step, cfg.n_video_lstm_step,
                                           cfg.n_caption_lstm_step, bias_init_vector=None, seed=cfg.seed, device=par.device,
-                                          residual=cfg.residual)
+                                          residual=cfg.residual, **({"loss_weight": 20} if averaged_embedding else {}))
     if scheduled_sampling is not None and getattr(model, "residual", False):
         raise ValueError("scheduled sampling is not implemented for a residual model (residual=True / --residual)")
+    if averaged_embedding and (scheduled_sampling is not None or getattr(model, "residual", False)):
+        raise ValueError("averaged-embedding training does not combine with scheduled sampling or a residual model")
     if grad_precision is not None:
         model.grad_precision = grad_precision          # (None: the model's default, S2VT_GRAD_PRECISION)
     par.attach(model)
@@ -82,7 +90,11 @@ def train(cfg: Config, train_corpus: Corpus, test_corpus: Corpus | None = None, 
                 if pending is not None:
                     pending()
             b = cur
-            if scheduled_sampling is None:
+            if averaged_embedding:
+                update = lambda: model.averaged_update(b["feats"], b["ind"], b["mask"], lr=learning_rate(cfg, model.global_step),
+                                                       clip_norm=cfg.clip_norm, clip="per_variable" if optimizer == "sgd" else "global",
+                                                       optimizer=optimizer, video_base=b["lo"])
+            elif scheduled_sampling is None:
                 update = lambda: model.xe_update(b["feats"], b["ind"], b["mask"], lr=learning_rate(cfg, model.global_step),
                                                  clip_norm=cfg.clip_norm, video_base=b["lo"], active_steps=b["steps"])
             else:
@@ -185,8 +197,16 @@ def main(argv=None):
     ap.add_argument("--bidirectional", action="store_true", help="the bidirectional captioner of bidirection_tf_s2vt.py with its own training rule: "
                     "plain SGD, tf.clip_by_norm 10 per variable, lr 0.01 halved every 10000 steps, loss_weight 20, batch 32, d = 1024, Tv = 25 "
                     "(train_bidirectional)")
-    ap.add_argument("--optimizer", choices=("adam", "sgd"), default="adam", help="sgd: the scheduled-sampling script's GradientDescentOptimizer")
+    ap.add_argument("--averaged-embedding", action="store_true", help="averaged-embedding training (average_generate_words_tf_s2vt.py): feed the "
+                    "mean of the ground-truth word's and the model's own argmax's embedding; SGD behind tf.clip_by_norm 10 per variable, loss_weight "
+                    "20, lr halved every 40000 steps, unless --optimizer adam")
+    ap.add_argument("--optimizer", choices=("adam", "sgd"), help="sgd: the scheduled-sampling script's GradientDescentOptimizer; default adam, "
+                    "with --averaged-embedding sgd")
     a = ap.parse_args(argv)
+    if a.averaged_embedding and (a.scheduled_sampling is not None or a.ss_k is not None or a.bidirectional or a.residual):
+        ap.error("--averaged-embedding does not combine with --scheduled-sampling, --ss-k, --bidirectional or --residual")
+    if a.optimizer is None:
+        a.optimizer = "sgd" if a.averaged_embedding else "adam"
     if a.ss_k is not None and a.scheduled_sampling is None:
         a.scheduled_sampling = 0.5
     if a.bidirectional:
@@ -197,14 +217,14 @@ def main(argv=None):
                      decay_steps=10000, clip_norm=10.0, model_path=a.model_path, model_name="bimodel")
         train_bidirectional(cfg, Corpus(a.train_sents, a.train_feats, vocabulary_file=a.vocab), resume=a.resume)
         return
-    if a.optimizer != "adam" and a.scheduled_sampling is None:
-        ap.error("--optimizer sgd is wired for --scheduled-sampling only")
+    if a.optimizer != "adam" and a.scheduled_sampling is None and not a.averaged_embedding:
+        ap.error("--optimizer sgd is wired for --scheduled-sampling and --averaged-embedding only")
     cfg = Config(n_epochs=a.epochs, batch_size=a.batch_size, model_path=a.model_path, model_name=f"batch_size{a.batch_size}_s2vt_model",
-                 residual=a.residual)
+                 residual=a.residual, **({"decay_steps": 40000} if a.averaged_embedding else {}))     # (:366-367: 40000)
     tr = Corpus(a.train_sents, a.train_feats, vocabulary_file=a.vocab)
     te = Corpus(a.test_sents, a.test_feats, vocabulary=tr.vocabulary) if a.test_sents and a.test_feats else None
     train(cfg, tr, te, resume=a.resume, grad_precision=a.grad_precision, scheduled_sampling=a.scheduled_sampling, ss_k=a.ss_k,
-          optimizer=a.optimizer)
+          optimizer=a.optimizer, averaged_embedding=a.averaged_embedding)
 
 
 if __name__ == "__main__":
