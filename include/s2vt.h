@@ -69,7 +69,7 @@ typedef struct s2vt_dims {
  *     bf16 / split scratch do not change.  A residual model's sampler always takes per-step launches (no persistent decode loop).
  *   Accepted, same behaviour (no logits there, or they only read what the calls above leave): s2vt_frame_embed_fwd / _bwd, s2vt_bptt_dvideo,
  *     s2vt_split_grad_dlogits_planes, s2vt_softmax_nll_fwd_bwd_split, s2vt_bf16_grad_workspace_bytes, s2vt_split_grad_workspace_bytes.
- *   Every other entry point that takes s2vt_dims (s2vt_sample_mix, s2vt_scheduled_fwd, s2vt_averaged_fwd / _bptt_bwd, s2vt_create and the handle calls, every s2vt_attn_*)
+ *   Every other entry point that takes s2vt_dims (s2vt_sample_mix, s2vt_scheduled_fwd, s2vt_averaged_fwd / _bptt_bwd, s2vt_topk_feed_fwd / _bptt_bwd / _decode, s2vt_create and the handle calls, every s2vt_attn_*)
  *     returns S2VT_E_BADARG (size functions: 0) when the bit is set.  Any other bit: S2VT_E_BADARG / 0 everywhere. */
 #define S2VT_MODEL_RESIDUAL 1
 
@@ -435,6 +435,65 @@ int s2vt_averaged_bptt_bwd(const s2vt_dims* d, const s2vt_params* p, const s2vt_
                            size_t workspace_bytes, const void* scratch, size_t scratch_bytes, int32_t precision, void* grad_ws, size_t grad_ws_bytes,
                            s2vt_stream stream);
 
+/* ---- top-k score-weighted embedding unroll: build_model / build_generator of sum_generate_words_tf_s2vt.py:101-275 ----------------------
+ * s2vt_averaged_fwd with another operand.  Step 0 feeds <bos> = 1 (:158-161); at step t >= 1 row n of LSTM2 is fed (:163-174,208-210)
+ *   scores, ids = top_k(logits[t - 1][n], k),   w = scores / reduce_sum(scores)   (raw logits, no softmax),   x[n] = sum_j w[j] Wemb[ids[j]]
+ * with top_k's order (value descending, index ascending on exact ties: s2vt_vocab_topk's), the sum of the scores added in ascending j, w
+ * an IEEE division, and x the chain ((((0 + w0 e0) + w1 e1) + ...) in ascending j, each product and each addition rounded on its own (no
+ * FMA).  A sum of 0 is the script's own 0/0 and is not repaired.  Quirk TK1: the coin of :156 is compared with a Python int (:165), which is
+ * always False, so the ground-truth branch is never built -- there is no coin and no p_gt here, and the caption enters as labels only.
+ * Both cells are dropout-wrapped (keep, seed, video_id, sample_id as s2vt_teacher_forced_fwd, the ids required whatever keep says).  The
+ * mask is the FED placeholder (:106,204), not a running mask.  Loss (:212-218): loss_weight * sum xent * mask / sum(mask) + weight decay.
+ * 1 <= k <= 8, k <= n_words (the script's k is 5).
+ * Outputs as s2vt_averaged_fwd: logits_out [Tc*N, V] time-major; generated [N, Tc] int32 = ids[.][0]; coef_tm [Tc*N] = loss_weight * mask
+ * and target_tm [Tc*N]; *mask_sum, *mask_sum_copy (each may be NULL).  One fused cell launch, one pick launch and one mix launch per step,
+ * no host round trip.
+ * workspace: the training workspace (s2vt_train_workspace_bytes, unchanged).
+ * scratch: s2vt_topk_feed_scratch_bytes(d, N, k) bytes (0 on bad arguments), 256-byte aligned: the packed picks, then what the backward
+ * reads again, time-major, block t holding what step t was fed -- X [Tc*N, E] (block 0: Wemb[1] for every row), ids / w [Tc*N, k] and the
+ * raw sums S [Tc*N] (block 0: ids 1, w (1, 0, ...), S 1).
+ * Errors: S2VT_E_BADARG (a NULL pointer other than the two sums, N % B != 0, keep <= 0, k outside 1..8 or above n_words, a model bit),
+ * S2VT_E_ALIGN, S2VT_E_WORKSPACE (a short workspace or scratch), S2VT_E_CHAIN_TIMEOUT.
+ *
+ * s2vt_topk_feed_bptt_bwd: the backward of that unroll.  The ids are constants, everything else is differentiable -- no stop_gradient
+ * anywhere in :163-174 -- so the loss of step t reaches logits[t - 1] through the weights: with ds_j = dx . Wemb[ids_j] and
+ * g = sum_j w_j ds_j, dlogits[t - 1][n][ids_j] += (ds_j - g) / S, and from there embed_word_W, embed_word_b and LSTM2's earlier state.
+ * dlogits [Tc*N, V] is READ AND WRITTEN: on entry the softmax part (what s2vt_softmax_nll_fwd_bwd leaves), on return the completed
+ * gradient with respect to the logits.  dWemb[ids_j] += w_j dx (s2vt_embed_scatter_addk).  LSTM2's recurrence runs step by step (the
+ * new edge crosses its steps); fp32 products only -- the bf16 and split-bf16 product sets are not implemented for this backward -- and
+ * the whole pass only (no phases, live rows or step cuts).  Errors: as above. */
+size_t s2vt_topk_feed_scratch_bytes(const s2vt_dims* d, int32_t N, int32_t k);
+int s2vt_topk_feed_fwd(const s2vt_dims* d, const s2vt_params* p, const float* video, int32_t B, int32_t N, const int32_t* caption, const float* mask,
+                       float loss_weight, float keep, uint64_t seed, const int32_t* video_id, const int32_t* sample_id, int32_t k,
+                       float* logits_out, int32_t* generated, float* coef_tm, int32_t* target_tm, float* mask_sum, float* mask_sum_copy,
+                       void* workspace, size_t workspace_bytes, void* scratch, size_t scratch_bytes, s2vt_stream stream);
+int s2vt_topk_feed_bptt_bwd(const s2vt_dims* d, const s2vt_params* p, const s2vt_params* grads, const float* video, int32_t B, int32_t N,
+                            float* dlogits, float keep, uint64_t seed, const int32_t* video_id, const int32_t* sample_id, int32_t k,
+                            void* workspace, size_t workspace_bytes, const void* scratch, size_t scratch_bytes, s2vt_stream stream);
+/* build_generator of the same script (:221-275) for B videos: no dropout; per step the cell launch on the step's mix, the logits, then
+ * unshifted_softmax = 1: probs = exp(l) / sum exp(l) as s2vt_softmax_unshifted_argmax writes them (:255) and the emitted word
+ *   argmax(probs) (:257); 0: the emitted word is the first of the top-k ids;
+ * weights_mode = 1: top_k, weights and mix from the probabilities (:259-268; needs unshifted_softmax = 1) -- the script's generator;
+ *   0: from the raw logits, the training rule.
+ * The `break` of :273 tests a tensor and never fires: Tc words per video.  ids_out [B, Tc] int32; logits_out [Tc*B, V] time-major or NULL.
+ * workspace: s2vt_topk_feed_decode_workspace_bytes(d, B, k) bytes (0 on bad arguments), 256-byte aligned.  Errors: S2VT_E_BADARG,
+ * S2VT_E_ALIGN, S2VT_E_WORKSPACE, S2VT_E_CHAIN_TIMEOUT. */
+size_t s2vt_topk_feed_decode_workspace_bytes(const s2vt_dims* d, int32_t B, int32_t k);
+int s2vt_topk_feed_decode(const s2vt_dims* d, const s2vt_params* p, const float* video, int32_t B, int32_t k, int32_t weights_mode,
+                          int32_t unshifted_softmax, int32_t* ids_out, float* logits_out, void* workspace, size_t workspace_bytes,
+                          s2vt_stream stream);
+/* The mix alone (sum_generate_words_tf_s2vt.py:166-173), on R rows.  weights_mode 0: scores = logits [R, ld >= V] (plane NULL);
+ * 1: scores = plane [R, ldp >= V] (logits unread).  Writes ids [R, k], w [R, k], score_sum [R] and x [R, ldx >= E] as described above;
+ * Wemb [V, E] contiguous.  R = 0: nothing is launched. */
+int s2vt_topk_mix_fwd(const float* logits, int32_t ld, const float* plane, int32_t ldp, int32_t weights_mode, int32_t R, int32_t V, int32_t k,
+                      const float* Wemb, int32_t E, int32_t* ids, float* w, float* score_sum, float* x, int32_t ldx, s2vt_stream stream);
+/* Its backward, the ids constants: dscores[r][ids[r][j]] += (ds_j - g) / score_sum[r] (ds_j = dx[r] . Wemb[ids[r][j]], g = sum_j w_j ds_j;
+ * no other column of dscores [R, lds >= V] is written) and, dO non-NULL, dO[r][0:H] += sum_j that * Wout[:, ids[r][j]] (Wout [H, V],
+ * dO [R, ldo >= H]).  dx [R, lddx >= E]; the ids must lie inside Wemb. */
+int s2vt_topk_mix_bwd(const float* dx, int32_t lddx, const int32_t* ids, const float* w, const float* score_sum, const float* Wemb, int32_t E,
+                      const float* Wout, int32_t V, int32_t H, int32_t k, int32_t R, float* dscores, int32_t lds, float* dO, int32_t ldo,
+                      s2vt_stream stream);
+
 /* Same, inside a REINFORCE step: LSTM1's state trajectory depends only on the frames and the weights, and the
  * sampler pass of the step (s2vt_sample / s2vt_encode_fwd on the SAME video block, SAME weights) has just
  * computed it.  Pass that call's workspace (and its row count R = (K + with_greedy) * B) and the trajectory and
@@ -671,6 +730,11 @@ int s2vt_embed_scatter_add(const float* dE, int32_t ld, const int32_t* idx, int3
  * the ids must lie inside dWemb.  R = 0: nothing is launched. */
 int s2vt_embed_scatter_add2(const float* dE, int32_t ld, const int32_t* idx_a, const int32_t* idx_b, float scale, int32_t R, int32_t E,
                             float* dWemb, s2vt_stream stream);
+/* dWemb[ids[r][j], :] += w[r][j] * dE[r, :] for j < k -- the gradient of a weighted sum of k lookups with the weights held fixed
+ * (sum_generate_words_tf_s2vt.py:171-173); ids, w [R, k], 1 <= k <= 8; equal ids in a row each receive their addition.  dE [R, ld >= E];
+ * the ids must lie inside dWemb.  R = 0: nothing is launched. */
+int s2vt_embed_scatter_addk(const float* dE, int32_t ld, const int32_t* ids, const float* w, int32_t k, int32_t R, int32_t E, float* dWemb,
+                            s2vt_stream stream);
 
 /* ---- host glue of the REINFORCE step, on the device (decode_captions_masks, cider_evaluation.py:145-172; the objective's
  * coefficients, reinforcement_multisampling_tf_s2vt.py:641-646).

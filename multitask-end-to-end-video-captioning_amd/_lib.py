@@ -249,6 +249,15 @@ SIGNATURES = {
                                     _vp]),
     "s2vt_averaged_bptt_bwd": (C.c_int, [_DP, _PP, _PP, _vp, _i32, _i32, _vp, _f32, _u64, _vp, _vp, _vp, _sz, _vp, _sz, _i32, _vp, _sz, _vp]),
     "s2vt_embed_scatter_add2": (C.c_int, [_vp, _i32, _vp, _vp, _f32, _i32, _i32, _vp, _vp]),
+    "s2vt_topk_feed_scratch_bytes": (_sz, [_DP, _i32, _i32]),
+    "s2vt_topk_feed_fwd": (C.c_int, [_DP, _PP, _vp, _i32, _i32, _vp, _vp, _f32, _f32, _u64, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
+                                     _vp, _sz, _vp]),
+    "s2vt_topk_feed_bptt_bwd": (C.c_int, [_DP, _PP, _PP, _vp, _i32, _i32, _vp, _f32, _u64, _vp, _vp, _i32, _vp, _sz, _vp, _sz, _vp]),
+    "s2vt_topk_feed_decode_workspace_bytes": (_sz, [_DP, _i32, _i32]),
+    "s2vt_topk_feed_decode": (C.c_int, [_DP, _PP, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "s2vt_topk_mix_fwd": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp]),
+    "s2vt_topk_mix_bwd": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _vp]),
+    "s2vt_embed_scatter_addk": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp]),
     "s2vt_sgd_guarded": (C.c_int, [_vp, _vp, _i64, _vp, _f32, _f32, _i64, _vp, _vp]),
     "s2vt_adam_tf_guarded": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _f32, _f32, _i64, _f32, _f32, _f32, _vp, _vp]),
     "s2vt_allreduce_grads": (C.c_int, [_vp, _i64, _vp, _vp]),

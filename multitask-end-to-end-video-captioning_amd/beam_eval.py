@@ -2,13 +2,19 @@
 
     python -m s2vt_amd.beam_eval --checkpoint CKPT --test-sents SENTS --test-feats FEATS --vocab VOCAB \
         [--beam 3] [--lnf 0.0] [--batch-size 64] [--n-caption-lstm-step 35] [--out captions.txt] [--model auto|s2vt|attention|bidirectional]
+        [--topk-feed [--topk-k 5]]
 
 The checkpoint is loaded with optimistic_restore (an .npz dump or a TensorFlow checkpoint); the model's dimensions are read from
 its variables, Tv from the feature file.  The model class is read off the variable names too: a checkpoint that holds embed_att_Wa
 is the temporal-attention captioner (original_attention.py:64-86), one that holds the forward LSTM1 cell of bidirection_tf_s2vt.py's
 static_bidirectional_rnn (bidirection.TF_NAMES["lstm1_fw_W"]) the bidirectional captioner -- an XE or a REINFORCE checkpoint of it --, any
 other the S2VT model; --model overrides the detection.  Writes one `video_id<TAB>sentence` line per test video, as the reference does (the
-caption cut at its first <eos>, <bos> / <eos> dropped), and prints the mean CIDEr-D against the test set's references."""
+caption cut at its first <eos>, <bos> / <eos> dropped), and prints the mean CIDEr-D against the test set's references.
+
+--topk-feed decodes an S2VT checkpoint greedily by build_generator of sum_generate_words_tf_s2vt.py:221-275 instead: LSTM2 is fed the
+weighted sum of the embeddings of its own top-k words, weights and emitted word from the unshifted softmax (Video_Caption_Generator.
+generate_topk_feed) -- what a checkpoint of train_xe --topk-feed was trained to be decoded with.  Beam search over that soft feed is not
+implemented: --beam and --lnf are not read."""
 from __future__ import annotations
 
 import argparse
@@ -72,11 +78,15 @@ def main(argv=None):
     ap.add_argument("--model", choices=("auto", "s2vt", "attention", "bidirectional"), default="auto")
     ap.add_argument("--residual", action="store_true", help="decode as the residual captioner of residual_tf_s2vt.py (an S2VT checkpoint "
                     "does not say which script trained it)")
+    ap.add_argument("--topk-feed", action="store_true", help="greedy decoding by the generator of sum_generate_words_tf_s2vt.py (S2VT checkpoints)")
+    ap.add_argument("--topk-k", type=int, default=5, metavar="K", help="with --topk-feed: the number of words in the mix, 1..8")
     a = ap.parse_args(argv)
+    if a.topk_feed and (a.residual or a.model not in ("auto", "s2vt") or not 1 <= a.topk_k <= 8):
+        ap.error("--topk-feed decodes a plain S2VT checkpoint with 1 <= --topk-k <= 8")
 
     from . import hostglue, reward, tfckpt
     from . import model as M
-    from .train_common import Corpus, beam_eval, optimistic_restore
+    from .train_common import Corpus, beam_eval, greedy_eval, optimistic_restore
     corpus = Corpus(a.test_sents, a.test_feats, vocabulary_file=a.vocab)
     wordtoix, ixtoword = hostglue.preProBuildWordVocab(corpus.vocabulary)
     raw = tfckpt.read_checkpoint(a.checkpoint)
@@ -88,6 +98,8 @@ def main(argv=None):
     Tv = corpus.features.features.shape[1]
     Tc = a.n_caption_lstm_step
     kind = model_kind(raw, a.model)
+    if a.topk_feed and kind != "s2vt":
+        raise SystemExit(f"--topk-feed is an S2VT generator; this checkpoint is a {kind} model")
     if kind == "attention":
         from . import attention as A
         if a.residual:
@@ -102,6 +114,11 @@ def main(argv=None):
         model = M.Video_Caption_Generator(D, V, E, H, a.batch_size, Tv + Tc, Tv, Tc, bias_init_vector=None, residual=a.residual)
     optimistic_restore(model, a.checkpoint)
     scorer = reward.CiderD(corpus.index.refs_by_video(), wordtoix)
+    if a.topk_feed:
+        decoded, cider = greedy_eval(model, corpus, ixtoword, scorer, a.batch_size, decode=lambda f: model.generate_topk_feed(f, k=a.topk_k))
+        write_captions(a.out, [(v, caption_text([wordtoix[w] for w in decoded[v].split()], ixtoword)) for v in corpus.index.video_ids])
+        print(f"top-{a.topk_k} feed, greedy: {len(decoded)} videos, mean CIDEr-D {cider:.4f} -> {a.out}")
+        return 0
     decoded, cider = beam_eval(model, corpus, ixtoword, scorer, a.batch_size, a.beam, a.lnf)
     write_captions(a.out, [(v, caption_text([wordtoix[w] for w in decoded[v].split()], ixtoword)) for v in corpus.index.video_ids])
     print(f"beam {a.beam} lnf {a.lnf}: {len(decoded)} videos, mean CIDEr-D {cider:.4f} -> {a.out}")

@@ -9,6 +9,7 @@
 #include "api_util.h"
 #include "detmath.h"
 #include "rowreduce.h"
+#include "topk_select.h"
 
 using namespace s2vt_api;
 
@@ -26,22 +27,6 @@ namespace s2vt {
 // heads: xor-butterfly inside each wave, the four wave winners through LDS, the owning thread pops its head.  No atomics.
 // Inputs are finite logits: NaN is out of scope (a NaN never enters a list and poisons lse).
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ bool tk_better(float a, int ia, float b, int ib) { return a > b || (a == b && ia < ib); }
-
-template <int KMAX>
-__device__ __forceinline__ void tk_insert(float (&tv)[KMAX], int (&ti)[KMAX], float v, int i)
-{
-    if (!tk_better(v, i, tv[KMAX - 1], ti[KMAX - 1])) return;
-    tv[KMAX - 1] = v; ti[KMAX - 1] = i;
-#pragma unroll
-    for (int j = KMAX - 1; j > 0; --j) {
-        if (tk_better(tv[j], ti[j], tv[j - 1], ti[j - 1])) {
-            const float fv = tv[j]; tv[j] = tv[j - 1]; tv[j - 1] = fv;
-            const int fi = ti[j]; ti[j] = ti[j - 1]; ti[j - 1] = fi;
-        }
-    }
-}
-
 template <int KMAX>
 __global__ __launch_bounds__(256) void vocab_topk_kernel(const float* logits, int ld, int V, int k, int32_t* ids, float* logp)
 {

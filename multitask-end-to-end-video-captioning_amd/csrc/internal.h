@@ -101,6 +101,21 @@ hipError_t launch_gather_i32(const int32_t* src, const int32_t* idx, int R, int3
 hipError_t launch_scatter_add_rows(const float* dE, int ld, const int32_t* idx, int R, int E, float* dW, int ldw,
                                    hipStream_t st);
 hipError_t launch_transpose(const float* in, int ldi, float* out, int ldo, int R, int Cc, hipStream_t st);
+// ---- top-k score-weighted embedding feedback (topk_feed.hip; sum_generate_words_tf_s2vt.py:163-174)
+constexpr int kTopkFeedMax = 8;                        // the largest k (the script's is 5)
+// what the row's first thread writes beside the mix inside an unroll: generated[n][t] (emit[n] when given -- the generator's argmax of the
+// probabilities -- else the first id), and, with a caption, loss_weight * mask[n][t] and the clamped target
+struct TopkStep {
+    const int32_t* caption; const float* mask; int N, Tc, t; float loss_weight;
+    int32_t* generated; float* coef_tm; int32_t* target_tm; const int32_t* emit;
+};
+// ids / wts / S / x may be NULL together (the step's bookkeeping only); step may be NULL
+hipError_t launch_topk_mix_fwd(const float* scores, int ld, int R, int V, int k, const float* Wemb, int E, int32_t* ids, float* wts, float* S,
+                               float* x, int ldx, const TopkStep* step, hipStream_t st);
+hipError_t launch_topk_mix_bwd(const float* dx, int lddx, const int32_t* ids, const float* wts, const float* S, const float* Wemb, int E,
+                               const float* Wout, int V, int H, int k, int R, float* dscores, int lds, float* dO, int ldo, hipStream_t st);
+hipError_t launch_scatter_add_rowsk(const float* dE, int ld, const int32_t* ids, const float* wts, int k, int R, int E, float* dW, int ldw,
+                                    hipStream_t st);
 hipError_t launch_grad_finalize(float* g, const float* theta, int64_t n, const float* gscale, float wd, float* sumsq,
                                 hipStream_t st);
 // fault: optional device word -- nonzero makes the launch a no-op (a persistent recurrence timed out upstream: the

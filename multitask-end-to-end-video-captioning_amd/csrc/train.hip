@@ -4,6 +4,7 @@
 // global-norm clip + TF-form Adam.
 #include <hip/hip_runtime.h>
 
+#include <functional>
 #include <mutex>
 
 #include <cstdlib>
@@ -273,10 +274,13 @@ struct BwdScratch { float* slab; float* dc; float* bimg; float* bex; unsigned* b
 hipError_t lstm_recurrence_bwd(const float* W, int kw0, const float* gates, const float* C, const float* dext, size_t dext_tstride,
                                int ld_ext, int dext_t0, float* dZ, int M, int H, int T, float keep, uint64_t seed, uint32_t drop_code0,
                                const int32_t* video_id, const int32_t* sample_id, const BwdScratch& sc, int persistent, hipStream_t st,
-                               const int32_t* perm = nullptr, const int32_t* nlive = nullptr, bool split = false)
+                               const int32_t* perm = nullptr, const int32_t* nlive = nullptr, bool split = false,
+                               const std::function<hipError_t(int)>* between = nullptr)
 {
+    // between: a graph with an edge from step t's dZ to step t - 1's upstream gradient (the top-k feed: dZ2[t] -> dx[t] -> dext[t - 1]).
+    // The persistent chain cannot take such an edge, so the per-step form runs, and (*between)(t) is called behind step t's launches.
     const size_t MH = (size_t)M * H;
-    const bool can = sc.bimg && sc.bex && sc.bsync && bwd_chain_eligible(M, H) && !(reinterpret_cast<uintptr_t>(W) & 15);
+    const bool can = !between && sc.bimg && sc.bex && sc.bsync && bwd_chain_eligible(M, H) && !(reinterpret_cast<uintptr_t>(W) & 15);
     if (persistent == 1 && !can) return hipErrorInvalidValue;
     if (persistent == 1 || (persistent == -1 && can && bwd_chain_auto(M, H))) {
         BwdChainLaunch a;
@@ -301,6 +305,7 @@ hipError_t lstm_recurrence_bwd(const float* W, int kw0, const float* gates, cons
         if (t > 0) {
             e = nn_bwd(dZ + (size_t)t * 4 * MH, 4 * H, W + (size_t)kw0 * 4 * H, 4 * H, sc.slab, H, M, H, 4 * H, sp.splits, MH, st);
             if (e != hipSuccess) return e;
+            if (between && (e = (*between)(t)) != hipSuccess) return e;
         }
     }
     return hipSuccess;
@@ -627,6 +632,101 @@ struct AvgDecode {
         hipLaunchKernelGGL(avg_step_kernel, dim3(elem_blocks()), dim3(256), 0, st, picks(t), kPickStride, caption, mask, p->Wemb, N, Tc, t, V, E,
                            loss_weight, generated, coef_tm, target_tm, x.ida, x.idb, x.xbar);
         return hipGetLastError();
+    }
+    hipError_t close(float* mask_sum, float* mask_sum_copy)
+    {
+        hipLaunchKernelGGL(sched_mask_sum_kernel, dim3(1), dim3(256), 0, st, mask, N * Tc, mask_sum, mask_sum_copy);
+        return hipGetLastError();
+    }
+};
+
+// ---- top-k score-weighted embeddings (sum_generate_words_tf_s2vt.py:101-219): the averaged unroll with another operand.  Step t >= 1
+// feeds LSTM2 x = sum_j w_j Wemb[id_j] over the top-k logits of step t - 1, w = those logits over their sum (:163-174,208-210); the coin
+// of :156,165 never selects the ground truth (quirk TK1), so the caption enters as labels only.  Every step's operand is a dense block
+// X[t] [N, E]; ids, weights and the raw sums are kept for the backward, which differentiates the weights.
+
+// before step 0, one thread per element of the largest of [N, Tc], [N, E] and [N, k]: the ground truth as the workspace's time-major
+// targets and teacher-forced previous words, the all-argmax sample ids of the pick launches, and block 0 of the scratch -- Wemb[1] for
+// every row (:158-161), written as the mix (<bos>, weight 1) + (<bos>, weight 0) ... with sum 1, which is what its gradient is
+__global__ __launch_bounds__(256) void topk_open_kernel(const int32_t* caption, const float* Wemb, int N, int Tc, int V, int E, int k, int32_t* prev,
+                                                        int32_t* tgt, int32_t* argmax_sid, int32_t* ids, float* wts, float* sums, float* X)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const int32_t bos = clamp_word(1, V);
+    if (i < (size_t)N * Tc) {
+        const int t = (int)(i / N), n = (int)(i - (size_t)t * N);
+        tgt[i] = clamp_word(caption[(size_t)n * Tc + t], V);
+        prev[i] = t == 0 ? bos : clamp_word(caption[(size_t)n * Tc + t - 1], V);
+        if (t == 0) { argmax_sid[n] = -1; sums[n] = 1.0f; }
+    }
+    if (i < (size_t)N * k) { ids[i] = bos; wts[i] = i % k == 0 ? 1.0f : 0.0f; }
+    if (i < (size_t)N * E) X[i] = Wemb[(size_t)bos * E + i % E];
+}
+
+// The scratch of the top-k unroll beside the training workspace: every step's packed picks (zeroed up front), the pick launches' sample
+// ids, and what the backward reads again -- X [Tc N, E], ids / w [Tc N, k] and S [Tc N], time-major, block t the mix step t was fed
+struct TopkScratch { unsigned long long* packed; int32_t* argmax_sid; float* X; int32_t* ids; float *wts, *sums; };
+size_t carve_topk(Carver& c, const s2vt_dims* d, int N, int k, TopkScratch* out)
+{
+    const size_t R = (size_t)d->n_caption_lstm_step * N;
+    TopkScratch s;
+    s.packed = c.take<unsigned long long>(R * kPickStride);
+    s.argmax_sid = c.take<int32_t>(N);
+    s.X = c.take<float>(R * d->word_dim);
+    s.ids = c.take<int32_t>(R * k);
+    s.wts = c.take<float>(R * k);
+    s.sums = c.take<float>(R);
+    if (out) *out = s;
+    return c.off;
+}
+bool topk_k_ok(const s2vt_dims* d, int k) { return k >= 1 && k <= kTopkFeedMax && k <= d->n_words; }
+
+// The decoding stage of the top-k unroll: AvgDecode's stages, the step kernel replaced by the top-k mix of the step's logits
+struct TopkDecode {
+    const s2vt_params* p; const TrainWs& w; const TopkScratch& x;
+    int N, H, E, V, Tv, Tc, k; float keep; NoiseIds ids; hipStream_t st;
+    const int32_t* caption; const float* mask; float loss_weight;
+    float* logits; int32_t* generated; float* coef_tm; int32_t* target_tm;
+    size_t NH;
+
+    unsigned long long* picks(int t) const { return x.packed + (size_t)t * N * kPickStride; }
+
+    hipError_t open()
+    {
+        ZeroList z;
+        z.add(x.packed, (size_t)Tc * N * kPickStride * 8);
+        HIP_CHECK(launch_zero_regions(z, st));
+        const int widest = Tc > E ? (Tc > k ? Tc : k) : (E > k ? E : k);
+        const size_t n = (size_t)N * widest;
+        hipLaunchKernelGGL(topk_open_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, caption, p->Wemb, N, Tc, V, E, k, w.prev, w.tgt,
+                           x.argmax_sid, x.ids, x.wts, x.sums, x.X);
+        return hipGetLastError();
+    }
+    hipError_t decode_partials()
+    {
+        ASeg so = make_seg(w.O1 + (size_t)Tv * NH, H, H, 0);
+        return store_call(&so, 1, p->lstm2_W, 4 * H, nullptr, w.G2 + (size_t)Tv * 4 * NH, 4 * H, Tc * N, 4 * H, 0, -1, st);
+    }
+    hipError_t encode()
+    {
+        return lstm_recurrence(p->lstm2_W, H + E, p->lstm2_b, w.G2, (size_t)4 * NH, 4 * H, Tv, w.C2, w.H2, NH, w.G2, (size_t)4 * NH, w.O2, NH, N, H,
+                               Tv, keep, ids, 512u, w.chain_abuf, w.chain_sync, st);
+    }
+    hipError_t step(int t)
+    {
+        const int u = Tv + t;
+        float* const g2 = w.G2 + (size_t)u * 4 * NH;
+        ASeg s2[2] = {make_seg(x.X + (size_t)t * N * E, E, E, H), make_seg(w.H2 + (size_t)u * NH, H, H, H + E)};
+        HIP_CHECK(lstm_call(s2, 2, p->lstm2_W, p->lstm2_b, w.C2 + (size_t)u * NH, 0, w.C2 + (size_t)(u + 1) * NH, w.H2 + (size_t)(u + 1) * NH,
+                            w.O2 + (size_t)u * NH, g2, N, H, keep, ids, 512u + (uint32_t)u, -1, st, g2, 4 * H, 0));
+        const NoiseIds argmax{ids.video_id, x.argmax_sid, 0};
+        float* const lt = logits + (size_t)t * N * V;
+        HIP_CHECK(pick_call(w.O2 + (size_t)u * NH, H, p->embed_word_W, p->embed_word_b, N, H, V, argmax, t, picks(t), lt, -1, st, kPickStride));
+        const TopkStep ts{caption, mask, N, Tc, t, loss_weight, generated, coef_tm, target_tm, nullptr};
+        const size_t nx = (size_t)(t + 1) * N;                 // (the last step forms no mix: its bookkeeping only)
+        const bool more = t + 1 < Tc;
+        return launch_topk_mix_fwd(lt, V, N, V, k, p->Wemb, E, more ? x.ids + nx * k : nullptr, more ? x.wts + nx * k : nullptr,
+                                   more ? x.sums + nx : nullptr, more ? x.X + nx * E : nullptr, E, &ts, st);
     }
     hipError_t close(float* mask_sum, float* mask_sum_copy)
     {
@@ -1000,6 +1100,47 @@ int s2vt_averaged_fwd(const s2vt_dims* d, const s2vt_params* p, const float* vid
     return S2VT_OK;
 }
 
+size_t s2vt_topk_feed_scratch_bytes(const s2vt_dims* d, int32_t N, int32_t k)
+{
+    if (!dims_ok(d) || N <= 0 || !topk_k_ok(d, k)) return 0;
+    Carver c(nullptr, 0);
+    return carve_topk(c, d, N, k, nullptr);
+}
+
+int s2vt_topk_feed_fwd(const s2vt_dims* d, const s2vt_params* p, const float* video, int32_t B, int32_t N, const int32_t* caption, const float* mask,
+                       float loss_weight, float keep, uint64_t seed, const int32_t* video_id, const int32_t* sample_id, int32_t k,
+                       float* logits_out, int32_t* generated, float* coef_tm, int32_t* target_tm, float* mask_sum, float* mask_sum_copy,
+                       void* workspace, size_t workspace_bytes, void* scratch, size_t scratch_bytes, s2vt_stream stream)
+{
+    if (!dims_ok(d) || !params_ok(p) || !video || !caption || !mask || !video_id || !sample_id || !logits_out || !generated || !coef_tm ||
+        !target_tm || !workspace || !scratch || B <= 0 || N <= 0 || N % B || !topk_k_ok(d, k))
+        return S2VT_E_BADARG;
+    if (!(keep > 0.0f)) return S2VT_E_BADARG;                                                  // (a NaN fails the comparison)
+    if ((reinterpret_cast<uintptr_t>(workspace) | reinterpret_cast<uintptr_t>(scratch)) & 255u) return S2VT_E_ALIGN;
+    if (chain_fault()) return S2VT_E_CHAIN_TIMEOUT;
+    const int H = d->lstm_dim, E = d->word_dim, V = d->n_words, Tv = d->n_video_lstm_step, Tc = d->n_caption_lstm_step;
+    Carver c(workspace, workspace_bytes);
+    TrainWs w;
+    carve_train(c, d, B, N, &w);
+    Carver cs(scratch, scratch_bytes);
+    TopkScratch x;
+    carve_topk(cs, d, N, k, &x);
+    if (!c.ok() || !cs.ok()) return S2VT_E_WORKSPACE;
+    hipStream_t st = S(stream);
+    TopkDecode s{p, w, x, N, H, E, V, Tv, Tc, k, keep, NoiseIds{video_id, sample_id, seed}, st, caption, mask, loss_weight,
+                 logits_out, generated, coef_tm, target_tm, (size_t)N * H};
+    HIP_TRY(s.open());
+    {
+        const int rc = unroll_front(d, p, video, B, N, Tv + Tc, keep, seed, video_id, sample_id, w, nullptr, 0, 0, stream);
+        if (rc != S2VT_OK) return rc;
+    }
+    HIP_TRY(s.decode_partials());
+    HIP_TRY(s.encode());
+    for (int t = 0; t < Tc; ++t) HIP_TRY(s.step(t));
+    HIP_TRY(s.close(mask_sum, mask_sum_copy));
+    return S2VT_OK;
+}
+
 int s2vt_caption_mask(const int32_t* ids, int32_t N, int32_t Tc, float* mask, int32_t* target_tm, float* mask_sum, float* mask_sum_copy, s2vt_stream stream)
 {
     if (!ids || N <= 0 || Tc <= 0) return S2VT_E_BADARG;
@@ -1165,6 +1306,8 @@ struct BpttBwd {
     // (emb_idx NULL: row r itself).  (Wemb, prev, V) in every teacher-forced backward; (Xbar, none, Tc N) in the averaged one, whose
     // operand is no row of Wemb -- there emb_ida / emb_idb are the two rows of Wemb each operand row is the mean of (NULL otherwise).
     const float* emb_tab; const int32_t* emb_idx; int emb_rows; const int32_t *emb_ida, *emb_idb;
+    // (the top-k unroll: each operand row is sum_j emb_wk[r][j] Wemb[emb_idk[r][j]] over emb_k ids -- NULL / 0 otherwise)
+    const int32_t* emb_idk; const float* emb_wk; int emb_k;
     bool bf16, split, fused;             // bf16: either bf16 mode; fused: the split mode without transposed operands (carve_bf16)
     hipStream_t st, sd, sv;              // the caller's; LSTM2's weight gradients' and the deferred dWout's; the vocab stage's dWout's
     bool gate1, gate2;                   // gated overlap beside LSTM1's / LSTM2's recurrence
@@ -1215,8 +1358,11 @@ struct BpttBwd {
     }
     // embedding rows (gradient of tf.nn.embedding_lookup): scatter-add of the embed slice of dX2
     // (averaged: half of each row's gradient into either row of its id pair, average_generate_words_tf_s2vt.py:131-133)
+    // (top-k: each row's gradient, weighed, into its k rows, sum_generate_words_tf_s2vt.py:171-173)
     hipError_t wemb_scatter_add() const
     {
+        if (emb_idk)
+            return launch_scatter_add_rowsk(w.dX2 + (size_t)Tv * N * (H + E) + H, H + E, emb_idk, emb_wk, emb_k, Tc * N, E, grads->Wemb, E, st);
         if (emb_ida)
             return launch_scatter_add_rows2(w.dX2 + (size_t)Tv * N * (H + E) + H, H + E, emb_ida, emb_idb, 0.5f, Tc * N, E, grads->Wemb, E, st);
         if (live_rows) return launch_scatter_add_rows(w.dX2p + H, H + E, w.prevp, n_live, E, grads->Wemb, E, st);
@@ -1444,6 +1590,7 @@ static int bptt_bwd_body(const s2vt_dims* d, const s2vt_params* p, const s2vt_pa
     x.w = w; x.bw = bw; x.p = p; x.grads = grads; x.video = video; x.dlogits = dlogits; x.live_rows = live_rows; x.n_live = n_live;
     x.emb_tab = avg ? avg->xbar : p->Wemb; x.emb_idx = avg ? nullptr : w.prev; x.emb_rows = avg ? Tc * N : V;
     x.emb_ida = avg ? avg->ida : nullptr; x.emb_idb = avg ? avg->idb : nullptr;
+    x.emb_idk = nullptr; x.emb_wk = nullptr; x.emb_k = 0;
     x.keep = keep; x.seed = seed; x.video_id = video_id; x.sample_id = sample_id; x.bf16 = bf16; x.split = split; x.fused = fused;
     x.st = st; x.sd = sd; x.sv = (phase == kAll && ss.ok && ss.mode == 1) ? sd : st;   // (phase 1: its gradients must be final on the caller's stream)
     // The side stream and its events are ONE per process: two host threads driving distinct workspaces must not interleave their
@@ -1572,6 +1719,67 @@ int s2vt_averaged_bptt_bwd(const s2vt_dims* d, const s2vt_params* p, const s2vt_
     const int mode = precision == 2 ? split_grad_mode(N) : precision == 1 ? kGradBf16 : kGradFp32;
     return bptt_bwd_body(d, p, grads, video, B, N, dlogits, d->n_caption_lstm_step, nullptr, 0, keep, seed, video_id, sample_id, workspace,
                          workspace_bytes, kAll, mode, grad_ws, grad_ws_bytes, stream, &x);
+}
+
+// The backward of the top-k unroll.  Its graph has a second recurrent edge, dZ2[t] -> dx[t] -> dlogits[t - 1] -> dO2[t - 1]: the vocabulary
+// data gradient runs once up front on the softmax part of dlogits (the map is linear, the mix's part is added to dO2 step by step), LSTM2's
+// recurrence is unrolled in its per-step form with the mix backward between steps, and dWout / the bias gradient run once behind the
+// loop on the completed dlogits.  From there on, the stages of BpttBwd with the operand (X, none, Tc N).  One stream, fp32 products.
+int s2vt_topk_feed_bptt_bwd(const s2vt_dims* d, const s2vt_params* p, const s2vt_params* grads, const float* video, int32_t B, int32_t N,
+                            float* dlogits, float keep, uint64_t seed, const int32_t* video_id, const int32_t* sample_id, int32_t k,
+                            void* workspace, size_t workspace_bytes, const void* scratch, size_t scratch_bytes, s2vt_stream stream)
+{
+    if (!dims_ok(d) || !params_ok(p) || !params_ok(grads) || !video || !dlogits || !video_id || !sample_id || !workspace || !scratch || B <= 0 ||
+        N <= 0 || N % B || !topk_k_ok(d, k))
+        return S2VT_E_BADARG;
+    if (!(keep > 0.0f)) return S2VT_E_BADARG;                                                  // (a NaN fails the comparison)
+    if ((reinterpret_cast<uintptr_t>(workspace) | reinterpret_cast<uintptr_t>(scratch)) & 255u) return S2VT_E_ALIGN;
+    if (chain_fault()) return S2VT_E_CHAIN_TIMEOUT;
+    const int H = d->lstm_dim, E = d->word_dim, V = d->n_words, Tv = d->n_video_lstm_step, Tc = d->n_caption_lstm_step, T = Tv + Tc;
+    Carver c(workspace, workspace_bytes);
+    TrainWs w;
+    carve_train(c, d, B, N, &w);
+    Carver cs(const_cast<void*>(scratch), scratch_bytes);
+    TopkScratch ts;
+    carve_topk(cs, d, N, k, &ts);
+    if (!c.ok() || !cs.ok()) return S2VT_E_WORKSPACE;
+    hipStream_t st = S(stream);
+    const size_t NH = (size_t)N * H;
+    SideStream one_stream;                                   // (ok = false: everything on the caller's stream)
+    BpttBwd x{one_stream};
+    x.gate1 = x.gate2 = false;
+    x.H = H; x.E = E; x.V = V; x.D = d->dim_image; x.Tv = Tv; x.Tc = Tc; x.T = T; x.B = B; x.N = N;
+    x.K4 = bf16_pad(4 * H); x.Re = Tv * N; x.Rd = Tc * N; x.NH = NH;
+    x.w = w; x.bw = Bf16Ws{}; x.p = p; x.grads = grads; x.video = video; x.dlogits = dlogits; x.live_rows = nullptr; x.n_live = 0;
+    x.emb_tab = ts.X; x.emb_idx = nullptr; x.emb_rows = Tc * N; x.emb_ida = x.emb_idb = nullptr;
+    x.emb_idk = ts.ids; x.emb_wk = ts.wts; x.emb_k = k;
+    x.keep = keep; x.seed = seed; x.video_id = video_id; x.sample_id = sample_id; x.bf16 = x.split = x.fused = false;
+    x.st = x.sd = x.sv = st;
+    const BwdScratch sc{w.slab, w.dc, w.bimg, w.bex, w.bsync};
+
+    // ---- dO2 = dlogits Wout^T of the softmax part; dWout waits for the completed dlogits
+    TnArgs dwout;
+    HIP_TRY(x.vocab_fp32(x.Rd, w.dO2, &dwout));
+    // ---- LSTM2 back through time, step by step; behind decode step td >= 1: dx[td] = dZ2 W2[H : H + E]^T (the packed-row block of the
+    // workspace, unused in a whole pass, holds it), then the mix backward into dlogits[td - 1] and dO2[td - 1], which step td - 1 reads
+    const std::function<hipError_t(int)> between = [&](int t) -> hipError_t {
+        const int td = t - Tv;
+        if (td < 1) return hipSuccess;
+        HIP_CHECK(nn_bwd(w.dZ2 + (size_t)t * 4 * NH, 4 * H, p->lstm2_W + (size_t)H * 4 * H, 4 * H, w.dX2p, E, N, E, 4 * H, 1, 0, st));
+        const size_t r = (size_t)td * N;
+        return launch_topk_mix_bwd(w.dX2p, E, ts.ids + r * k, ts.wts + r * k, ts.sums + r, p->Wemb, E, p->embed_word_W, V, H, k, N,
+                                   dlogits + (size_t)(td - 1) * N * V, V, w.dO2 + (size_t)(td - 1) * NH, H, st);
+    };
+    HIP_TRY(lstm_recurrence_bwd(p->lstm2_W, H + E, w.G2, w.C2, w.dO2, NH, H, Tv, w.dZ2, N, H, T, keep, seed, 512u, video_id, sample_id, sc, 0, st,
+                                nullptr, nullptr, false, &between));
+    HIP_TRY(launch_gemm_tn(dwout, st));
+    HIP_TRY(x.l2_grads_fp32());
+    // ---- dX2, LSTM1 back through time on the B per-video rows, its tail (the embedding scatter takes the k weighted ids)
+    HIP_TRY(x.dx2_fp32());
+    HIP_TRY(launch_reduce_dropout(w.dX2, H + E, w.dH1, T, B, N, H, keep, seed, 256u, video_id, sample_id, st, nullptr, Tv));
+    HIP_TRY(lstm_recurrence_bwd(p->lstm1_W, E, w.G1, w.C1, w.dH1, (size_t)B * H, H, 0, w.dZ1, B, H, T, 1.0f, seed, 0u, nullptr, nullptr, sc, -1, st));
+    HIP_TRY(x.lstm1_tail_fp32());
+    return S2VT_OK;
 }
 
 int s2vt_split_grad_active(int32_t N)

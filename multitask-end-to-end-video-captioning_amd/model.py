@@ -315,7 +315,7 @@ class Video_Caption_Generator:
     dim_image (it reads mean_t(video), :375).
     `residual=True` is the architecture of residual_tf_s2vt.py: at every decode step output2 = output1 + output2 ahead of the
     vocabulary projection (:149-151, :206-208, :263-265); same variables and checkpoint layout.  The flag rides in the dims of every
-    library call; mix_sample / scheduled_update / averaged_update and their graphs are not implemented for it and raise ValueError."""
+    library call; mix_sample / scheduled_update / averaged_update / topk_feed_update and their graphs are not implemented for it and raise ValueError."""
 
     def __init__(self, dim_image, n_words, word_dim, lstm_dim, batch_size, n_lstm_steps, n_video_lstm_step,
                  n_caption_lstm_step, bias_init_vector=None, loss_weight=1, decay_value=0.00005, dropout_rate=0.9,
@@ -546,16 +546,23 @@ class Video_Caption_Generator:
             return {"sampled_captions": s.cpu().numpy().astype(np.int64)}
         return Output("sampled_captions", fn, [video]), video
 
-    def build_generator(self, beam_size=1, length_normalization_factor=0.5, unshifted_softmax=False):
+    def build_generator(self, beam_size=1, length_normalization_factor=0.5, unshifted_softmax=False, topk_feed=None):
         """B=1 greedy generator (tf_s2vt.py:169-214): (video, sentence, probs) where sentence is a
         list of Tc scalar fetches (the reference's `break` at :212 never fires).
         unshifted_softmax=True reproduces the reference's word choice to the letter: argmax of
         exp(l) / sum(exp(l)) computed in fp32 without a max shift (:208-209) -- NaN, hence <eos>, once a logit
-        reaches 88.72; the default is argmax of the logits, which is what that expression means wherever it is finite."""
+        reaches 88.72; the default is argmax of the logits, which is what that expression means wherever it is finite.
+        topk_feed=k: build_generator of sum_generate_words_tf_s2vt.py:221-275 instead -- LSTM2 is fed the weighted sum of its own top-k
+        words' embeddings, weights and the emitted word from the unshifted softmax (generate_topk_feed); greedy only."""
         video = self._video_placeholder(1)
         Tc = self.n_caption_lstm_step
+        if topk_feed is not None and beam_size > 1:
+            raise ValueError("build_generator(topk_feed=k) decodes greedily: beam search over a soft feed is not implemented")
 
         def fn(v):
+            if topk_feed is not None:
+                ids = self.generate_topk_feed(v, k=topk_feed).cpu().numpy().astype(np.int64)[0]
+                return {f"word_{t}": ids[t] for t in range(Tc)}
             v = self._features(v)
             if beam_size > 1:                    # final_beam_search.py:226-294 (B = 1, TopN beams)
                 from .beam_generator import BeamSearchGenerator
@@ -1147,6 +1154,127 @@ class Video_Caption_Generator:
         provides.update({o: o.name for o in graph["outputs"]})
         return Output("train_op", fn, graph["inputs"], provides=provides)
 
+    def topk_feed_update(self, video, caption, caption_mask, k=5, lr=1e-3, clip_norm=10.0, clip="per_variable", optimizer="sgd", video_base=0,
+                         keep=None):
+        """build_model + train_op of sum_generate_words_tf_s2vt.py:101-219,429-435: the unroll decodes, and at step t >= 1 LSTM2 is fed
+        sum_j w_j Wemb[id_j] over the model's own top-k words of step t - 1, the weights being those k raw logits over their sum
+        (:163-174,208-210); step 0 feeds <bos>.  The ids are the only constants: the loss of step t reaches logits[t - 1] through the
+        weights, and from there embed_word_W, embed_word_b and LSTM2's earlier state (ops.topk_feed_bptt_bwd).  The script's coin never
+        selects the ground truth (:165 compares a tensor with an int), so the caption enters as labels only -- there is no probability
+        argument.  Loss (:212-218): per-row softmax cross entropy against caption[:, t], weighed by the FED caption_mask, divided by
+        sum(mask), plus weight decay on the non-'bias' variables.  A row whose k logits sum to 0 is the script's own 0/0.
+        caption, caption_mask [N, Tc], N = rep * B sample-major rows over the B videos; 1 <= k <= 8.
+        clip / optimizer: averaged_update's rules, unchanged -- the defaults are the script's train(), tf.clip_by_norm per variable and
+        GradientDescentOptimizer.  The backward has the fp32 products only, whatever grad_precision / S2VT_SPLIT_GRADS say for the other
+        updates; grad_precision == "bf16" raises.
+        Returns StepStats (.loss without the weight-decay term) plus .generated [N, Tc] int32 and, for the per-variable clip, .var_sumsq."""
+        self._refuse_residual("topk_feed_update")
+        if clip not in ("per_variable", "global"):
+            raise ValueError(f"clip must be 'per_variable' or 'global', got {clip!r}")
+        if optimizer not in ("adam", "sgd"):
+            raise ValueError(f"optimizer must be 'adam' or 'sgd', got {optimizer!r}")
+        if self.grad_precision == "bf16":
+            raise ValueError("topk_feed_update: the top-k feed backward has no bf16 product set")
+        if not 1 <= int(k) <= min(8, self.n_words):
+            raise ValueError(f"k must lie in 1..{min(8, self.n_words)}, got {k!r}")
+        video = self._dev(video, torch.float32)
+        cap = self._dev(caption, torch.int32)
+        mask = self._dev(caption_mask, torch.float32)
+        B, N = video.shape[0], cap.shape[0]
+        if N % B or cap.dim() != 2 or cap.shape[1] != self.n_caption_lstm_step or tuple(mask.shape) != tuple(cap.shape):
+            raise ValueError(f"topk_feed_update: caption and caption_mask must be [rep * {B}, {self.n_caption_lstm_step}], got "
+                             f"{tuple(cap.shape)} and {tuple(mask.shape)}")
+        keep = self.dropout_rate if keep is None else keep
+        vid, sid = self._row_ids(B, N // B, video_base)
+        seed = self.dropout_seed + 104729 * self.global_step
+        st_ = self.store
+        f = ops.topk_feed_fwd(self.dims, st_.params, video, cap, mask, N, int(k), self.loss_weight, keep, seed, vid, sid,
+                              mask_sum_copy=st_.grad[st_.numel:st_.numel + 1])
+        logits, coef, target, msum = f["logits"], f["coef_tm"], f["target_tm"], f["mask_sum"]
+        self.last_topk_feed = f                                  # (build_topk_feed_model's fetches read the logits before the softmax overwrites them)
+        if getattr(self, "_keep_topk_feed_logits", False):
+            f["probs"] = logits.clone()
+        nll, _ = ops.softmax_nll_fwd_bwd(logits, target, coef, 0.0)
+        self._coef_used = coef
+        ops.zero_(st_.grad[:st_.numel])                          # (sum(mask) already sits in the tail slot)
+        self._pending, self._early = [], None
+        ops.topk_feed_bptt_bwd(self.dims, st_.params, st_.grads, video, N, logits, f["ws"], f["scratch"], int(k), keep, seed, vid, sid)
+        f["dlogits"] = logits                                    # (completed by the backward: sum(mask) times d loss / d logits)
+        if clip == "global" or optimizer == "adam":
+            self.apply_gradients(None, lr, clip_norm, weight_decay=self.decay_value, loss_terms=(coef, nll, msum), optimizer=optimizer)
+            var_sumsq = None
+        else:
+            var_sumsq = self._apply_per_variable(lr, clip_norm, (coef, nll, msum))
+        st = StepStats(self._loss[0], self._sumsq, msum[0])
+        st.generated, st.var_sumsq = f["generated"], var_sumsq
+        return st
+
+    def build_topk_feed_model(self, k=5):
+        """The top-k feed graph: (loss, video, caption, caption_mask, probs, steps) as sum_generate_words_tf_s2vt.py:101-219.
+        caption_mask is an INPUT (:106), probs a list of Tc fetches [B, V] (the logits), steps a placeholder that may be fed and is
+        ignored, as in the script.  Fetching loss / probs evaluates the forward only; minimize() builds the train_op of :429-435."""
+        self._refuse_residual("build_topk_feed_model")
+        B, Tc = self.batch_size, self.n_caption_lstm_step
+        video = self._video_placeholder(B)
+        caption = Placeholder("caption", (B, Tc), np.int32)
+        caption_mask = Placeholder("caption_mask", (B, Tc), np.float32)
+        steps = Placeholder("steps", (), np.int32)
+
+        def fetches(f, loss):
+            out = {"loss": loss}
+            pr = f["probs"].view(Tc, -1, self.n_words).cpu().numpy()
+            out.update({f"probs_{t}": pr[t] for t in range(Tc)})
+            return out
+
+        def fn(v, c, m):
+            v = self._features(v, dropout=True, draw=0)
+            c = self._dev(c, torch.int32)
+            m = self._dev(m, torch.float32)
+            n = c.shape[0]
+            vid, sid = self._row_ids(v.shape[0], n // v.shape[0], 0)
+            seed = self.dropout_seed + 104729 * self.global_step
+            f = ops.topk_feed_fwd(self.dims, self.store.params, v, c, m, n, int(k), self.loss_weight, self.dropout_rate, seed, vid, sid)
+            f["probs"] = f["logits"].clone()
+            nll, _ = ops.softmax_nll_fwd_bwd(f["logits"], f["target_tm"], f["coef_tm"], 0.0)
+            return fetches(f, float(torch.dot(f["coef_tm"], nll) / f["mask_sum"][0]) + self.l2_term())
+        inputs = [video, caption, caption_mask]
+        loss = Output("loss", fn, inputs)
+        probs = [Output(f"probs_{t}", fn, inputs) for t in range(Tc)]
+        loss.graph = {"kind": "build_topk_feed_model", "inputs": inputs, "fetches": fetches, "outputs": probs, "k": int(k)}
+        return loss, video, caption, caption_mask, probs, steps
+
+    def _minimize_topk_feed(self, loss, learning_rate, clip_norm, optimizer, clip):
+        graph = loss.graph
+        lr = learning_rate.value if hasattr(learning_rate, "value") else (lambda: float(learning_rate))
+
+        def fn(v, c, m):
+            wd = self.l2_term()                                                # the l2 term of :216-218, pre-update
+            self._keep_topk_feed_logits = True
+            try:
+                st = self.topk_feed_update(self._features(v, dropout=True, draw=0), c, m, k=graph["k"], lr=lr(), clip_norm=clip_norm, clip=clip,
+                                           optimizer=optimizer)
+            finally:
+                self._keep_topk_feed_logits = False
+            out = graph["fetches"](self.last_topk_feed, float(st.loss) + wd)
+            out["train_op"] = None
+            return out
+        provides = {loss: "loss"}
+        provides.update({o: o.name for o in graph["outputs"]})
+        return Output("train_op", fn, graph["inputs"], provides=provides)
+
+    def generate_topk_feed(self, video, k=5, weights_mode=1, unshifted_softmax=True, batch_size=64):
+        """build_generator of sum_generate_words_tf_s2vt.py:221-275 over a block of videos: greedy decoding in which LSTM2 is fed the
+        weighted sum of its own top-k words' embeddings.  The defaults are the script's rule -- probs = exp(l) / sum exp(l) without a max
+        shift, top_k and weights from the probabilities, the emitted word argmax(probs); weights_mode = 0 mixes from the raw logits, the
+        rule of training.  Every video emits Tc words (the `break` of :273 never fires).  Returns ids [n, Tc] int32 (device)."""
+        self._refuse_residual("generate_topk_feed")
+        n = video.shape[0] if hasattr(video, "shape") else len(video)
+        out = []
+        for a in range(0, n, batch_size):
+            v = self._features(video[a:a + batch_size]).contiguous()
+            out.append(ops.topk_feed_decode(self.dims, self.store.params, v, int(k), int(weights_mode), bool(unshifted_softmax)))
+        return torch.cat(out, 0)
+
     @staticmethod
     def inverse_sigmoid_prob(k_value, steps):
         """The commented schedule of generate_words_tf_s2vt.py:134: p = k / (k + exp(steps / k)), in float64."""
@@ -1427,8 +1555,11 @@ class Video_Caption_Generator:
         if getattr(loss, "graph", None) and loss.graph.get("kind") == "build_averaged_model":
             return self._minimize_averaged(loss, learning_rate, clip_norm, "sgd" if optimizer is None else optimizer,
                                            "per_variable" if clip is None else clip)
+        if getattr(loss, "graph", None) and loss.graph.get("kind") == "build_topk_feed_model":
+            return self._minimize_topk_feed(loss, learning_rate, clip_norm, "sgd" if optimizer is None else optimizer,
+                                            "per_variable" if clip is None else clip)
         if clip not in (None, "global"):
-            raise ValueError("minimize(clip='per_variable') needs build_averaged_model()'s outputs")
+            raise ValueError("minimize(clip='per_variable') needs build_averaged_model()'s or build_topk_feed_model()'s outputs")
         optimizer = "adam" if optimizer is None else optimizer
         if getattr(loss, "graph", None) and loss.graph.get("kind") == "build_scheduled_model":
             return self._minimize_scheduled(loss, learning_rate, clip_norm, optimizer)

@@ -674,6 +674,121 @@ def averaged_bptt_bwd(dims: Dims, params: Params, grads: Params, video, N: int, 
                                        0 if gws is None else gws.numel(), _stream()), "s2vt_averaged_bptt_bwd")
 
 
+def topk_feed_fwd(dims: Dims, params: Params, video, caption, mask, N: int, k=5, loss_weight=1.0, keep=1.0, seed=0, video_id=None,
+                  sample_id=None, ws=None, mask_sum=None, mask_sum_copy=None, scratch=None):
+    """The top-k score-weighted unroll of sum_generate_words_tf_s2vt.py:101-219 (s2vt_topk_feed_fwd): the training forward decodes, and at
+    step t >= 1 LSTM2 is fed sum_j w_j Wemb[id_j] over the top-k logits of step t-1, w = those logits over their sum; step 0 feeds <bos>.
+    Arguments as averaged_fwd, plus k (1..8).  Returns a dict: logits [Tc*N, V] time-major, generated [N, Tc] int32, coef_tm [Tc*N]
+    (= loss_weight * mask), target_tm [Tc*N] int32, mask_sum [1], k, ws -- the training workspace -- and scratch, which holds the operands
+    X, the ids, the weights and the raw sums (topk_feed_scratch_views): topk_feed_bptt_bwd takes both."""
+    _chk_f32(video, mask, mask_sum, mask_sum_copy)
+    assert video.is_contiguous() and mask.is_contiguous()
+    assert caption.is_cuda and caption.dtype == torch.int32 and caption.is_contiguous()
+    Tc = dims.n_caption_lstm_step
+    assert tuple(caption.shape) == (N, Tc) and tuple(mask.shape) == (N, Tc)
+    for t in (video_id, sample_id):
+        assert t is not None and t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.numel() == N, "video_id / sample_id: int32 [N]"
+    B = video.shape[0]
+    dev = video.device
+    L = lib()
+    if ws is None:
+        ws = train_workspace(dims, B, N, dev)
+    if scratch is None:
+        nb = L.s2vt_topk_feed_scratch_bytes(C.byref(dims), N, int(k))
+        assert nb > 0, "bad dims / N / k"
+        scratch = workspace(nb, dev, "topk_feed")
+    out = dict(logits=torch.empty((Tc * N, dims.n_words), dtype=torch.float32, device=dev),
+               generated=torch.empty((N, Tc), dtype=torch.int32, device=dev), coef_tm=torch.empty(Tc * N, dtype=torch.float32, device=dev),
+               target_tm=torch.empty(Tc * N, dtype=torch.int32, device=dev),
+               mask_sum=torch.empty(1, dtype=torch.float32, device=dev) if mask_sum is None else mask_sum, k=int(k), ws=ws, scratch=scratch)
+    check(L.s2vt_topk_feed_fwd(C.byref(dims), C.byref(params), _ptr(video), B, N, _ptr(caption), _ptr(mask), float(loss_weight), float(keep), seed,
+                               _ptr(video_id), _ptr(sample_id), int(k), _ptr(out["logits"]), _ptr(out["generated"]), _ptr(out["coef_tm"]),
+                               _ptr(out["target_tm"]), _ptr(out["mask_sum"]), _ptr(mask_sum_copy), _ptr(ws), ws.numel(), _ptr(scratch),
+                               scratch.numel(), _stream()), "s2vt_topk_feed_fwd")
+    return out
+
+
+def topk_feed_scratch_views(dims: Dims, N: int, k: int, scratch):
+    """Views into topk_feed_fwd's scratch (uint8 tensor), time-major: X [Tc, N, E] fp32, ids [Tc, N, k] int32, w [Tc, N, k] fp32, S [Tc, N]
+    fp32 -- block t is what step t was fed.  The layout is include/s2vt.h's: 256-byte granules, the packed picks and the pick launches'
+    sample ids in front."""
+    Tc, E = dims.n_caption_lstm_step, dims.word_dim
+    R = Tc * N
+    g = lambda nbytes: (nbytes + 255) // 256 * 256
+    off = g(R * 16 * 8) + g(N * 4)
+    out = {}
+    for name, n, dt, shape in (("X", R * E, torch.float32, (Tc, N, E)), ("ids", R * k, torch.int32, (Tc, N, k)),
+                               ("w", R * k, torch.float32, (Tc, N, k)), ("S", R, torch.float32, (Tc, N))):
+        out[name] = scratch[off:off + n * 4].view(dt).view(shape)
+        off += g(n * 4)
+    assert off <= scratch.numel()
+    return out
+
+
+def topk_feed_bptt_bwd(dims: Dims, params: Params, grads: Params, video, N: int, dlogits, ws, scratch, k=5, keep=1.0, seed=0, video_id=None,
+                       sample_id=None):
+    """The backward of topk_feed_fwd (s2vt_topk_feed_bptt_bwd) on its workspace and scratch; gradients are accumulated into `grads`.
+    dlogits [Tc*N, V] is read AND written: it comes in as the softmax part (what softmax_nll_fwd_bwd leaves) and holds the completed
+    gradient with respect to the logits on return -- the mix's weights are differentiated.  fp32 products only."""
+    _chk_f32(video, dlogits)
+    assert dlogits.is_contiguous() and tuple(dlogits.shape) == (dims.n_caption_lstm_step * N, dims.n_words)
+    check(lib().s2vt_topk_feed_bptt_bwd(C.byref(dims), C.byref(params), C.byref(grads), _ptr(video), video.shape[0], N, _ptr(dlogits), float(keep),
+                                        seed, _ptr(video_id), _ptr(sample_id), int(k), _ptr(ws), ws.numel(), _ptr(scratch), scratch.numel(),
+                                        _stream()), "s2vt_topk_feed_bptt_bwd")
+
+
+def topk_feed_decode(dims: Dims, params: Params, video, k=5, weights_mode=1, unshifted_softmax=True, return_logits=False, ws=None):
+    """build_generator of sum_generate_words_tf_s2vt.py:221-275 for the B videos of `video` (s2vt_topk_feed_decode): greedy decoding with
+    a soft feed.  weights_mode 1 with unshifted_softmax (the defaults) is the script's generator -- top-k, weights and mix from the
+    unshifted softmax's probabilities, the emitted word argmax(probs); weights_mode 0 mixes from the raw logits, the training rule.
+    Returns ids [B, Tc] int32, or (ids, logits [Tc*B, V] time-major) with return_logits."""
+    _chk_f32(video)
+    assert video.is_contiguous()
+    B, dev = video.shape[0], video.device
+    L = lib()
+    if ws is None:
+        nb = L.s2vt_topk_feed_decode_workspace_bytes(C.byref(dims), B, int(k))
+        assert nb > 0, "bad dims / B / k"
+        ws = workspace(nb, dev, "topk_feed_decode")
+    ids = torch.empty((B, dims.n_caption_lstm_step), dtype=torch.int32, device=dev)
+    logits = torch.empty((dims.n_caption_lstm_step * B, dims.n_words), dtype=torch.float32, device=dev) if return_logits else None
+    check(L.s2vt_topk_feed_decode(C.byref(dims), C.byref(params), _ptr(video), B, int(k), int(weights_mode), int(bool(unshifted_softmax)),
+                                  _ptr(ids), _ptr(logits), _ptr(ws), ws.numel(), _stream()), "s2vt_topk_feed_decode")
+    return (ids, logits) if return_logits else ids
+
+
+def topk_mix_fwd(scores, Wemb, k, weights_mode=0):
+    """The top-k mix alone (s2vt_topk_mix_fwd) on the rows of `scores` [R, V] (a row-strided view is fine): weights_mode 0 reads them as
+    logits, 1 as a caller-made plane (the unshifted softmax's probabilities in the generator) -- the rule is the same, the entry's
+    argument differs.  Returns ids [R, k] int32, w [R, k], S [R], x [R, E]."""
+    _chk_f32(scores, Wemb)
+    assert scores.dim() == 2 and scores.stride(1) == 1 and Wemb.is_contiguous()
+    R, V = scores.shape
+    E = Wemb.shape[1]
+    dev = scores.device
+    ids = torch.empty((R, k), dtype=torch.int32, device=dev)
+    w = torch.empty((R, k), dtype=torch.float32, device=dev)
+    S = torch.empty(R, dtype=torch.float32, device=dev)
+    x = torch.empty((R, E), dtype=torch.float32, device=dev)
+    a = (None, 0, _ptr(scores), scores.stride(0)) if weights_mode else (_ptr(scores), scores.stride(0), None, 0)
+    check(lib().s2vt_topk_mix_fwd(a[0], a[1], a[2], a[3], int(weights_mode), R, V, int(k), _ptr(Wemb), E, _ptr(ids), _ptr(w), _ptr(S), _ptr(x), E,
+                                  _stream()), "s2vt_topk_mix_fwd")
+    return ids, w, S, x
+
+
+def topk_mix_bwd(dx, ids, w, S, Wemb, dscores, Wout=None, dO=None):
+    """The mix's backward (s2vt_topk_mix_bwd), in place: dscores[r, ids[r, j]] += (ds_j - g) / S[r] and, with Wout [H, V] and dO [R, H],
+    dO[r] += sum_j that * Wout[:, ids[r, j]].  dx [R, E], dscores [R, V] and dO may be row-strided views."""
+    _chk_f32(dx, w, S, Wemb, dscores, Wout, dO)
+    R, k = ids.shape
+    assert ids.dtype == torch.int32 and ids.is_contiguous() and w.is_contiguous() and S.is_contiguous() and Wemb.is_contiguous()
+    assert dx.stride(1) == 1 and dscores.stride(1) == 1 and (dO is None) == (Wout is None)
+    assert dO is None or (dO.stride(1) == 1 and Wout.is_contiguous())
+    check(lib().s2vt_topk_mix_bwd(_ptr(dx), dx.stride(0), _ptr(ids), _ptr(w), _ptr(S), _ptr(Wemb), Wemb.shape[1], _ptr(Wout), dscores.shape[1],
+                                  0 if dO is None else dO.shape[1], k, R, _ptr(dscores), dscores.stride(0), _ptr(dO),
+                                  0 if dO is None else dO.stride(0), _stream()), "s2vt_topk_mix_bwd")
+
+
 def softmax_nll_fwd_bwd(logits, target, coef, smoothing=0.0):
     """In place: logits <- coef * (softmax - q).  Returns (nll [R], lp_target [R]).  smoothing: a float, or a CUDA fp32
     tensor [R] with one label-smoothing value per row."""
@@ -1628,6 +1743,16 @@ def embed_scatter_add2(dE, idx_a, idx_b, dWemb, scale=0.5):
     assert dE.dim() == 2 and dE.stride(1) == 1 and dWemb.is_contiguous() and dWemb.shape[1] == dE.shape[1]
     check(lib().s2vt_embed_scatter_add2(_ptr(dE), dE.stride(0), _ptr(idx_a), _ptr(idx_b), float(scale), dE.shape[0], dE.shape[1], _ptr(dWemb),
                                         _stream()), "s2vt_embed_scatter_add2")
+
+
+def embed_scatter_addk(dE, ids, w, dWemb):
+    """dWemb[ids[r, j], :] += w[r, j] * dE[r, :] for every j (s2vt_embed_scatter_addk): dE [R, E] may be a row-strided view, ids int32 and
+    w fp32 [R, k] and dWemb [V, E] are contiguous."""
+    _chk_f32(dE, w, dWemb)
+    assert ids.dtype == torch.int32 and ids.is_cuda and ids.is_contiguous() and w.is_contiguous() and ids.shape == w.shape
+    assert dE.dim() == 2 and dE.stride(1) == 1 and dWemb.is_contiguous() and dWemb.shape[1] == dE.shape[1] and ids.shape[0] == dE.shape[0]
+    check(lib().s2vt_embed_scatter_addk(_ptr(dE), dE.stride(0), _ptr(ids), _ptr(w), ids.shape[1], dE.shape[0], dE.shape[1], _ptr(dWemb), _stream()),
+          "s2vt_embed_scatter_addk")
 
 
 def global_norm_clip(g, clip_norm: float):

@@ -216,18 +216,20 @@ def all_ranks_healthy(model) -> bool:
     return bad == 0.0
 
 
-def greedy_eval(model, corpus: Corpus, ixtoword, scorer: "reward.CiderD | None", batch_size: int, par: "DataParallel | None" = None):
+def greedy_eval(model, corpus: Corpus, ixtoword, scorer: "reward.CiderD | None", batch_size: int, par: "DataParallel | None" = None, decode=None):
     """Greedy captions for every test video (tf_s2vt.py:508-524) and their mean CIDEr-D against the video's own
     references when a scorer over that corpus is given (the reference reports BLEU/METEOR/ROUGE/CIDEr through
     the external coco-caption package, which is not part of this build).  Data parallel: the videos are dealt
-    round-robin over the ranks, captions gathered, the score averaged over all of them."""
+    round-robin over the ranks, captions gathered, the score averaged over all of them.
+    decode: features -> ids [n, Tc] (a device tensor) in place of the model's greedy sampler -- the generator of a script that decodes by
+    another rule (model.generate_topk_feed)."""
     vids = corpus.index.video_ids
     if par is not None and par.world > 1:
         vids = vids[par.rank::par.world]
     decoded, total, count = {}, 0.0, 0
     for a in range(0, len(vids), batch_size):
         ids = vids[a:a + batch_size]
-        _, g = model.sample(corpus.features.batch(ids), 0, True)
+        g = decode(corpus.features.batch(ids)) if decode is not None else model.sample(corpus.features.batch(ids), 0, True)[1]
         g = g.cpu().numpy()
         model.check_health()
         for v, s in zip(ids, hostglue.decode_captions(g, ixtoword)):

@@ -15,7 +15,11 @@ sigmoid schedule K / (K + exp(step / K)) of its commented line :134; --optimizer
 
 --averaged-embedding trains as average_generate_words_tf_s2vt.py does (Video_Caption_Generator.averaged_update): the unroll decodes and
 LSTM2 is fed the mean of the ground-truth word's and the model's own argmax's embedding, with that script's rule -- SGD behind
-tf.clip_by_norm 10 per variable, loss_weight 20, lr halved every 40000 steps -- unless --optimizer adam is given (Adam behind the global clip)."""
+tf.clip_by_norm 10 per variable, loss_weight 20, lr halved every 40000 steps -- unless --optimizer adam is given (Adam behind the global clip).
+
+--topk-feed [--topk-k 5] trains as sum_generate_words_tf_s2vt.py does (Video_Caption_Generator.topk_feed_update): the unroll decodes and
+LSTM2 is fed the weighted sum of the embeddings of the model's own top-k words, the weights those k logits over their sum and
+differentiated; the same update rule with lr halved every 20000 steps.  The per-epoch evaluation decodes with that script's generator."""
 from __future__ import annotations
 
 import argparse
@@ -31,8 +35,10 @@ from .train_common import (Config, Corpus, DataParallel, StepLog, epoch_batches,
 
 
 def train(cfg: Config, train_corpus: Corpus, test_corpus: Corpus | None = None, model=None, log=print, resume=None,
-          grad_precision=None, scheduled_sampling=None, ss_k=None, optimizer="adam", averaged_embedding=False):
-    """averaged_embedding: averaged_update instead of xe_update (optimizer "sgd": behind the per-variable clip, the script's train();
+          grad_precision=None, scheduled_sampling=None, ss_k=None, optimizer="adam", averaged_embedding=False, topk_feed=None):
+    """topk_feed: k -- topk_feed_update with that many words in the mix instead of xe_update, under averaged_embedding's optimizer rules and
+    loss_weight; the epoch's evaluation then decodes with generate_topk_feed(k).
+    averaged_embedding: averaged_update instead of xe_update (optimizer "sgd": behind the per-variable clip, the script's train();
     "adam": behind the global clip); a model built here then takes the script's loss_weight = 20.
     scheduled_sampling: None = cross entropy; a probability = scheduled sampling with that true-word probability (ss_k: the inverse
     sigmoid schedule on the step counter instead).  Its mask comes from the model's own picks, so a batch in which every row emits <eos>
@@ -49,7 +55,9 @@ def train(cfg: Config, train_corpus: Corpus, test_corpus: Corpus | None = None, 
         model = M.Video_Caption_Generator(cfg.dim_image, len(wordtoix), cfg.word_dim, cfg.lstm_dim, B,
                                           cfg.n_video_lstm_step + cfg.n_caption_lstm_step, cfg.n_video_lstm_step,
                                           cfg.n_caption_lstm_step, bias_init_vector=None, seed=cfg.seed, device=par.device,
-                                          residual=cfg.residual, **({"loss_weight": 20} if averaged_embedding else {}))
+                                          residual=cfg.residual, **({"loss_weight": 20} if averaged_embedding or topk_feed is not None else {}))
+    if topk_feed is not None and (averaged_embedding or scheduled_sampling is not None or getattr(model, "residual", False)):
+        raise ValueError("top-k feed training does not combine with averaged embeddings, scheduled sampling or a residual model")
     if scheduled_sampling is not None and getattr(model, "residual", False):
         raise ValueError("scheduled sampling is not implemented for a residual model (residual=True / --residual)")
     if averaged_embedding and (scheduled_sampling is not None or getattr(model, "residual", False)):
@@ -90,7 +98,11 @@ def train(cfg: Config, train_corpus: Corpus, test_corpus: Corpus | None = None, 
                 if pending is not None:
                     pending()
             b = cur
-            if averaged_embedding:
+            if topk_feed is not None:
+                update = lambda: model.topk_feed_update(b["feats"], b["ind"], b["mask"], k=topk_feed, lr=learning_rate(cfg, model.global_step),
+                                                        clip_norm=cfg.clip_norm, clip="per_variable" if optimizer == "sgd" else "global",
+                                                        optimizer=optimizer, video_base=b["lo"])
+            elif averaged_embedding:
                 update = lambda: model.averaged_update(b["feats"], b["ind"], b["mask"], lr=learning_rate(cfg, model.global_step),
                                                        clip_norm=cfg.clip_norm, clip="per_variable" if optimizer == "sgd" else "global",
                                                        optimizer=optimizer, video_base=b["lo"])
@@ -117,7 +129,8 @@ def train(cfg: Config, train_corpus: Corpus, test_corpus: Corpus | None = None, 
             pending()
         entry = {"epoch": epoch, "loss": float(np.mean(losses)) if losses else None}
         if test_corpus is not None:
-            _, entry["ciderD"] = greedy_eval(model, test_corpus, ixtoword, scorer, B, par)
+            decode = (lambda f: model.generate_topk_feed(f, k=topk_feed)) if topk_feed is not None else None
+            _, entry["ciderD"] = greedy_eval(model, test_corpus, ixtoword, scorer, B, par, decode=decode)
         ck = save_checkpoint_checked(model, cfg, epoch, step_name="Variable", chief=par.chief, tf_version=1)   # the XE script's saver writes V1 (tf_s2vt.py:440)      # tf_s2vt.py:441: the unnamed counter
         if par.chief:
             entry["checkpoint"] = ck
@@ -200,13 +213,23 @@ def main(argv=None):
     ap.add_argument("--averaged-embedding", action="store_true", help="averaged-embedding training (average_generate_words_tf_s2vt.py): feed the "
                     "mean of the ground-truth word's and the model's own argmax's embedding; SGD behind tf.clip_by_norm 10 per variable, loss_weight "
                     "20, lr halved every 40000 steps, unless --optimizer adam")
+    ap.add_argument("--topk-feed", action="store_true", help="top-k score-weighted embedding training (sum_generate_words_tf_s2vt.py): feed the "
+                    "weighted sum of the embeddings of the model's own top-k words; SGD behind tf.clip_by_norm 10 per variable, loss_weight 20, lr "
+                    "halved every 20000 steps, unless --optimizer adam")
+    ap.add_argument("--topk-k", type=int, default=5, metavar="K", help="with --topk-feed: the number of words in the mix, 1..8 (the script's 5)")
     ap.add_argument("--optimizer", choices=("adam", "sgd"), help="sgd: the scheduled-sampling script's GradientDescentOptimizer; default adam, "
-                    "with --averaged-embedding sgd")
+                    "with --averaged-embedding / --topk-feed sgd")
     a = ap.parse_args(argv)
+    if a.topk_feed and (a.averaged_embedding or a.scheduled_sampling is not None or a.ss_k is not None or a.bidirectional or a.residual):
+        ap.error("--topk-feed does not combine with --averaged-embedding, --scheduled-sampling, --ss-k, --bidirectional or --residual")
+    if a.topk_feed and not 1 <= a.topk_k <= 8:
+        ap.error("--topk-k must lie in 1..8")
+    if a.topk_feed and a.grad_precision == "bf16":
+        ap.error("--topk-feed has the fp32 gradient products only")
     if a.averaged_embedding and (a.scheduled_sampling is not None or a.ss_k is not None or a.bidirectional or a.residual):
         ap.error("--averaged-embedding does not combine with --scheduled-sampling, --ss-k, --bidirectional or --residual")
     if a.optimizer is None:
-        a.optimizer = "sgd" if a.averaged_embedding else "adam"
+        a.optimizer = "sgd" if a.averaged_embedding or a.topk_feed else "adam"
     if a.ss_k is not None and a.scheduled_sampling is None:
         a.scheduled_sampling = 0.5
     if a.bidirectional:
@@ -217,14 +240,15 @@ def main(argv=None):
                      decay_steps=10000, clip_norm=10.0, model_path=a.model_path, model_name="bimodel")
         train_bidirectional(cfg, Corpus(a.train_sents, a.train_feats, vocabulary_file=a.vocab), resume=a.resume)
         return
-    if a.optimizer != "adam" and a.scheduled_sampling is None and not a.averaged_embedding:
-        ap.error("--optimizer sgd is wired for --scheduled-sampling and --averaged-embedding only")
+    if a.optimizer != "adam" and a.scheduled_sampling is None and not a.averaged_embedding and not a.topk_feed:
+        ap.error("--optimizer sgd is wired for --scheduled-sampling, --averaged-embedding and --topk-feed only")
     cfg = Config(n_epochs=a.epochs, batch_size=a.batch_size, model_path=a.model_path, model_name=f"batch_size{a.batch_size}_s2vt_model",
-                 residual=a.residual, **({"decay_steps": 40000} if a.averaged_embedding else {}))     # (:366-367: 40000)
+                 residual=a.residual, **({"decay_steps": 40000} if a.averaged_embedding else {"decay_steps": 20000} if a.topk_feed else {}))
+    # (average_generate_words_tf_s2vt.py:366-367: 40000; sum_generate_words_tf_s2vt.py:429-431: 20000)
     tr = Corpus(a.train_sents, a.train_feats, vocabulary_file=a.vocab)
     te = Corpus(a.test_sents, a.test_feats, vocabulary=tr.vocabulary) if a.test_sents and a.test_feats else None
     train(cfg, tr, te, resume=a.resume, grad_precision=a.grad_precision, scheduled_sampling=a.scheduled_sampling, ss_k=a.ss_k,
-          optimizer=a.optimizer, averaged_embedding=a.averaged_embedding)
+          optimizer=a.optimizer, averaged_embedding=a.averaged_embedding, topk_feed=a.topk_k if a.topk_feed else None)
 
 
 if __name__ == "__main__":
