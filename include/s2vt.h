@@ -1221,6 +1221,29 @@ int s2vt_allreduce_grads(float* bucket, int64_t n, void* rccl_comm, s2vt_stream 
 /* Register the `ncclAllReduce` of the host's own RCCL (needed when it was loaded RTLD_LOCAL); NULL unregisters. */
 int s2vt_set_rccl_allreduce(void* nccl_allreduce_fn_ptr);
 
+/* ---- ROUGE-L reward on the device (csrc/rouge.hip; the arithmetic contract: DESIGN.md section 3) ----
+ * The reward of the reference's rouge_* scripts (`from rouge_evaluation import *`: evaluate_captions_cider returns pycocoevalcap's
+ * Rouge, beta = 1.2, one candidate against ALL references of its video) scored where the sampler's ids are born.
+ * The reference corpus, uploaded once: every reference's token ids in one stream, the references sorted by video. */
+typedef struct s2vt_rouge_refs {       /* all device pointers */
+    const int32_t* tokens;             /* [ref_offsets[n_refs]] */
+    const int32_t* ref_offsets;        /* [n_refs + 1] ascending */
+    const int32_t* video_refs;         /* [n_videos + 1] ascending: video v owns references [video_refs[v], video_refs[v+1]), >= 1 each */
+    int32_t n_videos, n_refs;
+} s2vt_rouge_refs;
+/* out[n] = float32(ROUGE-L F-measure) of row n = ids[n * ld .. n * ld + Tc) cut BEFORE its first eos_id (m ids; m = 0 scores 0)
+ * against the references of video video_of_row[n]:
+ *     l_j = LCS(candidate, r_j);  p = max_j double(l_j) / double(m);  r = max_j double(l_j) / double(len r_j)
+ *     score = p == 0 || r == 0 ? 0 : ((1 + beta2) * p * r) / (r + beta2 * p)
+ * every operation one IEEE double operation in this order, none fused: bit-equal to s2vt_rouge_score (s2vt_host.h).  pr_out
+ * (may be NULL): [N][2] = p, r.  One launch, no workspace, no atomics; two runs give equal bits.  ld >= Tc (rows of a wider buffer
+ * work), 1 <= Tc <= 128, any number of references per video, any reference length.  N == 0: S2VT_OK, nothing launched.
+ * S2VT_E_BADARG (answered without a GPU): NULL pointers, ld < Tc, Tc outside [1, 128], N < 0, n_videos < 1, beta2 negative or not
+ * finite.  A video_of_row[n] outside [0, n_videos) is device data the host cannot see: that row's out (and pr_out) is NaN, nothing
+ * else is touched. */
+int s2vt_rouge_l_score(const s2vt_rouge_refs* refs, const int32_t* ids, int32_t ld, int32_t N, int32_t Tc, int32_t eos_id,
+                       const int32_t* video_of_row, double beta2, float* out, double* pr_out, s2vt_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

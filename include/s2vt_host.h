@@ -46,6 +46,23 @@ int s2vt_cider_score(const s2vt_cider* h, const int32_t* ids, int32_t N, int32_t
 
 int32_t s2vt_cider_num_videos(const s2vt_cider* h);
 
+/* ---- ROUGE-L (csrc_host/rouge.cpp) ------------------------------------------------------------------------
+ * The reward of the reference's rouge_* scripts (`from rouge_evaluation import *`: their evaluate_captions_cider returns
+ * pycocoevalcap's Rouge, beta = 1.2, one candidate against all references of its video) on token ids: epoch evaluation, CPU-only
+ * callers, and the second implementation the device kernel (s2vt_rouge_l_score, s2vt.h) is compared with bit for bit.
+ *   l_j = LCS(candidate, r_j) (the classic table);  p = max_j double(l_j) / double(m);  r = max_j double(l_j) / double(len r_j)
+ *   score = p == 0 || r == 0 ? 0 : ((1 + beta2) * p * r) / (r + beta2 * p),  beta2 = beta^2 as the caller's double
+ * every operation one IEEE double operation in this order, none fused.
+ * create: the arguments of s2vt_cider_create; NULL on bad arguments. */
+typedef struct s2vt_rouge s2vt_rouge;
+s2vt_rouge* s2vt_rouge_create(const int32_t* tokens, const int64_t* offsets, const int32_t* video_of_ref, int32_t n_refs,
+                              int32_t n_videos);
+void s2vt_rouge_destroy(s2vt_rouge* h);
+/* out[n] = float32(score) of row n: the ids BEFORE its first eos_id (none: score 0) against the references of video_of_row[n].
+ * n_threads as s2vt_cider_score.  Returns 0, or -1 on bad arguments (a video index out of range, a negative or non-finite beta2). */
+int s2vt_rouge_score(const s2vt_rouge* h, const int32_t* ids, int32_t N, int32_t Tc, int32_t eos_id, const int32_t* video_of_row,
+                     double beta2, float* out, int32_t n_threads);
+
 /* ---- feature files ------------------------------------------------------
  * The reference stores Inception-ResNet-v2 pool features as TEXT, one line per frame,
  * "vid<N>_frame_<k>,f0,...,f<d-1>" (writer tf_feature_extract.py:153-154), and re-parses the whole file into

@@ -79,6 +79,11 @@ class BidirParams(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in BIDIR_PARAM_FIELDS]
 
 
+class RougeRefs(C.Structure):
+    """s2vt_rouge_refs: the reference corpus of s2vt_rouge_l_score as device pointers, references sorted by video."""
+    _fields_ = [("tokens", C.c_void_p), ("ref_offsets", C.c_void_p), ("video_refs", C.c_void_p), ("n_videos", C.c_int32), ("n_refs", C.c_int32)]
+
+
 def lib_path() -> str:
     return os.environ.get("S2VT_LIB") or os.path.join(_HERE, "libs2vt_hip.so")   # S2VT_LIB: dev A/B builds only
 
@@ -262,6 +267,7 @@ SIGNATURES = {
     "s2vt_adam_tf_guarded": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _f32, _f32, _i64, _f32, _f32, _f32, _vp, _vp]),
     "s2vt_allreduce_grads": (C.c_int, [_vp, _i64, _vp, _vp]),
     "s2vt_set_rccl_allreduce": (C.c_int, [_vp]),
+    "s2vt_rouge_l_score": (C.c_int, [C.POINTER(RougeRefs), _vp, _i32, _i32, _i32, _i32, _vp, C.c_double, _vp, _vp, _vp]),
 }
 
 

@@ -1126,6 +1126,29 @@ def pg_coef(mask, rewards, baseline, scale=1.0):
     return coef
 
 
+def rouge_l_score(tokens, ref_offsets, video_refs, n_refs, ids, video_of_row, beta2, eos_id=0, want_pr=False, out=None, pr_out=None):
+    """ROUGE-L of ids [N, Tc] (int32, unit stride along Tc, any row stride >= Tc) against the references of video_of_row [N] (int32):
+    float32 [N], one launch (s2vt_rouge_l_score).  tokens / ref_offsets [n_refs + 1] / video_refs [n_videos + 1]: the corpus as int32
+    device tensors, references sorted by video.  want_pr: also the [N, 2] float64 (p, r)."""
+    for t in (tokens, ref_offsets, video_refs, ids, video_of_row):
+        assert t.is_cuda and t.dtype == torch.int32, "expected a CUDA int32 tensor"
+    assert tokens.is_contiguous() and ref_offsets.is_contiguous() and video_refs.is_contiguous() and video_of_row.is_contiguous()
+    assert ids.dim() == 2 and (ids.shape[1] == 1 or ids.stride(1) == 1) and ref_offsets.numel() == n_refs + 1
+    N, Tc = ids.shape
+    assert video_of_row.numel() == N
+    ld = int(ids.stride(0)) if N > 1 else max(int(ids.stride(0)), Tc)
+    if out is None:
+        out = torch.empty(N, dtype=torch.float32, device=ids.device)
+    if want_pr and pr_out is None:
+        pr_out = torch.empty((N, 2), dtype=torch.float64, device=ids.device)
+    if N == 0:
+        return (out, pr_out) if want_pr else out
+    refs =_lib.RougeRefs(tokens.data_ptr(), ref_offsets.data_ptr(), video_refs.data_ptr(), video_refs.numel() - 1, int(n_refs))
+    check(lib().s2vt_rouge_l_score(C.byref(refs), _ptr(ids), ld, N, Tc, int(eos_id), _ptr(video_of_row), float(beta2), _ptr(out), _ptr(pr_out),
+                                   _stream()), "s2vt_rouge_l_score")
+    return (out, pr_out) if want_pr else out
+
+
 def xe_prep(mask, caption, loss_weight, n_global, q1):
     """(coef_tm [Tc*N], target_tm [Tc*N] int32, sum(mask) [1]) of the XE update in one launch (s2vt_xe_prep)."""
     _chk_f32(mask)

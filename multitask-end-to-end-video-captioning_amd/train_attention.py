@@ -23,7 +23,7 @@ import torch
 
 from . import hostglue, reward
 from .train_common import (Config, Corpus, DataParallel, StepLog, beam_eval, epoch_batches, greedy_eval, learning_rate, lookahead,
-                           optimistic_restore, run_step, save_checkpoint_checked)
+                           optimistic_restore, reward_scorers, run_step, save_checkpoint_checked)
 
 
 def attention_config(**kw):
@@ -64,9 +64,14 @@ def train(cfg: Config, train_corpus: Corpus, test_corpus: Corpus | None = None, 
         log(f"restored: {optimistic_restore(model, restore, step_names=('g_step',))}")
     if resume:
         log(f"resumed: {optimistic_restore(model, resume)} at step {model.global_step}")
-    scorer = reward.CiderD(test_corpus.index.refs_by_video(), wordtoix) if test_corpus is not None else None
     K = int(samples)
-    train_scorer = reward.CiderD(train_corpus.index.refs_by_video(), wordtoix) if reinforce else None
+    on_device = reinforce and cfg.reward == "rouge"     # the reward is scored on the sampler's own tensors (reward.RougeL.score_ids_device)
+    if reinforce:
+        train_scorer, scorer, metric = reward_scorers(cfg, train_corpus.index.refs_by_video(),
+                                                      test_corpus.index.refs_by_video() if test_corpus is not None else None, wordtoix, model.device)
+    else:
+        scorer = reward.CiderD(test_corpus.index.refs_by_video(), wordtoix) if test_corpus is not None else None
+        train_scorer, metric = None, "ciderD"
     rng = random.Random(cfg.seed)
     caps = train_corpus.captions
     history = []
@@ -76,8 +81,12 @@ def train(cfg: Config, train_corpus: Corpus, test_corpus: Corpus | None = None, 
         idx, lo = par.shard(gidx)
         vid = caps[idx, 0]
         if reinforce:
-            return dict(lo=lo, feats=model._dev(train_corpus.features.batch(vid), torch.float32),
-                        rows=np.asarray([train_corpus.index.row[v] for v in vid], np.int32))
+            out = dict(lo=lo, feats=model._dev(train_corpus.features.batch(vid), torch.float32),
+                       rows=np.asarray([train_corpus.index.row[v] for v in vid], np.int32))
+            if on_device:
+                out["rows_dev"] = model._dev(out["rows"], torch.int32)
+                out["rows_dev_k"] = out["rows_dev"].repeat(K)              # [K*B], sample-major like the ids
+            return out
         g_ind, g_mask = hostglue.sentence_padding_toix(caps[gidx, 1].tolist(), wordtoix, cfg.n_caption_lstm_step)
         g_mask = np.asarray(g_mask, np.float32)
         return dict(lo=lo, ind=np.asarray(g_ind, np.int32)[lo:lo + len(idx)], mask=g_mask[lo:lo + len(idx)],
@@ -106,6 +115,10 @@ def train(cfg: Config, train_corpus: Corpus, test_corpus: Corpus | None = None, 
                 s_host, g_host = sampled.cpu().numpy(), greedy.cpu().numpy()
 
                 def rewards():              # on the host while the GPU runs the teacher-forced forward
+                    if on_device:           # two launches behind the forward; the baseline is tiled on the device
+                        rb["r"] = train_scorer.score_ids_device(sampled, b["rows_dev_k"])
+                        rb["b"] = train_scorer.score_ids_device(greedy, b["rows_dev"])
+                        return rb["r"], rb["b"].repeat(K)
                     rb["r"] = train_scorer.score_ids(s_host, np.tile(b["rows"], K))      # [K*B], sample-major like the ids
                     rb["b"] = train_scorer.score_ids(g_host, b["rows"])                  # [B]
                     return rb["r"], hostglue.tile_baseline(rb["b"], K)
@@ -122,9 +135,11 @@ def train(cfg: Config, train_corpus: Corpus, test_corpus: Corpus | None = None, 
                                     log, overlap=overlap)
             losses.append(loss)
             t1 = time.time()
-            rm, bm = (float(rb["r"].mean()), float(rb["b"].mean())) if reinforce else (None, None)
+            rm, bm = (float(rb["r"].mean()), float(rb["b"].mean())) if reinforce and not on_device else (None, None)
 
-            def pending(it=it, loss=loss, lr=learning_rate(cfg, model.global_step), step=model.global_step, secs=t1 - t0, rm=rm, bm=bm):
+            def pending(it=it, loss=loss, lr=learning_rate(cfg, model.global_step), step=model.global_step, secs=t1 - t0, rm=rm, bm=bm, rb=rb):
+                if on_device:               # device-resident rewards: their means are read when the log line is written, not in the step
+                    rm, bm = float(rb["r"].mean()), float(rb["b"].mean())
                 if reinforce:
                     log(f"idx: {it * cfg.batch_size} rate: {lr:g} Epoch: {epoch} loss: {loss:.5f} r: {rm:.4f} b: {bm:.4f} Elapsed time: {secs:.3f}")
                     steplog.write(kind="step", epoch=epoch, step=step, lr=lr, loss=loss, reward=rm, baseline=bm, seconds=secs)
@@ -137,9 +152,9 @@ def train(cfg: Config, train_corpus: Corpus, test_corpus: Corpus | None = None, 
         entry = {"epoch": epoch, "loss": float(np.mean(losses)) if losses else None}
         if test_corpus is not None:
             if eval_beam > 0:
-                _, entry["ciderD"] = beam_eval(model, test_corpus, ixtoword, scorer, B, eval_beam, eval_lnf, par)
+                _, entry[metric] =beam_eval(model, test_corpus, ixtoword, scorer, B, eval_beam, eval_lnf, par)
             else:
-                _, entry["ciderD"] = greedy_eval(model, test_corpus, ixtoword, scorer, B, par)
+                _, entry[metric] =greedy_eval(model, test_corpus, ixtoword, scorer, B, par)
         ck = save_checkpoint_checked(model, cfg, epoch, step_name="g_step" if reinforce else "Variable", chief=par.chief)
         if par.chief:
             entry["checkpoint"] = ck
@@ -150,7 +165,7 @@ def train(cfg: Config, train_corpus: Corpus, test_corpus: Corpus | None = None, 
     return model, history
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--train-sents", required=True); ap.add_argument("--train-feats", required=True)
     ap.add_argument("--test-sents"); ap.add_argument("--test-feats")
@@ -164,9 +179,12 @@ def main():
     ap.add_argument("--samples", type=int, default=5, help="multinomial samples per video and step of --reinforce (K)")
     ap.add_argument("--restore", help="--reinforce: the XE checkpoint to start from (variables and Adam slots; the step counter starts at 0)")
     ap.add_argument("--stop-at-eos", action="store_true", help="samples leave the decode loop at their first <eos> (same update, shorter sampler loop)")
-    a = ap.parse_args()
-    make = reinforce_config if a.reinforce else attention_config
-    cfg = make(n_epochs=a.epochs, batch_size=a.batch_size, model_path=a.model_path, n_video_lstm_step=a.frames, stop_at_eos=a.stop_at_eos,
+    ap.add_argument("--reward", choices=reward.REWARDS, default="cider", help="--reinforce: CIDEr-D on the host (default) or ROUGE-L scored on the device")
+    a = ap.parse_args(argv)
+    if a.reward != "cider" and not a.reinforce:
+        ap.error("--reward belongs to --reinforce")
+    make =reinforce_config if a.reinforce else attention_config
+    cfg = make(n_epochs=a.epochs, batch_size=a.batch_size, model_path=a.model_path, n_video_lstm_step=a.frames, stop_at_eos=a.stop_at_eos, reward=a.reward,
                model_name=f"batch_size{a.batch_size}_beta10_m05_{a.frames}img_attention_{'reinforce_' if a.reinforce else ''}model")
     tr = Corpus(a.train_sents, a.train_feats, vocabulary_file=a.vocab)
     te = Corpus(a.test_sents, a.test_feats, vocabulary=tr.vocabulary) if a.test_sents and a.test_feats else None

@@ -48,6 +48,19 @@ class Config:
                                        # the epoch records of the step log carry it
     mix_baseline: float | None = None  # RL: P = the baseline is the reward of a greedy decode fed ground-truth words with probability P / 1.00001 and the
                                        # greedy caption is the sample (reinforce_multitask_e2e_attribute_by_groudtruth_greedy_s2vt.py:957-979: 0.9); None = off
+    reward: str = "cider"              # RL: "cider" (CIDEr-D on the host) or "rouge" -- ROUGE-L, what the rouge_* scripts and the multitask script optimise
+                                       # (`from rouge_evaluation import *`, reinforce_multitask_e2e_attribute_loss.py:18), scored on the device from the
+                                       # sampler's own tensors (reward.RougeL); the epoch's test score is then reported as "rougeL"
+
+
+def reward_scorers(cfg: Config, train_refs, test_refs, wordtoix, device):
+    """(train scorer, test scorer | None, the epoch entry's metric key) of a REINFORCE driver for cfg.reward.  The training scorer of
+    "rouge" holds its corpus on `device` (score_ids_device); the test scorer scores the epoch's greedy captions on the host."""
+    if cfg.reward not in reward.REWARDS:
+        raise ValueError(f"reward must be one of {reward.REWARDS}, got {cfg.reward!r}")
+    scorer = reward.make_scorer(cfg.reward, train_refs, wordtoix, device=device)
+    test_scorer = reward.make_scorer(cfg.reward, test_refs, wordtoix) if test_refs is not None else None
+    return scorer, test_scorer, reward.METRIC_KEY[cfg.reward]
 
 
 class Corpus:

@@ -178,14 +178,19 @@ def train_reinforce(cfg: Config, sents, video_frames, vocabulary, cnn=None, mode
     if resume:
         log(f"cnn resumed: {len(load_cnn(trainer, resume_cnn or cnn_checkpoint_of(resume)))} tensors")
 
-    def side(sents_, frames_):
+    on_device = cfg.reward == "rouge"           # the reward is scored on the sampler's own tensors (reward.RougeL.score_ids_device)
+    metric = reward.METRIC_KEY.get(cfg.reward)
+    if metric is None:
+        raise ValueError(f"reward must be one of {reward.REWARDS}, got {cfg.reward!r}")
+
+    def side(sents_, frames_, device=None):
         index = data.CaptionIndex(sents_)
         lab = None
         if multitask:
             d = hostglue.get_multilabel(index.by_video, attr_vocabulary)
             lab = np.stack([d[v] for v in index.video_ids]).astype(np.float32)
-        return index, reward.CiderD(index.refs_by_video(), wordtoix), lab, frames_
-    index, scorer, labels, _ = side(sents, video_frames)
+        return index, reward.make_scorer(cfg.reward, index.refs_by_video(), wordtoix, device=device), lab, frames_
+    index, scorer, labels, _ = side(sents, video_frames, device=model.device)
     tside = side(*test) if test is not None else None
 
     def evaluate():
@@ -202,7 +207,7 @@ def train_reinforce(cfg: Config, sents, video_frames, vocabulary, cnn=None, mode
             total += float(sc.sum()); count += len(sc)
             if multitask:
                 tot += np.asarray(hostglue.get_metrics(trainer.evaluate_multilabel(frames).cpu().numpy(), tlab[rows], 0.5), np.int64)
-        out = {"ciderD": par.mean(total, count)}
+        out = {metric: par.mean(total, count)}
         if multitask:
             tp, tn, fp, fn, cp, cn = (int(x) for x in par.sum_ints(tot))
             out["multilabel"] = dict(true_positive=tp, true_negative=tn, false_positive=fp, false_negative=fn)
@@ -227,6 +232,12 @@ def train_reinforce(cfg: Config, sents, video_frames, vocabulary, cnn=None, mode
             rb = {}
 
             def reward_fn(samples, greedy):
+                if on_device:               # two launches on the sampler's own tensors; reinforce_step tiles the baseline on the device
+                    rows_dev = model._dev(rows, torch.int32)
+                    rb["r"] = scorer.score_ids_device(samples, rows_dev.repeat(K))
+                    rb["b"] = scorer.score_ids_device(greedy, rows_dev)
+                    model.check_health()
+                    return rb["r"], rb["b"]
                 rb["r"] = scorer.score_ids(samples.cpu().numpy(), np.tile(rows, K))
                 rb["b"] = scorer.score_ids(greedy.cpu().numpy(), rows)
                 model.check_health()
@@ -236,7 +247,7 @@ def train_reinforce(cfg: Config, sents, video_frames, vocabulary, cnn=None, mode
                                                                       sample_seed=cfg.seed + 7919 * (model.global_step + 1)), log)
             losses.append(loss); adv.append(float(rb["r"].mean() - rb["b"].mean()))
             log(f"idx: {it * cfg.batch_size} rate: {learning_rate(cfg, model.global_step):g} Epoch: {epoch} loss: {loss:.5f} "
-                f"r: {rb['r'].mean():.4f} b: {rb['b'].mean():.4f} Elapsed time: {time.time() - t0:.3f}")
+                f"r: {float(rb['r'].mean()):.4f} b: {float(rb['b'].mean()):.4f} Elapsed time: {time.time() - t0:.3f}")
         entry = {"epoch": epoch, "loss": float(np.mean(losses)) if losses else None, "advantage": float(np.mean(adv)) if adv else None}
         if tside is not None:
             entry.update(evaluate())
@@ -249,7 +260,7 @@ def train_reinforce(cfg: Config, sents, video_frames, vocabulary, cnn=None, mode
     return trainer, history
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--train-sents", required=True); ap.add_argument("--frames", required=True)
     ap.add_argument("--vocab", required=True); ap.add_argument("--cnn-npz")
@@ -262,8 +273,12 @@ def main():
     ap.add_argument("--reinforce", action="store_true", help="reinforcement_e2e.py: self-critical REINFORCE through the CNN")
     ap.add_argument("--samples", type=int, default=1); ap.add_argument("--test-sents")
     ap.add_argument("--attr-vocab", help="multitask scripts: one attribute word per line"); ap.add_argument("--alpha", type=float, default=0.05)
-    a = ap.parse_args()
-    cfg = e2e_config(n_epochs=a.epochs, batch_size=a.batch_size, model_path=a.model_path, multisample=a.samples, alpha=a.alpha,
+    ap.add_argument("--reward", choices=("cider", "rouge"), default="cider", help="--reinforce: CIDEr-D on the host (default) or ROUGE-L scored on the "
+                    "device (what reinforce_multitask_e2e_attribute_loss.py optimises: `from rouge_evaluation import *`)")
+    a = ap.parse_args(argv)
+    if a.reward != "cider" and not a.reinforce:
+        ap.error("--reward belongs to --reinforce")
+    cfg = e2e_config(n_epochs=a.epochs, batch_size=a.batch_size, model_path=a.model_path, multisample=a.samples, alpha=a.alpha, reward=a.reward,
                      **({"model_name": "e2e_reinforce_model"} if a.reinforce else {}))       # (its own files beside the XE run's in one --model-path)
     sents, frames = data.get_video_frame_caption_pair(a.train_sents, a.frames, cfg.n_video_lstm_step)
     variables = None

@@ -8,6 +8,8 @@ Step of the reference                                   | here
 decode_captions_masks: ids -> strings + mask (:783-784) | mask on the device (s2vt_caption_mask), no strings
 get_captions scan + evaluate_captions_cider x2 (:787-803| reward.CiderD.score_ids on the int32 ids (C++ inverted index, ~3 ms,
   pyciderevalcap on strings)                            |   under the GPU's teacher-forced forward); references indexed once
+the rouge_* scripts' `from rouge_evaluation import *`   | --reward rouge: reward.RougeL.score_ids_device on the sampler's own tensors (one HIP launch
+  (evaluate_captions_cider returns ROUGE-L there)       |   each for r and b, the baseline tiled on the device); the epoch reports rougeL
 features tiled x8 on the host (:779-782)                | never tiled: rows address video n % B
 sess.run([train_op, sum_loss]) (:823)                   | model.reinforce_update (forward with dropout, reward-scaled
                                                         |   NLL, BPTT, all-reduce, clip 5, Adam, lr 1e-6 * 0.5^(step//1000))
@@ -24,7 +26,7 @@ import numpy as np
 
 from . import hostglue, reward
 from .train_common import (Config, Corpus, DataParallel, StepLog, epoch_batches, greedy_eval, learning_rate, lookahead, optimistic_restore,
-                           run_step, save_checkpoint, save_checkpoint_checked)
+                           reward_scorers, run_step, save_checkpoint, save_checkpoint_checked)
 
 
 def rl_config(**kw):
@@ -107,14 +109,15 @@ def train(cfg: Config, train_corpus: Corpus, test_corpus: Corpus | None = None, 
         log(f"restored: {optimistic_restore(model, restore, step_names=('g_step',))}")
     if resume:
         log(f"resumed: {optimistic_restore(model, resume)} at step {model.global_step}")
-    scorer = reward.CiderD(train_corpus.index.refs_by_video(), wordtoix)
-    test_scorer = reward.CiderD(test_corpus.index.refs_by_video(), wordtoix) if test_corpus is not None else None
+    scorer, test_scorer, metric = reward_scorers(cfg, train_corpus.index.refs_by_video(),
+                                                 test_corpus.index.refs_by_video() if test_corpus is not None else None, wordtoix, model.device)
+    on_device = cfg.reward == "rouge"           # the reward is scored on the sampler's own tensors: the advantage never waits for the host
     rng = random.Random(cfg.seed)
     caps = train_corpus.captions
     history = []
     steplog = StepLog(cfg.step_log if par.chief else None)
     if test_corpus is not None:
-        log(f"before train: ciderD {greedy_eval(model, test_corpus, ixtoword, test_scorer, B, par)[1]}")
+        log(f"before train: {metric} {greedy_eval(model, test_corpus, ixtoword, test_scorer, B, par)[1]}")
     def prepare(gidx):
         """Host side of one step: this rank's shard of the batch, its features on their way to the GPU (one copy, shared by
         sample + update), the reward tables' rows of its videos."""
@@ -122,6 +125,9 @@ def train(cfg: Config, train_corpus: Corpus, test_corpus: Corpus | None = None, 
         vid = caps[idx, 0]
         rows = np.asarray([train_corpus.index.row[v] for v in vid], np.int32)
         out = dict(lo=lo, video=model._dev(train_corpus.features.batch(vid), torch.float32), rows=rows)
+        if on_device:
+            out["rows_dev"] = model._dev(rows, torch.int32)
+            out["rows_dev_k"] = out["rows_dev"].repeat(K)                  # [K*B], sample-major like the ids
         if multitask:
             out["labels"] = model._dev(labels[rows], torch.float32)
         if (multitask and cfg.lambda_loss > 0) or mix_p is not None:
@@ -146,6 +152,10 @@ def train(cfg: Config, train_corpus: Corpus, test_corpus: Corpus | None = None, 
                 model.check_health()            # the ids just came to the host: a starved sampler recurrence is caught before it is scored
 
                 def rewards():                  # runs on the host while the GPU does the teacher-forced forward
+                    if on_device:               # two launches behind the forward, on the sampler's own tensors; the baseline is tiled on the device
+                        rb["r"] = scorer.score_ids_device(samples, cur["rows_dev_k"])
+                        rb["b"] = scorer.score_ids_device(greedy_words, cur["rows_dev"])
+                        return rb["r"], rb["b"].repeat(K)
                     rb["r"] = scorer.score_ids(s_host, np.tile(rows, K))                 # [K*B], sample-major like the ids
                     rb["b"] = scorer.score_ids(g_host, rows)                            # [B]
                     return rb["r"], hostglue.tile_baseline(rb["b"], K)
@@ -170,7 +180,10 @@ def train(cfg: Config, train_corpus: Corpus, test_corpus: Corpus | None = None, 
                 mix, greedy_words = model.mix_sample(video, cur["gt"], mix_p, True, seed=cfg.seed + 7919 * (model.global_step + 1), video_base=lo)
                 m_host, g_host = mix.cpu().numpy(), greedy_words.cpu().numpy()
                 model.check_health()
-                rb["r"], rb["b"] = scorer.score_ids(g_host, rows), scorer.score_ids(m_host, rows)
+                if on_device:
+                    rb["r"], rb["b"] = scorer.score_ids_device(greedy_words, cur["rows_dev"]), scorer.score_ids_device(mix, cur["rows_dev"])
+                else:
+                    rb["r"], rb["b"] = scorer.score_ids(g_host, rows), scorer.score_ids(m_host, rows)
                 g_mask = hostglue.masks_from_ids(g_host)
                 labels_ = cur["labels"] if multitask else None
                 if cfg.lambda_loss > 0:
@@ -186,10 +199,16 @@ def train(cfg: Config, train_corpus: Corpus, test_corpus: Corpus | None = None, 
                     pending()
             st, loss = run_step(model, step if mix_p is None else step_mix, log, overlap=overlap)
             r, b = rb["r"], rb["b"]
-            losses.append(loss); adv.append(float(r.mean() - b.mean()))
+            losses.append(loss)
+            if not on_device:
+                adv.append(float(r.mean() - b.mean()))
             t1 = time.time()
 
-            def pending(it=it, loss=loss, lr=learning_rate(cfg, model.global_step), step=model.global_step, rm=float(r.mean()), bm=float(b.mean()), secs=t1 - t0):
+            def pending(it=it, loss=loss, lr=learning_rate(cfg, model.global_step), step=model.global_step, rm=None if on_device else float(r.mean()),
+                        bm=None if on_device else float(b.mean()), secs=t1 - t0, r=r, b=b):
+                if on_device:                   # device-resident rewards: their means are read when the log line is written, not in the step
+                    rm, bm = float(r.mean()), float(b.mean())
+                    adv.append(rm - bm)
                 log(f"idx: {it * cfg.batch_size} rate: {lr:g} Epoch: {epoch} loss: {loss:.5f} r: {rm:.4f} b: {bm:.4f} Elapsed time: {secs:.3f}")
                 steplog.write(kind="step", epoch=epoch, step=step, lr=lr, loss=loss, reward=rm, baseline=bm, seconds=secs)
             t0, cur = t1, (nxt if gnext is not None else None)
@@ -197,7 +216,7 @@ def train(cfg: Config, train_corpus: Corpus, test_corpus: Corpus | None = None, 
             pending()
         entry = {"epoch": epoch, "loss": float(np.mean(losses)) if losses else None, "r_minus_b": float(np.mean(adv)) if adv else None}
         if test_corpus is not None:
-            _, entry["ciderD"] = greedy_eval(model, test_corpus, ixtoword, test_scorer, B, par)
+            _, entry[metric] = greedy_eval(model, test_corpus, ixtoword, test_scorer, B, par)
             if multitask:
                 entry["multilabel"] = multilabel_eval(model, test_corpus, test_labels, B)
         ck = save_checkpoint_checked(model, cfg, epoch, step_name="g_step", chief=par.chief)
@@ -235,14 +254,15 @@ def train_bidirectional(cfg: Config, train_corpus: Corpus, test_corpus: Corpus |
     if resume:
         model.restore(resume)
         log(f"resumed: {resume} at step {model.global_step}")
-    scorer = reward.CiderD(train_corpus.index.refs_by_video(), wordtoix)
-    test_scorer = reward.CiderD(test_corpus.index.refs_by_video(), wordtoix) if test_corpus is not None else None
+    scorer, test_scorer, metric = reward_scorers(cfg, train_corpus.index.refs_by_video(),
+                                                 test_corpus.index.refs_by_video() if test_corpus is not None else None, wordtoix, model.device)
+    on_device = cfg.reward == "rouge"
     rng = random.Random(cfg.seed)
     caps = train_corpus.captions
     history = []
     steplog = StepLog(cfg.step_log)
     if test_corpus is not None:
-        log(f"before train: ciderD {greedy_eval(model, test_corpus, ixtoword, test_scorer, B)[1]}")
+        log(f"before train: {metric} {greedy_eval(model, test_corpus, ixtoword, test_scorer, B)[1]}")
     for epoch in range(cfg.n_epochs):
         losses, adv = [], []
         for it, idx in enumerate(epoch_batches(len(caps), B, rng)):
@@ -261,6 +281,11 @@ def train_bidirectional(cfg: Config, train_corpus: Corpus, test_corpus: Corpus |
                 model.check_health()            # the ids just came to the host: a starved recurrence is caught before it is scored
 
                 def rewards():                  # runs on the host while the GPU does the teacher-forced forward
+                    if on_device:               # two launches on the sampler's own tensors, the baseline tiled on the device
+                        rows_dev = model._dev(rows, torch.int32)
+                        rb["r"] = scorer.score_ids_device(samples, rows_dev.repeat(K))
+                        rb["b"] = scorer.score_ids_device(greedy_words, rows_dev)
+                        return rb["r"], rb["b"].repeat(K)
                     rb["r"] = scorer.score_ids(s_host, np.tile(rows, K))                 # [K*B], sample-major like the ids
                     rb["b"] = scorer.score_ids(g_host, rows)                            # [B]
                     return rb["r"], hostglue.tile_baseline(rb["b"], K)
@@ -275,7 +300,7 @@ def train_bidirectional(cfg: Config, train_corpus: Corpus, test_corpus: Corpus |
             steplog.write(kind="step", epoch=epoch, step=model.global_step, lr=lr, loss=loss, reward=rm, baseline=bm, seconds=secs)
         entry = {"epoch": epoch, "loss": float(np.mean(losses)) if losses else None, "r_minus_b": float(np.mean(adv)) if adv else None}
         if test_corpus is not None:
-            _, entry["ciderD"] = greedy_eval(model, test_corpus, ixtoword, test_scorer, B)
+            _, entry[metric] = greedy_eval(model, test_corpus, ixtoword, test_scorer, B)
         model.check_health()
         os.makedirs(cfg.model_path, exist_ok=True)
         entry["checkpoint"] = os.path.join(cfg.model_path, f"{cfg.model_name}-{epoch}")
@@ -306,18 +331,20 @@ def main(argv=None):
     ap.add_argument("--bidirectional", action="store_true", help="the bidirectional captioner of bidirection_tf_s2vt.py (d = 1024, Tv = 25) under this "
                     "script's self-critical stage: LSTM1 runs once per video, the samples share it (train_bidirectional); --restore takes a "
                     "train_xe --bidirectional checkpoint")
+    ap.add_argument("--reward", choices=reward.REWARDS, default="cider", help="the self-critical reward: CIDEr-D on the host (default), or ROUGE-L as the "
+                    "rouge_* scripts and reinforce_multitask_e2e_attribute_loss.py optimise it, scored on the device from the sampler's own tensors")
     a = ap.parse_args(argv)
     if a.bidirectional:
         if a.residual or a.mix_baseline is not None or a.stop_at_eos or a.attr_vocab or a.grad_precision:
             ap.error("--bidirectional does not combine with --residual, --mix-baseline, --stop-at-eos, --attr-vocab or --grad-precision")
         cfg = rl_config(dim_image=1024, n_video_lstm_step=25, n_caption_lstm_step=35, n_epochs=a.epochs, batch_size=a.batch_size, multisample=a.samples,
-                        model_path=a.model_path, model_name="reinforce_bimodel")
+                        model_path=a.model_path, model_name="reinforce_bimodel", reward=a.reward)
         tr = Corpus(a.train_sents, a.train_feats, vocabulary_file=a.vocab)
         te = Corpus(a.test_sents, a.test_feats, vocabulary=tr.vocabulary) if a.test_sents and a.test_feats else None
         train_bidirectional(cfg, tr, te, restore=a.restore, resume=a.resume)
         return
     cfg = rl_config(n_epochs=a.epochs, batch_size=a.batch_size, multisample=a.samples, model_path=a.model_path, stop_at_eos=a.stop_at_eos,
-                    alpha=a.alpha, lambda_loss=a.lambda_loss, mix_baseline=a.mix_baseline, residual=a.residual)
+                    alpha=a.alpha, lambda_loss=a.lambda_loss, mix_baseline=a.mix_baseline, residual=a.residual, reward=a.reward)
     tr = Corpus(a.train_sents, a.train_feats, vocabulary_file=a.vocab)
     te = Corpus(a.test_sents, a.test_feats, vocabulary=tr.vocabulary) if a.test_sents and a.test_feats else None
     attr = [l.strip() for l in open(a.attr_vocab)] if a.attr_vocab else None
